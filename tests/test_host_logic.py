@@ -425,3 +425,28 @@ def test_cptramg_oracle_time_loop_and_vector_view():
     assert np.abs(S - ua[2]).max() < 1e-6
     b.u.dat.data[b.i_S_o][...] = 0.5            # the entry the reference's time loop writes (thermalmodel.py:229)
     assert np.all(b.u._store[2] == 0.5) and b.u.dev_stale
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the state after a time step as <field>.npy (float64, the reference's cell order); above
+    the size cap the same seeded sample of cells for every field, with its indices, within the cap."""
+    import bench
+    m = bench.make_model("c4", engine_factory=OracleEngine, Nxyz=(6, 8, 5))
+    m.start()
+    m.step()
+    fields = [f.copy() for f in m.u.split()]
+    bench.dump_outputs(m, str(tmp_path/"all"), 0)
+    names = ["pressure", "temperature", "saturation_o"]
+    assert sorted(p.name for p in (tmp_path/"all").iterdir()) == sorted(n + ".npy" for n in names)
+    for n, f in zip(names, fields):
+        a = np.load(tmp_path/"all"/(n + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, f)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5000)          # 3 fields x 240 cells x 8 B = 5760 B: over the cap
+    for d in ("s1", "s2"):
+        bench.dump_outputs(m, str(tmp_path/d), 0)
+    idx = np.load(tmp_path/"s1"/"cell_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path/"s2"/"cell_index.npy"))
+    assert 0 < len(idx) < fields[0].size and np.all(np.diff(idx) > 0)
+    assert sum(p.stat().st_size for p in (tmp_path/"s1").iterdir()) <= 5000
+    for n, f in zip(names, fields):
+        assert np.array_equal(np.load(tmp_path/"s1"/(n + ".npy")), f[idx.astype(np.int64)])
