@@ -158,3 +158,34 @@ def test_cport_bilu_matches_numpy_oracle(levels):
     d_c, its_c, reason_c, _ = c.fgmres(F)
     assert reason_c == reason_o == 2 and its_c == its_o
     assert rel2(d_c, d_o) < 1e-7
+
+
+@pytest.mark.parametrize("restart,maxit", [(1, 300), (2, 300), (5, 300), (40, 300), (200, 1), (200, 7), (3, 7)])
+def test_cport_fgmres_restart_and_limit_match_numpy_oracle(restart, maxit):
+    """cp_fgmres with ksp_restart < its (several cycles) and ksp_max_it below what the case needs (DIVERGED_ITS with a
+    partial solution): the same counts, reason and final residual norm as oracle.linalg.fgmres."""
+    if maxit == 300:
+        spec, u0, *_ = cases.c3_spe10_2d(Nx=10, Ny=12, nphase=2)
+        dt = 8640.0
+    else:
+        spec, u0, *_ = cases.c4_spe10_3d(Nx=5, Ny=6, Nz=4, nphase=2)
+        dt = 4000.0
+    opts = dict(pc="cptr", ksp_rtol=1e-10, ksp_restart=restart, ksp_max_it=maxit)
+    o, c = OracleEngine(spec, opts), CPortEngine(spec, opts)
+    u = cases.perturbed_state(spec, seed=7, amp=0.3)
+    for e in (o, c):
+        e.set_old(u0)
+        e.set_dt(dt)
+        e.set_state(u)
+    J, Sm = o.jacobian(want_schur=True)
+    c.jacobian(want_schur=True)
+    o.pc.setup(J, Sm)
+    c.pc_setup()
+    F = o.residual()
+    d_o, its_o, reason_o, hist = la.fgmres(lambda v: la.spmv_block(J, v), o.pc.apply, F, rtol=1e-10,
+                                           maxit=maxit, restart=restart)
+    d_c, its_c, reason_c, rn_c = c.fgmres(F)
+    assert reason_o == (-3 if maxit < 300 else 2)
+    assert (reason_c, its_c) == (reason_o, its_o)
+    assert abs(rn_c - hist[-1]) <= 1e-10*np.linalg.norm(F)
+    assert rel2(d_c, d_o) < 1e-8

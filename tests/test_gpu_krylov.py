@@ -1,0 +1,444 @@
+"""The HIP FGMRES loop (tp_solver.hip: fgmres) and its reductions (tp_linalg.hip: k_multi_dot, k_reduce_partials,
+k_multi_axpy) on the paths the parity tests never take: several restart cycles, the iteration limit, a basis that grows
+while speculative work is in flight, a zero right-hand side, a speculation that is discarded, the preconditioner
+application count, a non-finite right-hand side, the fall-back switches read once per process, and reductions at the
+lengths where their tails and remainders change.
+
+Reference: oracle.linalg.fgmres on the same J and preconditioner (tests/test_oracle_linalg.py checks it against direct
+solves and extended-precision residuals), and exact sums for the reductions.  "Bitwise" below means equal float64 bit
+patterns: the code claims those paths perform the same IEEE operations in the same order."""
+import ctypes as C
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import cases
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def rel2(a, b):
+    return np.linalg.norm((a - b).ravel())/max(np.linalg.norm(b.ravel()), 1e-300)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+# the four preconditioner families of the issue: cptr two-phase 3-D, cpr single-phase 2-D, system AMG, whole-slab ILU(0)
+CASES = [
+    ("cptr_3d", cases.c4_spe10_3d, dict(Nx=7, Ny=13, Nz=9, nphase=2), dict(pc="cptr")),
+    ("cpr_2d_1ph", cases.c3_spe10_2d, dict(Nx=14, Ny=19, nphase=1), dict(pc="cpr", decoup="QI", ilu_tile=(1 << 30, 64, 1))),
+    ("cptramg_qi", cases.c4_spe10_3d, dict(Nx=9, Ny=14, Nz=8, nphase=2), dict(pc="cptramg", decoup="QI")),
+    ("cptr_whole_ilu", cases.c4_spe10_3d, dict(Nx=11, Ny=13, Nz=17, nphase=2), dict(pc="cptr", ilu_whole=True, ilu_tile=(5, 4, 7))),
+]
+CASE = {c[0]: c[1:] for c in CASES}
+# preconditioner applications per pc_apply, as tp_solve_info.vcycles counts them
+PER_APPLY = {"cpr": 1, "cptramg": 1, "cptr": 3, "bilu": 0}
+
+
+def hip_setup(spec, u0, opts, u):
+    from thermalporous_amd.engine import HipEngine
+    h = HipEngine(spec, opts)
+    h.set_old(u0)
+    h.set_dt(8640.0)
+    h.set_state(u)
+    return h
+
+
+def linear_pair(name, **extra):
+    """Oracle and HIP engine on the same perturbed state; J and the preconditioner set up on both sides (HIP: by tp_fgmres,
+    which sets up on first use).  Returns (oracle, hip, J, F, matvec)."""
+    from oracle.engine import OracleEngine
+    import oracle.linalg as la
+    builder, kw, opts = CASE[name]
+    opts = dict(opts, **extra)
+    spec, u0, *_ = builder(**kw)
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    o = OracleEngine(spec, opts)
+    o.set_old(u0)
+    o.set_dt(8640.0)
+    o.set_state(u)
+    schur = opts["pc"] in ("cptr", "fieldsplit_cd")
+    out = o.jacobian(want_schur=schur)
+    J, Sm = out if schur else (out, None)
+    o.pc.setup(J, Sm)
+    h = hip_setup(spec, u0, opts, u)
+    h.jacobian()
+    h.residual()
+    h.copy_residual_to("b")
+    return o, h, J, o.residual(), (lambda v: la.spmv_block(J, v))
+
+
+def oracle_fgmres(o, mv, F, **kw):
+    import oracle.linalg as la
+    oo = o.opts
+    args = dict(rtol=oo["ksp_rtol"], atol=oo["ksp_atol"], restart=oo["ksp_restart"], maxit=oo["ksp_max_it"])
+    args.update(kw)
+    return la.fgmres(mv, o.pc.apply, F, **args)
+
+
+def true_residual_norm(J, F, x):
+    import oracle.linalg as la
+    ld = np.longdouble
+    r = F.astype(ld) - la.spmv_block(J.astype(ld), x.astype(ld))
+    return float(np.sqrt(np.sum(r*r)))
+
+
+# ---- 1. restarts ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c[0] for c in CASES])
+def test_restarted_fgmres_matches_oracle(name):
+    """ksp_restart in {1, 2, 5, 31, 33} at rtol 1e-10: several cycles, each starting from the true residual b - J x.
+    (FGMRES(1) and (2) stall on the 3-D cases: both sides then stop at ksp_max_it with DIVERGED_ITS.)"""
+    o, h, J, F, mv = linear_pair(name, ksp_rtol=1e-10)
+    counts = []
+    for restart in (1, 2, 5, 31, 33):
+        h.set_options(ksp_restart=restart)
+        its_h, reason_h, rn_h = h.fgmres("b", "x")
+        x_o, its_o, reason_o, hist = oracle_fgmres(o, mv, F, restart=restart)
+        counts.append((restart, its_h, its_o))
+        assert reason_h == reason_o, (name, restart, reason_h, reason_o)
+        assert abs(its_h - its_o) <= 1, (name, restart, its_h, its_o)
+        assert rel2(h.vec_get("x"), x_o) <= 1e-6, (name, restart)
+    print("restart sweep %s (restart, its_hip, its_oracle): %s" % (name, counts))
+    h.close()
+
+
+# ---- 2. iteration limit ---------------------------------------------------------------------------------------------
+LIMITS = [("cptr_3d", 1), ("cptr_3d", 2), ("cptr_3d", 7), ("cpr_2d_1ph", 1), ("cpr_2d_1ph", 2),
+          ("cptramg_qi", 1), ("cptramg_qi", 7), ("cptr_whole_ilu", 2), ("cptr_whole_ilu", 7)]
+
+
+@pytest.mark.parametrize("name,maxit", LIMITS, ids=["%s-%d" % p for p in LIMITS])
+def test_iteration_limit_returns_partial_solution(name, maxit):
+    """ksp_max_it below what the case needs: DIVERGED_ITS after exactly ksp_max_it iterations, the partial solution of
+    the oracle, and an rnorm that is the true residual norm of the returned x."""
+    o, h, J, F, mv = linear_pair(name, ksp_rtol=1e-10)
+    _, its_full, reason_full, _ = oracle_fgmres(o, mv, F)
+    assert reason_full == 2 and its_full > maxit
+    h.set_options(ksp_max_it=maxit)
+    Jh = h.jacobian()                          # tp_export_jacobian: the operator the solve below uses
+    h.copy_residual_to("b")
+    its_h, reason_h, rn_h = h.fgmres("b", "x")
+    x_o, its_o, reason_o, hist = oracle_fgmres(o, mv, F, maxit=maxit)
+    assert (reason_h, its_h) == (reason_o, its_o) == (-3, maxit)
+    x_h = h.vec_get("x")
+    assert rel2(x_h, x_o) <= 1e-9
+    bn = np.linalg.norm(F)
+    assert abs(rn_h - hist[-1]) <= 1e-9*bn
+    assert abs(rn_h - true_residual_norm(Jh, F, x_h)) <= 1e-9*bn
+    h.close()
+
+
+# ---- 3. basis growth -------------------------------------------------------------------------------------------------
+def test_basis_growth_then_bitwise_repeat():
+    """pc_bilu at rtol 1e-10 on a 9x14x8 two-phase box needs ~90 iterations in ONE cycle: the Krylov basis grows
+    32 -> 64 -> 128 vectors (a device copy while the next speculative pc_apply is queued) and the pc_apply graphs are
+    captured for the new (V_j, Z_j) addresses.  The repeat on the same context (no growth, graphs partly cached) must be
+    bitwise equal to the first solve."""
+    from oracle.engine import OracleEngine
+    import oracle.linalg as la
+    spec, u0, *_ = cases.c4_spe10_3d(Nx=9, Ny=14, Nz=8, nphase=2)
+    opts = dict(pc="bilu", ksp_rtol=1e-10)
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    o = OracleEngine(spec, opts)
+    o.set_old(u0)
+    o.set_dt(8640.0)
+    o.set_state(u)
+    J = o.jacobian()
+    o.pc.setup(J)
+    F = o.residual()
+    h = hip_setup(spec, u0, opts, u)
+    h.jacobian()
+    h.residual()
+    h.copy_residual_to("b")
+    its1, reason1, rn1 = h.fgmres("b", "x")
+    x1 = h.vec_get("x")
+    x_o, its_o, reason_o, _ = la.fgmres(lambda v: la.spmv_block(J, v), o.pc.apply, F, rtol=1e-10)
+    print("basis growth bilu 9x14x8: its hip %d oracle %d" % (its1, its_o))
+    assert its1 > 64 and reason1 == reason_o == 2
+    assert abs(its1 - its_o) <= 1
+    assert rel2(x1, x_o) <= 1e-6
+    its2, reason2, rn2 = h.fgmres("b", "x")
+    assert (its2, reason2) == (its1, reason1)
+    assert bits(rn2) == bits(rn1)
+    assert np.array_equal(bits(h.vec_get("x")), bits(x1))
+    h.close()
+
+
+# ---- 4. zero right-hand side -----------------------------------------------------------------------------------------
+def test_zero_rhs_zeroes_x():
+    o, h, J, F, mv = linear_pair("cptr_3d")
+    h.vec_set("x", np.random.default_rng(3).standard_normal(F.shape)*1e3)
+    h.vec_set("zero", np.zeros_like(F))
+    its, reason, rn = h.fgmres("zero", "x")
+    assert (its, reason, rn) == (0, 2, 0.0)
+    assert not np.any(h.vec_get("x"))
+    h.close()
+
+
+# ---- 5. a speculation that is discarded, and what it leaves behind ---------------------------------------------------
+# At ksp_rtol 0.2 these cases converge in ONE iteration.  The loop has already queued the speculative z_1 = M^-1 v_1 and
+# J z_1 by then (the predicted residual, |b|, is above TP_SPEC_MARGIN x tol = 0.8 |b|); that work is discarded.
+@pytest.mark.parametrize("name", ["cptr_3d", "cpr_2d_1ph"])
+def test_discarded_speculation_leaves_no_trace(name):
+    o, h, J, F, mv = linear_pair(name, ksp_rtol=0.2)
+    its, reason, _ = h.fgmres("b", "x")
+    _, its_o, reason_o, _ = oracle_fgmres(o, mv, F)
+    assert (its, reason) == (its_o, reason_o) == (1, 2)
+    # the full solve that follows on this context == the same solve on a fresh context
+    h.set_options(ksp_rtol=1e-10)
+    r1 = h.fgmres("b", "x")
+    x1 = h.vec_get("x")
+    builder, kw, opts = CASE[name]
+    spec, u0, *_ = builder(**kw)
+    g = hip_setup(spec, u0, dict(opts, ksp_rtol=1e-10), cases.perturbed_state(spec, seed=5, amp=0.3))
+    g.jacobian()
+    g.residual()
+    g.pc_setup()
+    g.copy_residual_to("b")
+    r2 = g.fgmres("b", "x")
+    assert r1[1] == 2 and r1[:2] == r2[:2] and bits(r1[2]) == bits(r2[2])
+    assert np.array_equal(bits(x1), bits(g.vec_get("x")))
+    h.close()
+    g.close()
+
+
+@pytest.mark.parametrize("name", ["cptr_3d", "cpr_2d_1ph"])
+def test_vcycles_count_only_used_applications(name):
+    """tp_solve_info.vcycles counts the preconditioner's V-cycles of the applications FGMRES USED: a discarded speculative
+    application is taken back.  ksp_rtol 0.2: one linear solve that converges in one iteration (one application used, one
+    discarded), then two Newton solves whose linear solves end the same way.  vcycles = per-application count x (1 + lits)
+    exactly, and its increase over the second Newton solve divided by that solve's lits is the per-application count."""
+    o, h, J, F, mv = linear_pair(name, ksp_rtol=0.2, snes_max_it=40)
+    per = PER_APPLY[CASE[name][2]["pc"]]
+    its, reason, _ = h.fgmres("b", "x")
+    assert (its, reason) == (1, 2)
+    h.set_state(CASE[name][0](**CASE[name][1])[1])     # Newton from the uniform initial state, as the time loop starts
+    h.set_old()
+    h.set_dt(86.4)
+    r1 = dict(h.newton_solve())
+    h.set_old()
+    r2 = dict(h.newton_solve())
+    assert r1["lits"] > 0 and r2["lits"] > 0, (r1, r2)
+    assert r1["vcycles"] == per*(1 + r1["lits"]), (r1, per)
+    assert (r2["vcycles"] - r1["vcycles"]) == per*r2["lits"], (r1, r2, per)
+    print("vcycles %s: per application %d, lits %d + %d, vcycles %d -> %d" % (name, per, r1["lits"], r2["lits"],
+                                                                            r1["vcycles"], r2["vcycles"]))
+    h.close()
+
+
+def test_vcycles_with_restarts():
+    """ksp_restart 5: no speculative application may be issued on the last iteration of a cycle (the restart discards the
+    basis, and such an application would never be used or taken back)."""
+    builder, kw, opts = CASE["cptr_3d"]
+    spec, u0, *_ = builder(**kw)
+    h = hip_setup(spec, u0, dict(opts, ksp_restart=5, ksp_rtol=1e-10, snes_max_it=25), u0)
+    h.set_dt(86.4)
+    r = dict(h.newton_solve())
+    assert r["reason"] > 0 and r["lits"] > 5*r["nits"], r       # at least one restart per linear solve on average
+    assert r["vcycles"] == PER_APPLY["cptr"]*r["lits"], r
+    h.close()
+
+
+# ---- 6. non-finite right-hand side, then recovery ---------------------------------------------------------------------
+def recovery_steps(h, u, u0):
+    """Valid state u: jacobian, pc_setup, fgmres; then one Newton solve from u0.  Returns every result, bit patterns
+    included."""
+    h.set_state(u)
+    h.jacobian()
+    h.residual()
+    h.pc_setup()
+    h.copy_residual_to("b")
+    its, reason, rn = h.fgmres("b", "x")
+    x = h.vec_get("x")
+    h.set_state(u0)
+    h.set_old()
+    h.set_dt(86.4)
+    r = dict(h.newton_solve())
+    return (its, reason, bits(rn)), bits(x), (r["nits"], r["lits"], r["reason"], bits(r["fnorm"])), bits(h.get_state())
+
+
+@pytest.mark.parametrize("failure", ["nan_rhs", "diverged_its"])
+def test_recovery_after_failed_solve_is_bitwise(failure):
+    """A failed solve leaves nothing behind in the context.  nan_rhs: F at a state with one NaN cell (tp_residual keeps J and
+    the preconditioner of the valid state) -> KSP_DIVERGED_NANORINF (-9) before any iteration, as PETSc returns; the numpy
+    oracle has no such test and runs to DIVERGED_ITS (-3) on the same input.  diverged_its: a solve stopped by ksp_max_it.
+    Then the valid state through jacobian, pc_setup, fgmres and a Newton solve must be bitwise what a fresh context gives.
+    (NaN in J itself cannot reach the Krylov loop through the C ABI without passing through pc_setup: tp_jacobian drops the
+    set-up, and tp_fgmres redoes it on first use.  Set-up on non-finite values is not exercised here.)"""
+    o, h, J, F, mv = linear_pair("cptr_3d")
+    builder, kw, opts = CASE["cptr_3d"]
+    spec = o.spec
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    h.pc_setup()
+    if failure == "nan_rhs":
+        bad = u.copy()
+        bad[0, 4, 6, 3] = np.nan
+        Fb = h.residual(bad)
+        assert np.isnan(Fb).any()
+        h.copy_residual_to("bad")
+        its, reason, rn = h.fgmres("bad", "x")
+        assert (its, reason) == (0, -9) and not math.isfinite(rn)
+        _, its_o, reason_o, _ = oracle_fgmres(o, mv, Fb, maxit=5)
+        assert (its_o, reason_o) == (5, -3)
+    else:
+        h.set_options(ksp_max_it=2, ksp_rtol=1e-12)
+        h.copy_residual_to("b")
+        its, reason, rn = h.fgmres("b", "x")
+        assert (its, reason) == (2, -3)
+        h.set_options(ksp_max_it=200, ksp_rtol=opts.get("ksp_rtol", 1e-7))
+    u0 = builder(**kw)[1]
+    got = recovery_steps(h, u, u0)
+    g = hip_setup(spec, u0, opts, u)
+    ref = recovery_steps(g, u, u0)
+    assert got[0] == ref[0] and got[2] == ref[2]
+    assert np.array_equal(got[1], ref[1]) and np.array_equal(got[3], ref[3])
+    h.close()
+    g.close()
+
+
+# ---- 7. switches read once per process --------------------------------------------------------------------------------
+BITWISE_ENVS = [{"TP_FGMRES_PIPE": "0"}, {"TP_PIN": "0"}, {"TP_GRAPH": "0"}, {"TP_SPEC_MARGIN": "0"},
+                {"TP_SPEC_MARGIN": "1e300"}, {"TP_GS_REVERSE": "0"}, {"TP_HALO_OVERLAP": "0"}]
+
+
+def run_child(tmp_path, env, tag):
+    path = str(tmp_path/("krylov_%s.npz" % tag))
+    full = {k: v for k, v in os.environ.items() if not k.startswith(("TP_FGMRES_PIPE", "TP_PIN", "TP_GRAPH", "TP_SPEC_MARGIN",
+                                                                    "TP_GS_REVERSE", "TP_HALO_OVERLAP", "TP_MD_CHUNK"))}
+    full.update(env)
+    r = subprocess.run([sys.executable, os.path.join(HERE, "krylov_env_check.py"), path], env=full,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+def test_env_switches_keep_krylov_results(tmp_path):
+    """The fall-back paths (no pipelining, no pinned hand-over, no graphs, always / never speculate, forward Gram-Schmidt
+    traversal, no halo overlap) perform the same arithmetic as the default: every iterate, norm, state and V-cycle count
+    is bitwise equal.  Never speculating (TP_SPEC_MARGIN=1e300) against always speculating (0) checks that discarded
+    applications are taken out of vcycles.  TP_MD_CHUNK=4 changes the summation order: parity bars only."""
+    base = run_child(tmp_path, {}, "default")
+    lin = sorted({k.split(".")[0] for k in base if k.endswith(".its")})
+    newt = sorted({k.split(".")[0] for k in base if k.endswith(".nits")})
+    assert lin and len(newt) == 4
+    print("child default:", {n: (int(base[n + ".its"]), int(base[n + ".reason"])) for n in lin},
+          {n: (base[n + ".nits"].tolist(), base[n + ".lits"].tolist(), base[n + ".vcycles"].tolist()) for n in newt})
+    assert int(base["maxit7.reason"]) == -3 and int(base["maxit7.its"]) == 7
+    assert int(base["restart5.its"]) > 5
+    for i, env in enumerate(BITWISE_ENVS):
+        got = run_child(tmp_path, env, "b%d" % i)
+        assert sorted(got) == sorted(base)
+        for k in base:
+            assert np.array_equal(bits(got[k]) if base[k].dtype == np.float64 else got[k],
+                                  bits(base[k]) if base[k].dtype == np.float64 else base[k]), (env, k)
+    got = run_child(tmp_path, {"TP_MD_CHUNK": "4"}, "chunk4")
+    for n in lin:
+        assert int(got[n + ".reason"]) == int(base[n + ".reason"]), n
+        assert abs(int(got[n + ".its"]) - int(base[n + ".its"])) <= 1, n
+        assert rel2(got[n + ".x"], base[n + ".x"]) <= 1e-9, n
+    for n in newt:
+        for k in ("nits", "reason"):
+            assert np.array_equal(got[n + "." + k], base[n + "." + k]), (n, k)
+        assert np.abs(got[n + ".lits"] - base[n + ".lits"]).max() <= len(base[n + ".nits"]), n
+        assert rel2(got[n + ".u"], base[n + ".u"]) <= 1e-9, n
+
+
+# ---- 8. reductions against exact sums ---------------------------------------------------------------------------------
+# (grid, nphase): b * nown mod 512 = 0, 1, 63, 64, 65, 511 (512 = 64 lanes x 8 entries per lane: the tail of the last
+# wave), and one grid of 2.2 M entries = 4297 waves, more than the 4096 that k_reduce_partials sums with its four-way loop
+GRIDS = [((8, 8, 4), 1, 0), ((3, 3, 19), 2, 1), ((1, 3, 7), 2, 63), ((2, 4, 4), 1, 64), ((3, 11, 11), 2, 65),
+         ((1, 11, 31), 2, 511), ((100, 100, 110), 1, None)]
+
+
+def raw_engine(n, nphase):
+    from thermalporous_amd.engine import HipEngine
+    spec, *_ = cases.c4_spe10_3d(Nx=n[0], Ny=n[1], Nz=n[2], nphase=nphase, homogeneous=True)
+    return HipEngine(spec, dict(pc="cpr"))
+
+
+def raw_set(h, vid, a):
+    """Whole device vector, halo planes included (HipEngine.vec_set would overwrite them with copies of the boundary)."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert a.size == h.b*h.ntot
+    h._ck(h.lib.tp_vec_set(h.ctx, vid, a.ctypes.data_as(C.POINTER(C.c_double))))
+
+
+def raw_get(h, vid):
+    out = np.empty((h.b, h.n[2] + 2, h.n[1], h.n[0]))
+    h._ck(h.lib.tp_vec_get(h.ctx, vid, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def with_junk(rng, owned, h):
+    """Owned values inside, NaN in the halo planes: a reduction that reads a halo cell returns NaN."""
+    a = np.full((h.b, h.n[2] + 2, h.n[1], h.n[0]), np.nan)
+    a[:, 1:-1] = owned
+    return a
+
+
+def exact_dot(a, b):
+    ld = np.longdouble
+    return float(np.sum(a.astype(ld)*b.astype(ld))), float(np.sum(np.abs(a.astype(ld)*b.astype(ld))))
+
+
+@pytest.mark.parametrize("grid,nphase,tail", GRIDS, ids=["tail%s" % (t if t is not None else "_4297waves") for _, _, t in GRIDS])
+def test_reductions_against_exact_sums(grid, nphase, tail):
+    h = raw_engine(grid, nphase)
+    nown = grid[0]*grid[1]*grid[2]
+    if tail is not None:
+        assert (h.b*nown) % 512 == tail
+    else:
+        assert h.b*nown > 4096*512
+    rng = np.random.default_rng(nown)
+    shape = (h.b, h.n[2], h.n[1], h.n[0])
+    w = rng.standard_normal(shape)*np.exp(rng.uniform(-3, 3, shape))
+    wid = h.vec("w")
+    sizes = [1, 3, 4, 5, 8, 9] + ([1100] if tail == 0 else [])
+    if tail is None:
+        sizes = [1, 5, 9]
+    nmax = max(sizes)
+    first = h.vec_batch("v", nmax)
+    V = []
+    for i in range(nmax):
+        vi = rng.standard_normal(shape) if i < 16 else rng.integers(-8, 9, shape).astype(float)
+        V.append(vi)
+        raw_set(h, first + i, with_junk(rng, vi, h))
+    raw_set(h, wid, with_junk(rng, w, h))
+    for n in sizes:
+        out = np.zeros(n)
+        h._ck(h.lib.tp_vec_dot_batch(h.ctx, first, n, wid, out.ctypes.data_as(C.POINTER(C.c_double))))
+        for i in range(n):
+            ex, mag = exact_dot(V[i], w)
+            assert abs(out[i] - ex) <= 1e-14*mag, (grid, n, i, out[i], ex)
+    # ||w||: the same two-stage sum with the w2 = w output
+    nrm = C.c_double()
+    h._ck(h.lib.tp_vec_norm2(h.ctx, wid, C.byref(nrm)))
+    ex = math.sqrt(exact_dot(w, w)[0])
+    assert abs(nrm.value - ex) <= 1e-14*ex
+    # w += sum_i c_i v_i on dyadic data (every product and partial sum exact in float64): the result is exact
+    iw = rng.integers(-2**20, 2**20, shape).astype(float)*2.0**-10
+    for n in sizes:
+        coef = rng.integers(-2**10, 2**10, n).astype(float)*2.0**-6
+        Vd = [np.round(V[i]*2**12)*2.0**-12 for i in range(n)]
+        for i in range(n):
+            raw_set(h, first + i, with_junk(rng, Vd[i], h))
+        before = with_junk(rng, iw, h)
+        raw_set(h, wid, before)
+        h._ck(h.lib.tp_vec_axpy_batch(h.ctx, first, n, coef.ctypes.data_as(C.POINTER(C.c_double)), wid))
+        after = raw_get(h, wid)
+        ld = np.longdouble
+        ex = iw.astype(ld) + sum(ld(coef[i])*Vd[i].astype(ld) for i in range(n))
+        ulp = np.spacing(np.abs(ex.astype(float)))
+        assert np.all(np.abs(after[:, 1:-1].astype(ld) - ex) <= 2*ulp), (grid, n)
+        # halo planes untouched (still the NaN junk)
+        assert np.isnan(after[:, 0]).all() and np.isnan(after[:, -1]).all()
+    h.close()

@@ -306,3 +306,58 @@ def test_slab_emulation_keeps_iteration_counts():
     for nits, lits, u in res[1:]:
         assert nits == res[0][0] and abs(lits - res[0][1]) <= max(3, 0.15*res[0][1])
         assert np.linalg.norm(u[0] - res[0][2][0])/np.linalg.norm(res[0][2][0]) < 1e-8
+
+
+# ---- FGMRES paths beyond "converges within one cycle": restarts, the iteration limit, a zero right-hand side.  The GPU
+# Krylov tests (tests/test_gpu_krylov.py) compare against this function on exactly these paths.
+def _linear_case(builder, kw, opts, dt=4000.0):
+    spec, o = setup_case(builder=builder, opts=opts, **kw)
+    o.set_dt(dt)
+    schur = opts["pc"] in ("cptr", "fieldsplit_cd")
+    out = o.jacobian(want_schur=schur)
+    J, Sm = out if schur else (out, None)
+    o.pc.setup(J, Sm)
+    return o, J, o.residual()
+
+
+def true_residual_norm(J, F, x):
+    """||F - J x||_2 evaluated in extended precision (np.longdouble)."""
+    ld = np.longdouble
+    r = F.astype(ld) - la.spmv_block(J.astype(ld), x.astype(ld))
+    return float(np.sqrt(np.sum(r*r)))
+
+
+@pytest.mark.parametrize("restart", [1, 2, 5, 40])
+def test_fgmres_restarted_converges_to_direct_solution(restart):
+    # 2-D two-phase cptr: FGMRES(1) still converges here (it stalls on the 3-D cases), in several cycles for restart < 12
+    o, J, F = _linear_case(cases.c3_spe10_2d, dict(Nx=10, Ny=12, nphase=2), dict(pc="cptr"), dt=8640.0)
+    mv = lambda v: la.spmv_block(J, v)
+    x, its, reason, hist = la.fgmres(mv, o.pc.apply, F, rtol=1e-10, restart=restart, maxit=300)
+    assert reason == 2 and len(hist) == its + 1
+    if restart < 5:
+        assert its > restart                   # more than one cycle ran
+    xd = spla.spsolve(la.to_csr(J).tocsc(), flat(F))
+    assert np.linalg.norm(flat(x) - xd)/np.linalg.norm(xd) < 1e-6
+    # the restart recomputes the true residual, so the final recurrence norm is the true one up to round-off
+    assert true_residual_norm(J, F, x) <= 2e-10*np.linalg.norm(F)
+    assert hist[-1] <= 1e-10*np.linalg.norm(F)
+
+
+@pytest.mark.parametrize("maxit,restart", [(1, 200), (2, 200), (7, 200), (7, 3)])
+def test_fgmres_iteration_limit_returns_partial_solution(maxit, restart):
+    o, J, F = _linear_case(cases.c4_spe10_3d, dict(Nx=5, Ny=6, Nz=4, nphase=2), dict(pc="cptr"))
+    mv = lambda v: la.spmv_block(J, v)
+    _, its_full, reason_full, _ = la.fgmres(mv, o.pc.apply, F, rtol=1e-10, maxit=200)
+    assert reason_full == 2 and its_full > maxit            # the limit is below what the case needs
+    x, its, reason, hist = la.fgmres(mv, o.pc.apply, F, rtol=1e-10, restart=restart, maxit=maxit)
+    assert reason == -3 and its == maxit and len(hist) == maxit + 1
+    bn = np.linalg.norm(F)
+    assert abs(hist[-1] - true_residual_norm(J, F, x)) <= 1e-10*bn
+    assert 0.0 < hist[-1] < bn
+
+
+def test_fgmres_zero_rhs():
+    o, J, F = _linear_case(cases.c4_spe10_3d, dict(Nx=5, Ny=6, Nz=4, nphase=2), dict(pc="cptr"))
+    x, its, reason, hist = la.fgmres(lambda v: la.spmv_block(J, v), o.pc.apply, np.zeros_like(F))
+    assert (its, reason) == (0, 2) and hist == [0.0]
+    assert x.shape == F.shape and not np.any(x)

@@ -38,11 +38,14 @@ void vec_axpy_owned(tp_ctx *c, int nf, double a, const double *x, double *y) {
     hipLaunchKernelGGL(k_axpy_owned<true>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, a, x, y);
 }
 // x[f][c] *= 1 / sqrt(*n2) over owned cells: v_{j+1} = w / ||w|| with the norm still on the device (the same IEEE operations
-// as the host's 1.0 / sqrt(n2) followed by vec_scale_to: bit-identical)
-__global__ void k_scale_dev_norm(GridDev g, int nf, const double *__restrict__ n2, double *x) {
+// as the host's 1.0 / sqrt(n2) followed by vec_scale_to: bit-identical).  The pipelined FGMRES loop issues this before the
+// host has seen n2: a zero (happy breakdown) or non-finite norm scales by 0 instead of inf/NaN, so that the speculative
+// pc_apply and SpMV that follow -- discarded in that case -- run on finite data
+__global__ void k_scale_dev_norm(GridDev g, int nf, const double *__restrict__ n2p, double *x) {
     const long t = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
     if (t >= g.nown * nf) return;
-    const double a = 1.0 / sqrt(*n2);
+    const double n2 = *n2p;
+    const double a = (n2 > 0.0 && isfinite(n2)) ? 1.0 / sqrt(n2) : 0.0;
     const long f = t / g.nown, i = t - f * g.nown;
     const long c = f * g.ntot + g.np + i;
     x[c] = a * x[c];
