@@ -44,8 +44,6 @@ struct StencilT {
     __host__ __device__ const R *slot(int s) const { return base + (long)s * slot_stride; }
 };
 
-static inline dim3 grid_for(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
-
 __device__ __forceinline__ void cell_ijk(const GridDev &g, long tid, int &i0, int &i1, int &i2) {
     // 32-bit unsigned divisions (every slab has fewer than 2^31 cells, tp_create): a 64-bit division is ~150 instructions on
     // this ISA, and the few-thousand-cell levels of a V-cycle are bound by exactly that kind of per-cell index arithmetic
@@ -55,12 +53,6 @@ __device__ __forceinline__ void cell_ijk(const GridDev &g, long tid, int &i0, in
     i1 = (int)q1;
     i0 = (int)(rem - q1 * n0);
 }
-
-// Multi-GPU: along the slab axis (2) the C points are the even GLOBAL planes, so a slab that starts on an odd
-// plane is shifted by one; its F neighbours / C parents across the slab boundary live in the halo planes.
-__device__ __forceinline__ int par_of(const GridDev &gf, int a) { return a == 2 ? (gf.off2 & 1) : 0; }
-__device__ __forceinline__ bool open_lo(const GridDev &g, int a) { return a == 2 && g.nb_lo; }
-__device__ __forceinline__ bool open_hi(const GridDev &g, int a) { return a == 2 && g.nb_hi; }
 
 // ---- set-up kernels --------------------------------------------------------------------------------
 // interpolation weights of every cell w.r.t. axis a (only odd cells are used) + invd = omega/diag
@@ -775,37 +767,82 @@ __global__ __launch_bounds__(1024) void k_amg_tail(const LevelDevT<R> *lv, int l
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-static std::vector<int> schedule(const int n_[3], const double strength[3], int min_cells) {
-    int n[3] = {n_[0], n_[1], n_[2]};
-    double s[3];
-    for (int a = 0; a < 3; ++a) s[a] = n[a] > 1 ? strength[a] : -1.0;
-    std::vector<int> sched;
-    while ((long)n[0] * n[1] * n[2] > min_cells && sched.size() < 40) {
-        int best = -1;
-        for (int a = 0; a < 3; ++a)
-            if (n[a] > 1 && (best < 0 || s[a] > s[best])) best = a;
-        if (best < 0) break;
-        sched.push_back(best);
-        n[best] = (n[best] + 1) / 2;
-        for (int q = 0; q < 3; ++q) s[q] = (q == best) ? s[q] * 0.5 : s[q] * 2.0;
+std::vector<std::pair<int, int>> rank_slabs(const tp_ctx *c) {
+    std::vector<std::pair<int, int>> slabs(c->dist ? c->grid.nranks : 0);
+    for (size_t r = 0; r < slabs.size(); ++r) slab_of(c, (int)r, slabs[r].first, slabs[r].second);
+    return slabs;
+}
+
+// g0: the grid the hierarchy coarsens -- the slab itself on one GPU, the GLOBAL grid on several.  There the top
+// levels (more than gather_cells cells, at least two planes on every rank) stay distributed over the slabs
+// and the rest of the hierarchy is built on the gathered global grid, replicated on every rank; a problem
+// smaller than gather_cells is replicated from the top (dist_levels = 0: its V-cycle is launch-latency
+// bound and would only get slower with a halo exchange between sweeps).
+AmgPlan amg_plan(const GridDev &g0, const double strength[3], const tp_options &o, int me,
+                 const std::vector<std::pair<int, int>> &slabs, long gather_cells, long tail_cells) {
+    AmgPlan P;
+    int m[3] = {g0.n0, g0.n1, g0.n2};
+    {   // schedule: coarsen the axis of the strongest coupling, which halves its strength and doubles the others'
+        int n[3] = {m[0], m[1], m[2]};
+        double s[3];
+        for (int a = 0; a < 3; ++a) s[a] = n[a] > 1 ? strength[a] : -1.0;
+        while ((long)n[0] * n[1] * n[2] > std::max(1, o.amg_min_cells) && P.sched.size() < 40) {
+            int best = -1;
+            for (int a = 0; a < 3; ++a)
+                if (n[a] > 1 && (best < 0 || s[a] > s[best])) best = a;
+            if (best < 0) break;
+            P.sched.push_back(best);
+            n[best] = (n[best] + 1) / 2;
+            for (int q = 0; q < 3; ++q) s[q] = (q == best) ? s[q] * 0.5 : s[q] * 2.0;
+        }
     }
-    return sched;
+    std::vector<std::pair<int, int>> cur = slabs;          // owned global planes of every rank at the current level
+    if (cur.empty()) cur = {{0, m[2]}};
+    bool still = !slabs.empty() && gather_cells >= 0;
+    const int nu = std::max(1, o.amg_nu);
+    for (size_t l = 0; l <= P.sched.size(); ++l) {
+        AmgPlan::Level L;
+        if (still) {
+            int minp = 1 << 30;
+            for (auto &q : cur) minp = std::min(minp, q.second - q.first);
+            still = (long)m[0] * m[1] * m[2] > gather_cells && minp >= 2 && l < P.sched.size();
+            if (still) P.dist_levels = (int)l + 1;
+        }
+        P.ranges.push_back(cur);
+        // a distributed level is this rank's slab of the level (live halo planes towards the neighbours);
+        // every other level is the whole box with dead halo planes
+        L.g = still ? make_grid(m[0], m[1], cur[me].second - cur[me].first, m[2], cur[me].first)
+                    : make_grid(m[0], m[1], m[2], m[2], 0);
+        // cycle shape: V(nu,nu) on the first levels, V(coarse_pre, coarse_post) below, and V(coarse_pre, tail_post) on
+        // the levels of <= 1024 cells (a property of the level size, so that the oracle can mirror it)
+        const bool full = (int)l < o.amg_full_levels;
+        const bool small = L.g.np * (long)L.g.gn2 <= 1024;
+        L.pre = full ? nu : std::max(0, o.amg_coarse_pre);
+        L.post = full ? nu : std::max(1, small ? o.amg_tail_post : o.amg_coarse_post);
+        // mid levels (neither full nor small): every second one is a pure transfer level -- the hierarchy then coarsens
+        // two directions per smoothing level there, which costs no Krylov iterations (454 -> 456 on C4) and lets the
+        // cycle fuse the two transfers
+        if (o.amg_mid_skip && !full && !small && (((int)l - o.amg_full_levels) & 1)) { L.pre = 0; L.post = 0; }
+        if (l < P.sched.size()) {
+            L.axis = P.sched[l];
+            m[L.axis] = (m[L.axis] + 1) / 2;
+            if (L.axis == 2)
+                for (auto &q : cur) q = {(q.first + 1) / 2, (q.second + 1) / 2};     // even global planes survive
+        }
+        P.lv.push_back(L);
+    }
+    P.tail_level = (int)P.lv.size() - 1;
+    for (size_t l = (size_t)P.dist_levels; l < P.lv.size(); ++l)
+        if (P.lv[l].g.nown <= tail_cells) { P.tail_level = (int)l; break; }
+    return P;
 }
 
 template <class R>
-static LevelDevT<R> dev_of(const AmgLevel *L, int level, const tp_options &o) {
+static LevelDevT<R> dev_of(const Amg *amg, int level) {
+    const AmgLevel *L = amg->lv[level];
     LevelDevT<R> d;
-    const int nu = std::max(1, o.amg_nu);
-    const bool full = level < o.amg_full_levels;
-    // cycle shape: V(nu,nu) on the first levels, V(coarse_pre, coarse_post) below, and V(coarse_pre, tail_post) on
-    // the levels of <= 1024 cells (a property of the level size, so that the oracle can mirror it)
-    const bool small = L->g.np * (long)L->g.gn2 <= 1024;
-    d.pre = full ? nu : std::max(0, o.amg_coarse_pre);
-    d.post = full ? nu : std::max(1, small ? o.amg_tail_post : o.amg_coarse_post);
-    // mid levels (neither full nor small): every second one is a pure transfer level -- the hierarchy then coarsens
-    // two directions per smoothing level there, which costs no Krylov iterations (454 -> 456 on C4) and lets the
-    // cycle fuse the two transfers
-    if (o.amg_mid_skip && !full && !small && ((level - o.amg_full_levels) & 1)) { d.pre = 0; d.post = 0; }
+    d.pre = amg->plan.lv[level].pre;
+    d.post = amg->plan.lv[level].post;
     d.pad_ = 0;
     d.g = L->g;
     d.op.base = (R *)L->op.base;
@@ -816,46 +853,17 @@ static LevelDevT<R> dev_of(const AmgLevel *L, int level, const tp_options &o) {
     return d;
 }
 
-// g0: the grid the hierarchy coarsens -- the slab itself on one GPU, the GLOBAL grid on several.  There the top
-// levels (more than amg_gather_cells cells, at least two planes on every rank) stay distributed over the slabs
-// and the rest of the hierarchy is built on the gathered global grid, replicated on every rank; a problem
-// smaller than amg_gather_cells is replicated from the top (dist_levels = 0: its V-cycle is launch-latency
-// bound and would only get slower with a halo exchange between sweeps).
-void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]) {
+void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3], long gather_cells) {
     delete amg;
     amg = new Amg();
     c->graph_epoch++;            // a new hierarchy may reuse the old one's addresses: never replay graphs across a rebuild
     amg->single = c->opt.amg_single != 0;
-    const int n[3] = {g0.n0, g0.n1, g0.n2};
-    amg->sched = schedule(n, strength, std::max(1, c->opt.amg_min_cells));
-    const int nranks = c->dist ? c->grid.nranks : 1, me = c->dist ? c->grid.rank : 0;
-    std::vector<std::pair<int, int>> cur(nranks);          // owned global planes of every rank at the current level
-    for (int r = 0; r < nranks; ++r) {
-        if (c->dist) slab_of(c, r, cur[r].first, cur[r].second);
-        else cur[r] = {0, n[2]};
-    }
-    const long gather_cells = c->gather_override != -2 ? c->gather_override : (long)c->opt.amg_gather_cells;
-    bool still = c->dist && gather_cells >= 0;
-    int m[3] = {n[0], n[1], n[2]};
-    for (size_t l = 0; l <= amg->sched.size(); ++l) {
+    const long tail_cells = getenv("TP_AMG_TAIL_CELLS") ? atol(getenv("TP_AMG_TAIL_CELLS")) : 1024;
+    amg->plan = amg_plan(g0, strength, c->opt, c->dist ? c->grid.rank : 0, rank_slabs(c), gather_cells, tail_cells);
+    for (const AmgPlan::Level &P : amg->plan.lv) {
         AmgLevel *L = new AmgLevel();
-        if (still) {
-            int minp = 1 << 30;
-            for (auto &q : cur) minp = std::min(minp, q.second - q.first);
-            still = (long)m[0] * m[1] * m[2] > gather_cells && minp >= 2 && l < amg->sched.size();
-            if (still) amg->dist_levels = (int)l + 1;
-        }
-        amg->ranges.push_back(cur);
-        // a distributed level is this rank's slab of the level (live halo planes towards the neighbours);
-        // every other level is the whole box with dead halo planes
-        L->g = still ? make_grid(m[0], m[1], cur[me].second - cur[me].first, m[2], cur[me].first)
-                     : make_grid(m[0], m[1], m[2], m[2], 0);
-        if (l < amg->sched.size()) {
-            L->axis = amg->sched[l];
-            m[L->axis] = (m[L->axis] + 1) / 2;
-            if (L->axis == 2)
-                for (auto &q : cur) q = {(q.first + 1) / 2, (q.second + 1) / 2};     // even global planes survive
-        }
+        L->g = P.g;
+        L->axis = P.axis;
         amg->lv.push_back(L);
     }
     // carve every level's buffers out of one arena (32-double = 256-byte aligned slices)
@@ -889,19 +897,14 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
     TP_HIP(hipHostMalloc((void **)&amg->ratio_host, 64 * 8 * sizeof(double)));
     TP_HIP(hipEventCreateWithFlags(&amg->ev_ratio, hipEventDisableTiming));
     amg->coarse_inv.alloc((size_t)2 * amg->ncoarse * amg->ncoarse);
-    // first level handled by the single-workgroup tail kernel
-    const long tail_cells = getenv("TP_AMG_TAIL_CELLS") ? atol(getenv("TP_AMG_TAIL_CELLS")) : 1024;
     amg->fuse_below = getenv("TP_AMG_FUSE_BELOW") ? atol(getenv("TP_AMG_FUSE_BELOW")) : 200000;
-    amg->tail_level = (int)amg->lv.size() - 1;
-    for (size_t l = (size_t)amg->dist_levels; l < amg->lv.size(); ++l)
-        if (amg->lv[l]->g.nown <= tail_cells) { amg->tail_level = (int)l; break; }
     amg->lvdev.alloc(amg->lv.size() * sizeof(LevelDevT<double>));
     // the tail keeps its vectors (b, e, x, x2 of every level) in LDS when they fit next to the level descriptors
     long tot = 0;
-    for (size_t l = (size_t)amg->tail_level; l < amg->lv.size(); ++l) tot += amg->lv[l]->g.ntot;
+    for (size_t l = (size_t)amg->plan.tail_level; l < amg->lv.size(); ++l) tot += amg->lv[l]->g.ntot;
     const bool lds_on = !(getenv("TP_AMG_TAIL_LDS") && atoi(getenv("TP_AMG_TAIL_LDS")) == 0);
     amg->tail_lds = (lds_on && 4 * tot * (long)sizeof(double) <= 120 * 1024) ? (int)tot : 0;
-    if (getenv("TP_DEBUG")) fprintf(stderr, "[tp] amg tail: level %d of %zu, %ld doubles per vector set, lds %d\n", amg->tail_level, amg->lv.size(), tot, amg->tail_lds);
+    if (getenv("TP_DEBUG")) fprintf(stderr, "[tp] amg tail: level %d of %zu, %ld doubles per vector set, lds %d\n", amg->plan.tail_level, amg->lv.size(), tot, amg->tail_lds);
     if (amg->tail_lds > 0) {
         const int bytes = 120 * 1024;      // per-function limit shared by every hierarchy: always the maximum
         TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_amg_tail<double>),
@@ -909,24 +912,6 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
         TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_amg_tail<float>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     }
-}
-
-// level l+1 as its parent level l sees it.  Below the last distributed level that is this rank's planes of the
-// global (replicated) arrays -- pointer arithmetic, no copy: plane 0 of the view is the lower halo.
-struct CoarseView {
-    GridDev g;
-    long off;          // element offset of the view inside the level's arrays
-    long slot_stride;  // operator slot stride of the level's arrays
-};
-static CoarseView coarse_view(const tp_ctx *c, const Amg *amg, int l) {
-    const AmgLevel *Lc = amg->lv[l + 1];
-    CoarseView v;
-    v.slot_stride = Lc->g.ntot;
-    if (l + 1 < amg->dist_levels || l >= amg->dist_levels) { v.g = Lc->g; v.off = 0; return v; }
-    const auto &q = amg->ranges[l + 1][c->grid.rank];
-    v.g = make_grid(Lc->g.n0, Lc->g.n1, q.second - q.first, Lc->g.n2, q.first);
-    v.off = Lc->g.np * q.first;
-    return v;
 }
 
 // level-0 operator: double stencil view of the Jacobian -> storage type R
@@ -942,7 +927,7 @@ __global__ void k_amg_import(GridDev g, Stencil A0, R *out) {
 template <class R>
 static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     AmgLevel *L0 = amg->lv[0];
-    const int lg = amg->dist_levels;
+    const int lg = amg->plan.dist_levels;
     if (sizeof(R) == sizeof(double)) {
         L0->op = A0;                     // zero-copy view of the Jacobian planes
     } else {
@@ -970,11 +955,11 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
         }
         if (L->axis >= 0) {
             AmgLevel *Lc = amg->lv[l + 1];
-            const CoarseView cv = coarse_view(c, amg, (int)l);
+            const AmgPlan::View cv = amg->plan.coarse_view((int)l, c->grid.rank);
             hipLaunchKernelGGL(k_amg_coarsen<R>, grid_for(cv.g.nown), dim3(256), 0, c->stream, L->g, cv.g, op, L->axis,
-                               (const R *)L->wm.p, (const R *)L->wp.p, (R *)Lc->A.p + cv.off, cv.slot_stride);
+                               (const R *)L->wm.p, (const R *)L->wp.p, (R *)Lc->A.p + cv.off, Lc->g.ntot);
             if ((int)l + 1 == lg)        // first replicated level: everybody gets everybody's rows
-                gather_ranges(c, Lc->A.p, Lc->g.np, amg->ranges[lg], 7, (size_t)Lc->g.ntot * sizeof(R), sizeof(R));
+                gather_ranges(c, Lc->A.p, Lc->g.np, amg->plan.ranges[lg], 7, (size_t)Lc->g.ntot * sizeof(R), sizeof(R));
         }
     }
     AmgLevel *Lc = amg->lv.back();
@@ -1002,7 +987,7 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
                            amg->coarse_inv.p + (size_t)n * n);
     amg->dense_done = true;
     std::vector<LevelDevT<R>> h;
-    for (size_t l = 0; l < amg->lv.size(); ++l) h.push_back(dev_of<R>(amg->lv[l], (int)l, c->opt));
+    for (size_t l = 0; l < amg->lv.size(); ++l) h.push_back(dev_of<R>(amg, (int)l));
     amg->lvhost.assign((const char *)h.data(), (const char *)h.data() + h.size() * sizeof(LevelDevT<R>));
     TP_HIP(hipMemcpyAsync(amg->lvdev.p, amg->lvhost.data(), amg->lvhost.size(), hipMemcpyHostToDevice, c->stream));
     if (nratio > 0) {
@@ -1047,7 +1032,7 @@ void amg_setup(tp_ctx *c, Amg *amg, const Stencil &A0) {
 // grid, every rank computing the same thing.  (b's halo planes are overwritten by the exchange.)
 template <class R>
 static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
-    const int nlev = (int)amg->lv.size(), lt = amg->tail_level, lg = amg->dist_levels;
+    const int nlev = (int)amg->lv.size(), lt = amg->plan.tail_level, lg = amg->plan.dist_levels;
     const int trunc = amg->trunc;               // >= 0: that level ends the cycle with two Jacobi sweeps (amg_dom_tau)
     const int ltop = (trunc >= 0 && trunc < lt) ? trunc : lt;      // big levels [0, ltop) run their normal down/up sweeps
     const dim3 bl(256);
@@ -1057,7 +1042,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     auto paired = [&](int l) {
         if (!pair_on || l < lg || l + 2 > lt || amg->lv[l]->g.nown >= amg->fuse_below) return false;
         if (trunc >= 0 && l + 2 > trunc) return false;          // (the truncation level is among the V(nu,nu) levels: never paired)
-        const LevelDevT<R> A = dev_of<R>(amg->lv[l], l, c->opt), B = dev_of<R>(amg->lv[l + 1], l + 1, c->opt);
+        const AmgPlan::Level &A = amg->plan.lv[l], &B = amg->plan.lv[l + 1];
         return A.pre == 0 && A.post >= 1 && B.pre == 0 && B.post == 0;
     };
     auto hx = [&](int l, const double *v) {        // halo exchange of a level-l vector (no-op below lg)
@@ -1067,8 +1052,8 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     for (int l = 0; l < ltop; ++l) {
         AmgLevel *L = amg->lv[l];
         AmgLevel *Lc = amg->lv[l + 1];
-        const LevelDevT<R> Ld = dev_of<R>(L, l, c->opt);
-        const CoarseView cv = coarse_view(c, amg, l);
+        const LevelDevT<R> Ld = dev_of<R>(amg, l);
+        const AmgPlan::View cv = amg->plan.coarse_view(l, c->grid.rank);
         const double *bl_ = (l == 0) ? b : L->b.p;
         double *bc = Lc->b.p + cv.off;
         const dim3 gr = xcd_grid(L->g.nown);
@@ -1076,7 +1061,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         if (paired(l)) {
             AmgLevel *L2 = amg->lv[l + 2];
             hipLaunchKernelGGL(k_amg_restrict2<R>, xcd_grid(L2->g.nown), bl, 0, c->stream, Ld,
-                               dev_of<R>(amg->lv[l + 1], l + 1, c->opt), L2->g, bl_, L2->b.p);
+                               dev_of<R>(amg, l + 1), L2->g, bl_, L2->b.p);
             ++l;                                    // level l+1 has nothing else to do on the way down
             continue;
         }
@@ -1104,7 +1089,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             }
         }
         if (l + 1 == lg)        // restricted residual of every slab -> the replicated levels' right-hand side
-            gather_ranges(c, Lc->b.p, Lc->g.np, amg->ranges[lg], 1, 0, sizeof(double));
+            gather_ranges(c, Lc->b.p, Lc->g.np, amg->plan.ranges[lg], 1, 0, sizeof(double));
     }
     if (trunc >= 0 && trunc < lt) {
         // relaxation-only big level: x = x1 + invd (b - A x1), x1 = invd b (the fused double sweep), nothing below it
@@ -1112,7 +1097,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         const double *bt = (trunc == 0) ? b : L->b.p;
         double *et = (trunc == 0) ? x : L->e.p;
         hx(trunc, bt);                              // the fused double sweep reads invd*b of the neighbours
-        hipLaunchKernelGGL(k_amg_pre<R>, xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(L, trunc, c->opt), bt, 1, et);
+        hipLaunchKernelGGL(k_amg_pre<R>, xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, trunc), bt, 1, et);
     } else {
         // the tail: every level from lt down to the coarsest (or the truncation level) and back, one launch
         AmgLevel *Lt = amg->lv[lt];
@@ -1127,8 +1112,8 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     for (int l = ltop - 1; l >= 0; --l) {
         AmgLevel *L = amg->lv[l];
         AmgLevel *Lc = amg->lv[l + 1];
-        const LevelDevT<R> Ld = dev_of<R>(L, l, c->opt);
-        const CoarseView cv = coarse_view(c, amg, l);
+        const LevelDevT<R> Ld = dev_of<R>(amg, l);
+        const AmgPlan::View cv = amg->plan.coarse_view(l, c->grid.rank);
         const double *bl_ = (l == 0) ? b : L->b.p;
         double *out = (l == 0) ? x : L->e.p;
         const double *ec = Lc->e.p + cv.off;
@@ -1138,7 +1123,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         if (l >= 1 && paired(l - 1)) continue;      // transfer-only level folded into its parent's launch
         if (paired(l)) {
             AmgLevel *L2 = amg->lv[l + 2];
-            hipLaunchKernelGGL(k_amg_prolong2_jacobi<R>, gr, bl, 0, c->stream, Ld, dev_of<R>(Lc, l + 1, c->opt), L2->g, bl_,
+            hipLaunchKernelGGL(k_amg_prolong2_jacobi<R>, gr, bl, 0, c->stream, Ld, dev_of<R>(amg, l + 1), L2->g, bl_,
                                (const double *)L2->e.p, dst);
             for (int k = 1; k < Ld.post; ++k) {
                 src = dst;

@@ -24,39 +24,6 @@
 
 namespace tp {
 
-struct BAmgLevel {
-    GridDev g;
-    DBuf<double> A;            // 7*NB*NB planes (levels >= 1; level 0 views the Jacobian / decoupled operator)
-    BStencil op;
-    DBuf<double> invD;         // NB*NB planes: omega * inverse of the diagonal block
-    DBuf<double> wm, wp;       // NB planes each
-    DBuf<double> b, x, x2, r, e;
-    int axis = -1;
-    int pre = 0, post = 0;
-};
-
-struct BAmg {
-    int nb = 2;
-    std::vector<BAmgLevel *> lv;
-    std::vector<int> sched;
-    DBuf<double> dense;        // [M | Minv] of the coarsest grid, (nb*ncoarse)^2 each
-    int ncoarse = 0;
-    int dist_levels = 0;       // levels [0, dist_levels) are this rank's slab of the level; the rest global + replicated
-    int tail_level = 0;        // first level of the single-workgroup tail kernel (k_bamg_tail)
-    long fuse_below = 0;       // replicated levels with fewer cells fuse prolongation + first post-sweep
-    DBuf<char> lvdev;          // device array of BTailLevel descriptors
-    std::vector<char> lvhost;
-    std::vector<std::vector<std::pair<int, int>>> ranges;   // [level][rank] -> owned global planes along axis 2
-    ~BAmg() { for (auto *l : lv) delete l; }
-};
-
-// slab parity / open ends along the slab axis (as in tp_amg.hip)
-__device__ __forceinline__ int b_par(const GridDev &gf, int a) { return a == 2 ? (gf.off2 & 1) : 0; }
-__device__ __forceinline__ bool b_open_lo(const GridDev &g, int a) { return a == 2 && g.nb_lo; }
-__device__ __forceinline__ bool b_open_hi(const GridDev &g, int a) { return a == 2 && g.nb_hi; }
-
-static inline dim3 grid_for(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
-
 template <int NB>
 struct BLevelDev {
     GridDev g;
@@ -119,11 +86,11 @@ __global__ void k_bamg_coarsen(BLevelDev<NB> L, GridDev gc, BStencil Ac) {
     b_ijk(gc, tid, I[0], I[1], I[2]);
     const long cc = gc.np + tid;
     int F[3] = {I[0], I[1], I[2]};
-    F[a] = 2 * I[a] + b_par(gf, a);
+    F[a] = 2 * I[a] + par_of(gf, a);
     const int nfa = a == 0 ? gf.n0 : (a == 1 ? gf.n1 : gf.n2);
     const long stride = a == 0 ? 1 : (a == 1 ? gf.n0 : gf.np);
     const long f = gf.np + (long)F[0] + (long)gf.n0 * F[1] + gf.np * F[2];
-    const bool hm = F[a] - 1 >= 0 || b_open_lo(gf, a), hp = F[a] + 1 < nfa || b_open_hi(gf, a);
+    const bool hm = F[a] - 1 >= 0 || open_lo(gf, a), hp = F[a] + 1 < nfa || open_hi(gf, a);
     const long gm = hm ? f - stride : f, gp = hp ? f + stride : f;
     const long ntf = gf.ntot;
 #pragma unroll
@@ -362,11 +329,11 @@ __global__ __launch_bounds__(256) void k_bamg_restrict(BLevelDev<NB> Lf, GridDev
     int I[3];
     b_ijk(gc, tid, I[0], I[1], I[2]);
     int F[3] = {I[0], I[1], I[2]};
-    F[a] = 2 * I[a] + b_par(gf, a);
+    F[a] = 2 * I[a] + par_of(gf, a);
     const int nfa = a == 0 ? gf.n0 : (a == 1 ? gf.n1 : gf.n2);
     const long stride = a == 0 ? 1 : (a == 1 ? gf.n0 : gf.np);
     const long f = gf.np + (long)F[0] + (long)gf.n0 * F[1] + gf.np * F[2];
-    const bool hm = F[a] - 1 >= 0 || b_open_lo(gf, a), hp = F[a] + 1 < nfa || b_open_hi(gf, a);
+    const bool hm = F[a] - 1 >= 0 || open_lo(gf, a), hp = F[a] + 1 < nfa || open_hi(gf, a);
     const long fm = hm ? f - stride : f, fp = hp ? f + stride : f;
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
@@ -388,7 +355,7 @@ __global__ __launch_bounds__(256) void k_bamg_prolong(BLevelDev<NB> Lf, GridDev 
     const int a = Lf.axis;
     int i[3];
     b_ijk(g, tid, i[0], i[1], i[2]);
-    const int p = b_par(g, a);
+    const int p = par_of(g, a);
     const int Fa = i[a], Ia = (Fa - p) >> 1;          // (Fa - p may be -1: the C parent below the slab, in the halo plane)
     int I[3] = {i[0], i[1], i[2]};
     I[a] = Ia;
@@ -396,7 +363,7 @@ __global__ __launch_bounds__(256) void k_bamg_prolong(BLevelDev<NB> Lf, GridDev 
     const long cs = a == 0 ? 1 : (a == 1 ? gc.n0 : gc.np);
     const int nca = a == 0 ? gc.n0 : (a == 1 ? gc.n1 : gc.n2);
     const long c = g.np + tid;
-    const bool isF = (Fa + p) & 1, hasR = isF && (Ia + 1 < nca || b_open_hi(gc, a));
+    const bool isF = (Fa + p) & 1, hasR = isF && (Ia + 1 < nca || open_hi(gc, a));
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
         const double e0 = ec[(long)q * cstride + ci], e1 = ec[(long)q * cstride + (hasR ? ci + cs : ci)];
@@ -464,7 +431,7 @@ __device__ __forceinline__ void b_prolong_val(const BLevelDev<NB> &Lf, const Gri
                                               long cstride, int F0, int F1, int F2, double (&v)[NB]) {
     const GridDev &g = Lf.g;
     const int a = Lf.axis;
-    const int p = b_par(g, a);
+    const int p = par_of(g, a);
     const int Fa = a == 0 ? F0 : (a == 1 ? F1 : F2);
     const int Ia = (Fa - p) >> 1;
     const bool isF = (Fa + p) & 1;
@@ -473,7 +440,7 @@ __device__ __forceinline__ void b_prolong_val(const BLevelDev<NB> &Lf, const Gri
     const long cf = g.np + (long)F0 + (long)g.n0 * F1 + g.np * F2;
     const long cs = a == 0 ? 1 : (a == 1 ? gc.n0 : gc.np);
     const int nca = a == 0 ? gc.n0 : (a == 1 ? gc.n1 : gc.n2);
-    const bool hasR = isF && (Ia + 1 < nca || b_open_hi(gc, a));
+    const bool hasR = isF && (Ia + 1 < nca || open_hi(gc, a));
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
         const double wm = Lf.wm[(long)q * g.ntot + cf], wp = Lf.wp[(long)q * g.ntot + cf];
@@ -546,11 +513,11 @@ __device__ __forceinline__ void b_restrict_cell(const BLevelDev<NB> &Lf, const G
     int I[3];
     b_ijk(gc, tidc, I[0], I[1], I[2]);
     int F[3] = {I[0], I[1], I[2]};
-    F[a] = 2 * I[a] + b_par(gf, a);
+    F[a] = 2 * I[a] + par_of(gf, a);
     const int nfa = a == 0 ? gf.n0 : (a == 1 ? gf.n1 : gf.n2);
     const long stride = a == 0 ? 1 : (a == 1 ? gf.n0 : gf.np);
     const long f = gf.np + (long)F[0] + (long)gf.n0 * F[1] + gf.np * F[2];
-    const bool hm = F[a] - 1 >= 0 || b_open_lo(gf, a), hp = F[a] + 1 < nfa || b_open_hi(gf, a);
+    const bool hm = F[a] - 1 >= 0 || open_lo(gf, a), hp = F[a] + 1 < nfa || open_hi(gf, a);
     const long fm = hm ? f - stride : f, fp = hp ? f + stride : f;
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
@@ -747,41 +714,14 @@ void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[
     amg = new BAmg();
     c->graph_epoch++;
     const int NB = amg->nb;
-    int n[3] = {g0.n0, g0.n1, g0.n2};
-    double s[3];
-    for (int a = 0; a < 3; ++a) s[a] = n[a] > 1 ? strength[a] : -1.0;
-    while ((long)n[0] * n[1] * n[2] > std::max(1, c->opt.amg_min_cells) && amg->sched.size() < 40) {
-        int best = -1;
-        for (int a = 0; a < 3; ++a)
-            if (n[a] > 1 && (best < 0 || s[a] > s[best])) best = a;
-        if (best < 0) break;
-        amg->sched.push_back(best);
-        n[best] = (n[best] + 1) / 2;
-        for (int q = 0; q < 3; ++q) s[q] = (q == best) ? s[q] * 0.5 : s[q] * 2.0;
-    }
-    int m[3] = {g0.n0, g0.n1, g0.n2};
-    const int nu = std::max(1, c->opt.amg_nu);
-    // multi-GPU: the rule of tp_amg.hip:amg_build -- a level stays on the slabs while it has more than amg_gather_cells
-    // cells and every rank owns at least two of its planes
-    const int nranks = c->dist ? c->grid.nranks : 1, me = c->dist ? c->grid.rank : 0;
-    std::vector<std::pair<int, int>> cur(nranks);
-    for (int r = 0; r < nranks; ++r) {
-        if (c->dist) slab_of(c, r, cur[r].first, cur[r].second);
-        else cur[r] = {0, m[2]};
-    }
-    const long gather_cells = c->opt.amg_gather_cells;
-    bool still = c->dist && gather_cells >= 0;
-    for (size_t l = 0; l <= amg->sched.size(); ++l) {
+    // first level of the single-workgroup tail; replicated levels below fuse_below cells fuse prolongation + first post-sweep
+    const long tail_cells = getenv("TP_BAMG_TAIL_CELLS") ? atol(getenv("TP_BAMG_TAIL_CELLS")) : 1024;
+    amg->fuse_below = getenv("TP_BAMG_FUSE_BELOW") ? atol(getenv("TP_BAMG_FUSE_BELOW")) : 200000;
+    amg->plan = amg_plan(g0, strength, c->opt, c->dist ? c->grid.rank : 0, rank_slabs(c), c->opt.amg_gather_cells, tail_cells);
+    for (size_t l = 0; l < amg->plan.lv.size(); ++l) {
+        const AmgPlan::Level &P = amg->plan.lv[l];
         BAmgLevel *L = new BAmgLevel();
-        if (still) {
-            int minp = 1 << 30;
-            for (auto &q : cur) minp = std::min(minp, q.second - q.first);
-            still = (long)m[0] * m[1] * m[2] > gather_cells && minp >= 2 && l < amg->sched.size();
-            if (still) amg->dist_levels = (int)l + 1;
-        }
-        amg->ranges.push_back(cur);
-        L->g = still ? make_grid(m[0], m[1], cur[me].second - cur[me].first, m[2], cur[me].first)
-                     : make_grid(m[0], m[1], m[2], m[2], 0);
+        L->g = P.g; L->axis = P.axis; L->pre = P.pre; L->post = P.post;
         const size_t nt = (size_t)L->g.ntot;
         if (l > 0) {
             L->A.alloc(7 * NB * NB * nt);
@@ -789,28 +729,10 @@ void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[
         }
         L->invD.alloc(NB * NB * nt);
         L->b.alloc(NB * nt); L->x.alloc(NB * nt); L->x2.alloc(NB * nt); L->r.alloc(NB * nt); L->e.alloc(NB * nt);
-        // cycle shape: the rules of tp_amg.hip:dev_of (mirrored by oracle/linalg.py)
-        const bool full = (int)l < c->opt.amg_full_levels;
-        const bool small = L->g.np * (long)L->g.gn2 <= 1024;
-        L->pre = full ? nu : std::max(0, c->opt.amg_coarse_pre);
-        L->post = full ? nu : std::max(1, small ? c->opt.amg_tail_post : c->opt.amg_coarse_post);
-        if (c->opt.amg_mid_skip && !full && !small && (((int)l - c->opt.amg_full_levels) & 1)) { L->pre = 0; L->post = 0; }
-        if (l < amg->sched.size()) {
-            L->axis = amg->sched[l];
-            L->wm.alloc(NB * nt); L->wp.alloc(NB * nt);
-            m[L->axis] = (m[L->axis] + 1) / 2;
-            if (L->axis == 2)
-                for (auto &q : cur) q = {(q.first + 1) / 2, (q.second + 1) / 2};     // even global planes survive
-        }
+        if (L->axis >= 0) { L->wm.alloc(NB * nt); L->wp.alloc(NB * nt); }
         amg->lv.push_back(L);
     }
-    // first level of the single-workgroup tail; replicated levels below fuse_below cells fuse prolongation + first post-sweep
-    const long tail_cells = getenv("TP_BAMG_TAIL_CELLS") ? atol(getenv("TP_BAMG_TAIL_CELLS")) : 1024;
-    amg->fuse_below = getenv("TP_BAMG_FUSE_BELOW") ? atol(getenv("TP_BAMG_FUSE_BELOW")) : 200000;
-    amg->tail_level = (int)amg->lv.size() - 1;
-    for (size_t l = (size_t)amg->dist_levels; l < amg->lv.size(); ++l)
-        if (amg->lv[l]->g.nown <= tail_cells) { amg->tail_level = (int)l; break; }
-    TP_REQUIRE((int)amg->lv.size() - amg->tail_level <= 24, "system-AMG tail has too many levels");
+    TP_REQUIRE((int)amg->lv.size() - amg->plan.tail_level <= 24, "system-AMG tail has too many levels");
     amg->lvdev.alloc(amg->lv.size() * sizeof(BTailLevel<2>));
     amg->ncoarse = (int)amg->lv.back()->g.nown;
     TP_REQUIRE(amg->ncoarse * NB <= 2048, "coarsest system-AMG grid too large for the dense solve");
@@ -818,24 +740,11 @@ void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[
     amg->dense.alloc(2 * nd * nd);
 }
 
-// level l+1 as its parent level l sees it: below the last distributed level that is this rank's planes of the global
-// (replicated) arrays -- plane 0 of the view is the lower halo (tp_amg.hip:coarse_view)
-struct BCoarseView { GridDev g; long off; };
-static BCoarseView bcoarse_view(const tp_ctx *c, const BAmg *amg, int l) {
-    const BAmgLevel *Lc = amg->lv[l + 1];
-    BCoarseView v;
-    if (l + 1 < amg->dist_levels || l >= amg->dist_levels) { v.g = Lc->g; v.off = 0; return v; }
-    const auto &q = amg->ranges[l + 1][c->grid.rank];
-    v.g = make_grid(Lc->g.n0, Lc->g.n1, q.second - q.first, Lc->g.n2, q.first);
-    v.off = Lc->g.np * q.first;
-    return v;
-}
-
 void bamg_setup(tp_ctx *c, BAmg *amg, const BStencil &A0) {
     constexpr int NB = 2;
     TP_REQUIRE(amg->nb == NB, "system AMG is built for 2x2 blocks");
     amg->lv[0]->op = A0;
-    const int lg = amg->dist_levels;
+    const int lg = amg->plan.dist_levels;
     for (size_t l = 0; l < amg->lv.size(); ++l) {
         BAmgLevel *L = amg->lv[l];
         const BLevelDev<NB> Ld = bdev<NB>(L);
@@ -854,12 +763,12 @@ void bamg_setup(tp_ctx *c, BAmg *amg, const BStencil &A0) {
         }
         if (L->axis >= 0) {
             BAmgLevel *Lc = amg->lv[l + 1];
-            const BCoarseView cv = bcoarse_view(c, amg, (int)l);
+            const AmgPlan::View cv = amg->plan.coarse_view((int)l, c->grid.rank);
             BStencil Ac = Lc->op;
             Ac.base += cv.off;
             hipLaunchKernelGGL(k_bamg_coarsen<NB>, grid_for(cv.g.nown), dim3(256), 0, c->stream, Ld, cv.g, Ac);
             if ((int)l + 1 == lg)        // first replicated level: everybody gets everybody's rows
-                gather_ranges(c, Lc->A.p, Lc->g.np, amg->ranges[lg], 7 * NB * NB, (size_t)Lc->g.ntot * sizeof(double), sizeof(double));
+                gather_ranges(c, Lc->A.p, Lc->g.np, amg->plan.ranges[lg], 7 * NB * NB, (size_t)Lc->g.ntot * sizeof(double), sizeof(double));
         }
     }
     {
@@ -893,11 +802,11 @@ void bamg_setup(tp_ctx *c, BAmg *amg, const BStencil &A0) {
 // x = V-cycle(b): b, x are NB planes with the stride of level 0 (= ntot of the grid the hierarchy was built on)
 void bamg_vcycle(tp_ctx *c, BAmg *amg, const double *b, double *x) {
     constexpr int NB = 2;
-    const int nlev = (int)amg->lv.size(), lt = amg->tail_level;
+    const int nlev = (int)amg->lv.size(), lt = amg->plan.tail_level;
     const dim3 bl(256);
     std::vector<double *> xs(nlev, nullptr);
     const size_t nd = (size_t)amg->ncoarse * NB;
-    const int lg = amg->dist_levels;
+    const int lg = amg->plan.dist_levels;
     auto hx = [&](int l, const double *v) {        // halo exchange of the NB planes of a level-l vector (no-op below lg)
         if (l < lg) halo_exchange(c, amg->lv[l]->g, const_cast<double *>(v), NB, amg->lv[l]->g.ntot);
     };
@@ -928,11 +837,11 @@ void bamg_vcycle(tp_ctx *c, BAmg *amg, const double *b, double *x) {
             res = L->r.p;
         }
         if (slab_axis) hx(l, res);
-        const BCoarseView cv = bcoarse_view(c, amg, l);
+        const AmgPlan::View cv = amg->plan.coarse_view(l, c->grid.rank);
         hipLaunchKernelGGL(k_bamg_restrict<NB>, xcd_grid(cv.g.nown), bl, 0, c->stream, Ld, cv.g, res, Lc->b.p + cv.off,
                            (long)Lc->g.ntot);
         if (l + 1 == lg)        // restricted residual of every slab -> the replicated levels' right-hand side
-            gather_ranges(c, Lc->b.p, Lc->g.np, amg->ranges[lg], NB, (size_t)Lc->g.ntot * sizeof(double), sizeof(double));
+            gather_ranges(c, Lc->b.p, Lc->g.np, amg->plan.ranges[lg], NB, (size_t)Lc->g.ntot * sizeof(double), sizeof(double));
     }
     {   // the tail: every level from lt down to the dense solve and back, one launch
         BAmgLevel *Lt = amg->lv[lt];
@@ -949,7 +858,7 @@ void bamg_vcycle(tp_ctx *c, BAmg *amg, const double *b, double *x) {
         double *out = (l == 0) ? x : L->e.p;
         const dim3 gr = xcd_grid(L->g.nown);
         hx(l + 1, Lc->e.p);                         // distributed coarse level: parents across the boundary
-        const BCoarseView cv = bcoarse_view(c, amg, l);
+        const AmgPlan::View cv = amg->plan.coarse_view(l, c->grid.rank);
         const double *ec = Lc->e.p + cv.off;
         double *src;
         int k0 = 0;
@@ -976,11 +885,5 @@ void bamg_vcycle(tp_ctx *c, BAmg *amg, const double *b, double *x) {
     }
     TP_HIP(hipGetLastError());
 }
-
-void bamg_destroy(BAmg *amg) { delete amg; }
-
-int bamg_levels(const BAmg *amg) { return (int)amg->lv.size(); }
-int bamg_dist_levels(const BAmg *amg) { return amg ? amg->dist_levels : 0; }
-const std::vector<int> &bamg_sched(const BAmg *amg) { return amg->sched; }
 
 }  // namespace tp

@@ -246,7 +246,7 @@ tp_ctx::~tp_ctx() {
     for (auto *v : vecs) delete v;
     delete amg_p;
     delete amg_T;
-    if (bamg) tp::bamg_destroy(bamg);
+    delete bamg;
     for (auto &gph : pc_graphs) (void)hipGraphExecDestroy(gph.exec);
     for (auto &pr : pc_programs)
         for (auto &st : pr.steps)
@@ -379,7 +379,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     if (tile_changed) c->ilu.slots = 0;
     if (amg_changed) {
         delete c->amg_p; c->amg_p = nullptr; delete c->amg_T; c->amg_T = nullptr;
-        if (c->bamg) { bamg_destroy(c->bamg); c->bamg = nullptr; }
+        if (c->bamg) { delete c->bamg; c->bamg = nullptr; }
     }
     if (schur_of(*opt) && c->Sm.n == 0) c->Sm.alloc((size_t)7 * c->g.ntot);
     c->pc_ready = false;
@@ -467,7 +467,7 @@ int tp_finalize_fields(tp_ctx *c) {
     c->fields_ready = true;
     delete c->amg_p; c->amg_p = nullptr;
     delete c->amg_T; c->amg_T = nullptr;
-    if (c->bamg) { bamg_destroy(c->bamg); c->bamg = nullptr; }
+    if (c->bamg) { delete c->bamg; c->bamg = nullptr; }
     c->pc_ready = false;
     c->graph_epoch++;
     TP_API_END
@@ -775,7 +775,7 @@ int tp_amg_vcycle(tp_ctx *c, int32_t which, int32_t field_b, int32_t b, int32_t 
     Amg *amg = which == 0 ? c->amg_p : c->amg_T;
     TP_REQUIRE(amg, "this AMG hierarchy does not exist for the selected preconditioner");
     resolve_cycle_shapes(c);
-    TP_REQUIRE(!c->dist || amg->dist_levels > 0, "tp_amg_vcycle works on slab vectors: not available when the hierarchy is replicated on the gathered global grid");
+    TP_REQUIRE(!c->dist || amg->plan.dist_levels > 0, "tp_amg_vcycle works on slab vectors: not available when the hierarchy is replicated on the gathered global grid");
     TP_REQUIRE(field_b >= 0 && field_b < c->b && field_x >= 0 && field_x < c->b, "bad field index");
     TP_REQUIRE(!(b == x && field_b == field_x), "b and x must differ");
     amg_vcycle(c, amg, vec_of(c, b).p + (long)field_b * c->g.ntot, vec_of(c, x).p + (long)field_x * c->g.ntot);
@@ -786,7 +786,7 @@ int tp_schur_apply(tp_ctx *c, int32_t x, int32_t y) {
     TP_API_BEGIN
     TP_REQUIRE(c->pc_ready && c->amg_T, "S~ AMG not set up (pc_cptr only)");
     resolve_cycle_shapes(c);
-    TP_REQUIRE(!c->dist || c->amg_T->dist_levels > 0, "tp_schur_apply works on slab vectors: not available when the hierarchy is replicated on the gathered global grid");
+    TP_REQUIRE(!c->dist || c->amg_T->plan.dist_levels > 0, "tp_schur_apply works on slab vectors: not available when the hierarchy is replicated on the gathered global grid");
     TP_REQUIRE(x != y, "x and y must differ");
     amg_vcycle(c, c->amg_T, vec_of(c, x).p + c->g.ntot, vec_of(c, y).p + c->g.ntot);
     TP_API_END
@@ -826,7 +826,7 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
             case 2:
                 resolve_cycle_shapes(c);
                 if (sysamg_of(c->opt)) { TP_REQUIRE(!c->dist, "single slab only"); bamg_vcycle(c, c->bamg, c->R.p, c->w2.p); break; }
-                if (c->dist && c->amg_p->dist_levels == 0) amg_vcycle(c, c->amg_p, c->gvec.p, c->gvec.p + 2 * c->gfull.ntot);   // global-grid buffers
+                if (c->dist && c->amg_p->plan.dist_levels == 0) amg_vcycle(c, c->amg_p, c->gvec.p, c->gvec.p + 2 * c->gfull.ntot);   // global-grid buffers
                 else amg_vcycle(c, c->amg_p, c->R.p, c->w2.p);
                 break;
             case 3: assemble(c, true, schur_of(c->opt)); break;
@@ -853,25 +853,29 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
     TP_API_END
 }
 
-int tp_amg_info(tp_ctx *c, int32_t which, int32_t *nlevels, double *op_complexity) {
-    TP_API_BEGIN
+// layout of hierarchy `which`: 0 pressure, 1 temperature / Schur, 2 the (p,T) system hierarchy of pc_cptramg
+static const AmgPlan &plan_of(tp_ctx *c, int which) {
     if (which == 2) {
         TP_REQUIRE(c->bamg, "system AMG hierarchy not built");
-        if (nlevels) *nlevels = bamg_levels(c->bamg);
-        if (op_complexity) *op_complexity = 0.0;
-        return 0;
+        return c->bamg->plan;
     }
     Amg *amg = which == 0 ? c->amg_p : c->amg_T;
     TP_REQUIRE(amg, "AMG hierarchy not built");
-    if (nlevels) *nlevels = (int)amg->lv.size();
+    return amg->plan;
+}
+
+int tp_amg_info(tp_ctx *c, int32_t which, int32_t *nlevels, double *op_complexity) {
+    TP_API_BEGIN
+    const AmgPlan &P = plan_of(c, which);
+    if (nlevels) *nlevels = (int)P.lv.size();
     double s = 0.0, s0 = 0.0;       // global cells per level (a distributed level holds this rank's slab only)
-    for (size_t l = 0; l < amg->lv.size(); ++l) {
-        const GridDev &g = amg->lv[l]->g;
+    for (size_t l = 0; l < P.lv.size(); ++l) {
+        const GridDev &g = P.lv[l].g;
         const double cells = (double)g.np * g.gn2;
         s += cells;
         if (l == 0) s0 = cells;
     }
-    if (op_complexity) *op_complexity = s / s0;
+    if (op_complexity) *op_complexity = which == 2 ? 0.0 : s / s0;
     TP_API_END
 }
 
@@ -887,19 +891,10 @@ int tp_amg_trunc(tp_ctx *c, int32_t which, int32_t *level, double *ratio0) {
 
 int tp_amg_layout(tp_ctx *c, int32_t which, int32_t *dist_levels, int32_t *axes, int32_t cap, int32_t *naxes) {
     TP_API_BEGIN
-    if (which == 2) {       // the (p,T) system hierarchy of pc_cptramg
-        TP_REQUIRE(c->bamg, "system AMG hierarchy not built");
-        const std::vector<int> &sc = bamg_sched(c->bamg);
-        if (dist_levels) *dist_levels = bamg_dist_levels(c->bamg);
-        if (naxes) *naxes = (int)sc.size();
-        for (int i = 0; axes && i < cap && i < (int)sc.size(); ++i) axes[i] = sc[i];
-        return 0;
-    }
-    Amg *amg = which == 0 ? c->amg_p : c->amg_T;
-    TP_REQUIRE(amg, "AMG hierarchy not built");
-    if (dist_levels) *dist_levels = amg->dist_levels;
-    if (naxes) *naxes = (int)amg->sched.size();
-    for (int i = 0; axes && i < cap && i < (int)amg->sched.size(); ++i) axes[i] = amg->sched[i];
+    const AmgPlan &P = plan_of(c, which);
+    if (dist_levels) *dist_levels = P.dist_levels;
+    if (naxes) *naxes = (int)P.sched.size();
+    for (int i = 0; axes && i < cap && i < (int)P.sched.size(); ++i) axes[i] = P.sched[i];
     TP_API_END
 }
 

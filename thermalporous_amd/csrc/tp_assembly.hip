@@ -557,7 +557,6 @@ __global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *
 }
 
 // ------------------------------------------------------------------------------------------------
-static inline dim3 grid_for(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 void compute_trans(tp_ctx *c) {
     const GridDev &g = c->g;

@@ -68,11 +68,17 @@ __device__ __forceinline__ long xcd_tid() {
     const unsigned rb = (b & 7u) * (nb >> 3) + (b >> 3);
     return (long)rb * TP_BLOCK + threadIdx.x;
 }
+// Multi-GPU AMG (tp_amg.hip, tp_amg_block.hip): along the slab axis (2) the C points are the even GLOBAL planes, so a slab that
+// starts on an odd plane is shifted by one; its F neighbours / C parents across the slab boundary live in the halo planes.
+__device__ __forceinline__ int par_of(const GridDev &gf, int a) { return a == 2 ? (gf.off2 & 1) : 0; }
+__device__ __forceinline__ bool open_lo(const GridDev &g, int a) { return a == 2 && g.nb_lo; }
+__device__ __forceinline__ bool open_hi(const GridDev &g, int a) { return a == 2 && g.nb_hi; }
 #endif
 inline dim3 xcd_grid(long n, int bs = 256) {
     const long nb = (n + bs - 1) / bs;
     return dim3((unsigned)(((nb + 7) / 8) * 8));
 }
+inline dim3 grid_for(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // pc_kind: 0 pc_cpr, 1 pc_cptr, 2 pc_fieldsplit_cd, 3 pc_cptramg.  1 and 2 run the fieldsplit-Schur-FULL stage on
 // (p,T) and need the S~ operator from the assembly; 3 runs ONE system-AMG V-cycle on the 2x2-block (p,T) operator.
@@ -95,7 +101,6 @@ struct BStencil {
     __host__ __device__ const double *at(int s, int q, int r) const { return base + s * ss + q * rs + r * cs; }
     __host__ __device__ double *at(int s, int q, int r) { return base + s * ss + q * rs + r * cs; }
 };
-struct BAmg;
 
 // Derived closure constants (device copy of tp_params + precomputed factors).
 struct DevPrm {
@@ -138,17 +143,48 @@ struct DBuf {
     DBuf &operator=(const DBuf &) = delete;
 };
 
+// Layout of one semicoarsening hierarchy, shared by the scalar (tp_amg.hip) and the system (tp_amg_block.hip) AMG: pure host-side
+// integer logic, built once by amg_plan (tp_amg.hip), mirrored by oracle/linalg.py and reported by tp_amg_layout.  Every option it
+// is derived from is in tp_set_options' amg_changed list, which deletes the hierarchies: a plan never outlives its options.
+struct AmgPlan {
+    struct Level {
+        GridDev g;             // levels [0, dist_levels): this rank's slab of the level; below: the whole box, dead halo planes
+        int axis = -1;         // coarsening axis towards the next level (-1: coarsest)
+        int pre = 0, post = 0; // smoothing sweeps V(pre, post); post == 0: pure transfer level
+    };
+    std::vector<int> sched;    // axis of every coarsening step
+    std::vector<Level> lv;     // sched.size() + 1 levels
+    // multi-GPU: levels [0, dist_levels) live on this rank's slab (halo exchanges between sweeps), the levels
+    // below on the gathered global grid, replicated on every rank.  0 = the whole hierarchy is replicated.
+    int dist_levels = 0;
+    int tail_level = 0;        // first level handled by the single-workgroup tail kernel
+    std::vector<std::vector<std::pair<int, int>>> ranges;   // [level][rank] -> owned global planes along axis 2
+    // level l+1 as its parent level l sees it.  Below the last distributed level that is `rank`'s planes of the global
+    // (replicated) arrays -- pointer arithmetic, no copy: plane 0 of the view is the lower halo.
+    struct View {
+        GridDev g;
+        long off;              // element offset of the view inside the level's arrays
+    };
+    View coarse_view(int l, int rank) const {
+        const GridDev &gc = lv[l + 1].g;
+        if (l + 1 < dist_levels || l >= dist_levels) return {gc, 0};
+        const auto &q = ranges[l + 1][rank];
+        return {make_grid(gc.n0, gc.n1, q.second - q.first, gc.n2, q.first), gc.np * q.first};
+    }
+};
+
 struct AmgLevel {
-    GridDev g;
+    GridDev g;                 // (copies of the plan's, filled by amg_build)
     DBuf<double> A;        // 7 planes (levels >= 1); level 0 uses an external stencil view
     Stencil op;
     DBuf<double> invd;     // omega / diag
     DBuf<double> wm, wp;   // interpolation weights of F points along `axis`
     DBuf<double> b, x, x2, r, e;
-    int axis = -1;         // coarsening axis towards the next level (-1: coarsest)
+    int axis = -1;
 };
 
 struct Amg {
+    AmgPlan plan;
     // one allocation for every buffer of every level: the coarse levels are tiny, and with one hipMalloc each
     // (~150 of them) every small kernel of the cycle starts with TLB misses on half a dozen scattered pages
     DBuf<double> arena;
@@ -156,13 +192,8 @@ struct Amg {
     DBuf<double> coarse_inv;   // dense inverse on the coarsest grid
     int ncoarse = 0;
     bool single = false;       // operators / weights / inverse diagonals stored in fp32
-    int tail_level = 0;        // first level handled by the single-workgroup tail kernel
     int tail_lds = 0;          // doubles per LDS-resident vector set of the tail (0: tail vectors stay in global memory)
     long fuse_below = 200000;  // levels with fewer cells use the fused (launch-saving) kernels
-    // multi-GPU: levels [0, dist_levels) live on this rank's slab (halo exchanges between sweeps), the levels
-    // below on the gathered global grid, replicated on every rank.  0 = the whole hierarchy is replicated.
-    int dist_levels = 0;
-    std::vector<std::vector<std::pair<int, int>>> ranges;   // [level][rank] -> owned global planes along axis 2
     // relaxation-only truncation (tp_options.amg_dom_tau): dominance ratios of the V(nu,nu) levels, measured by the set-up
     // kernels into 64 slots per level (spread atomics), copied to pinned host memory behind `ev_ratio`
     DBuf<double> ratio_dev;
@@ -174,12 +205,35 @@ struct Amg {
     double ratio0 = 0.0;
     DBuf<char> lvdev;          // device array of level descriptors (LevelDev) for the tail kernel
     std::vector<char> lvhost;
-    std::vector<int> sched;
     ~Amg() {
         for (auto *l : lv) delete l;
         if (ratio_host) (void)hipHostFree(ratio_host);
         if (ev_ratio) (void)hipEventDestroy(ev_ratio);
     }
+};
+
+// system AMG on the (p,T) blocks (tp_amg_block.hip)
+struct BAmgLevel {
+    GridDev g;                 // (copies of the plan's, filled by bamg_build)
+    DBuf<double> A;            // 7*NB*NB planes (levels >= 1; level 0 views the Jacobian / decoupled operator)
+    BStencil op;
+    DBuf<double> invD;         // NB*NB planes: omega * inverse of the diagonal block
+    DBuf<double> wm, wp;       // NB planes each
+    DBuf<double> b, x, x2, r, e;
+    int axis = -1;
+    int pre = 0, post = 0;
+};
+
+struct BAmg {
+    AmgPlan plan;
+    int nb = 2;
+    std::vector<BAmgLevel *> lv;
+    DBuf<double> dense;        // [M | Minv] of the coarsest grid, (nb*ncoarse)^2 each
+    int ncoarse = 0;
+    long fuse_below = 0;       // replicated levels with fewer cells fuse prolongation + first post-sweep
+    DBuf<char> lvdev;          // device array of BTailLevel descriptors
+    std::vector<char> lvhost;
+    ~BAmg() { for (auto *l : lv) delete l; }
 };
 
 struct IluData {
@@ -274,7 +328,6 @@ struct tp_ctx {
     static constexpr int H_PIN = 1024;   // doubles of pinned, device-mapped host memory the reductions write their results to
     double *h_pin = nullptr;
     hipEvent_t ev_h = nullptr;           // recorded behind the reductions of an orthogonalisation (pipelined FGMRES loop)
-    long gather_override = -2;     // != -2: replaces tp_options.amg_gather_cells in amg_build (selfp on several GPUs: 0)
     tp_ksp_monitor_fn monitor = nullptr;      // per-field true-residual monitor (ksp_monitor_residuals)
     void *monitor_user = nullptr;
     ~tp_ctx();
@@ -327,8 +380,12 @@ void ilu_setup(tp_ctx *c);
 void ilu_factor(tp_ctx *c);
 // x = addto + M^-1 r ; only the first nadd fields of addto are read, the others count as zero (< 0: all fields)
 void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int nadd = -1);
-// AMG
-void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]);
+// AMG.  slabs: each rank's owned global planes along axis 2 (rank_slabs; empty: not distributed); a level stays on the slabs
+// while it has more than gather_cells cells (< 0: never), the tail kernel starts at the first replicated level of <= tail_cells
+AmgPlan amg_plan(const GridDev &g0, const double strength[3], const tp_options &o, int me,
+                 const std::vector<std::pair<int, int>> &slabs, long gather_cells, long tail_cells);
+std::vector<std::pair<int, int>> rank_slabs(const tp_ctx *c);
+void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3], long gather_cells);
 void amg_setup(tp_ctx *c, Amg *amg, const Stencil &A0);
 void amg_vcycle(tp_ctx *c, Amg *amg, const double *b, double *x);
 bool amg_resolve_trunc(tp_ctx *c, Amg *amg);      // waits for the set-up's dominance ratios; true if the cycle shape changed
@@ -336,10 +393,6 @@ bool amg_resolve_trunc(tp_ctx *c, Amg *amg);      // waits for the set-up's domi
 void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[3]);
 void bamg_setup(tp_ctx *c, BAmg *amg, const BStencil &A0);
 void bamg_vcycle(tp_ctx *c, BAmg *amg, const double *b, double *x);     // b, x: 2 planes, stride = ntot of the grid
-void bamg_destroy(BAmg *amg);
-int bamg_levels(const BAmg *amg);
-int bamg_dist_levels(const BAmg *amg);
-const std::vector<int> &bamg_sched(const BAmg *amg);
 // comm
 void halo_exchange(tp_ctx *c, const GridDev &g, double *x, int nf, long fstride);
 void halo_exchange_raw(tp_ctx *c, const GridDev &g, void *x, int nf, size_t fstride_bytes, size_t elem_bytes);

@@ -7,7 +7,6 @@
 
 namespace tp {
 
-static inline dim3 grid_for(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // ---- elementwise ---------------------------------------------------------------------------------
 __global__ void k_zero(double *x, long n) {

@@ -94,7 +94,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
     BStencil A0;
     if (c->opt.decoup == 0) { A0.base = c->J.p; A0.ss = (long)c->b * c->b * nt; A0.rs = (long)c->b * nt; A0.cs = nt; }
     else { A0.base = c->At.p; A0.ss = 4 * nt; A0.rs = 2 * nt; A0.cs = nt; }
-    if (c->dist && bamg_dist_levels(c->bamg) == 0) {
+    if (c->dist && c->bamg->plan.dist_levels == 0) {
         // small grids: the hierarchy lives on the gathered global grid, replicated on every rank (as small scalar hierarchies
         // do); larger ones keep their top levels on the slabs (tp_amg_block.hip) and work on the slab operator directly
         const size_t ng = (size_t)c->gfull.ntot;
@@ -136,11 +136,11 @@ void pc_setup(tp_ctx *c) {
     const GridDev gam = c->dist ? c->gfull : make_grid(c->g.n0, c->g.n1, c->g.n2, c->g.n2, 0);
     // selfp on several GPUs works on slab vectors (its exact-Sp sweep needs the slab's own Jacobian rows): the hierarchies
     // keep every level with >= 2 planes per rank distributed, whatever amg_gather_cells says
-    c->gather_override = (c->dist && cptr && c->opt.schur_a11 == 2) ? 0 : -2;
+    const long gather_cells = (c->dist && cptr && c->opt.schur_a11 == 2) ? 0 : (long)c->opt.amg_gather_cells;
     if (!c->amg_p) {
         double st[3];
         face_strengths(c, st);         // coarsening schedule decided once; structure is static
-        amg_build(c, c->amg_p, gam, st);
+        amg_build(c, c->amg_p, gam, st, gather_cells);
         if (cptr) {
             double sg[3];
             const int n[3] = {gam.n0, gam.n1, gam.n2};
@@ -148,8 +148,8 @@ void pc_setup(tp_ctx *c) {
                 const double hh = c->grid.h[a];
                 sg[a] = n[a] > 1 ? c->vol / (hh * hh) : 0.0;
             }
-            amg_build(c, c->amg_T, gam, sg);
-            TP_REQUIRE((c->amg_p->dist_levels > 0) == (c->amg_T->dist_levels > 0), "stage-1 hierarchies disagree on distribution");
+            amg_build(c, c->amg_T, gam, sg, gather_cells);
+            TP_REQUIRE((c->amg_p->plan.dist_levels > 0) == (c->amg_T->plan.dist_levels > 0), "stage-1 hierarchies disagree on distribution");
         }
     }
     Stencil Sl;
@@ -160,7 +160,7 @@ void pc_setup(tp_ctx *c) {
     if (selfp) {
         // pc_fieldsplit_schur_precondition selfp (pc_fieldsplit_selfp, singlephase.py:322-330)
         TP_REQUIRE(c->opt.pc_kind == 2, "selfp is the single-phase pc_fieldsplit_selfp preset's Schur preconditioner");
-        TP_REQUIRE(!c->dist || c->amg_p->dist_levels > 0, "selfp on several GPUs needs slabs of at least two planes (its Schur "
+        TP_REQUIRE(!c->dist || c->amg_p->plan.dist_levels > 0, "selfp on several GPUs needs slabs of at least two planes (its Schur "
                    "sweep works on slab vectors; the replicated global-grid stage 1 has no exact-Sp sweep)");
         if (c->spbuf.n < (size_t)10 * c->g.ntot) c->spbuf.alloc((size_t)10 * c->g.ntot);
         Sl.base = c->spbuf.p;                  // S7, filled by selfp_build on the stream of the S set-up below
@@ -173,7 +173,7 @@ void pc_setup(tp_ctx *c) {
         if (c->opt.decoup == 0) Sl.base = c->J.p + (long)(c->b + 1) * c->g.ntot;
     }
     if (cptr && !selfp) TP_REQUIRE(Sl.base, "pc_cptr needs the S~ operator (assemble with want_schur)");
-    if (c->dist && c->amg_p->dist_levels == 0) {
+    if (c->dist && c->amg_p->plan.dist_levels == 0) {
         const size_t ng = (size_t)c->gfull.ntot;
         // every buffer is tested on its own size (an options switch cpr -> cptr, or cptr -> cptramg -> cptr, on a live
         // context must not find gvec shrunk or gA01/gA10/gSm missing because some OTHER buffer was already large enough)
@@ -260,7 +260,7 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
     }
     if (sysamg_of(c->opt)) {
         // pc_cptramg: y_pT = K(Atilde_00) r_pT, one V-cycle of the 2x2-block system AMG (r0, r1 are adjacent planes)
-        if (c->dist && bamg_dist_levels(c->bamg) == 0) {
+        if (c->dist && c->bamg->plan.dist_levels == 0) {
             const long ng = c->gfull.ntot;
             gather_slabs(c, r0, nt, c->gvec.p, ng, 2);
             bamg_vcycle(c, c->bamg, c->gvec.p, c->gvec.p + 2 * ng);
@@ -272,7 +272,7 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
         }
         return;
     }
-    if (c->dist && c->amg_p->dist_levels == 0) {
+    if (c->dist && c->amg_p->plan.dist_levels == 0) {
         // gathered global system: work vectors gr0, gr1, gy0, gy1, gt, gw on the global grid
         const GridDev &G = c->gfull;
         const long ng = G.ntot;
@@ -335,7 +335,7 @@ static void pc_apply_body(tp_ctx *c, const double *x, double *y) {
     const int npri = npri_of(c->opt);
     // (y's secondary fields are left untouched: the second stage below never reads them and overwrites them)
     stage1_apply(c, x, y, false);                 // multi-GPU, replicated stage 1: y comes back with live halo planes
-    if (c->dist && ((c->amg_p && c->amg_p->dist_levels > 0) || (sysamg_of(c->opt) && bamg_dist_levels(c->bamg) > 0)))
+    if (c->dist && ((c->amg_p && c->amg_p->plan.dist_levels > 0) || (sysamg_of(c->opt) && c->bamg && c->bamg->plan.dist_levels > 0)))
         halo_exchange(c, c->g, y, npri, c->g.ntot);       // (slab-distributed hierarchies return owned cells only)
     if (c->opt.pc_kind == 2) return;                          // pc_fieldsplit_cd: the Schur stage IS the preconditioner
     resid_block_cols(c, c->J.p, x, y, npri, c->w1.p);        // secondary fields of y are zero
