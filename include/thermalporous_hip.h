@@ -111,6 +111,20 @@ typedef struct tp_options {
                                 reference's `sub_1_pc_bjacobi_blocks: 1` (tests/test_homo_wells.py:112, pc_cptr_a11
                                 twophase.py:612): couplings between the tiles are kept; the tiles (ilu_t0 x ilu_t1 x ilu_t2,
                                 now only the unit of the sweep) are swept one tile-diagonal T0+T1+T2 per launch.  ILU(0) only. */
+    /* Inner solve of the stage-1 PRESSURE block K(A00) (pc_kind 0, 1, 2) or of the (p,T) SYSTEM block (pc_kind 3): what PETSc
+     * does when the sub-solver's ksp_type is not preonly.  The V-cycle becomes the (right) preconditioner of a small
+     * Krylov method whose every scalar stays on the device, so it lives inside the captured pc_apply graph:
+     *   s1_ksp 0 preonly     one V-cycle (the default; the launch sequence is unchanged)
+     *          1 richardson  s1_max_it V-cycles as a stationary iteration from x0 = 0: x <- x + V(r - A x)
+     *                        (pc_hypre_boomeramg_max_iter k, or ksp_type richardson + ksp_max_it k)
+     *          2 fgmres      right-preconditioned GMRES(s1_max_it) without restart, 1 <= s1_max_it <= 32
+     * Exactly s1_max_it iterations are always LAUNCHED; convergence (recurrence residual <= max(s1_rtol ||rhs||, s1_atol),
+     * or a happy breakdown) is latched on the device at iteration j*, and the result is the iterate GMRES returns when it
+     * stops at j*: the later iterations are wasted work, not different arithmetic.  The Schur / temperature solves stay one
+     * V-cycle.  Several GPUs: needs the replicated stage-1 hierarchy (amg_gather_cells < 0, or a grid small enough to be
+     * gathered); with slab-distributed top levels tp_pc_setup fails. */
+    int32_t s1_ksp, s1_max_it;
+    double  s1_rtol, s1_atol;
 } tp_options;
 
 /* Result of one nonlinear solve (SNES iteration number / linear iterations / reason:
@@ -205,6 +219,15 @@ int tp_amg_setup(tp_ctx *ctx, int32_t which);              /* v_cycle dict (sing
 /* which: 0 pressure hierarchy, 1 S~ hierarchy, 2 the (p,T) system hierarchy of pc_cptramg (fields 0,1 of b -> x) */
 int tp_amg_vcycle(tp_ctx *ctx, int32_t which, int32_t field_b, int32_t b, int32_t field_x, int32_t x);
 int tp_schur_apply(tp_ctx *ctx, int32_t x, int32_t y);     /* ConvDiffSchur*PC.apply: one V-cycle on S~, field 1 */
+
+/* Inner solves (s1_ksp != 0) since the last tp_pc_setup: how many ran, the sum of the iterations they USED (the latch
+ * iteration j* of each fgmres solve, s1_max_it per richardson solve), and how many fgmres solves ended at s1_max_it above
+ * their tolerance (with s1_rtol = s1_atol = 0 that is every one).  The counters live on the device, are updated by the
+ * inner solve's own kernels, and are copied out only by this call (one stream synchronisation).  All zero with preonly.
+ * They count every preconditioner application that was LAUNCHED: the pipelined FGMRES loop issues the next application
+ * before it knows whether the current iteration is the last, so a linear solve usually carries one application more
+ * than it has iterations (tp_solve_info.vcycles is corrected for those on the host; device counters cannot be). */
+int tp_inner_stats(tp_ctx *ctx, int64_t *applies, int64_t *its, int64_t *unconverged);
 
 /* Krylov / Newton (PETSc KSP fgmres + SNES newtonls in the reference: twophase.py:416-433, singlephase.py:289-301;
  * reasons use PETSc's numbering so that the host raises ConvergenceError where Firedrake does, thermalmodel.py:170) */

@@ -1,0 +1,436 @@
+"""Inner Krylov solve of the stage-1 pressure / (p,T) block on the GPU (tp_options.s1_ksp) against a reference composed from
+what the numpy oracle exports: oracle.linalg.fgmres (right-preconditioned GMRES, classical Gram-Schmidt, stop on the
+recurrence residual) with the oracle's own V-cycle as preconditioner, dropped into a copy of TwoStagePC.stage1 / apply.
+
+Tolerances: stage outputs rel2 < 1e-10 as in tests/test_gpu_parity.py (1e-9 at C4's true size); Krylov counts +-1; inner
+iteration counts equal on inputs whose reference residual history stays a factor 2 away from the tolerance."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import cases
+
+pytestmark = pytest.mark.gpu
+
+
+def rel2(a, b):
+    return np.linalg.norm((a - b).ravel())/max(np.linalg.norm(b.ravel()), 1e-300)
+
+
+class Composed:
+    """TwoStagePC of the oracle with K(A00) (pc cptramg: the system solve) replaced by an inner solve."""
+
+    def __init__(self, pc, ksp="preonly", k=1, rtol=0.0, atol=0.0):
+        import oracle.linalg as la
+        self.la, self.pc, self.ksp, self.k, self.rtol, self.atol = la, pc, ksp, k, rtol, atol
+        self.its, self.hists = [], []
+
+    def matvec(self, v):                       # (operators read at call time: the oracle's Newton loop sets the PC up again)
+        la, pc, o = self.la, self.pc, self.pc.o
+        if o["pc"] == "cptramg":
+            At = pc.At
+            return np.array([la.spmv_scalar(At[:, q, 0], v[0]) + la.spmv_scalar(At[:, q, 1], v[1]) for q in range(2)])
+        A00 = pc.At[:, 0, 0] if o["pc"] != "cpr" else la.decouple(pc.J, o["decoup"], [0])[0][:, 0, 0]
+        return la.spmv_scalar(A00, v)
+
+    def prec(self, r):
+        return (self.pc.amg_pT if self.pc.o["pc"] == "cptramg" else self.pc.amg_p).vcycle(r)
+
+    def K(self, r):
+        if self.ksp == "preonly":
+            return self.prec(r)
+        if self.ksp == "richardson":
+            x = self.prec(r)
+            for _ in range(self.k - 1):
+                x = x + self.prec(r - self.matvec(x))
+            self.its.append(self.k)
+            return x
+        x, its, reason, hist = self.la.fgmres(self.matvec, self.prec, r, rtol=self.rtol, atol=self.atol, restart=self.k, maxit=self.k)
+        self.its.append(its)
+        self.hists.append(hist)
+        return x
+
+    def stage1(self, x):                       # (oracle/linalg.py: TwoStagePC.stage1)
+        la, pc = self.la, self.pc
+        y = np.zeros_like(x)
+        o = pc.o
+        s = x.shape[0] - 1
+        if o["pc"] == "cpr":
+            if pc.d is None:
+                r = x[0]
+            elif o["decoup"] in ("QI_temp", "TI_temp"):
+                r = x[0] - pc.d[0][0]*x[1] - pc.d[0][1]*x[2]
+            else:
+                r = x[0] - pc.d[0]*x[s]
+            y[0] = self.K(r)
+        elif o["pc"] == "cptramg":
+            r0 = x[0] if pc.d is None else x[0] - pc.d[0]*x[s]
+            r1 = x[1] if pc.d is None else x[1] - pc.d[1]*x[s]
+            y[:2] = self.K(np.array([r0, r1]))
+        else:
+            r0 = x[0] if pc.d is None else x[0] - pc.d[0]*x[s]
+            r1 = x[1] if pc.d is None else x[1] - pc.d[1]*x[s]
+            At = pc.At
+            y0 = self.K(r0)
+            y1 = pc.amg_T.vcycle(r1 - la.spmv_scalar(At[:, 1, 0], y0))
+            y0 = self.K(r0 - la.spmv_scalar(At[:, 0, 1], y1))
+            y[0], y[1] = y0, y1
+        return y
+
+    def apply(self, x):                        # (TwoStagePC.apply)
+        y = self.stage1(x)
+        if self.pc.o["pc"] == "fieldsplit_cd":
+            return y
+        return y + self.pc.ilu.solve(x - self.la.spmv_block(self.pc.J, y))
+
+
+def make(builder, kw, opts, dt=8640.0, seed=5, amp=0.3):
+    """Oracle and GPU engine at the same perturbed state, Jacobians assembled, both preconditioners set up."""
+    from oracle.engine import OracleEngine
+    from thermalporous_amd.engine import HipEngine
+    spec, u0, *_ = builder(**kw)
+    o, h = OracleEngine(spec, opts), HipEngine(spec, opts)
+    u = cases.perturbed_state(spec, seed=seed, amp=amp)
+    for e in (o, h):
+        e.set_old(u0)
+        e.set_dt(dt)
+        e.set_state(u)
+    schur = opts["pc"] in ("cptr", "fieldsplit_cd")
+    out = o.jacobian(want_schur=schur)
+    J, Sm = out if schur else (out, None)
+    h.jacobian()
+    o.pc.setup(J, Sm)
+    h.pc_setup()
+    return spec, u0, u, o, h, J
+
+
+def inner(h, **kw):
+    """Switch the inner solve of a live engine (options invalidate the set-up)."""
+    h.set_options(**kw)
+    h.pc_setup()
+
+
+C1 = (cases.c1_homogeneous, dict(N=12, nphase=1))
+C3 = (cases.c3_spe10_2d, dict(Nx=14, Ny=19, nphase=2))
+C4 = (cases.c4_spe10_3d, dict(Nx=7, Ny=13, Nz=9, nphase=2))
+T2D = (1 << 30, 64, 1)
+PRESETS = [("c4_cpr", C4, dict(pc="cpr")), ("c4_cptr", C4, dict(pc="cptr")), ("c4_cptramg", C4, dict(pc="cptramg", decoup="QI"))]
+
+
+@pytest.mark.parametrize("name,case,opts", PRESETS, ids=[p[0] for p in PRESETS])
+def test_richardson_one_is_the_vcycle_bit_for_bit(name, case, opts):
+    spec, u0, u, o, h, J = make(case[0], case[1], opts)
+    x = np.random.default_rng(11).standard_normal(u.shape)
+    h.vec_set("x", x)
+    h.stage1_apply("x", "y")
+    h.pc_apply("x", "z")
+    s_pre, p_pre = h.vec_get("y"), h.vec_get("z")
+    assert h.inner_stats() == (0, 0, 0)
+    inner(h, s1_ksp="richardson", s1_max_it=1)
+    h.stage1_apply("x", "y")
+    h.pc_apply("x", "z")
+    assert np.array_equal(h.vec_get("y"), s_pre) and np.array_equal(h.vec_get("z"), p_pre)
+    napp = 2 if opts["pc"] == "cptr" else 1
+    assert h.inner_stats() == (2*napp, 2*napp, 0)
+    h.close()
+
+
+FIXED = [("c1_cpr_No", C1, dict(pc="cpr", ilu_tile=T2D)), ("c1_cpr_QI", C1, dict(pc="cpr", decoup="QI", ilu_tile=T2D)),
+         ("c3_cptr_No", C3, dict(pc="cptr", ilu_tile=T2D)), ("c3_cptr_QI", C3, dict(pc="cptr", decoup="QI", ilu_tile=T2D)),
+         ("c3_cptramg_QI", C3, dict(pc="cptramg", decoup="QI", ilu_tile=T2D)),
+         ("c4_cptr_No", C4, dict(pc="cptr")), ("c4_cpr_QI", C4, dict(pc="cpr", decoup="QI")), ("c4_cptr_QI", C4, dict(pc="cptr", decoup="QI")),
+         ("c4_cptramg_No", C4, dict(pc="cptramg")), ("c4_cptramg_QI", C4, dict(pc="cptramg", decoup="QI"))]
+
+
+@pytest.mark.parametrize("name,case,opts", FIXED, ids=[p[0] for p in FIXED])
+def test_fixed_count_gmres_matches_the_composed_reference(name, case, opts):
+    spec, u0, u, o, h, J = make(case[0], case[1], opts)
+    x = np.random.default_rng(11).standard_normal(u.shape)
+    h.vec_set("x", x)
+    for k in (1, 3, 8):
+        inner(h, s1_ksp="fgmres", s1_max_it=k, s1_rtol=0.0, s1_atol=0.0)
+        ref = Composed(o.pc, "fgmres", k)
+        h.stage1_apply("x", "y")
+        err = rel2(h.vec_get("y"), ref.stage1(x))
+        print("fixed count", name, "k =", k, "rel2 =", err)
+        assert err < 1e-10, (name, k, err)
+        a, its, unconv = h.inner_stats()
+        assert a == len(ref.its) and its == sum(ref.its) == k*a and unconv == a      # (tolerance 0: every solve ends at k above it)
+    for k in (2, 5):                         # the stationary iteration against the same composition
+        inner(h, s1_ksp="richardson", s1_max_it=k)
+        h.stage1_apply("x", "y")
+        err = rel2(h.vec_get("y"), Composed(o.pc, "richardson", k).stage1(x))
+        print("richardson", name, "k =", k, "rel2 =", err)
+        assert err < 1e-10, (name, k, err)
+    h.close()
+
+
+def test_fixed_count_gmres_at_c4_true_size():
+    """60x220x85, pc_cpr: GMRES(3) on the pressure block; the reference side sets up the pressure hierarchy only (the numpy
+    tiled ILU is not needed for stage 1)."""
+    import oracle.linalg as la
+    from oracle.engine import OracleEngine
+    from thermalporous_amd.engine import HipEngine
+    spec, u0, *_ = cases.c4_spe10_3d(Nx=60, Ny=220, Nz=85, nphase=2)
+    opts = dict(pc="cpr", s1_ksp="fgmres", s1_max_it=3)
+    o, h = OracleEngine(spec, dict(pc="cpr")), HipEngine(spec, opts)
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    for e in (o, h):
+        e.set_old(u0)
+        e.set_dt(8640.0)
+        e.set_state(u)
+    J = o.jacobian()
+    h.jacobian()
+    h.pc_setup()
+    A00 = np.ascontiguousarray(J[:, 0, 0])
+    o.pc.amg_p.setup(A00)
+    x = np.random.default_rng(11).standard_normal(u.shape)
+    ref, its, _, _ = la.fgmres(lambda v: la.spmv_scalar(A00, v), o.pc.amg_p.vcycle, x[0], rtol=0.0, atol=0.0, restart=3, maxit=3)
+    h.vec_set("x", x)
+    h.stage1_apply("x", "y")
+    y = h.vec_get("y")
+    err = rel2(y[0], ref)
+    print("fixed count c4 true size k = 3 rel2 =", err)
+    assert err < 1e-9 and its == 3
+    assert not y[1:].any()
+    assert h.inner_stats() == (1, 3, 1)
+    h.close()
+
+
+def _clear_of_tolerance(hist, tol):
+    return not any(tol/2 <= r <= 2*tol for r in hist[1:])
+
+
+@pytest.mark.parametrize("name,case,opts", [PRESETS[0], PRESETS[1], PRESETS[2]], ids=[p[0] for p in PRESETS])
+@pytest.mark.parametrize("rtol", [1e-2, 1e-6])
+def test_latch_stops_where_the_reference_stops(name, case, opts, rtol):
+    """dt = 0.05 s: the accumulation term dominates and the V-cycle gains two to three digits per inner iteration, so the
+    reference's residual history steps OVER the band [tol/2, 2 tol] (checked for all four seeds on the CPU: the reference
+    stops after 1 iteration at rtol 1e-2 and after 3 at 1e-6).  At the dt = 8640 s of the other tests it gains a factor 3 per
+    iteration and nearly every history has an entry inside the band."""
+    spec, u0, u, o, h, J = make(case[0], case[1], opts, dt=0.05)
+    inner(h, s1_ksp="fgmres", s1_max_it=16, s1_rtol=rtol)
+    for seed in (11, 12, 13, 14):
+        x = np.random.default_rng(seed).standard_normal(u.shape)
+        ref = Composed(o.pc, "fgmres", 16, rtol=rtol)
+        want = ref.stage1(x)
+        tols = [rtol*hh[0] for hh in ref.hists]
+        # (a history within a factor 2 of the tolerance could latch one apart for rounding alone: none of these does)
+        assert all(_clear_of_tolerance(hh, t) for hh, t in zip(ref.hists, tols)), (seed, ref.hists)
+        h.pc_setup()                        # restart the device counters
+        h.vec_set("x", x)
+        h.stage1_apply("x", "y")
+        err = rel2(h.vec_get("y"), want)
+        a, its, unconv = h.inner_stats()
+        print("latch", name, rtol, "seed", seed, "its", ref.its, "rel2 =", err)
+        assert (a, its, unconv) == (len(ref.its), sum(ref.its), 0), (ref.its, (a, its, unconv))
+        assert all(1 <= i < 16 for i in ref.its)
+        assert err < 1e-10, err
+    h.close()
+
+
+@pytest.mark.parametrize("jstar", [8, 10])
+def test_latch_in_the_middle_of_the_basis(jstar):
+    """The latch at j* = 8 and 10 of 16, behind the rotations of the later Hessenberg columns: dt = 8640 s, pc_cpr, where the
+    V-cycle gains a factor 2-5 per inner iteration.  The tolerance comes from the REFERENCE's fixed-count history: the
+    geometric mean of its entries j* - 1 and j*, which for this right-hand side are a factor > 4.3 apart (checked on the CPU:
+    4.31 and 4.79), so the history stays a factor 2 away from the tolerance on both sides."""
+    spec, u0, u, o, h, J = make(C4[0], C4[1], dict(pc="cpr"))
+    x = np.random.default_rng(12).standard_normal(u.shape)
+    free = Composed(o.pc, "fgmres", 16)
+    free.stage1(x)
+    hist = free.hists[0]
+    atol = float(np.sqrt(hist[jstar - 1]*hist[jstar]))
+    assert _clear_of_tolerance(hist, atol), [r/atol for r in hist]
+    ref = Composed(o.pc, "fgmres", 16, atol=atol)
+    want = ref.stage1(x)
+    assert ref.its == [jstar]
+    inner(h, s1_ksp="fgmres", s1_max_it=16, s1_rtol=0.0, s1_atol=atol)
+    h.vec_set("x", x)
+    h.stage1_apply("x", "y")
+    err = rel2(h.vec_get("y"), want)
+    print("latch mid-way j* =", jstar, "rel2 =", err, "stats", h.inner_stats())
+    assert h.inner_stats() == (1, jstar, 0)
+    assert err < 1e-10, err
+    h.close()
+
+
+def test_solved_to_tolerance():
+    spec, u0, u, o, h, J = make(C4[0], C4[1], dict(pc="cpr"))
+    inner(h, s1_ksp="fgmres", s1_max_it=32, s1_rtol=1e-10)
+    import oracle.linalg as la
+    A00 = J[:, 0, 0]
+    x = np.random.default_rng(11).standard_normal(u.shape)
+    ref = Composed(o.pc, "fgmres", 32, rtol=1e-10)
+    yo = ref.stage1(x)[0]
+    h.vec_set("x", x)
+    h.stage1_apply("x", "y")
+    yh = h.vec_get("y")[0]
+    true = lambda y: np.linalg.norm(x[0] - la.spmv_scalar(A00, y))/np.linalg.norm(x[0])
+    print("solved to tolerance: true residual gpu", true(yh), "reference", true(yo), "its", ref.its)
+    assert true(yh) <= 2*true(yo)
+    a, its, unconv = h.inner_stats()
+    assert unconv == 0 and a == 1 and abs(its - ref.its[0]) <= 1
+    h.close()
+
+
+def test_breakdown_zero_rhs_and_context_reuse():
+    from thermalporous_amd.engine import HipEngine
+    spec, u0, u, o, h, J = make(C4[0], C4[1], dict(pc="cpr"), dt=0.05)
+    inner(h, s1_ksp="fgmres", s1_max_it=8, s1_rtol=1e-6)
+    h.vec_set("x", np.zeros_like(u))
+    h.vec_set("y", np.ones_like(u))
+    h.stage1_apply("x", "y")
+    h.pc_apply("x", "z")
+    assert not h.vec_get("y").any() and not h.vec_get("z").any()
+    assert h.inner_stats() == (2, 0, 0)
+    # a right-hand side the reference solves in ONE iteration (dt = 0.05 s, rtol 1e-2: the first residual is far below the
+    # tolerance on both sides); the seven iterations still launched must not change the result
+    x = np.random.default_rng(11).standard_normal(u.shape)
+    ref = Composed(o.pc, "fgmres", 8, rtol=1e-2)
+    want = ref.stage1(x)
+    assert ref.its == [1] and _clear_of_tolerance(ref.hists[0], 1e-2*ref.hists[0][0])
+    inner(h, s1_ksp="fgmres", s1_max_it=8, s1_rtol=1e-2)
+    h.vec_set("x", x)
+    h.stage1_apply("x", "y")
+    y = h.vec_get("y")
+    assert np.isfinite(y).all() and rel2(y, want) < 1e-10
+    assert h.inner_stats() == (1, 1, 0)
+    # the same context, back on the default path, solves like a fresh one
+    h.set_options(s1_ksp="preonly", s1_max_it=1, s1_rtol=0.0, ksp_rtol=1e-8, snes_max_it=25)
+    f = HipEngine(spec, dict(pc="cpr", ksp_rtol=1e-8, snes_max_it=25))
+    for e in (h, f):
+        e.set_state(u0)
+        e.set_old(u0)
+        e.set_dt(86.4)
+    rh, rf = h.newton_solve(), f.newton_solve()
+    assert rh["reason"] > 0 and (rh["nits"], rh["lits"], rh["reason"]) == (rf["nits"], rf["lits"], rf["reason"])
+    assert np.array_equal(h.get_state(), f.get_state())
+    h.close()
+    f.close()
+
+
+@pytest.mark.parametrize("name,opts,s1", [("cpr_fgmres4", dict(pc="cpr"), dict(s1_ksp="fgmres", s1_max_it=4, s1_rtol=1e-2)),
+                                          ("cptr_richardson2", dict(pc="cptr"), dict(s1_ksp="richardson", s1_max_it=2))],
+                         ids=["cpr_fgmres4", "cptr_richardson2"])
+def test_outer_solve_counts(name, opts, s1):
+    import oracle.linalg as la
+    from oracle.engine import OracleEngine
+    opts = dict(opts, ksp_rtol=1e-8, snes_max_it=25)
+    spec, u0, u, o, h, J = make(C4[0], C4[1], opts)
+    inner(h, **s1)
+    ref = Composed(o.pc, s1["s1_ksp"], s1["s1_max_it"], rtol=s1.get("s1_rtol", 0.0))
+    F = o.residual()
+    h.residual()
+    h.copy_residual_to("b")
+    its_h, reason_h, _ = h.fgmres("b", "d")
+    d_o, its_o, reason_o, _ = la.fgmres(lambda v: la.spmv_block(J, v), ref.apply, F, rtol=1e-8, maxit=200, restart=200)
+    base = la.fgmres(lambda v: la.spmv_block(J, v), o.pc.apply, F, rtol=1e-8, maxit=200, restart=200)[1]
+    print("outer", name, "gpu", its_h, "composed reference", its_o, "one V-cycle", base)
+    assert reason_h == reason_o == 2 and abs(its_h - its_o) <= 1, (its_h, its_o)
+    assert rel2(h.vec_get("d"), d_o) < 1e-6
+    # one Newton solve: the reference is the oracle's Newton loop with the composed preconditioner
+    o2 = OracleEngine(spec, opts)
+    comp = Composed(o2.pc, s1["s1_ksp"], s1["s1_max_it"], rtol=s1.get("s1_rtol", 0.0))
+    o2.pc.apply = comp.apply
+    for e in (o2, h):
+        e.set_state(u0)
+        e.set_old(u0)
+        e.set_dt(86.4)
+    ro, rh = o2.newton_solve(), h.newton_solve()
+    print("newton", name, "gpu", rh["nits"], rh["lits"], "reference", ro["nits"], ro["lits"])
+    assert ro["reason"] > 0 and rh["reason"] == ro["reason"] and rh["nits"] == ro["nits"], (ro, rh)
+    assert abs(rh["lits"] - ro["lits"]) <= max(2, 0.1*ro["lits"])
+    h.close()
+
+
+@pytest.mark.parametrize("s1", ["fgmres", "richardson"])
+def test_graph_and_eager_agree(s1):
+    """TP_GRAPH is read once per process: tests/inner_env_check.py prints a digest of pc_apply outputs; the captured-graph
+    path and the eager path (TP_GRAPH=0) must print the same one."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    outs = []
+    for env in ({}, {"TP_GRAPH": "0"}):
+        r = subprocess.run([sys.executable, os.path.join(here, "inner_env_check.py"), s1], env={**os.environ, **env},
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
+        outs.append([ln for ln in r.stdout.splitlines() if ln.startswith("digest")])
+    assert outs[0] and outs[0] == outs[1], outs
+
+
+def test_two_slabs_replicated_and_the_distributed_error():
+    from test_gpu_slabs import run_linear_stage, run_slabs
+    spec, u0, *_ = cases.c4_spe10_3d(Nx=8, Ny=21, Nz=7, nphase=2)
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    xs = np.random.default_rng(11).standard_normal(u.shape)
+    for pc in (dict(pc="cpr"), dict(pc="cptr"), dict(pc="cptramg", decoup="QI")):
+        opts = dict(pc, amg_gather_cells=-1, s1_ksp="fgmres", s1_max_it=4, s1_rtol=1e-2)
+        one, _, _ = run_linear_stage(spec, opts, u0, u, 8640.0, xs, 1, vcycles=False)
+        two, lay, _ = run_linear_stage(spec, opts, u0, u, 8640.0, xs, 2, vcycles=False)
+        assert lay[0] == 0                  # the whole hierarchy is replicated
+        err = rel2(two["s1"], one["s1"])
+        print("slabs", pc, "stage 1 rel2 =", err)
+        assert err < 1e-10, (pc, err)
+    # outer counts: a Newton solve on one slab and on two (stage 2 is bjacobi per slab, so use tiles that do not cross the cut)
+    nopts = dict(pc="cpr", amg_gather_cells=-1, s1_ksp="fgmres", s1_max_it=4, s1_rtol=1e-2, ksp_rtol=1e-8, snes_max_it=25)
+    from thermalporous_amd.engine import HipEngine
+    h = HipEngine(spec, dict(nopts, ilu_tile=(1 << 30, 5, 11)))
+    h.set_state(u0)
+    h.set_old(None)
+    h.set_dt(86.4)
+    r1 = h.newton_solve()
+    h.close()
+    infos, _ = run_slabs(spec, dict(nopts, ilu_tile=(1 << 30, 5, 11)), u0, [86.4], 2)
+    print("slabs newton one slab", r1["nits"], r1["lits"], "two slabs", infos[0]["nits"], infos[0]["lits"])
+    # the slab axis has 21 planes = 11 + 10 and the tiles are 11 planes deep, so the one-GPU run cuts its tiles exactly where
+    # the slabs are cut; stage 1 is the one-GPU operator: the same preconditioner, hence the same counts
+    assert infos[0]["reason"] == r1["reason"] > 0 and infos[0]["nits"] == r1["nits"]
+    assert infos[0]["lits"] == r1["lits"], (infos[0]["lits"], r1["lits"])
+
+
+def test_distributed_top_levels_are_refused_and_preonly_recovers():
+    import ctypes as C
+    import threading
+    from thermalporous_amd import engine as E
+    spec, u0, *_ = cases.c4_spe10_3d(Nx=8, Ny=21, Nz=7, nphase=2)
+    u = cases.perturbed_state(spec, seed=5, amp=0.3)
+    xs = np.random.default_rng(11).standard_normal(u.shape)
+    lib = E.load_library()
+    group = C.c_void_p()
+    assert lib.tp_local_group_create(2, C.byref(group)) == 0
+    out, err = [None, None], []
+
+    def worker(rank):
+        try:
+            h = E.HipEngine(spec, dict(pc="cpr", amg_gather_cells=0, s1_ksp="fgmres", s1_max_it=4), rank=rank, nranks=2, local_group=group)
+            h.set_old(u0)
+            h.set_dt(8640.0)
+            h.set_state(u)
+            h.jacobian()
+            msg = None
+            try:
+                h.pc_setup()
+            except E.EngineError as e:
+                msg = str(e)
+            h.set_options(s1_ksp="preonly", s1_max_it=1)
+            h.pc_setup()
+            h.vec_set("x", xs)
+            h.pc_apply("x", "y")
+            out[rank] = (msg, h.vec_get("y"))
+            h.close()
+        except Exception as e:      # noqa: BLE001
+            err.append((rank, repr(e)))
+    ts = [threading.Thread(target=worker, args=(r,)) for r in range(2)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in ts), "slab worker hung"
+    lib.tp_local_group_destroy(group)
+    assert not err, err
+    for msg, y in out:
+        assert msg is not None and "amg_gather_cells < 0" in msg, msg
+        assert np.isfinite(y).all() and y.any()

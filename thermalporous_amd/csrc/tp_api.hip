@@ -318,6 +318,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     TP_HIP(hipGetDeviceCount(&ndev));
     TP_REQUIRE(ndev > 0, "no HIP device: the thermalporous hot path has no CPU fallback");
     TP_REQUIRE(device >= 0 && device < ndev, "bad device ordinal");
+    inner_check_options(*opt);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
     c->grid = *grid; c->prm = *prm; c->opt = *opt; c->device = device;
@@ -366,6 +367,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_API_BEGIN
     TP_REQUIRE(c && opt, "null argument");
     TP_REQUIRE(opt->ilu_levels == 0 || opt->ilu_levels == 1, "ilu_levels must be 0 or 1");
+    inner_check_options(*opt);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole;
     const bool amg_changed = opt->amg_min_cells != c->opt.amg_min_cells || opt->pc_kind != c->opt.pc_kind ||
@@ -802,6 +804,17 @@ int tp_fgmres(tp_ctx *c, int32_t b, int32_t x, int32_t *its, int32_t *reason, do
     if (its) *its = it;
     if (reason) *reason = r;
     if (rnorm) *rnorm = rn;
+    TP_API_END
+}
+
+int tp_inner_stats(tp_ctx *c, int64_t *applies, int64_t *its, int64_t *unconverged) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "null argument");
+    long long h[3] = {0, 0, 0};
+    if (c->inner.stats.n >= 3) copy_sync(c, h, c->inner.stats.p, sizeof(h), hipMemcpyDeviceToHost);
+    if (applies) *applies = h[0];
+    if (its) *its = h[1];
+    if (unconverged) *unconverged = h[2];
     TP_API_END
 }
 

@@ -236,6 +236,21 @@ struct BAmg {
     ~BAmg() { for (auto *l : lv) delete l; }
 };
 
+// Inner Krylov solve of the stage-1 pressure / (p,T) block (tp_inner.hip, tp_options.s1_ksp).  The operator the V-cycle
+// preconditions: nplanes == 1: A[0][0] (opA00, or the gathered gA00); nplanes == 2: the 2x2 block of pc_cptramg.
+struct InnerOp {
+    GridDev g;                 // grid of the vectors: nplanes planes of g.ntot doubles
+    Stencil A[2][2];
+};
+// workspace of the inner solve (sized by inner_ensure from ensure_work: never inside a capture).  Every scalar of the
+// iteration -- Hessenberg column, rotations, residual estimate, the convergence latch -- lives in `state` on the device.
+struct InnerWork {
+    DBuf<double> V, Z;         // fgmres: s1_max_it + 1 basis vectors, s1_max_it preconditioned vectors; richardson: V = (r, e)
+    DBuf<double> partial;      // per-wave partial sums of the fused reductions
+    DBuf<double> state;
+    DBuf<long long> stats;     // applies, iterations used, unconverged (tp_inner_stats)
+};
+
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
@@ -291,6 +306,8 @@ struct tp_ctx {
     tp::Stencil opA00, opA01, opA10;   // views used by stage 1
     tp::Amg *amg_p = nullptr, *amg_T = nullptr;
     tp::BAmg *bamg = nullptr;          // pc_cptramg: system AMG on the (p,T) blocks (tp_amg_block.hip)
+    tp::BStencil opPT;                 // pc_cptramg: the operator handed to bamg_setup (the slab's, or the gathered one)
+    tp::InnerWork inner;               // s1_ksp != preonly: workspace of the inner Krylov solve (tp_inner.hip)
     tp::DBuf<double> spbuf;            // selfp (schur_a11 == 2): S7 (7 planes), w/diag(Sp), two work planes
     tp::DBuf<double> gAt;              // multi-GPU pc_cptramg: the 28 operator planes gathered on the global grid
     tp::IluData ilu;
@@ -406,6 +423,14 @@ void seg_begin(tp_ctx *c);
 void seg_end(tp_ctx *c);
 // gather `nplanes` slab-distributed cell planes into arrays on the global grid (every rank gets all slabs)
 void gather_slabs(tp_ctx *c, const double *local, long lstride, double *global, long gstride, int nplanes);
+// inner Krylov solve of a stage-1 block (tp_inner.hip): out = K(op) rhs with the V-cycle `prec` as (right) preconditioner.
+// s1_ksp preonly: prec(rhs, out) and nothing else.  No host synchronisation: capturable.
+void inner_ensure(tp_ctx *c);         // workspace for the current options (called by ensure_work)
+void inner_check_options(const tp_options &o);
+void inner_reset_stats(tp_ctx *c);
+void inner_solve(tp_ctx *c, const InnerOp &op, const std::function<void(const double *, double *)> &prec, const double *rhs,
+                 double *out, int nplanes);
+int vcycles_per_apply(const tp_ctx *c);   // V-cycles one pc_apply launches
 // solver
 void resolve_cycle_shapes(tp_ctx *c);     // fix the AMG truncation levels after a set-up (host wait; never in a capture)
 void ensure_work(tp_ctx *c);          // scratch vectors w1..w4, dx of the preconditioner / Krylov loops

@@ -29,6 +29,7 @@ void ensure_work(tp_ctx *c) {
     if (c->w4.n < nv) { c->w4.alloc(nv); grew = true; }
     if (c->dx.n < nv) { c->dx.alloc(nv); grew = true; }
     if (grew) c->graph_epoch++;          // captured pc_apply graphs hold the old addresses
+    inner_ensure(c);                     // s1_ksp != preonly: basis and scalars of the inner solve
 }
 
 // multi-GPU scratch on the gathered global grid: grown on demand, never shrunk; captured graphs hold the old address
@@ -73,10 +74,19 @@ static void refresh_pc_signature(tp_ctx *c) {
                              (uintptr_t)c->w1.p, (uintptr_t)c->w3.p, (uintptr_t)c->w4.p, (uintptr_t)c->dcoef.p, (uintptr_t)c->spbuf.p,
                              (uintptr_t)c->opt.amg_nu, (uintptr_t)c->opt.pc_kind, (uintptr_t)c->opt.decoup,
                              (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip,
+                             (uintptr_t)c->opt.s1_ksp, (uintptr_t)c->opt.s1_max_it, (uintptr_t)c->inner.V.p, (uintptr_t)c->inner.Z.p,
                              (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole};
     uintptr_t h = 1469598103934665603ull;
     for (uintptr_t v : sig) h = (h ^ v) * 1099511628211ull;
     if (h != c->pc_sig) { c->pc_sig = h; c->graph_epoch++; }
+}
+
+// the inner solve's dot products are local: on several GPUs every rank must hold the whole stage-1 system
+static void require_replicated_for_inner(tp_ctx *c, const AmgPlan &plan) {
+    if (c->opt.s1_ksp == 0 || !c->dist) return;
+    TP_REQUIRE(plan.dist_levels == 0, "s1_ksp richardson/fgmres on several GPUs needs the replicated stage-1 hierarchy: with "
+               "slab-distributed top levels the inner dot products would need all-reduces between graph segments.  Set "
+               "amg_gather_cells < 0 (replicate the whole hierarchy) or s1_ksp preonly");
 }
 
 // pc_cptramg[_QI|_TI] (twophase.py:552-566): CPTRStage1PC.update with ONE system-AMG V-cycle as stage-1 solver
@@ -90,6 +100,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
         face_strengths(c, st);             // the pressure's coarsening schedule
         bamg_build(c, c->bamg, gam, st);
     }
+    require_replicated_for_inner(c, c->bamg->plan);
     const long nt = c->g.ntot;
     BStencil A0;
     if (c->opt.decoup == 0) { A0.base = c->J.p; A0.ss = (long)c->b * c->b * nt; A0.rs = (long)c->b * nt; A0.cs = nt; }
@@ -105,6 +116,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
                 gather_slabs(c, A0.at(s, q, 0), A0.cs, c->gAt.p + ((size_t)(s * 2 + q) * 2) * ng, (long)ng, 2);
         A0.base = c->gAt.p; A0.ss = 4 * (long)ng; A0.rs = 2 * (long)ng; A0.cs = (long)ng;
     }
+    c->opPT = A0;
     bamg_setup(c, c->bamg, A0);
     ilu_factor(c);
     c->pc_ready = true;
@@ -114,6 +126,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
 void pc_setup(tp_ctx *c) {
     TP_REQUIRE(c->jac_ready, "pc_setup needs an assembled Jacobian");
     ensure_work(c);
+    if (c->opt.s1_ksp) inner_reset_stats(c);      // tp_inner_stats counts since the last set-up
     if (c->opt.pc_kind == 4) {               // pc_bilu (twophase.py:758-762): bjacobi + ILU is the whole preconditioner
         ilu_factor(c);
         c->pc_ready = true;
@@ -152,6 +165,7 @@ void pc_setup(tp_ctx *c) {
             TP_REQUIRE((c->amg_p->plan.dist_levels > 0) == (c->amg_T->plan.dist_levels > 0), "stage-1 hierarchies disagree on distribution");
         }
     }
+    require_replicated_for_inner(c, c->amg_p->plan);
     Stencil Sl;
     Sl.base = c->Sm.p;
     Sl.slot_stride = c->g.ntot;
@@ -259,19 +273,32 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
         if (npri == 2) stage1_rhs(c, x, 1, r1);
     }
     if (sysamg_of(c->opt)) {
-        // pc_cptramg: y_pT = K(Atilde_00) r_pT, one V-cycle of the 2x2-block system AMG (r0, r1 are adjacent planes)
+        // pc_cptramg: y_pT = K(Atilde_00) r_pT, one V-cycle of the 2x2-block system AMG (r0, r1 are adjacent planes), or
+        // (s1_ksp) an inner solve preconditioned by it
+        InnerOp op;
+        op.g = (c->dist && c->bamg->plan.dist_levels == 0) ? c->gfull : g;
+        for (int q = 0; q < 2; ++q)
+            for (int r = 0; r < 2; ++r) { op.A[q][r].base = c->opPT.at(0, q, r); op.A[q][r].slot_stride = c->opPT.ss; }
+        const auto KPT = [&](const double *b, double *xx) { inner_solve(c, op, [&](const double *bb, double *xo) { bamg_vcycle(c, c->bamg, bb, xo); }, b, xx, 2); };
         if (c->dist && c->bamg->plan.dist_levels == 0) {
             const long ng = c->gfull.ntot;
             gather_slabs(c, r0, nt, c->gvec.p, ng, 2);
-            bamg_vcycle(c, c->bamg, c->gvec.p, c->gvec.p + 2 * ng);
+            KPT(c->gvec.p, c->gvec.p + 2 * ng);
             const long off = g.np * c->grid.off2;          // my slab INCLUDING its halo planes
             vec_copy(c, c->gvec.p + 2 * ng + off, y, nt);
             vec_copy(c, c->gvec.p + 3 * ng + off, y + nt, nt);
         } else {
-            bamg_vcycle(c, c->bamg, r0, y);
+            KPT(r0, y);
         }
         return;
     }
+    // K(A00): one V-cycle of the pressure hierarchy, or (s1_ksp) an inner solve preconditioned by it
+    InnerOp op;
+    const bool gathered = c->dist && c->amg_p->plan.dist_levels == 0;
+    op.g = gathered ? c->gfull : g;
+    op.A[0][0] = c->opA00;
+    if (gathered) { op.A[0][0].base = c->gA00.p; op.A[0][0].slot_stride = c->gfull.ntot; }
+    const auto K00 = [&](const double *b, double *xx) { inner_solve(c, op, [&](const double *bb, double *xo) { amg_vcycle(c, c->amg_p, bb, xo); }, b, xx, 1); };
     if (c->dist && c->amg_p->plan.dist_levels == 0) {
         // gathered global system: work vectors gr0, gr1, gy0, gy1, gt, gw on the global grid
         const GridDev &G = c->gfull;
@@ -280,20 +307,20 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
                *gw = gr0 + 5 * ng;
         gather_slabs(c, r0, nt, gr0, ng, npri);    // r0 (and r1: consecutive planes on both sides)
         if (npri == 1) {
-            amg_vcycle(c, c->amg_p, gr0, gy0);
+            K00(gr0, gy0);
         } else {
             Stencil A10, A01;
             A10.base = c->gA10.p; A10.slot_stride = ng;
             A01.base = c->gA01.p; A01.slot_stride = ng;
             if (c->opt.fs_additive) {               // PCFIELDSPLIT additive: one V-cycle per field
-                amg_vcycle(c, c->amg_p, gr0, gy0);
+                K00(gr0, gy0);
                 amg_vcycle(c, c->amg_T, gr1, gy1);
             } else {
-            amg_vcycle(c, c->amg_p, gr0, gw);
+            K00(gr0, gw);
             spmv_scalar(c, G, A10, gw, gt, -1.0, gr1);
             amg_vcycle(c, c->amg_T, gt, gy1);
             spmv_scalar(c, G, A01, gy1, gt, -1.0, gr0);
-            amg_vcycle(c, c->amg_p, gt, gy0);
+            K00(gt, gy0);
             }
         }
         // my slab of the result INCLUDING its halo planes (global planes lo-1 .. hi), so y needs no exchange
@@ -303,18 +330,18 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
         return;
     }
     if (npri == 1) {
-        amg_vcycle(c, c->amg_p, r0, y);
+        K00(r0, y);
         return;
     }
     // PCFIELDSPLIT schur FULL on (p,T) (twophase.py:536-545): K(A00), K(S~) = one V-cycle each
     // (multi-GPU with distributed AMG levels: the V-cycles return owned cells, the couplings read halos)
     double *y0 = y, *y1 = y + nt;
     if (c->opt.fs_additive) {              // PCFIELDSPLIT additive (pc_fieldsplit_diag, singlephase.py:371-375)
-        amg_vcycle(c, c->amg_p, r0, y0);
+        K00(r0, y0);
         amg_vcycle(c, c->amg_T, r1, y1);
         return;
     }
-    amg_vcycle(c, c->amg_p, r0, c->w4.p);                                   // y0 = K(A00) r0
+    K00(r0, c->w4.p);                                  // y0 = K(A00) r0
     if (c->dist) halo_exchange(c, g, c->w4.p, 1, nt);
     spmv_scalar(c, g, c->opA10, c->w4.p, t, -1.0, r1);                      // t = r1 - A10 y0
     if (c->opt.schur_a11 == 2) {                                            // selfp: V7 then one Jacobi sweep on the exact Sp
@@ -326,7 +353,7 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
     }
     if (c->dist) halo_exchange(c, g, y1, 1, nt);
     spmv_scalar(c, g, c->opA01, y1, t, -1.0, r0);                           // t = r0 - A01 y1
-    amg_vcycle(c, c->amg_p, t, y0);                                         // y0 = K(A00) t
+    K00(t, y0);                                     // y0 = K(A00) t
 }
 
 // composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r
@@ -372,7 +399,7 @@ void seg_end(tp_ctx *c) {
 void pc_apply(tp_ctx *c, const double *x, double *y) {
     TP_REQUIRE(c->pc_ready, "pc_apply before pc_setup");
     static const bool use_graph = !(getenv("TP_GRAPH") && atoi(getenv("TP_GRAPH")) == 0);
-    c->vcycles += c->opt.pc_kind == 4 ? 0 : c->opt.fs_additive ? 2 : schur_of(c->opt) ? 3 : 1;
+    c->vcycles += vcycles_per_apply(c);
     ensure_work(c);                      // never allocate inside a stream capture
     resolve_cycle_shapes(c);             // (waits for the last set-up's dominance ratios: not inside a capture either)
     if (!use_graph) {
@@ -569,7 +596,7 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
             res_prev = res;
             if (!std::isfinite(res) || res <= tol || hn == 0.0) {
                 if (have_w) ++c->spec_wasted;
-                if (have_w) c->vcycles -= c->opt.pc_kind == 4 ? 0 : c->opt.fs_additive ? 2 : schur_of(c->opt) ? 3 : 1;   // (discarded application)
+                if (have_w) c->vcycles -= vcycles_per_apply(c);   // (discarded application)
                 reason = !std::isfinite(res) ? -9 : 2;                     // KSP_DIVERGED_NANORINF | converged (or happy breakdown)
                 break;
             }

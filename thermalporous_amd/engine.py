@@ -46,7 +46,8 @@ class tp_options(C.Structure):
                 ("ilu_t1", C.c_int32), ("ilu_t2", C.c_int32), ("ilu_t0", C.c_int32),
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
-                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32)]
+                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
+                ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
 class tp_solve_info(C.Structure):
@@ -64,6 +65,7 @@ API_SYMBOLS = (
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
+    "tp_inner_stats",
 )
 
 DEFAULT_OPTS = dict(
@@ -87,6 +89,11 @@ DEFAULT_OPTS = dict(
     bjacobi_blocks=None,    # -sub_1_pc_bjacobi_blocks N: N blocks over the whole grid (tiles_for_blocks); overrides ilu_tile
     ilu_whole=False,        # one bjacobi block per rank: block-ILU(0) of the whole slab (= bjacobi_blocks 1 on one GPU, PETSc's
                             # default bjacobi on several); ilu_tile is then only the unit of the diagonal-by-diagonal sweep
+    # inner solve of the stage-1 pressure block K(A00) (pc cptramg: of the (p,T) system block), the V-cycle as its
+    # preconditioner, every scalar on the device (include/thermalporous_hip.h: tp_options.s1_ksp)
+    s1_ksp="preonly",       # "preonly": one V-cycle | "richardson": s1_max_it V-cycles from x0 = 0 | "fgmres": GMRES(s1_max_it <= 32)
+    s1_max_it=1,
+    s1_rtol=0.0, s1_atol=0.0,   # fgmres: latch on the recurrence residual <= max(s1_rtol*||rhs||, s1_atol); 0, 0 = fixed count
 )
 
 def default_ilu_tile(n, nslabs=1, ncu=256):
@@ -177,6 +184,7 @@ def tiles_for_blocks(n, nblocks, max_cols=64):
 
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
+_S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
 
 
 def load_library(path=None):
@@ -287,7 +295,9 @@ class HipEngine:
                           0 if t[0] >= (1 << 30) else int(t[0]), int(o["amg_full_levels"]), int(o["amg_coarse_pre"]),
                           int(o["amg_coarse_post"]), int(bool(o["amg_mid_skip"])), int(o["amg_tail_post"]), int(bool(o["amg_single"])), 2 if o.get("schur_selfp") else int(bool(o["schur_a11"])),
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
-                          int(bool(o.get("ilu_whole", False))))
+                          int(bool(o.get("ilu_whole", False))),
+                          _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
+                          float(o.get("s1_atol", 0.0)))
 
     def set_options(self, **kw):
         self.opts.update(kw)
@@ -512,6 +522,12 @@ class HipEngine:
         axes = (C.c_int32*64)()
         self._ck(self.lib.tp_amg_layout(self.ctx, which, C.byref(nd), axes, 64, C.byref(na)))
         return nd.value, [axes[i] for i in range(min(na.value, 64))]
+
+    def inner_stats(self):
+        """Inner solves (s1_ksp != preonly) since the last pc_setup: (applies, iterations used, ended above tolerance)."""
+        a, i, u = C.c_int64(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.tp_inner_stats(self.ctx, C.byref(a), C.byref(i), C.byref(u)))
+        return a.value, i.value, u.value
 
     def newton_solve(self):
         info = tp_solve_info()

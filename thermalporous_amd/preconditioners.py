@@ -71,8 +71,11 @@ class CPRStage1PC(PCBase):
         if self.decoup.endswith("_temp") and (self.kind != "cpr" or pc.engine.b != 3):
             raise NotImplementedError("QI_temp/TI_temp: two-phase CPRStage1PC only (:367-368)")
         eng = pc.engine
-        if eng.opts["pc"] != self.kind or eng.opts["decoup"] != self.decoup:
-            eng.set_options(pc=self.kind, decoup=self.decoup)
+        # inner solve of the stage-1 block (engine options s1_ksp, s1_max_it, s1_rtol, s1_atol): passed through when the
+        # application context carries them
+        inner = {k: appctx[k] for k in ("s1_ksp", "s1_max_it", "s1_rtol", "s1_atol") if k in appctx and eng.opts.get(k) != appctx[k]}
+        if eng.opts["pc"] != self.kind or eng.opts["decoup"] != self.decoup or inner:
+            eng.set_options(pc=self.kind, decoup=self.decoup, **inner)
         self.update(pc)
 
     def update(self, pc):

@@ -11,11 +11,15 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
      sub_0_pc_python_type  ...CPRStage1PC | ...CPTRStage1PC   sub_0_cpr_decoup  No|QI|TI
      sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur-FULL with ConvDiffSchurTwoPhasesPC
      sub_1_sub_pc_type ilu, sub_1_sub_pc_factor_levels 0, sub_1_pc_bjacobi_blocks
+  inner solve of the stage-1 PRESSURE solver K(A00) (pc_cptramg*: of the (p,T) system solver), under that solver's prefix
+  (_take_inner): pc_hypre_boomeramg_max_iter k | ksp_type richardson, ksp_max_it k | ksp_type fgmres (gmres + ksp_pc_side
+  right), ksp_max_it k <= 32, ksp_rtol, ksp_atol -- also spelled pc_type ksp + ksp_<the same keys> -> s1_ksp, s1_max_it,
+  s1_rtol, s1_atol.  The Schur / temperature solvers stay one V-cycle.
 
 Defaults the reference inherits silently from Firedrake/PETSc are fixed here explicitly
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
-ksp_atol 1e-50.  Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells,
-ilu_tile.  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
+Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol.  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -28,9 +32,19 @@ _VCYCLE_SUFFIXES = {"ksp_type": "preonly", "pc_type": "hypre", "pc_hypre_type": 
                     "pc_hypre_boomeramg_max_iter": 1}
 
 
-def _take_vcycle(sp, prefix, used):
+_SCHUR_WHY = ("an iterative solver on the Schur split is not implemented: PETSc would iterate on the TRUE Schur complement "
+              "A11 - A10 K(A00) A01, which needs nested A00 solves in every mat-vec; only the pressure solver K(A00) (and "
+              "the (p,T) system solver of pc_cptramg) can be an inner iteration")
+_ADDITIVE_WHY = ("an iterative solver on the temperature block of the additive split is not implemented: only the pressure "
+                 "solver K(A00) is wired to the inner iteration")
+_S1_MAXK = 32              # GMRES(k) without restart: k basis vectors of the stage-1 block are stored
+
+
+def _take_vcycle(sp, prefix, used, schur=False):
     """``<prefix>`` must configure exactly the reference's one-V-cycle solver (v_cycle dicts, singlephase.py:303-307,
-    twophase.py:478-482); hypre tuning keys are not honoured and therefore rejected."""
+    twophase.py:478-482); hypre tuning keys are not honoured and therefore rejected.  schur: the prefix is (inside) the
+    Schur split (or, "additive", the temperature block of the additive split), where an inner iteration is rejected with the
+    reason."""
     for suf, want in _VCYCLE_SUFFIXES.items():
         k = prefix + suf
         if k not in sp:
@@ -38,11 +52,103 @@ def _take_vcycle(sp, prefix, used):
                 continue
             raise NotImplementedError("%s missing: the stage-1 solver must be one BoomerAMG V-cycle (v_cycle)" % k)
         if sp[k] != want:
+            if schur and suf in ("ksp_type", "pc_hypre_boomeramg_max_iter"):
+                raise NotImplementedError("%s = %r: %s" % (k, sp[k], _ADDITIVE_WHY if schur == "additive" else _SCHUR_WHY))
             raise NotImplementedError("%s = %r: only %r (one V-cycle per application)" % (k, sp[k], want))
         used.add(k)
     for k in sp:
         if k.startswith(prefix + "pc_hypre_") and k not in used:
             raise NotImplementedError("%s: hypre tuning options do not apply to this build's own AMG" % k)
+
+
+def _set_inner(o, ksp, k, rtol=0.0, atol=0.0):
+    new = dict(s1_ksp=ksp, s1_max_it=int(k), s1_rtol=float(rtol), s1_atol=float(atol))
+    if o.get("s1_ksp", "preonly") != "preonly" and any(o[q] != v for q, v in new.items()):
+        raise ValueError("the inner stage-1 solve is configured twice and differently: build keys %r, PETSc keys %r"
+                         % ({q: o[q] for q in new}, new))
+    o.update(new)
+
+
+def _take_inner(sp, prefix, used, o, ksp_default=None):
+    """The V-cycle solver at ``<prefix>`` that may be an inner iteration: the stage-1 pressure solver K(A00), or the (p,T)
+    system solver of pc_cptramg*.  A python stage-1 class holds a PC, not a KSP (preconditioners.py:633 of the reference), so
+    PETSc itself wants ``<prefix>pc_type ksp`` with the solver keys under ``<prefix>ksp_``: both spellings are taken."""
+    kp = prefix
+    if sp.get(prefix + "pc_type") == "ksp":
+        used.add(prefix + "pc_type")
+        _take(sp, used, prefix + "ksp_type", ("preonly",))
+        kp = prefix + "ksp_"
+    ksp = sp.get(kp + "ksp_type", ksp_default if kp == prefix else None)    # (a PC handle has no ksp_type of its own)
+    if ksp is None:
+        raise NotImplementedError("%sksp_type missing: the stage-1 solver is a BoomerAMG V-cycle (v_cycle), alone or inside "
+                                  "richardson / fgmres" % kp)
+    if ksp not in ("preonly", "richardson", "fgmres", "gmres"):
+        raise NotImplementedError("%sksp_type = %r: preonly, richardson or fgmres (gmres with ksp_pc_side right) around "
+                                  "the V-cycle" % (kp, ksp))
+    if kp + "ksp_type" in sp:
+        used.add(kp + "ksp_type")
+    for suf, want in (("pc_type", "hypre"), ("pc_hypre_type", "boomeramg")):
+        if sp.get(kp + suf) != want:
+            raise NotImplementedError("%s%s = %r: only %r (the build's own AMG V-cycle)" % (kp, suf, sp.get(kp + suf), want))
+        used.add(kp + suf)
+    m = sp.get(kp + "pc_hypre_boomeramg_max_iter", 1)
+    if kp + "pc_hypre_boomeramg_max_iter" in sp:
+        used.add(kp + "pc_hypre_boomeramg_max_iter")
+    if int(m) != m or m < 1:
+        raise ValueError("%spc_hypre_boomeramg_max_iter = %r: a count >= 1" % (kp, m))
+    for k in sp:
+        if k.startswith(kp + "pc_hypre_") and k not in used:
+            raise NotImplementedError("%s: hypre tuning options do not apply to this build's own AMG" % k)
+    if ksp == "preonly":
+        if m > 1:                    # k V-cycles as a stationary iteration from x0 = 0
+            _set_inner(o, "richardson", m)
+        return
+    if m != 1:
+        raise NotImplementedError("%sksp_type %s around pc_hypre_boomeramg_max_iter %d: one V-cycle per inner iteration" % (kp, ksp, m))
+    if kp + "ksp_max_it" not in sp:
+        raise NotImplementedError("%sksp_max_it missing: the inner iteration count is fixed (PETSc's default of 10000 is not)" % kp)
+    k = sp[kp + "ksp_max_it"]
+    used.add(kp + "ksp_max_it")
+    if int(k) != k or k < 1:
+        raise ValueError("%sksp_max_it = %r: a count >= 1" % (kp, k))
+    if ksp == "richardson":
+        # exactly k V-cycles: ksp_rtol / ksp_atol are not consumed (they would be silently ignored, so they raise)
+        _take(sp, used, kp + "ksp_norm_type", ("none",))
+        _set_inner(o, "richardson", k)
+        return
+    side = _take(sp, used, kp + "ksp_pc_side", ("right",))
+    if ksp == "gmres" and side is None:
+        raise NotImplementedError("%sksp_type gmres without ksp_pc_side: PETSc would precondition from the LEFT; only "
+                                  "right-preconditioned (F)GMRES is implemented (the reference sets ksp_pc_side right, "
+                                  "singlephase.py:296)" % kp)
+    if k > _S1_MAXK:
+        raise NotImplementedError("%sksp_max_it = %d: the inner GMRES keeps its whole basis (no restart), at most %d iterations"
+                                  % (kp, k, _S1_MAXK))
+    restart = _take(sp, used, kp + "ksp_gmres_restart")
+    if restart is not None and restart < k:
+        raise NotImplementedError("%sksp_gmres_restart %d < ksp_max_it %d: the inner GMRES does not restart" % (kp, restart, k))
+    rtol = _take(sp, used, kp + "ksp_rtol", None, 1e-5)          # PETSc's KSP defaults
+    atol = _take(sp, used, kp + "ksp_atol", None, 1e-50)
+    if rtol < 0 or atol < 0:
+        raise ValueError("%sksp_rtol / ksp_atol must be >= 0" % kp)
+    _set_inner(o, "fgmres", k, rtol, atol)
+
+
+def _check_inner(o):
+    """Validate s1_* however they were given (build keys or PETSc spelling)."""
+    ksp, k = o["s1_ksp"], o["s1_max_it"]
+    if ksp not in ("preonly", "richardson", "fgmres"):
+        raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
+    if ksp == "preonly":
+        return
+    if o["pc"] == "bilu":
+        raise NotImplementedError("pc_bilu has no stage-1 solver: s1_ksp does not apply")
+    if int(k) != k or k < 1:
+        raise ValueError("s1_max_it = %r: a count >= 1" % (k,))
+    if ksp == "fgmres" and k > _S1_MAXK:
+        raise NotImplementedError("s1_max_it = %d: the inner GMRES keeps its whole basis (no restart), at most %d" % (k, _S1_MAXK))
+    if o["s1_rtol"] < 0 or o["s1_atol"] < 0:
+        raise ValueError("s1_rtol / s1_atol must be >= 0")
 
 
 def _take(sp, used, key, allowed=None, default=None):
@@ -55,6 +161,12 @@ def _take(sp, used, key, allowed=None, default=None):
                                   % (key, v, ", ".join(repr(a) for a in allowed)))
     used.add(key)
     return v
+
+
+def _reject_schur_krylov(sp, prefix):
+    v = sp.get(prefix + "ksp_type", "preonly")
+    if v != "preonly":
+        raise NotImplementedError("%sksp_type = %r: %s" % (prefix, v, _SCHUR_WHY))
 
 
 def _reject_unused(sp, used):
@@ -88,7 +200,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     o["fs_additive"] = False
     used = set()
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single",
-                  "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole")
+                  "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole",
+                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol")
     for k in build_keys:
         if k in sp:
             o[k] = sp.pop(k)
@@ -128,6 +241,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
             raise NotImplementedError("pc_bilu has no decoupling stage")
         o["pc"] = "bilu"
         _reject_unused(sp, used)
+        _check_inner(o)
         return o
     if pc_type is None:
         raise NotImplementedError("pc_type missing: only the composite CPR/CPTR preconditioners and pc_fieldsplit_cd/_a11 "
@@ -138,28 +252,30 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         # pc_fieldsplit_selfp (:322-330): Sp = A_TT - A_Tp diag(A_pp)^-1 A_pT
         if _take(sp, used, "pc_fieldsplit_type", ("schur", "additive")) == "additive":
             # pc_fieldsplit_diag (singlephase.py:371-375): block-diagonal, one V-cycle on A_pp and one on A_TT
-            _take_vcycle(sp, "fieldsplit_0_", used)
-            _take_vcycle(sp, "fieldsplit_1_", used)
+            _take_inner(sp, "fieldsplit_0_", used, o)
+            _take_vcycle(sp, "fieldsplit_1_", used, schur="additive")
             if model_name == "Two-phase" or o["decoup"] != "No":
                 raise NotImplementedError("pc_fieldsplit_diag is a single-phase preconditioner without decoupling")
             o["pc"], o["schur_a11"], o["fs_additive"] = "fieldsplit_cd", True, True
             _reject_unused(sp, used)
+            _check_inner(o)
             return o
         fact = str(_take(sp, used, "pc_fieldsplit_schur_fact_type", None, "")).upper()
         pre = _take(sp, used, "pc_fieldsplit_schur_precondition", ("a11", "selfp"))
         if "pc_fieldsplit_type" not in used or fact != "FULL":
             raise NotImplementedError("fieldsplit preconditioners on the hot path: schur FULL with ConvDiffSchurPC "
                                       "(pc_fieldsplit_cd), a11 (pc_fieldsplit_a11) or selfp (pc_fieldsplit_selfp)")
-        _take_vcycle(sp, "fieldsplit_0_", used)
+        _take_inner(sp, "fieldsplit_0_", used, o)
         if pre in ("a11", "selfp"):
-            _take_vcycle(sp, "fieldsplit_1_", used)
+            _take_vcycle(sp, "fieldsplit_1_", used, schur=True)
         else:
+            _reject_schur_krylov(sp, "fieldsplit_1_")
             _take(sp, used, "fieldsplit_1_ksp_type", ("preonly",))
             _take(sp, used, "fieldsplit_1_pc_type", ("python",))
             if not str(_take(sp, used, "fieldsplit_1_pc_python_type", None, "")).endswith("ConvDiffSchurPC"):
                 raise NotImplementedError("fieldsplit_1 must be ConvDiffSchurPC (pc_fieldsplit_cd) or a V-cycle "
                                           "(pc_fieldsplit_a11, pc_fieldsplit_selfp)")
-            _take_vcycle(sp, "fieldsplit_1_schur_", used)
+            _take_vcycle(sp, "fieldsplit_1_schur_", used, schur=True)
         o["schur_a11"] = pre == "a11"
         o["schur_selfp"] = pre == "selfp"                # (singlephase.py:322-330)
         if model_name == "Two-phase":
@@ -168,6 +284,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
             raise NotImplementedError("pc_fieldsplit_cd has no decoupling stage")
         o["pc"] = "fieldsplit_cd"
         _reject_unused(sp, used)
+        _check_inner(o)
         return o
     # ---- composite multiplicative (stage 1, bjacobi/ILU(0)) -----------------------------------------------------
     _take(sp, used, "pc_composite_type", ("multiplicative",))
@@ -204,7 +321,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         if first == "hypre":
             if f0 != "0":
                 raise NotImplementedError("one AMG V-cycle on an explicit multi-field split is not on the hot path")
-            _take_vcycle(sp, "sub_0_fieldsplit_0_", used)
+            _take_inner(sp, "sub_0_fieldsplit_0_", used, o)
             if model_name == "Two-phase" and vector and "sub_0_pc_fieldsplit_0_fields" not in used:
                 # pc_cptramg_gmres (twophase.py:698-713): no explicit fields, so with vector=True (forced at :953-955) the
                 # splits are the function space's own sub-spaces: (p,T) interleaved | S_o -- ONE V-cycle on the (p,T) system
@@ -214,6 +331,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         elif first == "fieldsplit":
             _take(sp, used, "sub_0_fieldsplit_0_pc_fieldsplit_type", ("schur",))
             fact = str(_take(sp, used, "sub_0_fieldsplit_0_pc_fieldsplit_schur_fact_type", None, "")).upper()
+            _reject_schur_krylov(sp, "sub_0_fieldsplit_0_fieldsplit_1_")
             _take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_ksp_type", ("preonly",))
             _take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_pc_type", ("python",))
             py = str(_take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_pc_python_type", None, ""))
@@ -221,8 +339,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
                 raise NotImplementedError("unsupported first split of the fieldsplit,bjacobi composite")
             if f0 not in ("0,1", "0, 1") or f1 not in (None, "2"):
                 raise NotImplementedError("pc_cptr_gmres splits fields (0,1 | 2)")
-            _take_vcycle(sp, "sub_0_fieldsplit_0_fieldsplit_0_", used)
-            _take_vcycle(sp, "sub_0_fieldsplit_0_fieldsplit_1_schur_", used)
+            _take_inner(sp, "sub_0_fieldsplit_0_fieldsplit_0_", used, o)
+            _take_vcycle(sp, "sub_0_fieldsplit_0_fieldsplit_1_schur_", used, schur=True)
             if model_name != "Two-phase":
                 raise NotImplementedError("pc_cptr_gmres needs the two-phase model")
             o["pc"] = "cptr"
@@ -230,29 +348,31 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
             raise NotImplementedError("unsupported first split of the fieldsplit,bjacobi composite "
                                       "(mg/LU/system-AMG variants are not on the hot path)")
         _reject_unused(sp, used)
+        _check_inner(o)
         return o
     pytype = str(_take(sp, used, "sub_0_pc_python_type", None, ""))
     if pytype.endswith("CPRStage1PC"):
         o["pc"] = "cpr"
-        _take_vcycle(sp, "sub_0_cpr_stage1_", used)
+        _take_inner(sp, "sub_0_cpr_stage1_", used, o)
     elif pytype.endswith("CPTRStage1PC"):
         if model_name != "Two-phase":
             raise NotImplementedError("CPTRStage1PC needs the two-phase model")
-        kind = _take(sp, used, "sub_0_cpr_stage1_pc_type", ("fieldsplit", "hypre"))
+        kind = _take(sp, used, "sub_0_cpr_stage1_pc_type", ("fieldsplit", "hypre", "ksp"))
+        if kind == "ksp":
+            # PCKSP around the stage-1 solver: only around the system V-cycle (an iteration around the whole Schur fieldsplit
+            # would nest the pressure and temperature solves in every inner mat-vec)
+            if sp.get("sub_0_cpr_stage1_ksp_pc_type") != "hypre":
+                raise NotImplementedError("sub_0_cpr_stage1_pc_type ksp: only around the (p,T) system V-cycle (sub_0_cpr_stage1_"
+                                          "ksp_pc_type hypre, pc_cptramg*); for pc_cptr put the inner solver on "
+                                          "sub_0_cpr_stage1_fieldsplit_0_")
+            kind = "hypre"
         if kind is None:
             raise NotImplementedError("CPTRStage1PC needs sub_0_cpr_stage1_pc_type fieldsplit (pc_cptr) or hypre "
                                       "(pc_cptramg*); the LU variants (pc_cptrlu*) are not on the hot path")
         if kind == "hypre":
             # pc_cptramg[_QI|_TI] (twophase.py:552-566): ONE BoomerAMG V-cycle on the interleaved (p,T) system
             o["pc"] = "cptramg"
-            _take(sp, used, "sub_0_cpr_stage1_pc_hypre_type", ("boomeramg",))
-            _take(sp, used, "sub_0_cpr_stage1_pc_hypre_boomeramg_max_iter", (1,))
-            _take(sp, used, "sub_0_cpr_stage1_ksp_type", ("preonly",))
-            if "sub_0_cpr_stage1_pc_hypre_type" not in used:
-                raise NotImplementedError("sub_0_cpr_stage1_pc_hypre_type boomeramg expected")
-            for k in sp:
-                if k.startswith("sub_0_cpr_stage1_pc_hypre_") and k not in used:
-                    raise NotImplementedError("%s: hypre tuning options do not apply to this build's own AMG" % k)
+            _take_inner(sp, "sub_0_cpr_stage1_", used, o, ksp_default="preonly")
             if o["decoup"] not in ("No", "QI", "TI"):
                 raise NotImplementedError("pc_cptramg: decoupling No, QI or TI (twophase.py:552-566)")
         else:
@@ -263,16 +383,17 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
                 raise NotImplementedError("CPTR stage 1: fieldsplit schur FULL only (twophase.py:536-538)")
             pre = _take(sp, used, "sub_0_cpr_stage1_pc_fieldsplit_schur_precondition", ("a11",))
             o["schur_a11"] = pre == "a11"                   # pc_cptr_a11 (twophase.py:598-616)
-            _take_vcycle(sp, "sub_0_cpr_stage1_fieldsplit_0_", used)
+            _take_inner(sp, "sub_0_cpr_stage1_fieldsplit_0_", used, o)
             if pre == "a11":
-                _take_vcycle(sp, "sub_0_cpr_stage1_fieldsplit_1_", used)
+                _take_vcycle(sp, "sub_0_cpr_stage1_fieldsplit_1_", used, schur=True)
             else:
+                _reject_schur_krylov(sp, "sub_0_cpr_stage1_fieldsplit_1_")
                 _take(sp, used, "sub_0_cpr_stage1_fieldsplit_1_ksp_type", ("preonly",))
                 _take(sp, used, "sub_0_cpr_stage1_fieldsplit_1_pc_type", ("python",))
                 py = str(_take(sp, used, "sub_0_cpr_stage1_fieldsplit_1_pc_python_type", None, ""))
                 if not py.endswith("ConvDiffSchurTwoPhasesPC"):
                     raise NotImplementedError("CPTR stage 1: the Schur split must be ConvDiffSchurTwoPhasesPC or a11")
-                _take_vcycle(sp, "sub_0_cpr_stage1_fieldsplit_1_schur_", used)
+                _take_vcycle(sp, "sub_0_cpr_stage1_fieldsplit_1_schur_", used, schur=True)
     else:
         raise NotImplementedError("sub_0_pc_python_type %r" % pytype)
     if o["decoup"] not in ("No", "QI", "TI", "QI_temp", "TI_temp"):
@@ -281,4 +402,5 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         raise NotImplementedError("QI_temp/TI_temp decouple temperature AND saturation from the pressure: "
                                   "two-phase pc_cpr only (preconditioners.py:367-368)")
     _reject_unused(sp, used)
+    _check_inner(o)
     return o
