@@ -111,6 +111,15 @@ typedef struct tp_options {
                                 reference's `sub_1_pc_bjacobi_blocks: 1` (tests/test_homo_wells.py:112, pc_cptr_a11
                                 twophase.py:612): couplings between the tiles are kept; the tiles (ilu_t0 x ilu_t1 x ilu_t2,
                                 now only the unit of the sweep) are swept one tile-diagonal T0+T1+T2 per launch.  ILU(0) only. */
+    int32_t ilu_block[3];    /* bjacobi block = a BOX of ilu_block[0] x [1] x [2] whole cells (internal axis order), independent of the
+                                sweep tile: `sub_1_pc_bjacobi_blocks N` for blocks larger than one tile (tests/test_homo_wells.py:112,125,
+                                twophase.py:612).  Blocks start at the slab's origin (the last one along an axis is the ragged one);
+                                couplings inside a block are kept, those across block faces dropped.  Every block is cut into
+                                its own ilu_t0 x ilu_t1 x ilu_t2 tiles (partial tile at the block's upper end) and swept one
+                                block-local tile-diagonal per launch, all blocks in the same launch.  All zero: off (every
+                                tile is a block); otherwise an entry <= 0 or beyond the slab means the whole extent.  Blocks
+                                no larger than the tile are the per-tile path with the tile clipped to the block.  ilu_whole
+                                is the case block = slab and excludes this field.  ILU(0) only for multi-tile blocks. */
     /* Inner solve of the stage-1 PRESSURE block K(A00) (pc_kind 0, 1, 2) or of the (p,T) SYSTEM block (pc_kind 3): what PETSc
      * does when the sub-solver's ksp_type is not preonly.  The V-cycle becomes the (right) preconditioner of a small
      * Krylov method whose every scalar stays on the device, so it lives inside the captured pc_apply graph:
@@ -215,6 +224,10 @@ int tp_stage1_update(tp_ctx *ctx);                         /* CPRStage1PC/CPTRSt
 int tp_stage1_apply(tp_ctx *ctx, int32_t x, int32_t y);    /* ....apply (preconditioners.py:881,1550) */
 int tp_ilu0_factor(tp_ctx *ctx);                           /* sub_1: bjacobi + ILU(0) numeric factorisation (singlephase.py:348-349) */
 int tp_ilu0_solve(tp_ctx *ctx, int32_t x, int32_t y);
+/* the stage-2 layout that was built from the options (read-only; sets the layout up if no factorisation has yet):
+ * out = {B0, B1, B2, number of bjacobi blocks, number of tiles, block-local tile-diagonals, most tiles in one launch,
+ * launches per sweep direction}.  One tile per block (the default): B = the tile, blocks = tiles, 1, tiles, 1. */
+int tp_ilu_layout(tp_ctx *ctx, int32_t out[8]);
 int tp_amg_setup(tp_ctx *ctx, int32_t which);              /* v_cycle dict (singlephase.py:303-307); 0: pressure operator, 1: S~ */
 /* which: 0 pressure hierarchy, 1 S~ hierarchy, 2 the (p,T) system hierarchy of pc_cptramg (fields 0,1 of b -> x) */
 int tp_amg_vcycle(tp_ctx *ctx, int32_t which, int32_t field_b, int32_t b, int32_t field_x, int32_t x);

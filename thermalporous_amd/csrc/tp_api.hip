@@ -369,7 +369,8 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_REQUIRE(opt->ilu_levels == 0 || opt->ilu_levels == 1, "ilu_levels must be 0 or 1");
     inner_check_options(*opt);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
-                              opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole;
+                              opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
+                              std::memcmp(opt->ilu_block, c->opt.ilu_block, sizeof(opt->ilu_block)) != 0;
     const bool amg_changed = opt->amg_min_cells != c->opt.amg_min_cells || opt->pc_kind != c->opt.pc_kind ||
                              opt->amg_nu != c->opt.amg_nu || opt->amg_full_levels != c->opt.amg_full_levels ||
                              opt->amg_coarse_pre != c->opt.amg_coarse_pre || opt->amg_coarse_post != c->opt.amg_coarse_post ||
@@ -908,6 +909,13 @@ int tp_amg_layout(tp_ctx *c, int32_t which, int32_t *dist_levels, int32_t *axes,
     if (dist_levels) *dist_levels = P.dist_levels;
     if (naxes) *naxes = (int)P.sched.size();
     for (int i = 0; axes && i < cap && i < (int)P.sched.size(); ++i) axes[i] = P.sched[i];
+    TP_API_END
+}
+
+int tp_ilu_layout(tp_ctx *c, int32_t out[8]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "null argument");
+    ilu_layout(c, out);
     TP_API_END
 }
 

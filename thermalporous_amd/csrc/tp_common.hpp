@@ -264,10 +264,13 @@ struct IluData {
     DBuf<double> fwdp, bwdp;
     DBuf<int> pref;
     int ptot = 0;
-    // tp_options.ilu_whole: one block per rank.  Tiles keep their couplings; tile-diagonal d = T0+T1+T2 is one launch:
+    // tp_options.ilu_whole (one block per rank) / ilu_block (boxes of bb cells): blocks of SEVERAL tiles.  The tiles of a
+    // block keep their couplings; block-local tile-diagonal d = T0'+T1'+T2' of every block is one launch:
     // tiles diag_tiles[diag_off[d] .. diag_off[d+1]) (device array); xtmp: the raw backward-sweep result of every
     // (tile, step, lane) for the tiles of later launches (x itself may already hold addto + result)
-    bool whole = false;
+    bool whole = false;            // block-bounded sweeps (false: every block is one tile)
+    int bb[3] = {0, 0, 0};         // block extents (clipped to the slab), pb: tiles per full block along each axis
+    int pb[3] = {1, 1, 1};
     int ndiag = 0;
     std::vector<int> diag_off;
     DBuf<int> diag_tiles;
@@ -395,6 +398,7 @@ void stage1_rhs(tp_ctx *c, const double *x, int q, double *out);                
 // ILU
 void ilu_setup(tp_ctx *c);
 void ilu_factor(tp_ctx *c);
+void ilu_layout(tp_ctx *c, int32_t out[8]);
 // x = addto + M^-1 r ; only the first nadd fields of addto are read, the others count as zero (< 0: all fields)
 void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int nadd = -1);
 // AMG.  slabs: each rank's owned global planes along axis 2 (rank_slabs; empty: not distributed); a level stays on the slabs

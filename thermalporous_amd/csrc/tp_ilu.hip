@@ -74,7 +74,10 @@ struct IluGeom {
     int ntiles;    // nt0*nt1*nt2
     int nl;        // lanes of a wave that carry a column: t1*t2 <= 64
     int rs;        // doubles per chunk row: 2*nl when the rows are as wide as the tile (CP kernels), else 128
-    int ws;        // whole-slab ILU(0) (tp_options.ilu_whole): couplings between tiles are kept
+    int ws;        // block-bounded ILU(0) (tp_options.ilu_whole / ilu_block): a bjacobi block is a box of bb0 x bb1 x bb2 cells cut
+                   // into its OWN tiles; couplings between the tiles of a block are kept, those across block faces dropped
+    int bb0, bb1, bb2;   // block extents (ilu_whole: the slab's); the last block along an axis is the ragged one
+    int pb0, pb1, pb2;   // tiles per full block along each axis: tile index T -> block T / pb, block-local index T % pb
     const int *pref;   // ILU(1) packed factor copy: slots before each step of a tile (null: padded 64-lane rows)
     int ptot;          // slots per tile = pref[nsteps]
 };
@@ -99,6 +102,8 @@ struct TileInfo {
     int base0, base1, base2;   // first cell of the tile
     int tt0, tj, tk;           // actual tile extents
     int j, k;                  // lane coordinates
+    bool lo0, lo1, lo2;        // block-bounded sweeps (tile_info_blk): the tile has a lower / upper neighbour tile IN ITS BLOCK
+    bool hi0, hi1, hi2;        // along the axis (the neighbour's index is tile -/+ 1, nt0, nt0*nt1: the tile grid stays a product)
 };
 
 __device__ __forceinline__ TileInfo tile_info(const IluGeom &G, int tile, int lane) {
@@ -108,6 +113,30 @@ __device__ __forceinline__ TileInfo tile_info(const IluGeom &G, int tile, int la
     t.tt0 = min(G.t0, G.g.n0 - t.base0);
     t.tj = min(G.t1, G.g.n1 - t.base1);
     t.tk = min(G.t2, G.g.n2 - t.base2);
+    t.j = lane % G.t1;
+    t.k = lane / G.t1;
+    t.lo0 = t.lo1 = t.lo2 = t.hi0 = t.hi1 = t.hi2 = false;
+    return t;
+}
+
+// Block-bounded layout (G.ws): every block starts a fresh tile grid at its origin, with its partial tile at its upper end, so
+// along an axis the tiles are pb per block (fewer in the ragged last block) and nt = sum over the blocks.  All blocks but the
+// last have the same extent, hence plain arithmetic instead of an origin table.
+__device__ __forceinline__ void tile_axis_blk(int T, int t, int bb, int pb, int n, int &base, int &ext, bool &lo, bool &hi) {
+    const int b = T / pb, L = T - b * pb;
+    const int end = min((b + 1) * bb, n);
+    base = b * bb + L * t;
+    ext = min(t, end - base);
+    lo = L > 0;
+    hi = base + t < end;
+}
+
+__device__ __forceinline__ TileInfo tile_info_blk(const IluGeom &G, int tile, int lane) {
+    TileInfo t;
+    const int T0 = tile % G.nt0, T1 = (tile / G.nt0) % G.nt1, T2 = tile / (G.nt0 * G.nt1);
+    tile_axis_blk(T0, G.t0, G.bb0, G.pb0, G.g.n0, t.base0, t.tt0, t.lo0, t.hi0);
+    tile_axis_blk(T1, G.t1, G.bb1, G.pb1, G.g.n1, t.base1, t.tj, t.lo1, t.hi1);
+    tile_axis_blk(T2, G.t2, G.bb2, G.pb2, G.g.n2, t.base2, t.tk, t.lo2, t.hi2);
     t.j = lane % G.t1;
     t.k = lane / G.t1;
     return t;
@@ -139,18 +168,16 @@ __global__ __launch_bounds__(64 * ILU_SEG) void k_ilu_gather(IluGeom G, const do
     const int ns = G.nsteps;
     if (s >= ns) return;
     const long nt = G.g.ntot;
-    const TileInfo ti = tile_info(G, tile, lane);
+    const TileInfo ti = G.ws ? tile_info_blk(G, tile, lane) : tile_info(G, tile, lane);
     int l0;
     long c;
     const bool ok = tile_cell(G, ti, s, l0, c);
-    // which of the 7 blocks survive: couplings to cells outside the tile are dropped (bjacobi) -- outside the SLAB when the
-    // whole slab is one block (G.ws)
-    const int g0 = ti.base0 + l0, g1 = ti.base1 + ti.j, g2 = ti.base2 + ti.k;
-    const bool ws = G.ws != 0;
+    // which of the 7 blocks survive: couplings to cells outside the tile are dropped (bjacobi) -- outside the BLOCK when a
+    // block holds several tiles (G.ws: a coupling across a tile face survives when the block goes on beyond the face)
     const bool keep[7] = {true,
-                          ws ? g0 > 0 : l0 > 0, ws ? g0 < G.g.n0 - 1 : l0 < ti.tt0 - 1,
-                          ws ? g1 > 0 : ti.j > 0, ws ? g1 < G.g.n1 - 1 : ti.j < ti.tj - 1,
-                          ws ? g2 > 0 : ti.k > 0, ws ? g2 < G.g.n2 - 1 : ti.k < ti.tk - 1};
+                          l0 > 0 || ti.lo0, l0 < ti.tt0 - 1 || ti.hi0,
+                          ti.j > 0 || ti.lo1, ti.j < ti.tj - 1 || ti.hi1,
+                          ti.k > 0 || ti.lo2, ti.k < ti.tk - 1 || ti.hi2};
     double v[2 * ILU_PPT];
 #pragma unroll
     for (int u = 0; u < 2 * ILU_PPT; ++u) {          // all loads of the thread in flight together
@@ -184,7 +211,7 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
     // compiler, which then drains ALL outstanding loads (s_waitcnt vmcnt(0)) at every step -- measured +40 % on C1
     const int la = CP ? (lane < NL ? lane : NL - 1) : lane;
     const bool live = CP ? lane < NL : true;
-    const TileInfo ti = tile_info(G, tile, lane);
+    const TileInfo ti = (MW && WS) ? tile_info_blk(G, tile, lane) : tile_info(G, tile, lane);
     const int ns = G.nsteps;
     double Dp[B][B];                       // D~^-1 of this lane's previous cell (axis-0 lower neighbour)
 #pragma unroll
@@ -254,16 +281,16 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
         double D[B][B], Di[B][B];
         constexpr int PFR = (3 * B + 1) / 2, PBR = (4 * B + 1) / 2;       // (IluMwLayout)
         if constexpr (MW && WS) {
-            // whole-slab ILU(0): a lower neighbour in ANOTHER tile (finished in an earlier launch: smaller T0+T1+T2) is not
-            // in this wave's registers.  Its D~^-1 comes from that tile's backward chunk, its A_mc from the re-ordered
-            // Jacobian.  Lower neighbour tiles are never partial along the axis they are crossed in.
+            // block-bounded ILU(0): a lower neighbour in ANOTHER tile of the block (finished in an earlier launch: smaller
+            // block-local T0+T1+T2) is not in this wave's registers.  Its D~^-1 comes from that tile's backward chunk, its A_mc
+            // from the re-ordered Jacobian.  Lower neighbour tiles are never partial along the axis they are crossed in (a
+            // block's partial tile is its last), and a tile on a block face has no such neighbour (ti.lo*).
             int l0c;
             long ccell;
             const bool okc = tile_cell(G, ti, s, l0c, ccell);
-            const int T0 = tile % G.nt0, T1 = (tile / G.nt0) % G.nt1, T2 = tile / (G.nt0 * G.nt1);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const bool cross = okc && (a == 0 ? (l0c == 0 && T0 > 0) : a == 1 ? (ti.j == 0 && T1 > 0) : (ti.k == 0 && T2 > 0));
+                const bool cross = okc && (a == 0 ? (l0c == 0 && ti.lo0) : a == 1 ? (ti.j == 0 && ti.lo1) : (ti.k == 0 && ti.lo2));
                 if (cross) {
                     const int tA = tile - (a == 0 ? 1 : a == 1 ? G.nt0 : G.nt0 * G.nt1);
                     const int lnA = a == 0 ? lane : a == 1 ? (G.t1 - 1) + G.t1 * ti.k : ti.j + G.t1 * (G.t2 - 1);
@@ -598,9 +625,10 @@ template <int B> struct IluMwLayout {
 // register arrays they capture by reference then live in scratch memory, and the sweep is ten times slower.)
 // BLK: grid-layout vectors moved in blocks of RF / RB steps (below); off for the short 2-D tiles, where the delayed block stores
 // only lengthen the tail
-// WS (tp_options.ilu_whole): the whole slab is ONE block.  A launch sweeps the tiles of one tile-diagonal (`tiles`), forward
-// (phase 1) or backward (phase 2); a neighbour value across a tile face was produced by an EARLIER launch and is read from
-// global memory -- y from ytmp, the raw backward result from xtmp -- instead of the LDS.  WS implies !YLDS.
+// WS (tp_options.ilu_whole / ilu_block): a bjacobi block holds SEVERAL tiles.  A launch sweeps the tiles of one block-local
+// tile-diagonal of every block (`tiles`), forward (phase 1) or backward (phase 2); a neighbour value across a tile face inside
+// the block was produced by an EARLIER launch and is read from global memory -- y from ytmp, the raw backward result from
+// xtmp -- instead of the LDS; a tile on a block face takes nothing from beyond it (masks ti.lo* / ti.hi*).  WS implies !YLDS.
 template <int B, bool YLDS, bool BLK, bool WS = false>
 __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double *__restrict__ fwd,
                                                          const double *__restrict__ bwd, const double *__restrict__ rhs,
@@ -618,7 +646,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
     const int la = min(lane, NL - 1);                 // idle lanes shadow the last live lane's loads ...
     const bool live = lane < NL;                      // ... and store to dump locations: no divergent branch in the loops
     const long nt = G.g.ntot;
-    const TileInfo ti = tile_info(G, tile, la);
+    const TileInfo ti = WS ? tile_info_blk(G, tile, la) : tile_info(G, tile, la);
     const long park = min((long)lane, G.g.np - 1);
     const int lm1 = max(la - 1, 0), lmt = max(la - G.t1, 0), lp1 = min(la + 1, NL - 1), lpt = min(la + G.t1, NL - 1);
     const int slotsz = B * NL;
@@ -632,7 +660,6 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
         return __longlong_as_double((long long)((((unsigned long long)__double_as_longlong(b)) & takeb) |
                                                 (((unsigned long long)__double_as_longlong(a)) & ~takeb)));
     };
-    const int T0 = tile % G.nt0, T1 = (tile / G.nt0) % G.nt1, T2 = tile / (G.nt0 * G.nt1);
     for (int i = threadIdx.x; i < slotsz; i += 64 * B) { yl[i] = 0.0; xl[i] = 0.0; xl[slotsz + i] = 0.0; }
     TP_LDS_BARRIER();
     int l0;
@@ -649,11 +676,11 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
         // load a valid dummy address and keep the LDS value (mask 0).
         double gy1[WS ? RF : 1][B], gy2[WS ? RF : 1][B], gy0[B];
         unsigned long long mk0[WS ? RF : 1];
-        const unsigned long long mk1 = (WS && ti.j == 0 && T1 > 0) ? ~0ull : 0ull, mk2 = (WS && ti.k == 0 && T2 > 0) ? ~0ull : 0ull;
+        const unsigned long long mk1 = (WS && ti.j == 0 && ti.lo1) ? ~0ull : 0ull, mk2 = (WS && ti.k == 0 && ti.lo2) ? ~0ull : 0ull;
         const double *y1b = ytmp + ((long)(mk1 ? tile - G.nt0 : tile) * ns * B) * NL + (mk1 ? (G.t1 - 1) + G.t1 * ti.k : la);
         const double *y2b = ytmp + ((long)(mk2 ? tile - G.nt0 * G.nt1 : tile) * ns * B) * NL + (mk2 ? ti.j + G.t1 * (G.t2 - 1) : la);
         if (WS) {
-            const bool c0 = T0 > 0;
+            const bool c0 = ti.lo0;
             const double *y0b = ytmp + (((long)(c0 ? tile - 1 : tile) * ns + min(G.t0 - 1 + ti.j + ti.k, ns - 1)) * B) * NL + la;
 #pragma unroll
             for (int q = 0; q < B; ++q) gy0[q] = c0 ? y0b[(long)q * NL] : 0.0;
@@ -685,7 +712,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
                     gy1[WS ? k : 0][q] = y1b[((long)s1 * B + q) * NL];
                     gy2[WS ? k : 0][q] = y2b[((long)s2 * B + q) * NL];
                 }
-                mk0[WS ? k : 0] = (T0 > 0 && s == ti.j + ti.k) ? ~0ull : 0ull;
+                mk0[WS ? k : 0] = (ti.lo0 && s == ti.j + ti.k) ? ~0ull : 0ull;
             }
         };
         auto step = [&](int k, int s, double rhs_k) __attribute__((always_inline)) {
@@ -747,13 +774,13 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
         // T2+1 at step s - k; +a0 when l0 == tt0-1 (step tt0-1 + j + k): the same lane of tile T0+1 at step j + k.
         double gx1[WS ? RB : 1][B], gx2[WS ? RB : 1][B], gx0[B];
         unsigned long long nk0[WS ? RB : 1];
-        const unsigned long long nk1 = (WS && ti.j == ti.tj - 1 && T1 < G.nt1 - 1) ? ~0ull : 0ull,
-                                 nk2 = (WS && ti.k == ti.tk - 1 && T2 < G.nt2 - 1) ? ~0ull : 0ull;
+        const unsigned long long nk1 = (WS && ti.j == ti.tj - 1 && ti.hi1) ? ~0ull : 0ull,
+                                 nk2 = (WS && ti.k == ti.tk - 1 && ti.hi2) ? ~0ull : 0ull;
         const double *xsrc = WS ? xtmp : ytmp;
         const double *x1b = xsrc + ((long)(nk1 ? tile + G.nt0 : tile) * ns * B) * NL + (nk1 ? G.t1 * ti.k : la);
         const double *x2b = xsrc + ((long)(nk2 ? tile + G.nt0 * G.nt1 : tile) * ns * B) * NL + (nk2 ? ti.j : la);
         if (WS) {
-            const bool c0 = T0 < G.nt0 - 1;
+            const bool c0 = ti.hi0;
             const double *x0b = xsrc + (((long)(c0 ? tile + 1 : tile) * ns + min(ti.j + ti.k, ns - 1)) * B) * NL + la;
 #pragma unroll
             for (int q = 0; q < B; ++q) gx0[q] = c0 ? x0b[(long)q * NL] : 0.0;
@@ -790,7 +817,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
                     gx1[WS ? k : 0][q] = x1b[((long)s1 * B + q) * NL];
                     gx2[WS ? k : 0][q] = x2b[((long)s2 * B + q) * NL];
                 }
-                nk0[WS ? k : 0] = (T0 < G.nt0 - 1 && s == ti.tt0 - 1 + ti.j + ti.k) ? ~0ull : 0ull;
+                nk0[WS ? k : 0] = (ti.hi0 && s == ti.tt0 - 1 + ti.j + ti.k) ? ~0ull : 0ull;
             }
         };
         auto step = [&](int k, int s) __attribute__((always_inline)) {
@@ -1470,6 +1497,8 @@ static IluGeom geom_of(const tp_ctx *c) {
     G.ntiles = c->ilu.ntiles;
     G.rs = ilu_compact(c) ? 2 * ((G.nl + ILU_ROW_ALIGN - 1) / ILU_ROW_ALIGN * ILU_ROW_ALIGN) : 128;
     G.ws = c->ilu.whole ? 1 : 0;
+    G.bb0 = c->ilu.bb[0]; G.bb1 = c->ilu.bb[1]; G.bb2 = c->ilu.bb[2];
+    G.pb0 = c->ilu.pb[0]; G.pb1 = c->ilu.pb[1]; G.pb2 = c->ilu.pb[2];
     G.pref = nullptr;           // (set by the ILU(1) sweeps and the repack kernel only: the factorisation uses padded rows)
     G.ptot = c->ilu.ptot;
     return G;
@@ -1499,13 +1528,35 @@ void ilu_setup(tp_ctx *c) {
     t2 = std::min(t2, g.n2);
     TP_REQUIRE(t0 >= 1 && t1 >= 1 && t2 >= 1 && t1 * t2 <= 64,
                "ILU tile must satisfy t1*t2 <= 64 (one wavefront per tile)");
+    // bjacobi blocks (tp_options.ilu_block; ilu_whole = one block, the slab): boxes of bb cells cut into their own tiles.
+    // Blocks that hold one tile each ARE tiles: the tile is clipped to the block and the per-tile kernels run as always.
+    const int32_t *ob = c->opt.ilu_block;
+    const bool boxed = ob[0] > 0 || ob[1] > 0 || ob[2] > 0;
+    TP_REQUIRE(!(boxed && c->opt.ilu_whole), "ilu_block and ilu_whole (one block per rank) exclude one another");
+    const int nn[3] = {g.n0, g.n1, g.n2};
+    int tt[3] = {t0, t1, t2};
+    bool multi = c->opt.ilu_whole != 0;
+    for (int a = 0; a < 3; ++a) {
+        d.bb[a] = (boxed && ob[a] > 0) ? std::min((int)ob[a], nn[a]) : nn[a];       // (<= 0: the whole extent)
+        if (boxed) tt[a] = std::min(tt[a], d.bb[a]);
+        d.pb[a] = (d.bb[a] + tt[a] - 1) / tt[a];
+        if (boxed && d.pb[a] > 1) multi = true;
+    }
+    t0 = tt[0]; t1 = tt[1]; t2 = tt[2];
+    if (!multi) {                  // tiles from the slab's origin (with blocks of one tile: the same boxes)
+        for (int a = 0; a < 3; ++a) { d.bb[a] = nn[a]; d.pb[a] = (nn[a] + tt[a] - 1) / tt[a]; }
+    }
     d.t0 = t0; d.t1 = t1; d.t2 = t2;
-    d.nt0 = (g.n0 + t0 - 1) / t0;
-    d.nt1 = (g.n1 + t1 - 1) / t1;
-    d.nt2 = (g.n2 + t2 - 1) / t2;
+    int ntx[3];
+    for (int a = 0; a < 3; ++a) {  // full blocks of pb tiles, then the ragged last block
+        const int nfull = (nn[a] - 1) / d.bb[a], last = nn[a] - nfull * d.bb[a];
+        ntx[a] = nfull * d.pb[a] + (last + tt[a] - 1) / tt[a];
+    }
+    d.nt0 = ntx[0]; d.nt1 = ntx[1]; d.nt2 = ntx[2];
     d.ntiles = d.nt0 * d.nt1 * d.nt2;
     TP_REQUIRE(c->opt.ilu_levels == 0 || c->opt.ilu_levels == 1, "ilu_levels must be 0 or 1");
     TP_REQUIRE(!(c->opt.ilu_whole && c->opt.ilu_levels), "ilu_whole (one bjacobi block per rank) is implemented for block-ILU(0)");
+    TP_REQUIRE(!(multi && c->opt.ilu_levels), "ilu_block with blocks of more than one tile is implemented for block-ILU(0)");
     d.levels = c->opt.ilu_levels;
     static const bool mw_on = !(getenv("TP_ILU_MW") && atoi(getenv("TP_ILU_MW")) == 0);
     d.mw = mw_on && d.levels == 0;
@@ -1524,6 +1575,7 @@ void ilu_setup(tp_ctx *c) {
         d.ytmp.alloc(chunks * c->b * 64);
         d.jt.free();
         d.whole = false;
+        d.ndiag = 0;
         d.ptot = 0;
         if (pack1) {
             std::vector<int> pf(d.nsteps + 1, 0);
@@ -1545,15 +1597,16 @@ void ilu_setup(tp_ctx *c) {
         return;
     }
     if (c->b == 3) alloc_factor<3>(d, ilu_compact(c)); else alloc_factor<2>(d, ilu_compact(c));
-    d.whole = c->opt.ilu_whole != 0;
+    d.whole = multi;
     d.ndiag = 0;
     if (d.whole) {
-        TP_REQUIRE(d.mw, "ilu_whole needs the multi-wave sweep kernel (TP_ILU_MW=0 is set)");
-        // tile-diagonals: every lower neighbour tile of a tile on diagonal d lies on diagonal d-1
-        d.ndiag = d.nt0 + d.nt1 + d.nt2 - 2;
+        TP_REQUIRE(d.mw, "ilu_whole / ilu_block need the multi-wave sweep kernel (TP_ILU_MW=0 is set)");
+        // block-local tile-diagonals: every lower neighbour tile (in its block) of a tile on diagonal d lies on diagonal d-1;
+        // blocks are independent, so a launch takes diagonal d of ALL blocks
+        auto diag_of = [&](int t) { return (t % d.nt0) % d.pb[0] + ((t / d.nt0) % d.nt1) % d.pb[1] + (t / (d.nt0 * d.nt1)) % d.pb[2]; };
+        for (int t = 0; t < d.ntiles; ++t) d.ndiag = std::max(d.ndiag, diag_of(t) + 1);
         std::vector<std::vector<int>> by(d.ndiag);
-        for (int t = 0; t < d.ntiles; ++t)
-            by[t % d.nt0 + (t / d.nt0) % d.nt1 + t / (d.nt0 * d.nt1)].push_back(t);
+        for (int t = 0; t < d.ntiles; ++t) by[diag_of(t)].push_back(t);
         std::vector<int> flat;
         d.diag_off.assign(1, 0);
         for (auto &v : by) { flat.insert(flat.end(), v.begin(), v.end()); d.diag_off.push_back((int)flat.size()); }
@@ -1734,6 +1787,23 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
     if (c->b == 3) TP_ILU_PICK(3); else TP_ILU_PICK(2);
 #undef TP_ILU_PICK
     TP_HIP(hipGetLastError());
+}
+
+// what ilu_setup built (tp_ilu_layout)
+void ilu_layout(tp_ctx *c, int32_t out[8]) {
+    if (c->ilu.slots == 0) ilu_setup(c);
+    const IluData &d = c->ilu;
+    const GridDev &g = c->g;
+    if (d.whole) {
+        int mx = 0;
+        for (int i = 0; i < d.ndiag; ++i) mx = std::max(mx, d.diag_off[i + 1] - d.diag_off[i]);
+        out[0] = d.bb[0]; out[1] = d.bb[1]; out[2] = d.bb[2];
+        out[3] = ((g.n0 + d.bb[0] - 1) / d.bb[0]) * ((g.n1 + d.bb[1] - 1) / d.bb[1]) * ((g.n2 + d.bb[2] - 1) / d.bb[2]);
+        out[4] = d.ntiles; out[5] = d.ndiag; out[6] = mx; out[7] = d.ndiag;
+    } else {                       // one tile per block: one launch sweeps every tile in both directions
+        out[0] = d.t0; out[1] = d.t1; out[2] = d.t2;
+        out[3] = d.ntiles; out[4] = d.ntiles; out[5] = 1; out[6] = d.ntiles; out[7] = 1;
+    }
 }
 
 }  // namespace tp

@@ -47,6 +47,7 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
+                ("ilu_block", C.c_int32*3),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
@@ -63,7 +64,7 @@ API_SYMBOLS = (
     "tp_set_dt", "tp_get_old_state", "tp_restore_state", "tp_saturation_range", "tp_clamp_saturation",
     "tp_residual", "tp_jacobian", "tp_get_residual", "tp_export_jacobian", "tp_export_schur",
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
-    "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_amg_setup",
+    "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
     "tp_inner_stats",
 )
@@ -86,7 +87,11 @@ DEFAULT_OPTS = dict(
     schur_selfp=False,      # pc_fieldsplit_schur_precondition selfp (pc_fieldsplit_selfp, singlephase.py:322-330)
     ilu_tile=None,          # None: see default_ilu_tile (3-D: whole axis-0 lines x a balanced t1 x t2; 2-D: ~24 x 32 cells)
     ilu_levels=0,           # sub_1_sub_pc_factor_levels: 0 (block-ILU(0)) or 1 (block-ILU(1), pc_cprilu1_gmres)
-    bjacobi_blocks=None,    # -sub_1_pc_bjacobi_blocks N: N blocks over the whole grid (tiles_for_blocks); overrides ilu_tile
+    bjacobi_blocks=None,    # -sub_1_pc_bjacobi_blocks N: N blocks over the whole grid; overrides ilu_tile.  One tile per block when
+                            # such tiles fit a wavefront (tiles_for_blocks), else boxes of several tiles (blocks_for_count -> ilu_block)
+    ilu_block=None,         # bjacobi block as a box (B0, B1, B2) of cells, independent of ilu_tile (1 << 30: the whole extent):
+                            # block-ILU(0) inside each box, its tiles swept one block-local tile-diagonal per launch; restarts
+                            # at every slab.  None: every tile is a block
     ilu_whole=False,        # one bjacobi block per rank: block-ILU(0) of the whole slab (= bjacobi_blocks 1 on one GPU, PETSc's
                             # default bjacobi on several); ilu_tile is then only the unit of the diagonal-by-diagonal sweep
     # inner solve of the stage-1 pressure block K(A00) (pc cptramg: of the (p,T) system block), the V-cycle as its
@@ -140,6 +145,57 @@ def whole_ilu_tile(n, nslabs=1):
     if n2 == 1:
         return t
     return (-(-n0//max(1, -(-n0//16))), t[1], t[2])
+
+
+def block_ilu_tile(block):
+    """Sweep unit (t0, t1, t2) for bjacobi blocks of extents `block` (``ilu_block``): the rule of whole_ilu_tile applied to
+    ONE block, which is swept exactly as a whole slab of that size is -- every block contributes its tiles of block-local
+    diagonal d to launch d, so the launch count follows the block's tile grid and the tiles per launch the number of blocks."""
+    return whole_ilu_tile(tuple(int(v) for v in block), nslabs=1)
+
+
+def blocks_for_count(n, nblocks):
+    """Box (B0, B1, B2) that cuts the grid n into exactly `nblocks` bjacobi blocks of ANY size (``-sub_1_pc_bjacobi_blocks``):
+    the rule of tiles_for_blocks without the one-wavefront limit -- whole axis-0 lines first, then the most compact box.
+    Raises NotImplementedError when no box tiling gives that count."""
+    return tiles_for_blocks(n, nblocks, max_cols=None)
+
+
+def resolve_ilu_options(opts, n, nranks=1):
+    """Stage-2 layout options (ilu_tile, ilu_whole, ilu_block) of an engine on grid n = (n0, n1, n2) cut into `nranks` slabs,
+    from the user's options (a copy is returned).  ``bjacobi_blocks = N``: N = nranks is one block per rank (ilu_whole); on one
+    rank, N tiles when a tile of that size fits one wavefront, else N boxes of several tiles (ilu_block, with the sweep tile
+    of block_ilu_tile); on several slabs any other count is refused.  An explicit ilu_block is taken as given."""
+    o = dict(opts)
+    nranks = int(nranks)
+    if o.get("bjacobi_blocks") is not None:
+        # PETSc counts blocks over ALL ranks and needs at least one per rank: N blocks on N slabs = one per rank
+        if int(o["bjacobi_blocks"]) == nranks:
+            o["ilu_whole"] = True
+        elif nranks > 1:
+            raise EngineError("bjacobi_blocks counts blocks over the whole grid: on multi-slab runs only one block per "
+                              "rank (bjacobi_blocks = number of slabs, or ilu_whole) or an explicit ilu_tile / ilu_block")
+        else:
+            try:
+                o["ilu_tile"] = tiles_for_blocks(n, o["bjacobi_blocks"], max_cols=64)
+            except NotImplementedError:
+                o["ilu_block"] = blocks_for_count(n, o["bjacobi_blocks"])
+                o["ilu_tile"] = None
+    blk = o.get("ilu_block")
+    if blk is not None:
+        blk = tuple(int(v) for v in blk)
+        if len(blk) != 3 or min(blk) < 1:
+            raise ValueError("ilu_block is a triple of extents >= 1 (1 << 30: the whole extent)")
+        if o.get("ilu_whole"):
+            raise EngineError("ilu_whole (one block per rank) and ilu_block exclude one another")
+        o["ilu_block"] = blk
+    if o.get("ilu_tile") is None:
+        n2l = -(-int(n[2])//max(1, nranks))
+        if blk is not None:
+            o["ilu_tile"] = block_ilu_tile((min(blk[0], int(n[0])), min(blk[1], int(n[1])), min(blk[2], n2l)))
+        else:
+            o["ilu_tile"] = (whole_ilu_tile if o.get("ilu_whole") else default_ilu_tile)(n, nslabs=nranks)
+    return o
 
 
 def tiles_for_blocks(n, nblocks, max_cols=64):
@@ -226,17 +282,7 @@ class HipEngine:
         self.spec = spec
         self.opts = dict(DEFAULT_OPTS)
         self.opts.update(opts or {})
-        if self.opts.get("bjacobi_blocks") is not None:
-            # PETSc counts blocks over ALL ranks and needs at least one per rank: N blocks on N slabs = one per rank
-            if int(self.opts["bjacobi_blocks"]) == int(nranks):
-                self.opts["ilu_whole"] = True
-            elif int(nranks) > 1:
-                raise EngineError("bjacobi_blocks counts blocks over the whole grid: on multi-slab runs only one block per "
-                                  "rank (bjacobi_blocks = number of slabs, or ilu_whole) or an explicit ilu_tile")
-            else:
-                self.opts["ilu_tile"] = tiles_for_blocks(spec["n"], self.opts["bjacobi_blocks"], max_cols=64)
-        if self.opts["ilu_tile"] is None:
-            self.opts["ilu_tile"] = (whole_ilu_tile if self.opts.get("ilu_whole") else default_ilu_tile)(spec["n"], nslabs=int(nranks))
+        self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -296,6 +342,7 @@ class HipEngine:
                           int(o["amg_coarse_post"]), int(bool(o["amg_mid_skip"])), int(o["amg_tail_post"]), int(bool(o["amg_single"])), 2 if o.get("schur_selfp") else int(bool(o["schur_a11"])),
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
                           int(bool(o.get("ilu_whole", False))),
+                          (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
 
@@ -522,6 +569,14 @@ class HipEngine:
         axes = (C.c_int32*64)()
         self._ck(self.lib.tp_amg_layout(self.ctx, which, C.byref(nd), axes, 64, C.byref(na)))
         return nd.value, [axes[i] for i in range(min(na.value, 64))]
+
+    def ilu_layout(self):
+        """The stage-2 layout that was built (tp_ilu_layout): block extents, blocks, tiles, block-local tile-diagonals, the
+        most tiles in one launch, launches per sweep direction."""
+        out = (C.c_int32*8)()
+        self._ck(self.lib.tp_ilu_layout(self.ctx, out))
+        return dict(block=(out[0], out[1], out[2]), nblocks=out[3], ntiles=out[4], ndiag=out[5], max_tiles_per_launch=out[6],
+                    launches=out[7])
 
     def inner_stats(self):
         """Inner solves (s1_ksp != preonly) since the last pc_setup: (applies, iterations used, ended above tolerance)."""

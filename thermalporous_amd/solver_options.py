@@ -200,7 +200,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     o["fs_additive"] = False
     used = set()
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single",
-                  "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole",
+                  "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol")
     for k in build_keys:
         if k in sp:
