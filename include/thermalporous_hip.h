@@ -260,6 +260,13 @@ int tp_amg_trunc(tp_ctx *ctx, int32_t which, int32_t *level, double *ratio0);
  * distributed over the slabs (0 on one GPU and when the hierarchy is replicated, see amg_gather_cells);
  * which: 0 pressure, 1 S~, 2 the (p,T) system hierarchy of pc_cptramg */
 int tp_amg_layout(tp_ctx *ctx, int32_t which, int32_t *dist_levels, int32_t *axes, int32_t cap, int32_t *naxes);
+/* the tail of hierarchy `which` (0 pressure, 1 S~), i.e. its levels of <= 1024 cells: out = {1 if the cycles since the last
+ * set-up apply the tail as one precomputed dense operator (TP_AMG_TAIL_DENSE) else 0, first tail level, cells
+ * of that level, dense operators formed, dense applications launched or captured, multilevel tail kernels launched or
+ * captured} -- the last three counted since the hierarchy was built.  Like tp_amg_trunc this is a query of the RESOLVED state:
+ * it waits for the last set-up's dominance ratios and may enqueue the forming of the dense operator, so it belongs neither in
+ * a timed region nor in a stream capture */
+int tp_amg_tail_info(tp_ctx *ctx, int32_t which, int64_t out[6]);
 
 #ifdef __cplusplus
 }

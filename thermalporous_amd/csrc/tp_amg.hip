@@ -632,62 +632,13 @@ __global__ __launch_bounds__(256) void k_amg_prolong_add(LevelDevT<R> Lf, GridDe
 }
 
 // ---- the tail: all small levels in one workgroup --------------------------------------------------------
+// down-sweep, coarse solve and up-sweep of the levels [l0, nlev) by one workgroup of 1024 threads; `lv`: descriptors in LDS.
+// Ends behind a workgroup barrier.
 template <class R>
-__global__ __launch_bounds__(1024) void k_amg_tail(const LevelDevT<R> *lv, int l0, int nlev_all, int trunc, int ncoarse,
-                                                   const double *Minv, const double *b_top, double *e_top,
-                                                   int lds_doubles) {
-    // trunc >= l0: the hierarchy ends at level `trunc` with two damped-Jacobi sweeps instead of the dense solve
-    const int nlev = trunc >= 0 ? trunc + 1 : nlev_all;
-    extern __shared__ double dyn[];          // 4 x lds_doubles: the b, e, x, x2 vectors of every tail level
+__device__ __forceinline__ void tail_sweeps(const LevelDevT<R> *lv, int l0, int nlev, int trunc, int ncoarse,
+                                            const double *Minv, const double *b_top, double *e_top) {
     constexpr int T = 1024;            // (the launch's block size, as a constant: no blockDim fetch -- tp_common.hpp:xcd_tid)
     const int t = threadIdx.x;
-    // level descriptors live in LDS: every phase below starts with LDS reads, not a global round trip
-    static_assert(sizeof(LevelDevT<R>) % sizeof(long) == 0, "LevelDev must be a whole number of words");
-    __shared__ long slv_raw[40 * sizeof(LevelDevT<R>) / sizeof(long)];
-    {
-        const int wpl = (int)(sizeof(LevelDevT<R>) / sizeof(long));
-        const long *src = reinterpret_cast<const long *>(lv);
-        for (int i = l0 * wpl + t; i < nlev * wpl; i += T) slv_raw[i] = src[i];
-        if (lds_doubles > 0)
-            for (int i = t; i < 4 * lds_doubles; i += T) dyn[i] = 0.0;      // (halo planes must read as zero)
-        __syncthreads();
-    }
-    if (lds_doubles > 0) {
-        // the tail's vectors live in LDS: a phase boundary is then an LDS store + barrier + LDS load instead of a
-        // global store that must drain (s_waitcnt vmcnt(0)) before the barrier and an L2 round trip after it.
-        // Done by re-pointing the LDS copy of the level descriptors; the sweeps below do not change.
-        if (t == 0) {
-            LevelDevT<R> *w = reinterpret_cast<LevelDevT<R> *>(slv_raw);
-            long off = 0;
-            for (int l = l0; l < nlev; ++l) {
-                w[l].b = dyn + off;
-                w[l].e = dyn + lds_doubles + off;
-                w[l].x = dyn + 2 * lds_doubles + off;
-                w[l].x2 = dyn + 3 * lds_doubles + off;
-                off += w[l].g.ntot;
-            }
-        }
-        __syncthreads();
-    }
-    lv = reinterpret_cast<const LevelDevT<R> *>(slv_raw);
-    // Touch every read-only array of the tail (operators, inverse diagonals, weights, the dense inverse) NOW, all
-    // at once: they were written by the set-up long ago and have left the L2; otherwise each of the ~10 phases below
-    // starts with its own HBM + TLB round trip (~3 us of a ~4 us phase).
-    {
-        double sink = 0.0;
-        for (int l = l0; l < nlev; ++l) {
-            const LevelDevT<R> &L = lv[l];
-            for (long i = L.g.np + t; i < L.g.np + L.g.nown; i += T) {
-#pragma unroll
-                for (int k = 0; k < 7; ++k) sink += (double)L.op.slot(k)[i];
-                sink += (double)L.invd[i];
-                if (L.axis >= 0) sink += (double)L.wm[i] + (double)L.wp[i];
-            }
-        }
-        if (trunc < 0)
-            for (int i = t; i < ncoarse * ncoarse; i += T) sink += Minv[i];
-        if (sink == 1.2345678e-300) e_top[0] = sink;       // never true: keeps the loads alive
-    }
     // down-sweep
     for (int l = l0; l < nlev - 1; ++l) {
         const LevelDevT<R> L = lv[l];
@@ -764,6 +715,117 @@ __global__ __launch_bounds__(1024) void k_amg_tail(const LevelDevT<R> *lv, int l
             __syncthreads();
         }
     }
+}
+
+// BUILD = false: one workgroup, e_top = (tail) b_top.
+// BUILD = true: the batched launch that forms the dense tail operator (Amg::tdense).  Workgroup g takes the unit vectors
+// e_j, j = g, g + gridDim.x, ... as right-hand sides -- generated here, in the level-l0 b vector the plain tail never
+// uses -- and stores each result as COLUMN j of the row-major n x n matrix Tm (a scattered store once per set-up, so that
+// k_amg_tail_dense reads rows coalesced).  Its level vectors are the workgroup's own: LDS, or a slice of `scratch`
+// (4 x vec_doubles per workgroup, zero in the halo planes, which nothing ever writes) when they do not fit.
+struct TailBuild {
+    double *Tm = nullptr, *scratch = nullptr;
+    int vec_doubles = 0;
+};
+template <class R, bool BUILD>
+__global__ __launch_bounds__(1024) void k_amg_tail(const LevelDevT<R> *lv, int l0, int nlev_all, int trunc, int ncoarse,
+                                                   const double *Minv, const double *b_top, double *e_top,
+                                                   int lds_doubles, TailBuild tb) {
+    // trunc >= l0: the hierarchy ends at level `trunc` with two damped-Jacobi sweeps instead of the dense solve
+    const int nlev = trunc >= 0 ? trunc + 1 : nlev_all;
+    extern __shared__ double dyn[];          // 4 x lds_doubles: the b, e, x, x2 vectors of every tail level
+    constexpr int T = 1024;            // (the launch's block size, as a constant: no blockDim fetch -- tp_common.hpp:xcd_tid)
+    const int t = threadIdx.x;
+    // level descriptors live in LDS: every phase below starts with LDS reads, not a global round trip
+    static_assert(sizeof(LevelDevT<R>) % sizeof(long) == 0, "LevelDev must be a whole number of words");
+    __shared__ long slv_raw[40 * sizeof(LevelDevT<R>) / sizeof(long)];
+    {
+        const int wpl = (int)(sizeof(LevelDevT<R>) / sizeof(long));
+        const long *src = reinterpret_cast<const long *>(lv);
+        for (int i = l0 * wpl + t; i < nlev * wpl; i += T) slv_raw[i] = src[i];
+        if (lds_doubles > 0)
+            for (int i = t; i < 4 * lds_doubles; i += T) dyn[i] = 0.0;      // (halo planes must read as zero)
+        __syncthreads();
+    }
+    if (lds_doubles > 0 || BUILD) {
+        // the tail's vectors live in LDS: a phase boundary is then an LDS store + barrier + LDS load instead of a
+        // global store that must drain (s_waitcnt vmcnt(0)) before the barrier and an L2 round trip after it.
+        // Done by re-pointing the LDS copy of the level descriptors; the sweeps below do not change.
+        // (BUILD without LDS: the same re-pointing, to this workgroup's slice of the scratch)
+        if (t == 0) {
+            LevelDevT<R> *w = reinterpret_cast<LevelDevT<R> *>(slv_raw);
+            double *base = dyn;
+            long vd = lds_doubles;
+            if (BUILD && lds_doubles == 0) { vd = tb.vec_doubles; base = tb.scratch + (long)blockIdx.x * 4 * vd; }
+            long off = 0;
+            for (int l = l0; l < nlev; ++l) {
+                w[l].b = base + off;
+                w[l].e = base + vd + off;
+                w[l].x = base + 2 * vd + off;
+                w[l].x2 = base + 3 * vd + off;
+                off += w[l].g.ntot;
+            }
+        }
+        __syncthreads();
+    }
+    lv = reinterpret_cast<const LevelDevT<R> *>(slv_raw);
+    // Touch every read-only array of the tail (operators, inverse diagonals, weights, the dense inverse) NOW, all
+    // at once: they were written by the set-up long ago and have left the L2; otherwise each of the ~10 phases below
+    // starts with its own HBM + TLB round trip (~3 us of a ~4 us phase).
+    {
+        double sink = 0.0;
+        for (int l = l0; l < nlev; ++l) {
+            const LevelDevT<R> &L = lv[l];
+            for (long i = L.g.np + t; i < L.g.np + L.g.nown; i += T) {
+#pragma unroll
+                for (int k = 0; k < 7; ++k) sink += (double)L.op.slot(k)[i];
+                sink += (double)L.invd[i];
+                if (L.axis >= 0) sink += (double)L.wm[i] + (double)L.wp[i];
+            }
+        }
+        if (trunc < 0)
+            for (int i = t; i < ncoarse * ncoarse; i += T) sink += Minv[i];
+        if (sink == 1.2345678e-300) (BUILD ? tb.Tm : e_top)[0] = sink;       // never true: keeps the loads alive
+    }
+    if constexpr (!BUILD) {
+        tail_sweeps(lv, l0, nlev, trunc, ncoarse, Minv, b_top, e_top);
+    } else {
+        double *ub = lv[l0].b, *ue = lv[l0].e;
+        const long np = lv[l0].g.np;
+        const int n = (int)lv[l0].g.nown;
+        for (int j = blockIdx.x; j < n; j += gridDim.x) {
+            if (t == 0) ub[np + j] = 1.0;
+            __syncthreads();
+            tail_sweeps(lv, l0, nlev, trunc, ncoarse, Minv, ub, ue);
+            for (int i = t; i < n; i += T) tb.Tm[(long)i * n + j] = ue[np + i];
+            if (t == 0) ub[np + j] = 0.0;
+            __syncthreads();
+        }
+    }
+}
+
+// e_top = T b_top, the tail as ONE dense mat-vec spread over the chip: one wavefront per row of the row-major n x n
+// matrix (n <= 64 NK), each lane NK products in ascending column order, then a fixed butterfly -- no atomics, the same bits
+// on every call.  Every load is issued up front (clamped address, selected value): the kernel is one memory round trip.
+template <int NK>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_tail_dense(const double *__restrict__ Tm, int n, long np,
+                                                             const double *__restrict__ b, double *__restrict__ e) {
+    const int row = (int)blockIdx.x * (TP_BLOCK / 64) + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const double *tr = Tm + (long)row * n;
+    double tv[NK], bv[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int q = lane + 64 * k, qc = q < n ? q : 0;
+        tv[k] = tr[qc];
+        bv[k] = b[np + qc];
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) s += (lane + 64 * k < n) ? tv[k] * bv[k] : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) e[np + row] = s;
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -907,10 +969,25 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
     if (getenv("TP_DEBUG")) fprintf(stderr, "[tp] amg tail: level %d of %zu, %ld doubles per vector set, lds %d\n", amg->plan.tail_level, amg->lv.size(), tot, amg->tail_lds);
     if (amg->tail_lds > 0) {
         const int bytes = 120 * 1024;      // per-function limit shared by every hierarchy: always the maximum
-        TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_amg_tail<double>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_amg_tail<float>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        const void *fns[4] = {reinterpret_cast<const void *>(&k_amg_tail<double, false>),
+                              reinterpret_cast<const void *>(&k_amg_tail<float, false>),
+                              reinterpret_cast<const void *>(&k_amg_tail<double, true>),
+                              reinterpret_cast<const void *>(&k_amg_tail<float, true>)};
+        for (const void *f : fns) TP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    }
+    // dense tail (Amg::tdense): worthwhile when the tail spans at least two levels, possible for n <= 1024 (k_amg_tail_dense).
+    // Allocated here, once, and rewritten in place by every set-up: the captured pc_apply graphs keep its address.
+    const long ntop = amg->lv[amg->plan.tail_level]->g.nown;
+    amg->tail_vec = tot;
+    amg->tdense_eligible = (int)amg->lv.size() - amg->plan.tail_level >= 2 && ntop <= 1024;
+    if (amg->tdense_eligible) {
+        amg->tdense.alloc((size_t)ntop * ntop);
+        amg->tdense_groups = (int)ntop;
+        if (amg->tail_lds == 0) {
+            // level vectors in global memory: a slice per workgroup of a scratch of at most 32 MB (allocated by the first build,
+            // so a hierarchy that never forms T never pays for it); each workgroup then builds several columns
+            amg->tdense_groups = (int)std::max(1L, std::min(ntop, (32L << 20) / (4 * tot * (long)sizeof(double))));
+        }
     }
 }
 
@@ -922,6 +999,38 @@ __global__ void k_amg_import(GridDev g, Stencil A0, R *out) {
     const long c = g.np + tid;
 #pragma unroll
     for (int s = 0; s < 7; ++s) out[(long)s * g.ntot + c] = (R)A0.slot(s)[c];
+}
+
+// Form T for the operators of the last set-up: the tested tail kernel on every unit vector, one batched launch on the
+// current stream (the AMG side stream of pc_setup, or the main stream from amg_resolve_trunc; never inside a capture).
+// The ONE condition under which T has to be formed now: the cycles since the last set-up apply it, they reach the tail, and T
+// does not yet carry that set-up's number.  shape_resolved: amg->trunc is a decision (false only in the first set-up of a
+// hierarchy with truncation levels, whose dominance ratios are still on their way to the host).
+static bool tail_dense_needed(const Amg *amg, bool shape_resolved) {
+    return amg->tdense_on && shape_resolved && amg->trunc < 0 && amg->tdense_stamp != amg->setup_id;
+}
+
+static void tail_dense_build(tp_ctx *c, Amg *amg) {
+    if (amg->tail_lds == 0 && !amg->tdense_scratch.p)      // (never inside a capture: set-up or amg_resolve_trunc)
+        amg->tdense_scratch.alloc((size_t)amg->tdense_groups * 4 * amg->tail_vec);
+    const int lt = amg->plan.tail_level, nlev = (int)amg->lv.size(), n = amg->ncoarse;
+    TailBuild tb;
+    tb.Tm = amg->tdense.p;
+    tb.scratch = amg->tdense_scratch.p;
+    tb.vec_doubles = (int)amg->tail_vec;
+    const size_t lds = (size_t)4 * amg->tail_lds * sizeof(double);
+    const double *Minv = amg->coarse_inv.p + (size_t)n * n;
+    if (amg->single)
+        hipLaunchKernelGGL((k_amg_tail<float, true>), dim3(amg->tdense_groups), dim3(1024), lds, c->stream,
+                           (const LevelDevT<float> *)amg->lvdev.p, lt, nlev, -1, n, Minv, (const double *)nullptr,
+                           (double *)nullptr, amg->tail_lds, tb);
+    else
+        hipLaunchKernelGGL((k_amg_tail<double, true>), dim3(amg->tdense_groups), dim3(1024), lds, c->stream,
+                           (const LevelDevT<double> *)amg->lvdev.p, lt, nlev, -1, n, Minv, (const double *)nullptr,
+                           (double *)nullptr, amg->tail_lds, tb);
+    TP_HIP(hipGetLastError());
+    amg->tdense_stamp = amg->setup_id;
+    amg->tdense_builds++;
 }
 
 template <class R>
@@ -965,11 +1074,7 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     AmgLevel *Lc = amg->lv.back();
     const int n = amg->ncoarse;
     const StencilT<R> opc{(R *)Lc->op.base, Lc->op.slot_stride};
-    // (TP_EXP_SKIP_DENSE=1: timing experiment only -- leaves the previous inverse in place; bounds what ANY faster coarse
-    // inverse, e.g. a blocked Gauss-Jordan on v_mfma_f64_16x16x4, could gain on pc_setup: DESIGN.md 4.5)
-    static const bool skip_dense = getenv("TP_EXP_SKIP_DENSE") && atoi(getenv("TP_EXP_SKIP_DENSE")) == 1;
-    if (skip_dense && amg->dense_done) {
-    } else if (n <= 64) {
+    if (n <= 64) {
         const bool mfma = !(getenv("TP_AMG_DENSE_MFMA") && atoi(getenv("TP_AMG_DENSE_MFMA")) == 0);  // (read per set-up: A/B in one process)
         if (mfma) {
             const int bytes = (64 * 128 + 4 * 128 + 64 * 4 + 16) * (int)sizeof(double);
@@ -985,7 +1090,6 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     else
         hipLaunchKernelGGL(k_amg_dense_inverse<R>, dim3(1), dim3(256), 0, c->stream, Lc->g, opc, n, amg->coarse_inv.p,
                            amg->coarse_inv.p + (size_t)n * n);
-    amg->dense_done = true;
     std::vector<LevelDevT<R>> h;
     for (size_t l = 0; l < amg->lv.size(); ++l) h.push_back(dev_of<R>(amg, (int)l));
     amg->lvhost.assign((const char *)h.data(), (const char *)h.data() + h.size() * sizeof(LevelDevT<R>));
@@ -999,6 +1103,18 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
         amg->trunc = -1;
         c->graph_epoch++;
     }
+    // dense tail: used where it is exact -- relaxation-only truncation is decided among the first nratio levels, so with
+    // tail_level >= nratio it ends the cycle above the tail or not at all.  T is formed now unless the last resolved cycle
+    // shape never reached the tail, or, at the first set-up, no shape has been resolved yet (amg_resolve_trunc forms it
+    // when the cycles turn out to need it).  (switch read per set-up: A/B in one process)
+    amg->setup_id++;
+    const bool dense_env = !(getenv("TP_AMG_TAIL_DENSE") && atoi(getenv("TP_AMG_TAIL_DENSE")) == 0);
+    const bool dense = dense_env && amg->tdense_eligible && amg->plan.tail_level >= nratio;
+    if (dense != amg->tdense_on) {
+        amg->tdense_on = dense;
+        c->graph_epoch++;            // another kernel in the captured cycles
+    }
+    if (tail_dense_needed(amg, nratio == 0 || amg->setup_id > 1)) tail_dense_build(c, amg);
     TP_HIP(hipGetLastError());
 }
 
@@ -1018,6 +1134,8 @@ bool amg_resolve_trunc(tp_ctx *c, Amg *amg) {
     }
     const bool changed = t != amg->trunc;
     amg->trunc = t;
+    // the set-up skipped T because the previous cycles ended above the tail; these will not
+    if (tail_dense_needed(amg, true)) tail_dense_build(c, amg);      // (on the main stream, in front of the first cycle)
     return changed;
 }
 
@@ -1104,9 +1222,23 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         const double *bt = (lt == 0) ? b : Lt->b.p;
         double *et = (lt == 0) ? x : Lt->e.p;
         const int n = amg->ncoarse;
-        hipLaunchKernelGGL(k_amg_tail<R>, dim3(1), dim3(1024), (size_t)4 * amg->tail_lds * sizeof(double), c->stream,
-                           (const LevelDevT<R> *)amg->lvdev.p, lt, nlev, trunc, n,
-                           (const double *)(amg->coarse_inv.p + (size_t)n * n), bt, et, amg->tail_lds);
+        if (amg->tdense_on) {
+            // a stale operator is impossible, not unlikely: T carries the number of the set-up it was formed for
+            TP_REQUIRE(trunc < 0 && amg->tdense_stamp == amg->setup_id, "the dense AMG tail was not formed for the last set-up");
+            const int nt = (int)Lt->g.nown;
+            const dim3 gd((unsigned)((nt + TP_BLOCK / 64 - 1) / (TP_BLOCK / 64))), bd(TP_BLOCK);
+            const double *Tm = amg->tdense.p;
+            if (nt <= 256) hipLaunchKernelGGL(k_amg_tail_dense<4>, gd, bd, 0, c->stream, Tm, nt, Lt->g.np, bt, et);
+            else if (nt <= 512) hipLaunchKernelGGL(k_amg_tail_dense<8>, gd, bd, 0, c->stream, Tm, nt, Lt->g.np, bt, et);
+            else if (nt <= 768) hipLaunchKernelGGL(k_amg_tail_dense<12>, gd, bd, 0, c->stream, Tm, nt, Lt->g.np, bt, et);
+            else hipLaunchKernelGGL(k_amg_tail_dense<16>, gd, bd, 0, c->stream, Tm, nt, Lt->g.np, bt, et);
+            amg->tdense_applies++;
+        } else {
+            hipLaunchKernelGGL((k_amg_tail<R, false>), dim3(1), dim3(1024), (size_t)4 * amg->tail_lds * sizeof(double), c->stream,
+                               (const LevelDevT<R> *)amg->lvdev.p, lt, nlev, trunc, n,
+                               (const double *)(amg->coarse_inv.p + (size_t)n * n), bt, et, amg->tail_lds, TailBuild());
+            amg->tail_launches++;
+        }
     }
     // up-sweep over the big levels
     for (int l = ltop - 1; l >= 0; --l) {

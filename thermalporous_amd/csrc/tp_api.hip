@@ -912,6 +912,20 @@ int tp_amg_layout(tp_ctx *c, int32_t which, int32_t *dist_levels, int32_t *axes,
     TP_API_END
 }
 
+int tp_amg_tail_info(tp_ctx *c, int32_t which, int64_t out[6]) {
+    TP_API_BEGIN
+    Amg *amg = which == 0 ? c->amg_p : c->amg_T;
+    TP_REQUIRE(amg && out, "AMG hierarchy not built");
+    resolve_cycle_shapes(c);
+    out[0] = amg->tdense_on ? 1 : 0;
+    out[1] = amg->plan.tail_level;
+    out[2] = amg->lv[amg->plan.tail_level]->g.nown;
+    out[3] = amg->tdense_builds;
+    out[4] = amg->tdense_applies;
+    out[5] = amg->tail_launches;
+    TP_API_END
+}
+
 int tp_ilu_layout(tp_ctx *c, int32_t out[8]) {
     TP_API_BEGIN
     TP_REQUIRE(c && out, "null argument");

@@ -201,8 +201,19 @@ struct Amg {
     hipEvent_t ev_ratio = nullptr;
     bool ratio_pending = false;
     int trunc = -1;            // level that ends the cycle with two Jacobi sweeps (-1: none)
-    bool dense_done = false;   // a coarse inverse exists (TP_EXP_SKIP_DENSE timing experiment)
     double ratio0 = 0.0;
+    // dense tail: between two set-ups the tail (levels >= plan.tail_level) is a fixed linear map e = T b on the n cells of
+    // its first level.  T (row-major, n x n, allocated once: its address is part of the captured pc_apply graphs) is formed
+    // by a batched launch of the tail kernel on the unit vectors after a set-up and applied by k_amg_tail_dense.
+    DBuf<double> tdense;
+    DBuf<double> tdense_scratch;   // per-workgroup level vectors of the batched build when they do not fit the LDS
+    long tail_vec = 0;             // doubles of one vector set (b, e, x or x2) over all tail levels
+    int tdense_groups = 0;         // workgroups of the build (each walks columns j, j + groups, ...)
+    bool tdense_eligible = false;  // the tail has >= 2 levels and <= 1024 cells on its first (amg_build)
+    bool tdense_on = false;        // the cycles after the last set-up apply T (TP_AMG_TAIL_DENSE, truncation cannot land in the tail)
+    uint64_t setup_id = 0;         // counts set-ups; T is valid iff tdense_stamp == setup_id
+    uint64_t tdense_stamp = ~(uint64_t)0;
+    long tdense_builds = 0, tdense_applies = 0, tail_launches = 0;   // launches enqueued or captured (tp_amg_tail_info)
     DBuf<char> lvdev;          // device array of level descriptors (LevelDev) for the tail kernel
     std::vector<char> lvhost;
     ~Amg() {

@@ -66,7 +66,7 @@ API_SYMBOLS = (
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
-    "tp_inner_stats",
+    "tp_inner_stats", "tp_amg_tail_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -562,6 +562,14 @@ class HipEngine:
         lv, r0 = C.c_int32(), C.c_double()
         self._ck(self.lib.tp_amg_trunc(self.ctx, which, C.byref(lv), C.byref(r0)))
         return lv.value, r0.value
+
+    def amg_tail_info(self, which=0):
+        """The tail (levels of <= 1024 cells) of hierarchy `which`: whether the cycles apply it as one dense operator, its first
+        level and that level's cells, and how many dense operators were formed / dense applications / multilevel tail
+        kernels were launched or captured since the hierarchy was built."""
+        out = (C.c_int64*6)()
+        self._ck(self.lib.tp_amg_tail_info(self.ctx, which, out))
+        return dict(dense=bool(out[0]), tail_level=out[1], n=out[2], builds=out[3], dense_applies=out[4], tail_launches=out[5])
 
     def amg_layout(self, which=0):
         """(number of slab-distributed top levels, coarsening axis of every level)."""
