@@ -120,6 +120,9 @@ typedef struct tp_options {
                                 tile is a block); otherwise an entry <= 0 or beyond the slab means the whole extent.  Blocks
                                 no larger than the tile are the per-tile path with the tile clipped to the block.  ilu_whole
                                 is the case block = slab and excludes this field.  ILU(0) only for multi-tile blocks. */
+    int32_t ilu_single;      /* 1: the block-ILU(0) factor stream stored in fp32 (the factorisation, the sweeps' arithmetic and
+                                every vector stay fp64): half the factor's memory and 43 % fewer bytes per sweep.  The default
+                                per-tile ILU(0) only: not with ilu_levels 1, ilu_whole or an ilu_block of several tiles */
     /* Inner solve of the stage-1 PRESSURE block K(A00) (pc_kind 0, 1, 2) or of the (p,T) SYSTEM block (pc_kind 3): what PETSc
      * does when the sub-solver's ksp_type is not preonly.  The V-cycle becomes the (right) preconditioner of a small
      * Krylov method whose every scalar stays on the device, so it lives inside the captured pc_apply graph:
@@ -228,6 +231,9 @@ int tp_ilu0_solve(tp_ctx *ctx, int32_t x, int32_t y);
  * out = {B0, B1, B2, number of bjacobi blocks, number of tiles, block-local tile-diagonals, most tiles in one launch,
  * launches per sweep direction}.  One tile per block (the default): B = the tile, blocks = tiles, 1, tiles, 1. */
 int tp_ilu_layout(tp_ctx *ctx, int32_t out[8]);
+/* device bytes of the stage-2 factor streams, forward plus backward, for the options in force (sets the layout up if no
+ * factorisation has yet): the (tile, step) chunks the sweeps read, row padding included; halved by ilu_single */
+int tp_ilu_factor_bytes(tp_ctx *ctx, int64_t *bytes);
 int tp_amg_setup(tp_ctx *ctx, int32_t which);              /* v_cycle dict (singlephase.py:303-307); 0: pressure operator, 1: S~ */
 /* which: 0 pressure hierarchy, 1 S~ hierarchy, 2 the (p,T) system hierarchy of pc_cptramg (fields 0,1 of b -> x) */
 int tp_amg_vcycle(tp_ctx *ctx, int32_t which, int32_t field_b, int32_t b, int32_t field_x, int32_t x);

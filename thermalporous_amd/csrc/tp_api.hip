@@ -367,9 +367,12 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_API_BEGIN
     TP_REQUIRE(c && opt, "null argument");
     TP_REQUIRE(opt->ilu_levels == 0 || opt->ilu_levels == 1, "ilu_levels must be 0 or 1");
+    TP_REQUIRE(!(opt->ilu_single && opt->ilu_levels), "ilu_single (fp32 factor) is implemented for block-ILU(0): not with ilu_levels 1");
+    TP_REQUIRE(!(opt->ilu_single && opt->ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
     inner_check_options(*opt);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
+                              (opt->ilu_single != 0) != (c->opt.ilu_single != 0) ||
                               std::memcmp(opt->ilu_block, c->opt.ilu_block, sizeof(opt->ilu_block)) != 0;
     const bool amg_changed = opt->amg_min_cells != c->opt.amg_min_cells || opt->pc_kind != c->opt.pc_kind ||
                              opt->amg_nu != c->opt.amg_nu || opt->amg_full_levels != c->opt.amg_full_levels ||
@@ -923,6 +926,13 @@ int tp_amg_tail_info(tp_ctx *c, int32_t which, int64_t out[6]) {
     out[3] = amg->tdense_builds;
     out[4] = amg->tdense_applies;
     out[5] = amg->tail_launches;
+    TP_API_END
+}
+
+int tp_ilu_factor_bytes(tp_ctx *c, int64_t *bytes) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && bytes, "null argument");
+    *bytes = ilu_factor_bytes(c);
     TP_API_END
 }
 

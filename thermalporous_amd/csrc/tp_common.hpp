@@ -265,6 +265,8 @@ struct InnerWork {
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
+    DBuf<float> fwd32, bwd32;      // tp_options.ilu_single: the same streams stored as floats (fwd / bwd are then empty)
+    bool single = false;
     DBuf<double> jt;               // the Jacobian blocks re-ordered the same way (input of the factorisation)
     long slots = 0;                // ntiles*nsteps*64
     bool mw = false;               // ILU(0): factor stored in the row-major layout of the multi-wave sweep (tp_ilu.hip)
@@ -410,6 +412,7 @@ void stage1_rhs(tp_ctx *c, const double *x, int q, double *out);                
 void ilu_setup(tp_ctx *c);
 void ilu_factor(tp_ctx *c);
 void ilu_layout(tp_ctx *c, int32_t out[8]);
+long ilu_factor_bytes(tp_ctx *c);
 // x = addto + M^-1 r ; only the first nadd fields of addto are read, the others count as zero (< 0: all fields)
 void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int nadd = -1);
 // AMG.  slabs: each rank's owned global planes along axis 2 (rank_slabs; empty: not distributed); a level stays on the slabs

@@ -91,6 +91,50 @@ template <int B> struct IluLayout {
     static constexpr int PY = (B + 1) / 2;                // pairs of the intermediate vector y
     static constexpr int NEJ = 7 * B * B;                 // Jacobian entries per cell (7 blocks)
     static constexpr int PJ = (NEJ + 1) / 2;              // pairs per chunk of the re-ordered Jacobian
+    static constexpr int QF = (NEF + 3) / 4;              // float4 quads per forward / backward chunk of the fp32 stream:
+    static constexpr int QB = (NEB + 3) / 4;              // half the pairs for B = 2 and 3
+};
+
+// Storage type R of the factor stream: double, or float (tp_options.ilu_single: stage 2 is only a preconditioner inside the
+// flexible outer GMRES).  The factorisation runs in double and rounds what it WRITES to the chunks; the sweeps convert every
+// loaded entry to double and accumulate in double in the same order; right-hand side, y, x, the LDS slots and ytmp stay
+// double.  A chunk row is one 16-byte vector per lane in both: [entry pair][lane][2] doubles or [entry quad][lane][4] floats.
+template <class R> struct IluVec;
+template <> struct IluVec<double> { using V = double2; static constexpr int W = 2; };
+template <> struct IluVec<float>  { using V = float4;  static constexpr int W = 4; };
+// ring depths of the multi-wave sweep's fp32 instantiation (forward, backward with y in LDS, backward with y in HBM): the same
+// bytes in flight cover twice the steps
+#ifndef TP_ILU_RF32
+#define TP_ILU_RF32 12
+#endif
+#ifndef TP_ILU_RB32Y
+#define TP_ILU_RB32Y 12
+#endif
+#ifndef TP_ILU_RB32
+#define TP_ILU_RB32 8
+#endif
+constexpr int ILU_BLK32 = TP_ILU_RF32 > TP_ILU_RB32Y ? (TP_ILU_RF32 > TP_ILU_RB32 ? TP_ILU_RF32 : TP_ILU_RB32)
+                                                      : (TP_ILU_RB32Y > TP_ILU_RB32 ? TP_ILU_RB32Y : TP_ILU_RB32);
+static_assert(TP_ILU_RF32 % 2 == 0 && TP_ILU_RB32Y % 2 == 0 && TP_ILU_RB32 % 2 == 0, "block loads move two steps per access");
+
+// fp32 multi-wave layout.  Forward: a block row has 3B entries, FULL = 3B/4 quads of its own and REM = 3B%4 entries left over;
+// the leftovers of the B rows share ONE quad behind the rows' own (B*REM <= 4), so a chunk is B*FULL + 1 = ceil(3B^2/4) quads:
+// [tile][step][quad][lane][4], quads r*FULL .. r*FULL+FULL-1 = entries 0 .. 4*FULL-1 of row r, quad B*FULL = slots
+// r*REM .. r*REM+REM-1 <- row r's last entries; every wave loads its own quads and the shared one.  Backward: 4B entries per
+// row are B quads exactly: [tile][step][row r][quad][lane][4].
+template <int B> struct IluMw32 {
+    static constexpr int FULL = (3 * B) / 4, REM = (3 * B) % 4;
+    static constexpr int QF = B * FULL + (REM ? 1 : 0);
+    static constexpr int QB = B * B;
+    static_assert(B * REM <= 4 && QF == IluLayout<B>::QF && QB == IluLayout<B>::QB, "the leftovers of all rows fit one quad");
+    // element index inside a chunk of forward entry e = a*B + q of row r / of backward entry e of row r
+    __host__ __device__ static constexpr long fidx(int r, int e, int nl, int lane) {
+        return e < 4 * FULL ? ((long)(r * FULL + (e >> 2)) * nl + lane) * 4 + (e & 3)
+                            : ((long)(B * FULL) * nl + lane) * 4 + (r * REM + e - 4 * FULL);
+    }
+    __host__ __device__ static constexpr long bidx(int r, int e, int nl, int lane) {
+        return ((long)(r * B + (e >> 2)) * nl + lane) * 4 + (e & 3);
+    }
 };
 
 __device__ __forceinline__ long chunk_idx(const IluGeom &G, int tile, int s) {
@@ -200,10 +244,13 @@ __global__ __launch_bounds__(64 * ILU_SEG) void k_ilu_gather(IluGeom G, const do
 // whole-slab branch, `if (s + 1 < ns) load` -- makes the compiler wait with vmcnt(0) at the next use and drains the prefetched
 // chunk.  Hence: WS is a template parameter, lanes without a column store into a dump chunk behind the arrays, and the loop body
 // is two unconditional steps with clamped prefetch indices.)
-template <int B, bool CP, bool MW, bool WS = false>
-__global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__restrict__ Jt, double *fwd,
-                                                   double *bwd, const int *__restrict__ tiles) {
+// R: storage type of the factor (IluVec).  The recurrence uses the unrounded D~^-1 of the registers; only the stores round.
+template <int B, bool CP, bool MW, bool WS = false, class R = double>
+__global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__restrict__ Jt, R *fwd,
+                                                   R *bwd, const int *__restrict__ tiles) {
     using L = IluLayout<B>;
+    constexpr bool F32 = std::is_same<R, float>::value;
+    static_assert(!(F32 && WS), "the fp32 factor stream is implemented for one tile per block");
     const int tile = tiles ? tiles[blockIdx.x] : blockIdx.x, lane = threadIdx.x;      // (tiles: one tile-diagonal, G.ws)
     const int NL = CP ? G.nl : 64, RS = CP ? G.rs : 128;
     // idle lanes (>= t1*t2) load a live lane's data and store nothing.  With wave-wide rows every lane is live and both
@@ -312,11 +359,16 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
         // allocates it with 128 doubles of slack -- instead of not storing)
         const bool mlive = lane < G.nl;
         const long chs = MW ? (mlive ? chunk_idx(G, tile, s) : (long)G.ntiles * G.nsteps) : chunk_idx(G, tile, s);
-        double *fch = fwd + chs * (MW ? (long)2 * B * PFR * G.nl : (long)L::PF * RS);
-        double *bch = bwd + chs * (MW ? (long)2 * B * PBR * G.nl : (long)L::PB * RS);
-        auto fidx = [&](int a, int r, int q) { return MW ? ((long)(r * PFR + ((a * B + q) >> 1)) * G.nl + lane) * 2 + ((a * B + q) & 1)
+        // (fp32: QF / QB quads of 4 floats per lane where the doubles have PF / PB pairs; a row is RS doubles = 2 RS floats)
+        R *fch = fwd + chs * (F32 ? (MW ? (long)4 * L::QF * G.nl : (long)L::QF * 2 * RS) : MW ? (long)2 * B * PFR * G.nl : (long)L::PF * RS);
+        R *bch = bwd + chs * (F32 ? (MW ? (long)4 * L::QB * G.nl : (long)L::QB * 2 * RS) : MW ? (long)2 * B * PBR * G.nl : (long)L::PB * RS);
+        auto fidx = [&](int a, int r, int q) { return F32 ? (MW ? IluMw32<B>::fidx(r, a * B + q, G.nl, lane)
+                                                                : (long)((((a * B + r) * B + q) >> 2) * 2 * RS + lane * 4 + (((a * B + r) * B + q) & 3)))
+                                                    : MW ? ((long)(r * PFR + ((a * B + q) >> 1)) * G.nl + lane) * 2 + ((a * B + q) & 1)
                                                          : (long)((((a * B + r) * B + q) >> 1) * RS + lane * 2 + (((a * B + r) * B + q) & 1)); };
-        auto bidx = [&](int a, int r, int q) { return MW ? ((long)(r * PBR + ((a * B + q) >> 1)) * G.nl + lane) * 2 + ((a * B + q) & 1)
+        auto bidx = [&](int a, int r, int q) { return F32 ? (MW ? IluMw32<B>::bidx(r, a * B + q, G.nl, lane)
+                                                                : (long)((((a * B + r) * B + q) >> 2) * 2 * RS + lane * 4 + (((a * B + r) * B + q) & 3)))
+                                                    : MW ? ((long)(r * PBR + ((a * B + q) >> 1)) * G.nl + lane) * 2 + ((a * B + q) & 1)
                                                          : (long)((((a * B + r) * B + q) >> 1) * RS + lane * 2 + (((a * B + r) * B + q) & 1)); };
 #pragma unroll
         for (int r = 0; r < B; ++r)
@@ -342,10 +394,16 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
 #pragma unroll
                     for (int t = 0; t < B; ++t) v += Bm[r][t] * Amc[a][t][q];
                     D[r][q] -= v;
-                    if (MW || live) fch[fidx(a, r, q)] = Bm[r][q];
+                    if (MW || live) fch[fidx(a, r, q)] = (R)Bm[r][q];
                 }
         }
-        if (!MW && (L::NEF & 1) && live) fch[(L::NEF >> 1) * RS + lane * 2 + 1] = 0.0;    // padding half of the last pair
+        if constexpr (!F32) {
+            if (!MW && (L::NEF & 1) && live) fch[(L::NEF >> 1) * RS + lane * 2 + 1] = 0.0;    // padding half of the last pair
+        } else {
+#pragma unroll
+            for (int e = L::NEF; e < 4 * L::QF; ++e)                                      // padding slots of the last quad
+                if (!MW && live) fch[(long)(e >> 2) * 2 * RS + lane * 4 + (e & 3)] = 0.0f;
+        }
         if (k.ok) {
             inv_block<B>(D, Di);
         } else {
@@ -364,13 +422,13 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
                     double v = 0.0;
 #pragma unroll
                     for (int t = 0; t < B; ++t) v += Di[r][t] * k.Aup[a][t][q];
-                    if (MW || live) bch[bidx(a, r, q)] = v;
+                    if (MW || live) bch[bidx(a, r, q)] = (R)v;
                 }
 #pragma unroll
         for (int r = 0; r < B; ++r)
 #pragma unroll
             for (int q = 0; q < B; ++q) {
-                if (MW || live) bch[bidx(3, r, q)] = Di[r][q];
+                if (MW || live) bch[bidx(3, r, q)] = (R)Di[r][q];
                 Dp[r][q] = Di[r][q];
             }
 #pragma unroll
@@ -391,16 +449,22 @@ __global__ __launch_bounds__(64) void k_ilu_factor(IluGeom G, const double *__re
     if (s < ns) step(buf[0], s);
 }
 
-// one chunk = NP double2 per live lane, coalesced (rows of nl double2)
-template <int NP>
-__device__ __forceinline__ void load_chunk(const double *__restrict__ ch, int lane, int nl, double2 (&v)[NP]) {
-    const double2 *p = reinterpret_cast<const double2 *>(ch) + lane;
+// one chunk = NP double2 (fp32 stream: float4) per live lane, coalesced (rows of nl 16-byte vectors)
+template <int NP, class R, class V>
+__device__ __forceinline__ void load_chunk(const R *__restrict__ ch, int lane, int nl, V (&v)[NP]) {
+    static_assert(std::is_same<V, typename IluVec<R>::V>::value, "one 16-byte vector per lane and row");
+    const V *p = reinterpret_cast<const V *>(ch) + lane;
 #pragma unroll
     for (int i = 0; i < NP; ++i) v[i] = p[i * nl];
 }
 template <int NP>
 __device__ __forceinline__ double chunk_get(const double2 (&v)[NP], int e) {
     return (e & 1) ? v[e >> 1].y : v[e >> 1].x;
+}
+__device__ __forceinline__ float quad_at(const float4 &t, int i) { return i == 0 ? t.x : i == 1 ? t.y : i == 2 ? t.z : t.w; }
+template <int NP>
+__device__ __forceinline__ double chunk_get(const float4 (&v)[NP], int e) {
+    return (double)quad_at(v[e >> 2], e & 3);
 }
 
 // x = addto + M^-1 r  (forward then backward sweep of one tile by one wavefront).
@@ -409,12 +473,16 @@ __device__ __forceinline__ double chunk_get(const double2 (&v)[NP], int e) {
 // step s+3 -- a single wave per CU keeps ~40 KB of HBM reads outstanding.
 // YLDS: the intermediate vector y of the tile (nsteps x B x 64 doubles, 147 KB on C4) stays in the CU's LDS between
 // the two sweeps instead of going through HBM (a write, a read and their row padding: 10 % of the kernel's traffic).
-template <int B, bool DEPTH2, bool YLDS, bool CP>
-__global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__restrict__ fwd,
-                                                  const double *__restrict__ bwd, const double *__restrict__ rhs,
+// R: storage type of the factor stream (IluVec); the ring keeps its depth, so the fp32 stream has half the bytes in flight.
+template <int B, bool DEPTH2, bool YLDS, bool CP, class R = double>
+__global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const R *__restrict__ fwd,
+                                                  const R *__restrict__ bwd, const double *__restrict__ rhs,
                                                   double *__restrict__ ytmp, double *x, const double *addto,
                                                   int nadd) {
     using L = IluLayout<B>;
+    using V = typename IluVec<R>::V;
+    constexpr bool F32 = std::is_same<R, float>::value;
+    constexpr int NVF = F32 ? L::QF : L::PF, NVB = F32 ? L::QB : L::PB;       // 16-byte vectors per lane and chunk
     extern __shared__ double ylds[];       // [step][field][lane] when YLDS
     const int tile = blockIdx.x, lane = threadIdx.x;
     const int NL = CP ? G.nl : 64, RS = CP ? G.rs : 128;
@@ -423,7 +491,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
     const long nt = G.g.ntot;
     const TileInfo ti = tile_info(G, tile, lane);
     const int ns = G.nsteps;
-    const long rowF = (long)L::PF * RS, rowB = (long)L::PB * RS, rowY = (long)L::PY * RS;
+    const long rowF = (long)NVF * (F32 ? 2 * RS : RS), rowB = (long)NVB * (F32 ? 2 * RS : RS), rowY = (long)L::PY * RS;
     const long park = min((long)lane, G.g.np - 1);     // an entry of the lower halo plane: where cell-less lanes read / write
     constexpr int RING = DEPTH2 ? 3 : 2;
     constexpr int UN = TP_ILU_UNROLL;          // rings per steady-state loop iteration
@@ -434,12 +502,12 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
         double yp[B];
 #pragma unroll
         for (int r = 0; r < B; ++r) yp[r] = 0.0;
-        double2 buf[RING][L::PF];
+        V buf[RING][NVF];
         double rr[RING][B];
         bool okk[RING];
         auto load = [&](int k, int step) {
             okk[k] = tile_cell(G, ti, step, l0, c);
-            load_chunk<L::PF>(fwd + chunk_idx(G, tile, step) * rowF, la, RS >> 1, buf[k]);
+            load_chunk<NVF>(fwd + chunk_idx(G, tile, step) * rowF, la, RS >> 1, buf[k]);
             // BRANCH-FREE: a lane without a cell at this step reads entry `lane` of the lower halo plane (valid memory,
             // finite) and the value is dropped by a select.  A load or store behind a divergent branch makes the compiler
             // drain every outstanding load (s_waitcnt vmcnt(0)) at each step, prefetch ring included.
@@ -462,7 +530,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
 #pragma unroll
                 for (int r = 0; r < B; ++r)
 #pragma unroll
-                    for (int q = 0; q < B; ++q) y[r] -= chunk_get<L::PF>(buf[k], (a * B + r) * B + q) * yn[a][q];
+                    for (int q = 0; q < B; ++q) y[r] -= chunk_get<NVF>(buf[k], (a * B + r) * B + q) * yn[a][q];
             double *ych = ytmp + chunk_idx(G, tile, s) * rowY;
             const long ydump = ((long)G.nsteps * gridDim.x - chunk_idx(G, tile, s)) * rowY + ((long)tile * 64 + lane) * B;
 #pragma unroll
@@ -511,7 +579,8 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
         double xp[B];
 #pragma unroll
         for (int r = 0; r < B; ++r) xp[r] = 0.0;
-        double2 buf[RING][L::PB], ybuf[RING][YLDS ? 1 : L::PY];
+        V buf[RING][NVB];
+        double2 ybuf[RING][YLDS ? 1 : L::PY];
         double aa[RING][B];
         bool okk[RING];
         long cc[RING];
@@ -527,7 +596,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
         auto load = [&](int k, int step) {
             okk[k] = tile_cell(G, ti, step, l0, c);
             cc[k] = c;
-            load_chunk<L::PB>(bwd + chunk_idx(G, tile, step) * rowB, la, RS >> 1, buf[k]);
+            load_chunk<NVB>(bwd + chunk_idx(G, tile, step) * rowB, la, RS >> 1, buf[k]);
             if (!YLDS) load_chunk<(YLDS ? 1 : L::PY)>(ytmp + chunk_idx(G, tile, step) * rowY, la, RS >> 1, ybuf[k]);
             const long cs = okk[k] ? c : park;                // branch-free, as in the forward sweep
 #pragma unroll
@@ -546,7 +615,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
             for (int r = 0; r < B; ++r) {
                 double v = 0.0;
 #pragma unroll
-                for (int q = 0; q < B; ++q) v += chunk_get<L::PB>(buf[k], (3 * B + r) * B + q) * yv[q];
+                for (int q = 0; q < B; ++q) v += chunk_get<NVB>(buf[k], (3 * B + r) * B + q) * yv[q];
                 xv[r] = v;
             }
 #pragma unroll
@@ -554,7 +623,7 @@ __global__ __launch_bounds__(64) void k_ilu_solve(IluGeom G, const double *__res
 #pragma unroll
                 for (int r = 0; r < B; ++r)
 #pragma unroll
-                    for (int q = 0; q < B; ++q) xv[r] -= chunk_get<L::PB>(buf[k], (a * B + r) * B + q) * xn[a][q];
+                    for (int q = 0; q < B; ++q) xv[r] -= chunk_get<NVB>(buf[k], (a * B + r) * B + q) * xn[a][q];
 #pragma unroll
             for (int r = 0; r < B; ++r) {
                 xv[r] = okk[k] ? xv[r] : 0.0;
@@ -629,18 +698,26 @@ template <int B> struct IluMwLayout {
 // tile-diagonal of every block (`tiles`), forward (phase 1) or backward (phase 2); a neighbour value across a tile face inside
 // the block was produced by an EARLIER launch and is read from global memory -- y from ytmp, the raw backward result from
 // xtmp -- instead of the LDS; a tile on a block face takes nothing from beyond it (masks ti.lo* / ti.hi*).  WS implies !YLDS.
-template <int B, bool YLDS, bool BLK, bool WS = false>
-__global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double *__restrict__ fwd,
-                                                         const double *__restrict__ bwd, const double *__restrict__ rhs,
+// R: storage type of the factor stream (IluVec, IluMw32); a wave then loads FULL + 1 forward and B backward quads per step
+// where the doubles take PFR and PBR pairs.
+template <int B, bool YLDS, bool BLK, bool WS = false, class R = double>
+__global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const R *__restrict__ fwd,
+                                                         const R *__restrict__ bwd, const double *__restrict__ rhs,
                                                          double *ytmp, double *x, const double *addto, int nadd,
                                                          const int *__restrict__ tiles = nullptr, int phase = 3,
                                                          double *xtmp = nullptr) {
     static_assert(!(WS && YLDS), "whole-slab sweeps keep y in global memory");
     extern __shared__ double lds[];
     using M = IluMwLayout<B>;
+    using Q = IluMw32<B>;
+    using V = typename IluVec<R>::V;
+    constexpr bool F32 = std::is_same<R, float>::value;
+    static_assert(!(F32 && WS), "the fp32 factor stream is implemented for one tile per block");
+    constexpr int NVF = F32 ? Q::FULL + (Q::REM ? 1 : 0) : M::PFR, NVB = F32 ? B : M::PBR;      // 16-byte loads per wave and step
     // ring depths: a wave may have 63 loads in flight; what the sweep's throughput follows is BYTES in flight per CU
-    // (B waves x ring x 16-byte loads: 3 x 8 x 6 x 864 B = 124 KB on C4, against 44 KB for the one-wave kernel)
-    constexpr int RF = 8, RB = YLDS ? 8 : 6;
+    // (B waves x ring x 16-byte loads: 3 x 8 x 6 x 864 B = 124 KB on C4, against 44 KB for the one-wave kernel).  fp32: half
+    // the loads per step, so twice the ring for the same bytes (TP_ILU_RF32 ...; what was tried: DESIGN.md 4.4)
+    constexpr int RF = F32 ? TP_ILU_RF32 : 8, RB = F32 ? (YLDS ? TP_ILU_RB32Y : TP_ILU_RB32) : (YLDS ? 8 : 6);
     const int tile = WS ? tiles[blockIdx.x] : blockIdx.x, lane = threadIdx.x & 63, r = threadIdx.x >> 6;
     const int NL = G.nl, ns = G.nsteps;
     const int la = min(lane, NL - 1);                 // idle lanes shadow the last live lane's loads ...
@@ -666,7 +743,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
     long c;
     // ---- forward: y_c[r] = rhs_c[r] - sum_a B_a[r][:] y_(m_a) ------------------------------------------------------
     if (phase & 1) {
-        double2 v[RF][M::PFR];
+        V v[RF][NVF];
         double rr[RF], rrA[RF], rrB[RF];
         bool okk[RF];
         // WS: lower neighbours across a tile face.  Cell (l0, j, k) of this tile at step s; its -a1 neighbour when j == 0 is
@@ -701,9 +778,16 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
         };
         auto load = [&](int k, int s) __attribute__((always_inline)) {
             okk[k] = tile_cell(G, ti, s, l0, c) && live;
+            if constexpr (F32) {           // the row's own quads, then the quad the rows share
+                const V *ch = reinterpret_cast<const V *>(fwd + chunk_idx(G, tile, s) * (long)(4 * Q::QF * NL)) + la;
+#pragma unroll
+                for (int p = 0; p < Q::FULL; ++p) v[k][p] = ch[(long)(r * Q::FULL + p) * NL];
+                if (Q::REM) v[k][Q::FULL] = ch[(long)(B * Q::FULL) * NL];
+            } else {
             const double2 *ch = reinterpret_cast<const double2 *>(fwd + (chunk_idx(G, tile, s) * B + r) * (long)(2 * M::PFR * NL)) + la;
 #pragma unroll
             for (int p = 0; p < M::PFR; ++p) v[k][p] = ch[(long)p * NL];
+            }
             if (!BLK) rr[k] = rhs[(long)r * nt + (okk[k] ? c : park)];
             if (WS) {
                 const int s1 = min(s + G.t1 - 1, ns - 1), s2 = min(s + G.t2 - 1, ns - 1);
@@ -714,6 +798,11 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
                 }
                 mk0[WS ? k : 0] = (ti.lo0 && s == ti.j + ti.k) ? ~0ull : 0ull;
             }
+        };
+        // entry e = a*B + q of this wave's row (fp32: the last REM entries sit in the shared quad at slot r*REM + ...)
+        auto fget = [&](int k, int e) __attribute__((always_inline)) {
+            if constexpr (F32) return e < 4 * Q::FULL ? chunk_get<NVF>(v[k], e) : (double)quad_at(v[k][NVF - 1], r * Q::REM + (e - 4 * Q::FULL));
+            else return chunk_get<M::PFR>(v[k], e);
         };
         auto step = [&](int k, int s, double rhs_k) __attribute__((always_inline)) {
             const double *yp = yl + (size_t)(YLDS ? s : (s & 1)) * slotsz;      // y of step s-1
@@ -726,7 +815,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
                 for (int q = 0; q < B; ++q) {
                     double yv = yp[q * NL + src];
                     if (WS) yv = a == 0 ? pick(yv, gy0[q], mk0[WS ? k : 0]) : a == 1 ? pick(yv, gy1[WS ? k : 0][q], mk1) : pick(yv, gy2[WS ? k : 0][q], mk2);
-                    t += chunk_get<M::PFR>(v[k], a * B + q) * yv;
+                    t += fget(k, a * B + q) * yv;
                 }
                 acc[a] = t;
             }
@@ -765,7 +854,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
     }
 // ---- backward: x_c[r] = D~^-1[r][:] y_c - sum_a C_a[r][:] x_(m_a) -------------------------------------------------
     if (phase & 2) {
-        double2 v[RB][M::PBR];
+        V v[RB][NVB];
         double yb[RB][YLDS ? 1 : B], aA[RB], aB[RB], xq[RB], aa[RB];
         bool okk[RB];
         long cc[RB];
@@ -802,9 +891,9 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
         };
         auto load = [&](int k, int s) __attribute__((always_inline)) {
             okk[k] = tile_cell(G, ti, s, l0, c) && live;
-            const double2 *ch = reinterpret_cast<const double2 *>(bwd + (chunk_idx(G, tile, s) * B + r) * (long)(2 * M::PBR * NL)) + la;
+            const V *ch = reinterpret_cast<const V *>(bwd + (chunk_idx(G, tile, s) * B + r) * (long)(IluVec<R>::W * NVB * NL)) + la;
 #pragma unroll
-            for (int p = 0; p < M::PBR; ++p) v[k][p] = ch[(long)p * NL];
+            for (int p = 0; p < NVB; ++p) v[k][p] = ch[(long)p * NL];
             if (!YLDS) {
 #pragma unroll
                 for (int q = 0; q < B; ++q) yb[k][q] = ytmp[(chunk_idx(G, tile, s) * B + q) * (long)NL + la];
@@ -825,7 +914,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
             const double *yv = yl + (size_t)(s + 1) * slotsz;                   // (YLDS only)
             double t = 0.0;
 #pragma unroll
-            for (int q = 0; q < B; ++q) t += chunk_get<M::PBR>(v[k], 3 * B + q) * (YLDS ? yv[q * NL + la] : yb[k][q]);
+            for (int q = 0; q < B; ++q) t += chunk_get<NVB>(v[k], 3 * B + q) * (YLDS ? yv[q * NL + la] : yb[k][q]);
             double acc[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -835,7 +924,7 @@ __global__ __launch_bounds__(64 * B) void k_ilu_solve_mw(IluGeom G, const double
                 for (int q = 0; q < B; ++q) {
                     double xn = xp[q * NL + src];
                     if (WS) xn = a == 0 ? pick(xn, gx0[q], nk0[WS ? k : 0]) : a == 1 ? pick(xn, gx1[WS ? k : 0][q], nk1) : pick(xn, gx2[WS ? k : 0][q], nk2);
-                    u += chunk_get<M::PBR>(v[k], a * B + q) * xn;
+                    u += chunk_get<NVB>(v[k], a * B + q) * xn;
                 }
                 acc[a] = u;
             }
@@ -1509,9 +1598,18 @@ static void alloc_factor(IluData &d, bool compact) {
     using L = IluLayout<B>;
     const size_t chunks = (size_t)d.ntiles * d.nsteps,
                  rs = compact ? (size_t)2 * ((d.t1 * d.t2 + ILU_ROW_ALIGN - 1) / ILU_ROW_ALIGN * ILU_ROW_ALIGN) : 128;
+    if (d.single) {
+        // fp32 stream: QF / QB quads per chunk in both layouts (the multi-wave rows are never wider than rs), rows of 2 rs
+        // floats; + one dump chunk and 256 floats of slack, as below
+        d.fwd.free(); d.bwd.free();
+        d.fwd32.alloc((chunks + 1) * L::QF * 2 * rs + 256);
+        d.bwd32.alloc((chunks + 1) * L::QB * 2 * rs + 256);
+    } else {
+    d.fwd32.free(); d.bwd32.free();
     // (+ one dump chunk and 128 doubles of slack: where k_ilu_factor's column-less lanes store in the multi-wave layout)
     d.fwd.alloc((chunks + 1) * std::max((size_t)L::PF * rs, (size_t)B * ((3 * B + 1) / 2) * 2 * d.t1 * d.t2) + 128);   // (multi-wave layout: padded rows)
     d.bwd.alloc((chunks + 1) * L::PB * rs + 128);
+    }
     d.ytmp.alloc(chunks * L::PY * rs + (size_t)d.ntiles * 64 * B);     // + parking slots of idle lanes (branch-free stores)
     d.jt.alloc(chunks * L::PJ * rs);
 }
@@ -1557,6 +1655,11 @@ void ilu_setup(tp_ctx *c) {
     TP_REQUIRE(c->opt.ilu_levels == 0 || c->opt.ilu_levels == 1, "ilu_levels must be 0 or 1");
     TP_REQUIRE(!(c->opt.ilu_whole && c->opt.ilu_levels), "ilu_whole (one bjacobi block per rank) is implemented for block-ILU(0)");
     TP_REQUIRE(!(multi && c->opt.ilu_levels), "ilu_block with blocks of more than one tile is implemented for block-ILU(0)");
+    // fp32 factor stream: the per-tile ILU(0) sweeps only (no silent fall-back to doubles)
+    TP_REQUIRE(!(c->opt.ilu_single && c->opt.ilu_levels), "ilu_single (fp32 factor) is implemented for block-ILU(0): not with ilu_levels 1");
+    TP_REQUIRE(!(c->opt.ilu_single && c->opt.ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
+    TP_REQUIRE(!(c->opt.ilu_single && multi), "ilu_single (fp32 factor) is implemented for one tile per block: not with an ilu_block of several tiles");
+    d.single = c->opt.ilu_single != 0;
     d.levels = c->opt.ilu_levels;
     static const bool mw_on = !(getenv("TP_ILU_MW") && atoi(getenv("TP_ILU_MW")) == 0);
     d.mw = mw_on && d.levels == 0;
@@ -1564,6 +1667,7 @@ void ilu_setup(tp_ctx *c) {
     d.slots = (long)d.ntiles * d.nsteps * 64;
     c->graph_epoch++;            // new tile layout / factor buffers: captured pc_apply graphs are stale
     if (d.levels) {
+        d.fwd32.free(); d.bwd32.free();
         const size_t chunks = (size_t)d.ntiles * d.nsteps, bb = (size_t)c->b * c->b;
         static const bool pack1 = !(getenv("TP_ILU1_PACK") && atoi(getenv("TP_ILU1_PACK")) == 0);
         if (pack1 && ilu1_per_tile()) {     // the per-tile factorisation writes the packed rows itself: no padded arrays
@@ -1673,6 +1777,11 @@ void ilu_factor(tp_ctx *c) {
                 hipLaunchKernelGGL((k_ilu_factor<BB, CC, true, true>), dim3(c->ilu.diag_off[dg + 1] - c->ilu.diag_off[dg]), dim3(64), 0, \
                                    c->stream, G, c->ilu.jt.p, c->ilu.fwd.p, c->ilu.bwd.p,                              \
                                    (const int *)c->ilu.diag_tiles.p + c->ilu.diag_off[dg]);                            \
+        } else if (c->ilu.single) {                                                                                    \
+            if (c->ilu.mw) hipLaunchKernelGGL((k_ilu_factor<BB, CC, true, false, float>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, \
+                                              c->ilu.jt.p, c->ilu.fwd32.p, c->ilu.bwd32.p, (const int *)nullptr);      \
+            else hipLaunchKernelGGL((k_ilu_factor<BB, CC, false, false, float>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, \
+                                    c->ilu.jt.p, c->ilu.fwd32.p, c->ilu.bwd32.p, (const int *)nullptr);                \
         } else if (c->ilu.mw) hipLaunchKernelGGL((k_ilu_factor<BB, CC, true>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, \
                                           c->ilu.jt.p, c->ilu.fwd.p, c->ilu.bwd.p, (const int *)nullptr);              \
         else hipLaunchKernelGGL((k_ilu_factor<BB, CC, false>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, c->ilu.jt.p, \
@@ -1684,19 +1793,19 @@ void ilu_factor(tp_ctx *c) {
     TP_HIP(hipGetLastError());
 }
 
-template <int BB, bool DD, bool CC>
+template <int BB, bool DD, bool CC, class R = double>
 static void ilu_solve_launch(tp_ctx *c, const IluGeom &G, bool ylds, size_t ybytes, const double *r, double *x,
-                             const double *addto, int nadd) {
+                             const double *addto, int nadd, const R *fwd, const R *bwd) {
     if (ylds) {
         // set before every launch: the attribute is per device, and a process-wide "already set" flag would be wrong for a
         // second device and racy between slab threads (the call is a host-side table update, legal inside a capture)
-        TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu_solve<BB, DD, true, CC>),
+        TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu_solve<BB, DD, true, CC, R>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        hipLaunchKernelGGL((k_ilu_solve<BB, DD, true, CC>), dim3(c->ilu.ntiles), dim3(64), ybytes, c->stream, G, c->ilu.fwd.p,
-                           c->ilu.bwd.p, r, c->ilu.ytmp.p, x, addto, nadd);
+        hipLaunchKernelGGL((k_ilu_solve<BB, DD, true, CC, R>), dim3(c->ilu.ntiles), dim3(64), ybytes, c->stream, G, fwd,
+                           bwd, r, c->ilu.ytmp.p, x, addto, nadd);
     } else {
-        hipLaunchKernelGGL((k_ilu_solve<BB, DD, false, CC>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, c->ilu.fwd.p,
-                           c->ilu.bwd.p, r, c->ilu.ytmp.p, x, addto, nadd);
+        hipLaunchKernelGGL((k_ilu_solve<BB, DD, false, CC, R>), dim3(c->ilu.ntiles), dim3(64), 0, c->stream, G, fwd,
+                           bwd, r, c->ilu.ytmp.p, x, addto, nadd);
     }
 }
 
@@ -1749,17 +1858,23 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
         }
         static const bool ylds_mw = !(getenv("TP_ILU_YLDS") && atoi(getenv("TP_ILU_YLDS")) == 0);
         const bool yl = ylds_mw && full <= 156 * 1024;
+#define TP_ILU_MW_LAUNCH_R(BB, YY, KK, RR, FW, BW)                                                                      \
+        do {                                                                                                            \
+            TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu_solve_mw<BB, YY, KK, false, RR>),          \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));   /* per device: every launch */ \
+            hipLaunchKernelGGL((k_ilu_solve_mw<BB, YY, KK, false, RR>), dim3(c->ilu.ntiles), dim3(64 * BB), YY ? full : ring, \
+                               c->stream, G, FW, BW, r, c->ilu.ytmp.p, x, addto, nadd);                                 \
+        } while (0)
 #define TP_ILU_MW_LAUNCH(BB, YY, KK)                                                                                    \
         do {                                                                                                            \
-            TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu_solve_mw<BB, YY, KK>),                     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));   /* per device: every launch */ \
-            hipLaunchKernelGGL((k_ilu_solve_mw<BB, YY, KK>), dim3(c->ilu.ntiles), dim3(64 * BB), YY ? full : ring,      \
-                               c->stream, G, c->ilu.fwd.p, c->ilu.bwd.p, r, c->ilu.ytmp.p, x, addto, nadd);             \
+            if (c->ilu.single) TP_ILU_MW_LAUNCH_R(BB, YY, KK, float, c->ilu.fwd32.p, c->ilu.bwd32.p);                   \
+            else TP_ILU_MW_LAUNCH_R(BB, YY, KK, double, c->ilu.fwd.p, c->ilu.bwd.p);                                    \
         } while (0)
         static const int blk_env = getenv("TP_ILU_BLOCK") ? atoi(getenv("TP_ILU_BLOCK")) : -1;
         // 3-D tiles: whole axis-0 lines, long sweeps.  The block loads clamp their start into the vector; that is harmless only
-        // while every cell of a clamped block is a halo-plane cell, i.e. a plane holds at least one block (RF = 8 values)
-        const bool blk = (blk_env >= 0 ? blk_env == 1 : c->g.gn2 > 1) && c->g.np >= 8;
+        // while every cell of a clamped block is a halo-plane cell, i.e. a plane holds at least one block (RF = 8 values; the
+        // fp32 instantiation: its deepest ring)
+        const bool blk = (blk_env >= 0 ? blk_env == 1 : c->g.gn2 > 1) && c->g.np >= (c->ilu.single ? ILU_BLK32 : 8);
         if (c->b == 3) {
             if (yl) { if (blk) TP_ILU_MW_LAUNCH(3, true, true); else TP_ILU_MW_LAUNCH(3, true, false); }
             else    { if (blk) TP_ILU_MW_LAUNCH(3, false, true); else TP_ILU_MW_LAUNCH(3, false, false); }
@@ -1768,6 +1883,7 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
             else    { if (blk) TP_ILU_MW_LAUNCH(2, false, true); else TP_ILU_MW_LAUNCH(2, false, false); }
         }
 #undef TP_ILU_MW_LAUNCH
+#undef TP_ILU_MW_LAUNCH_R
         TP_HIP(hipGetLastError());
         return;
     }
@@ -1777,16 +1893,35 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
     const size_t ybytes = (size_t)G.nsteps * c->b * 64 * sizeof(double);
     const bool ylds = ylds_on && ybytes <= 152 * 1024;
     const bool cp = ilu_compact(c);
+#define TP_ILU_PICK_R(BB, FW, BW)                                                                                     \
+    do {                                                                                                              \
+        if (deep) { if (cp) ilu_solve_launch<BB, true, true>(c, G, ylds, ybytes, r, x, addto, nadd, FW, BW);          \
+                    else ilu_solve_launch<BB, true, false>(c, G, ylds, ybytes, r, x, addto, nadd, FW, BW); }          \
+        else      { if (cp) ilu_solve_launch<BB, false, true>(c, G, ylds, ybytes, r, x, addto, nadd, FW, BW);         \
+                    else ilu_solve_launch<BB, false, false>(c, G, ylds, ybytes, r, x, addto, nadd, FW, BW); }         \
+    } while (0)
 #define TP_ILU_PICK(BB)                                                                                               \
     do {                                                                                                              \
-        if (deep) { if (cp) ilu_solve_launch<BB, true, true>(c, G, ylds, ybytes, r, x, addto, nadd);                  \
-                    else ilu_solve_launch<BB, true, false>(c, G, ylds, ybytes, r, x, addto, nadd); }                  \
-        else      { if (cp) ilu_solve_launch<BB, false, true>(c, G, ylds, ybytes, r, x, addto, nadd);                 \
-                    else ilu_solve_launch<BB, false, false>(c, G, ylds, ybytes, r, x, addto, nadd); }                 \
+        if (c->ilu.single) TP_ILU_PICK_R(BB, (const float *)c->ilu.fwd32.p, (const float *)c->ilu.bwd32.p);           \
+        else TP_ILU_PICK_R(BB, (const double *)c->ilu.fwd.p, (const double *)c->ilu.bwd.p);                           \
     } while (0)
     if (c->b == 3) TP_ILU_PICK(3); else TP_ILU_PICK(2);
 #undef TP_ILU_PICK
+#undef TP_ILU_PICK_R
     TP_HIP(hipGetLastError());
+}
+
+// device bytes of the factor streams, forward plus backward (tp_ilu_factor_bytes).  ILU(0): the chunks of every (tile, step) as
+// they lie in memory, row padding included -- not the dump chunk and the fixed slack behind them, which only the idle lanes of
+// the factorisation store into and no sweep reads (1 KiB per stream in either precision).  ILU(1): the arrays as allocated.
+long ilu_factor_bytes(tp_ctx *c) {
+    if (c->ilu.slots == 0) ilu_setup(c);
+    const IluData &d = c->ilu;
+    if (d.levels) return (long)((d.fwd.n + d.bwd.n + d.fwdp.n + d.bwdp.n) * sizeof(double));
+    // (alloc_factor: one dump chunk and 128 doubles / 256 floats of slack behind the chunks of each stream)
+    const size_t chunks = (size_t)d.ntiles * d.nsteps;
+    if (d.single) return (long)(((d.fwd32.n - 256) + (d.bwd32.n - 256)) / (chunks + 1) * chunks * sizeof(float));
+    return (long)(((d.fwd.n - 128) + (d.bwd.n - 128)) / (chunks + 1) * chunks * sizeof(double));
 }
 
 // what ilu_setup built (tp_ilu_layout)

@@ -47,7 +47,7 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
-                ("ilu_block", C.c_int32*3),
+                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
@@ -66,7 +66,7 @@ API_SYMBOLS = (
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
-    "tp_inner_stats", "tp_amg_tail_info",
+    "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes",
 )
 
 DEFAULT_OPTS = dict(
@@ -92,6 +92,8 @@ DEFAULT_OPTS = dict(
     ilu_block=None,         # bjacobi block as a box (B0, B1, B2) of cells, independent of ilu_tile (1 << 30: the whole extent):
                             # block-ILU(0) inside each box, its tiles swept one block-local tile-diagonal per launch; restarts
                             # at every slab.  None: every tile is a block
+    ilu_single=False,       # the ILU(0) factor stream stored in fp32, everything else fp64 (as amg_single for the AMG): half the
+                            # factor's memory; the default per-tile ILU(0) only (not with ilu_levels 1, ilu_whole, multi-tile ilu_block)
     ilu_whole=False,        # one bjacobi block per rank: block-ILU(0) of the whole slab (= bjacobi_blocks 1 on one GPU, PETSc's
                             # default bjacobi on several); ilu_tile is then only the unit of the diagonal-by-diagonal sweep
     # inner solve of the stage-1 pressure block K(A00) (pc cptramg: of the (p,T) system block), the V-cycle as its
@@ -195,6 +197,19 @@ def resolve_ilu_options(opts, n, nranks=1):
             o["ilu_tile"] = block_ilu_tile((min(blk[0], int(n[0])), min(blk[1], int(n[1])), min(blk[2], n2l)))
         else:
             o["ilu_tile"] = (whole_ilu_tile if o.get("ilu_whole") else default_ilu_tile)(n, nslabs=nranks)
+    if o.get("ilu_single"):
+        # the fp32 factor stream exists for the default per-tile block-ILU(0) only (tp_options.ilu_single): no silent doubles
+        if int(o.get("ilu_levels", 0)) != 0:
+            raise EngineError("ilu_single with ilu_levels = %r: the fp32 factor is implemented for block-ILU(0)" % (o["ilu_levels"],))
+        if o.get("ilu_whole"):
+            raise EngineError("ilu_single with ilu_whole (one block per rank, bjacobi_blocks = number of slabs): the fp32 factor "
+                              "is implemented for one tile per bjacobi block")
+        if blk is not None:
+            ext = (int(n[0]), int(n[1]), -(-int(n[2])//max(1, nranks)))
+            box = [min(blk[a], ext[a]) for a in range(3)]
+            if any(-(-box[a]//max(1, min(int(o["ilu_tile"][a]), box[a]))) > 1 for a in range(3)):
+                raise EngineError("ilu_single with an ilu_block of several tiles (block %r, tile %r): the fp32 factor is "
+                                  "implemented for one tile per bjacobi block" % (tuple(box), tuple(o["ilu_tile"])))
     return o
 
 
@@ -343,6 +358,7 @@ class HipEngine:
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
                           int(bool(o.get("ilu_whole", False))),
                           (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
+                          int(bool(o.get("ilu_single", False))),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
 
@@ -520,6 +536,9 @@ class HipEngine:
     def stage1_apply(self, x, y):
         self._ck(self.lib.tp_stage1_apply(self.ctx, self.vec(x), self.vec(y)))
 
+    def ilu_factor(self):
+        self._ck(self.lib.tp_ilu0_factor(self.ctx))
+
     def ilu_solve(self, x, y):
         self._ck(self.lib.tp_ilu0_solve(self.ctx, self.vec(x), self.vec(y)))
 
@@ -585,6 +604,12 @@ class HipEngine:
         self._ck(self.lib.tp_ilu_layout(self.ctx, out))
         return dict(block=(out[0], out[1], out[2]), nblocks=out[3], ntiles=out[4], ndiag=out[5], max_tiles_per_launch=out[6],
                     launches=out[7])
+
+    def ilu_factor_bytes(self):
+        """Device bytes of the stage-2 factor streams, forward plus backward (tp_ilu_factor_bytes)."""
+        out = C.c_int64()
+        self._ck(self.lib.tp_ilu_factor_bytes(self.ctx, C.byref(out)))
+        return out.value
 
     def inner_stats(self):
         """Inner solves (s1_ksp != preonly) since the last pc_setup: (applies, iterations used, ended above tolerance)."""

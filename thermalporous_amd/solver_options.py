@@ -134,8 +134,21 @@ def _take_inner(sp, prefix, used, o, ksp_default=None):
     _set_inner(o, "fgmres", k, rtol, atol)
 
 
+def _check_ilu_single(o):
+    """ilu_single stores the factor of the default per-tile block-ILU(0) in fp32; the other stage-2 variants keep doubles and
+    are refused with it (blocks of several tiles depend on the grid: thermalporous_amd.engine.resolve_ilu_options)."""
+    if not o.get("ilu_single"):
+        return
+    if int(o.get("ilu_levels", 0)) != 0:
+        raise NotImplementedError("ilu_single with ilu_levels = %r: the fp32 factor is implemented for block-ILU(0)"
+                                  % (o["ilu_levels"],))
+    if o.get("ilu_whole"):
+        raise NotImplementedError("ilu_single with ilu_whole: the fp32 factor is implemented for one tile per bjacobi block")
+
+
 def _check_inner(o):
-    """Validate s1_* however they were given (build keys or PETSc spelling)."""
+    """Validate s1_* however they were given (build keys or PETSc spelling), and ilu_single against the stage-2 layout."""
+    _check_ilu_single(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
         raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
@@ -199,7 +212,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     o["schur_selfp"] = False
     o["fs_additive"] = False
     used = set()
-    build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single",
+    build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol")
     for k in build_keys:
