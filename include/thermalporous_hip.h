@@ -123,6 +123,12 @@ typedef struct tp_options {
     int32_t ilu_single;      /* 1: the block-ILU(0) factor stream stored in fp32 (the factorisation, the sweeps' arithmetic and
                                 every vector stay fp64): half the factor's memory and 43 % fewer bytes per sweep.  The default
                                 per-tile ILU(0) only: not with ilu_levels 1, ilu_whole or an ilu_block of several tiles */
+    int32_t amg_line_levels; /* L >= 0: the first L levels of the scalar hierarchies (pressure, S~ / A_11) smooth with line-Jacobi
+                                along internal axis 0, x <- x + amg_omega T^-1 (b - A x), T = the tridiagonal part of the level's
+                                operator along that axis (one Thomas solve per line), instead of damped point Jacobi.  A level
+                                is a line level when it is above the single-workgroup tail, among the first L levels and has
+                                n0 >= 2; L <= amg_full_levels.  0 (default): off, the point-Jacobi launch sequence.  One slab
+                                only; not with amg_single, pc_kind 3 or schur_a11 = 2 (refused, never ignored) */
     /* Inner solve of the stage-1 PRESSURE block K(A00) (pc_kind 0, 1, 2) or of the (p,T) SYSTEM block (pc_kind 3): what PETSc
      * does when the sub-solver's ksp_type is not preonly.  The V-cycle becomes the (right) preconditioner of a small
      * Krylov method whose every scalar stays on the device, so it lives inside the captured pc_apply graph:
@@ -273,6 +279,9 @@ int tp_amg_layout(tp_ctx *ctx, int32_t which, int32_t *dist_levels, int32_t *axe
  * it waits for the last set-up's dominance ratios and may enqueue the forming of the dense operator, so it belongs neither in
  * a timed region nor in a stream capture */
 int tp_amg_tail_info(tp_ctx *ctx, int32_t which, int64_t out[6]);
+/* line relaxation of hierarchy `which` (0 pressure, 1 S~) as planned from amg_line_levels: out = {line levels in effect, lines
+ * per workgroup on level 0 (0 if level 0 is no line level), n0 of level 0, device bytes of the factor streams of all line levels} */
+int tp_amg_line_info(tp_ctx *ctx, int32_t which, int64_t out[4]);
 
 #ifdef __cplusplus
 }

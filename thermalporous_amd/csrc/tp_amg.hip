@@ -631,6 +631,91 @@ __global__ __launch_bounds__(256) void k_amg_prolong_add(LevelDevT<R> Lf, GridDe
     x[Lf.g.np + tid] += prolong_val<R, false>(Lf, gc, ec, i0, i1, i2);
 }
 
+// ---- line relaxation along axis 0 (tp_options.amg_line_levels) ------------------------------------------------
+// x <- x + omega T^-1 (b - A x), T = tridiag(A[1], A[0], A[2]) along axis 0: one independent system per line (i1, i2), solved
+// by the Thomas algorithm with factors computed once per set-up.  Axis 0 is the fastest in memory, so G consecutive lines
+// (flattened index i1 + n1 i2) are one contiguous run of G n0 doubles: a workgroup owns such a run.  The factor streams are
+// stored line-transposed, [group][i0][line of the group], so that with lane <-> line and step <-> i0 every step's loads are
+// contiguous over the lanes.
+struct LineDev {
+    const double *m, *invd, *ap;   // m_i = a-_i / d~_{i-1} (m_0 = 0), 1 / d~_i, a+_i
+    int G, S;                      // lines per workgroup; line stride of the LDS image in doubles (odd: ds_read_b64 of lane-per-
+                                   // line addresses j S + i hits 32 different bank pairs per half-wave)
+};
+
+// set-up: d~_0 = a0_0, m_i = a-_i / d~_{i-1}, d~_i = a0_i - m_i a+_{i-1}.  One lane per line, one workgroup per group: the stores are
+// contiguous over the lanes; the loads walk each lane's own line (neighbouring steps share cache lines), once per set-up.
+template <class R>
+__global__ __launch_bounds__(64) void k_amg_line_factor(GridDev g, StencilT<R> A, int G, double *m, double *invd, double *ap) {
+    const long nlines = (long)g.n1 * g.n2;
+    const long line = (long)blockIdx.x * G + threadIdx.x;
+    if ((int)threadIdx.x >= G || line >= nlines) return;
+    const int n0 = g.n0;
+    const long c = g.np + line * n0;
+    long q = (long)blockIdx.x * n0 * G + threadIdx.x;
+    double d = (double)A.slot(0)[c];
+    m[q] = 0.0;
+    invd[q] = 1.0 / d;
+    ap[q] = (double)A.slot(2)[c];
+    for (int i = 1; i < n0; ++i) {
+        q += G;
+        const double mi = (double)A.slot(1)[c + i] / d;
+        d = (double)A.slot(0)[c + i] - mi * (double)A.slot(2)[c + i - 1];
+        m[q] = mi;
+        invd[q] = 1.0 / d;
+        ap[q] = (double)A.slot(2)[c + i];
+    }
+}
+
+// one sweep, out = x + omega T^-1 (b - A x); ZERO: the first sweep from the zero guess, out = omega T^-1 b (x is not read).
+// Like k_amg_jacobi it reads only the OLD iterate (x != out) and depends on no other workgroup.
+//   A: every thread, cell by cell: the full 7-point residual into the LDS image [line][i0]
+//   B: lane j < lines of the group: forward y_i = r_i - m_i y_{i-1}, backward e_i = (y_i - a+_i e_{i+1}) / d~_i, in place
+//   C: every thread: out = x + omega e
+template <class R, bool ZERO>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_line_sweep(LevelDevT<R> L, LineDev F, double omega, const double *__restrict__ b,
+                                                             const double *__restrict__ x, double *__restrict__ out) {
+    extern __shared__ double img[];          // G x S
+    const int n0 = L.g.n0, G = F.G, S = F.S, t = threadIdx.x;
+    const long nlines = (long)L.g.n1 * L.g.n2, line0 = (long)blockIdx.x * G;
+    const int nl = (int)(nlines - line0 < G ? nlines - line0 : G);          // ragged last group
+    const int ncell = nl * n0;
+    const long c0 = L.g.np + line0 * n0;
+    for (int idx = t; idx < ncell; idx += TP_BLOCK) {
+        const unsigned j = (unsigned)idx / (unsigned)n0, i = (unsigned)idx - j * (unsigned)n0;
+        double r;
+        if constexpr (ZERO) r = b[c0 + idx];
+        else r = resid_at(L, b, x, c0 + idx);
+        img[j * S + i] = r;
+    }
+    __syncthreads();
+    if (t < nl) {
+        double *y = img + t * S;
+        const long q0 = (long)blockIdx.x * n0 * G + t;
+        double v = y[0];
+#pragma unroll 4
+        for (int i = 1; i < n0; ++i) {
+            v = y[i] - F.m[q0 + (long)i * G] * v;
+            y[i] = v;
+        }
+        v *= F.invd[q0 + (long)(n0 - 1) * G];
+        y[n0 - 1] = v;
+#pragma unroll 4
+        for (int i = n0 - 2; i >= 0; --i) {
+            const long q = q0 + (long)i * G;
+            v = (y[i] - F.ap[q] * v) * F.invd[q];
+            y[i] = v;
+        }
+    }
+    __syncthreads();
+    for (int idx = t; idx < ncell; idx += TP_BLOCK) {
+        const unsigned j = (unsigned)idx / (unsigned)n0, i = (unsigned)idx - j * (unsigned)n0;
+        const double e = omega * img[j * S + i];
+        if constexpr (ZERO) out[c0 + idx] = e;
+        else out[c0 + idx] = x[c0 + idx] + e;
+    }
+}
+
 // ---- the tail: all small levels in one workgroup --------------------------------------------------------
 // down-sweep, coarse solve and up-sweep of the levels [l0, nlev) by one workgroup of 1024 threads; `lv`: descriptors in LDS.
 // Ends behind a workgroup barrier.
@@ -835,6 +920,28 @@ std::vector<std::pair<int, int>> rank_slabs(const tp_ctx *c) {
     return slabs;
 }
 
+// Line relaxation (tp_options.amg_line_levels): the ONE place its layout rules live.  Lines per workgroup G of a level with
+// lines of n0 cells: the LDS image of a workgroup, G lines at a stride of S = n0 | 1 doubles, stays within 48 KiB (three
+// workgroups per CU beside each other, and below the 64 KiB a kernel may use without opting in); at most 64 (one lane per line:
+// the substitution is one wavefront) and no more than the level has lines.  n0 = 85 (C4): 64 lines; n0 = 340 (config 5): 18.
+static constexpr long LINE_LDS_BYTES = 48 * 1024;
+static int line_stride(int n0) { return n0 | 1; }
+static int line_group(const GridDev &g) {
+    const long fit = LINE_LDS_BYTES / ((long)sizeof(double) * line_stride(g.n0));
+    return (int)std::max(0L, std::min({64L, fit, (long)g.n1 * g.n2}));
+}
+
+void amg_line_check_options(const tp_options &o, int nranks) {
+    const int L = o.amg_line_levels;
+    TP_REQUIRE(L >= 0, "amg_line_levels must be >= 0");
+    if (L == 0) return;
+    TP_REQUIRE(L <= o.amg_full_levels, "amg_line_levels must not exceed amg_full_levels: line levels are V(nu,nu) levels, never pure-transfer or paired ones");
+    TP_REQUIRE(!o.amg_single, "amg_line_levels (line relaxation) keeps its factor streams in fp64: not with amg_single");
+    TP_REQUIRE(o.pc_kind != 3, "amg_line_levels (line relaxation) is implemented for the scalar hierarchies: not with pc_kind 3 (pc_cptramg, the system AMG)");
+    TP_REQUIRE(o.schur_a11 != 2, "amg_line_levels (line relaxation) is not implemented for schur_a11 = 2 (schur_selfp)");
+    TP_REQUIRE(nranks <= 1, "amg_line_levels (line relaxation) is implemented for one slab: not with nranks > 1");
+}
+
 // g0: the grid the hierarchy coarsens -- the slab itself on one GPU, the GLOBAL grid on several.  There the top
 // levels (more than gather_cells cells, at least two planes on every rank) stay distributed over the slabs
 // and the rest of the hierarchy is built on the gathered global grid, replicated on every rank; a problem
@@ -896,7 +1003,30 @@ AmgPlan amg_plan(const GridDev &g0, const double strength[3], const tp_options &
     P.tail_level = (int)P.lv.size() - 1;
     for (size_t l = (size_t)P.dist_levels; l < P.lv.size(); ++l)
         if (P.lv[l].g.nown <= tail_cells) { P.tail_level = (int)l; break; }
+    // line levels: above the tail, among the first amg_line_levels levels (all of them V(nu,nu): amg_line_check_options), n0 >= 2
+    for (int l = 0; l < std::min(o.amg_line_levels, P.tail_level); ++l)
+        if (P.lv[l].g.n0 >= 2) {
+            P.lv[l].line_g = line_group(P.lv[l].g);
+            TP_REQUIRE(P.lv[l].line_g >= 1, "amg_line_levels: a line of this level does not fit the LDS budget of the line sweep");
+        }
     return P;
+}
+
+static long line_groups(const AmgPlan::Level &P) { return ((long)P.g.n1 * P.g.n2 + P.line_g - 1) / P.line_g; }
+static size_t line_stream_doubles(const AmgPlan::Level &P) { return (size_t)line_groups(P) * P.g.n0 * P.line_g; }
+static LineDev line_of(const Amg *amg, int level) {
+    const AmgPlan::Level &P = amg->plan.lv[level];
+    const size_t n = line_stream_doubles(P);
+    const double *f = amg->lv[level]->linef.p;
+    return LineDev{f, f + n, f + 2 * n, P.line_g, line_stride(P.g.n0)};
+}
+
+void amg_line_info(const Amg *amg, int64_t out[4]) {
+    out[0] = out[3] = 0;
+    for (size_t l = 0; l < amg->lv.size(); ++l)
+        if (amg->plan.lv[l].line_g > 0) { out[0]++; out[3] += (int64_t)amg->lv[l]->linef.n * (int64_t)sizeof(double); }
+    out[1] = amg->plan.lv[0].line_g;
+    out[2] = amg->plan.lv[0].g.n0;
 }
 
 template <class R>
@@ -952,6 +1082,11 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
             take(L->b, nt, ntp); take(L->x, nt, ntp); take(L->x2, nt, ntp); take(L->e, nt, ntp);
             if (L->axis >= 0) { take(L->wm, nt, ntp); take(L->wp, nt, ntp); }
         }
+    }
+    // factor streams of the line levels: allocated here, once, and rewritten in place by every set-up (captured graphs keep them)
+    for (size_t l = 0; l < amg->lv.size(); ++l) {
+        const AmgPlan::Level &P = amg->plan.lv[l];
+        if (P.line_g > 0) amg->lv[l]->linef.alloc(3 * line_stream_doubles(P));
     }
     amg->ncoarse = (int)amg->lv.back()->g.nown;
     TP_REQUIRE(amg->ncoarse <= 1024, "coarsest AMG grid too large for the dense solve");
@@ -1054,6 +1189,13 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
         hipLaunchKernelGGL(k_amg_weights<R>, grid_for(L->g.nown, want_ratio ? 1024 : 256), dim3(want_ratio ? 1024 : 256), 0, c->stream, L->g, op, L->axis,
                            c->opt.amg_omega, (R *)L->wm.p, (R *)L->wp.p, (R *)L->invd.p,
                            (int)l < nratio ? (unsigned long long *)amg->ratio_dev.p + 64 * l : (unsigned long long *)nullptr);
+        if constexpr (sizeof(R) == sizeof(double)) {
+            if (amg->plan.lv[l].line_g > 0) {      // line level: Thomas factors of every line, in this hierarchy's stream chain
+                const LineDev F = line_of(amg, (int)l);
+                hipLaunchKernelGGL(k_amg_line_factor<R>, dim3((unsigned)line_groups(amg->plan.lv[l])), dim3(64), 0, c->stream, L->g, op,
+                                   F.G, const_cast<double *>(F.m), const_cast<double *>(F.invd), const_cast<double *>(F.ap));
+            }
+        }
         if ((int)l < lg) {
             // distributed level: the cycle reads inverse diagonals and weights of the neighbours' boundary planes,
             // coarsening along the slab axis also their operator rows
@@ -1166,6 +1308,20 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     auto hx = [&](int l, const double *v) {        // halo exchange of a level-l vector (no-op below lg)
         if (l < lg) halo_exchange(c, amg->lv[l]->g, const_cast<double *>(v), 1, 0);
     };
+    // line levels (amg_line_levels; one slab, fp64 operators: amg_line_check_options): every sweep is k_amg_line_sweep
+    auto is_line = [&](int l) { return amg->plan.lv[l].line_g > 0; };
+    auto line_sweep = [&](int l, const double *bb, const double *xin, double *xout) {      // xin == nullptr: from the zero guess
+        if constexpr (sizeof(R) == sizeof(double)) {
+            const AmgPlan::Level &P = amg->plan.lv[l];
+            const LineDev F = line_of(amg, l);
+            const dim3 gl((unsigned)line_groups(P));
+            const size_t lds = (size_t)F.G * F.S * sizeof(double);
+            if (xin) hipLaunchKernelGGL((k_amg_line_sweep<R, false>), gl, dim3(TP_BLOCK), lds, c->stream, dev_of<R>(amg, l), F, c->opt.amg_omega, bb, xin, xout);
+            else hipLaunchKernelGGL((k_amg_line_sweep<R, true>), gl, dim3(TP_BLOCK), lds, c->stream, dev_of<R>(amg, l), F, c->opt.amg_omega, bb, xin, xout);
+        } else {
+            throw Error("line relaxation (amg_line_levels) with fp32 operators (amg_single)");
+        }
+    };
     // down-sweep over the big levels
     for (int l = 0; l < ltop; ++l) {
         AmgLevel *L = amg->lv[l];
@@ -1188,12 +1344,20 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             hipLaunchKernelGGL(k_amg_restrict<R>, xcd_grid(cv.g.nown), bl, 0, c->stream, Ld, cv.g, bl_, bc);
         } else {
             double *cur = L->x.p, *oth = L->x2.p;
+            if (is_line(l)) {                       // the sweep from the zero guess, then plain line sweeps
+                line_sweep(l, bl_, nullptr, cur);
+                for (int k = 1; k < Ld.pre; ++k) {
+                    line_sweep(l, bl_, cur, oth);
+                    std::swap(cur, oth);
+                }
+            } else {
             if (Ld.pre >= 2) hx(l, bl_);            // the fused double sweep reads invd*b of the neighbours
             hipLaunchKernelGGL(k_amg_pre<R>, gr, bl, 0, c->stream, Ld, bl_, Ld.pre >= 2 ? 1 : 0, cur);
             for (int k = 2; k < Ld.pre; ++k) {
                 hx(l, cur);
                 hipLaunchKernelGGL(k_amg_jacobi<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)cur, oth);
                 std::swap(cur, oth);
+            }
             }
             xs[l] = cur;
             hx(l, cur);
@@ -1214,8 +1378,13 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         AmgLevel *L = amg->lv[trunc];
         const double *bt = (trunc == 0) ? b : L->b.p;
         double *et = (trunc == 0) ? x : L->e.p;
+        if (is_line(trunc)) {                       // its two sweeps as line sweeps
+            line_sweep(trunc, bt, nullptr, L->x.p);
+            line_sweep(trunc, bt, L->x.p, et);
+        } else {
         hx(trunc, bt);                              // the fused double sweep reads invd*b of the neighbours
         hipLaunchKernelGGL(k_amg_pre<R>, xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, trunc), bt, 1, et);
+        }
     } else {
         // the tail: every level from lt down to the coarsest (or the truncation level) and back, one launch
         AmgLevel *Lt = amg->lv[lt];
@@ -1267,6 +1436,17 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         hx(l + 1, Lc->e.p);                         // distributed coarse level: parents across the boundary
         if (Ld.post == 0) {                         // pure transfer level
             hipLaunchKernelGGL(k_amg_prolong_set<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, out);
+            continue;
+        }
+        if (is_line(l)) {                           // the unfused sequence whatever fuse_below says: x += P ec, then line sweeps
+            TP_REQUIRE(src, "a line level has pre-smoothing sweeps");
+            hipLaunchKernelGGL(k_amg_prolong_add<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, src);
+            line_sweep(l, bl_, src, dst);
+            for (int k = 1; k < Ld.post; ++k) {
+                src = dst;
+                dst = (k == Ld.post - 1) ? out : (src == L->x.p ? L->x2.p : L->x.p);
+                line_sweep(l, bl_, src, dst);
+            }
             continue;
         }
         if (src && L->g.nown >= amg->fuse_below) {

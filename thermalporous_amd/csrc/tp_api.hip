@@ -319,6 +319,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     TP_REQUIRE(ndev > 0, "no HIP device: the thermalporous hot path has no CPU fallback");
     TP_REQUIRE(device >= 0 && device < ndev, "bad device ordinal");
     inner_check_options(*opt);
+    amg_line_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
     c->grid = *grid; c->prm = *prm; c->opt = *opt; c->device = device;
@@ -370,6 +371,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_levels), "ilu_single (fp32 factor) is implemented for block-ILU(0): not with ilu_levels 1");
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
     inner_check_options(*opt);
+    amg_line_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
                               (opt->ilu_single != 0) != (c->opt.ilu_single != 0) ||
@@ -378,7 +380,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
                              opt->amg_nu != c->opt.amg_nu || opt->amg_full_levels != c->opt.amg_full_levels ||
                              opt->amg_coarse_pre != c->opt.amg_coarse_pre || opt->amg_coarse_post != c->opt.amg_coarse_post ||
                              opt->amg_tail_post != c->opt.amg_tail_post || opt->amg_mid_skip != c->opt.amg_mid_skip ||
-                             opt->amg_dom_tau != c->opt.amg_dom_tau ||
+                             opt->amg_dom_tau != c->opt.amg_dom_tau || opt->amg_line_levels != c->opt.amg_line_levels ||
                              opt->amg_single != c->opt.amg_single || opt->amg_gather_cells != c->opt.amg_gather_cells ||
                              opt->schur_a11 != c->opt.schur_a11 || opt->fs_additive != c->opt.fs_additive;
     c->opt = *opt;
@@ -926,6 +928,15 @@ int tp_amg_tail_info(tp_ctx *c, int32_t which, int64_t out[6]) {
     out[3] = amg->tdense_builds;
     out[4] = amg->tdense_applies;
     out[5] = amg->tail_launches;
+    TP_API_END
+}
+
+int tp_amg_line_info(tp_ctx *c, int32_t which, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out && (which == 0 || which == 1), "bad arguments");
+    Amg *amg = which == 0 ? c->amg_p : c->amg_T;
+    TP_REQUIRE(amg, "AMG hierarchy not built");
+    amg_line_info(amg, out);
     TP_API_END
 }
 

@@ -151,6 +151,9 @@ struct AmgPlan {
         GridDev g;             // levels [0, dist_levels): this rank's slab of the level; below: the whole box, dead halo planes
         int axis = -1;         // coarsening axis towards the next level (-1: coarsest)
         int pre = 0, post = 0; // smoothing sweeps V(pre, post); post == 0: pure transfer level
+        // line relaxation (tp_options.amg_line_levels): the level's sweeps are line-Jacobi along axis 0, one workgroup per
+        // line_g consecutive lines (flattened line index i1 + n1 i2); line_g == 0: point Jacobi
+        int line_g = 0;
     };
     std::vector<int> sched;    // axis of every coarsening step
     std::vector<Level> lv;     // sched.size() + 1 levels
@@ -180,6 +183,9 @@ struct AmgLevel {
     DBuf<double> invd;     // omega / diag
     DBuf<double> wm, wp;   // interpolation weights of F points along `axis`
     DBuf<double> b, x, x2, r, e;
+    // line levels: Thomas factors m, 1/d~ and the super-diagonal a+ of every line, three streams of ngroups * n0 * line_g
+    // doubles in the order [group of line_g lines][i0][line of the group] (allocated once by amg_build)
+    DBuf<double> linef;
     int axis = -1;
 };
 
@@ -423,6 +429,8 @@ std::vector<std::pair<int, int>> rank_slabs(const tp_ctx *c);
 void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3], long gather_cells);
 void amg_setup(tp_ctx *c, Amg *amg, const Stencil &A0);
 void amg_vcycle(tp_ctx *c, Amg *amg, const double *b, double *x);
+void amg_line_check_options(const tp_options &o, int nranks);      // what amg_line_levels excludes (throws, naming both options)
+void amg_line_info(const Amg *amg, int64_t out[4]);
 bool amg_resolve_trunc(tp_ctx *c, Amg *amg);      // waits for the set-up's dominance ratios; true if the cycle shape changed
 // system AMG (2x2 blocks on (p,T))
 void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[3]);

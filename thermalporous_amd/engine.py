@@ -47,7 +47,7 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
-                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
+                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
@@ -66,7 +66,7 @@ API_SYMBOLS = (
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
-    "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes",
+    "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -77,6 +77,9 @@ DEFAULT_OPTS = dict(
                             # over 80 time steps, measured twice; 0.88-0.9 is a plateau, 0.95 starts to fail solves, 1.0 loses 40 %; C1-C3 neutral)
     amg_min_cells=64, amg_nu=2, amg_full_levels=3, amg_coarse_pre=0, amg_coarse_post=1, amg_mid_skip=True, amg_tail_post=2, amg_single=False,
     amg_dom_tau=0.25,       # relaxation-only truncation of diagonally dominant AMG hierarchies (oracle/linalg.py:SemiAMG)
+    amg_line_levels=0,      # L: line-Jacobi along internal axis 0 (Thomas solve per line) instead of point Jacobi on the first L levels of
+                            # the scalar hierarchies that lie above the single-workgroup tail (L <= amg_full_levels).  0: off.  One slab,
+                            # fp64 operators, not pc cptramg, not schur_selfp (check_amg_line_options)
     # multi-GPU: AMG levels with more cells than this stay distributed over the slabs.  Cost model: a V(2,2)
     # level streams ~6 sweeps x 104 B per cell (5.5 TB/s on one GPU) and needs 6 halo exchanges when distributed; with N
     # slabs it saves (1 - 1/N) of its streaming time and pays 6 x t_exchange (~10 us per grouped RCCL send/recv): the
@@ -253,6 +256,26 @@ def tiles_for_blocks(n, nblocks, max_cols=64):
     return best[1]
 
 
+def check_amg_line_options(o, nranks=1, exc=EngineError):
+    """amg_line_levels (tp_options.amg_line_levels) against the options it excludes: refused naming both, never ignored."""
+    L = o.get("amg_line_levels", 0)
+    if isinstance(L, bool) or int(L) != L or L < 0:
+        raise ValueError("amg_line_levels = %r: an integer >= 0" % (L,))
+    if L == 0:
+        return
+    if L > int(o["amg_full_levels"]):
+        raise ValueError("amg_line_levels = %d exceeds amg_full_levels = %d: line levels are V(nu,nu) levels, never pure-transfer "
+                         "or paired ones" % (L, o["amg_full_levels"]))
+    if o.get("amg_single"):
+        raise exc("amg_line_levels with amg_single: the line factors are kept in fp64")
+    if o.get("pc") == "cptramg":
+        raise exc("amg_line_levels with pc cptramg (pc_kind 3): line relaxation is implemented for the scalar hierarchies")
+    if o.get("schur_selfp"):
+        raise exc("amg_line_levels with schur_selfp (schur_a11 = 2): not implemented")
+    if int(nranks) > 1:
+        raise exc("amg_line_levels with nranks = %d: line relaxation is implemented for one slab" % int(nranks))
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -298,6 +321,7 @@ class HipEngine:
         self.opts = dict(DEFAULT_OPTS)
         self.opts.update(opts or {})
         self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
+        check_amg_line_options(self.opts, nranks)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -358,11 +382,12 @@ class HipEngine:
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
                           int(bool(o.get("ilu_whole", False))),
                           (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
-                          int(bool(o.get("ilu_single", False))),
+                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
 
     def set_options(self, **kw):
+        check_amg_line_options({**self.opts, **kw}, self.nranks)
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
         self._ck(self.lib.tp_set_options(self.ctx, C.byref(self._opt)))
@@ -589,6 +614,13 @@ class HipEngine:
         out = (C.c_int64*6)()
         self._ck(self.lib.tp_amg_tail_info(self.ctx, which, out))
         return dict(dense=bool(out[0]), tail_level=out[1], n=out[2], builds=out[3], dense_applies=out[4], tail_launches=out[5])
+
+    def amg_line_info(self, which=0):
+        """Line relaxation of hierarchy `which` (tp_amg_line_info): line levels in effect, lines per workgroup and n0 of level 0,
+        device bytes of the factor streams."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_amg_line_info(self.ctx, which, out))
+        return dict(levels=out[0], group=out[1], n0=out[2], bytes=out[3])
 
     def amg_layout(self, which=0):
         """(number of slab-distributed top levels, coarsening axis of every level)."""
