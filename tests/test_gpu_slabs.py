@@ -269,18 +269,20 @@ def test_rccl_calls_on_a_one_rank_communicator(gather):
 
 
 def _pc_sequence_on_slabs(spec, u0, u, dt, xs, nranks, seq):
-    """On every slab of an in-process group: for each options dict of `seq` in turn, set_options -> jacobian ->
-    pc_setup -> pc_apply(xs).  Returns the global results of every stage of the sequence."""
+    """On every slab of an in-process group (one slab: a plain context, the library refuses a group of one): for each
+    options dict of `seq` in turn, set_options -> jacobian -> pc_setup -> pc_apply(xs).  Returns the global results of
+    every stage of the sequence."""
     from thermalporous_amd import engine as E
     lib = E.load_library()
     group = C.c_void_p()
-    assert lib.tp_local_group_create(nranks, C.byref(group)) == 0
+    if nranks > 1:
+        assert lib.tp_local_group_create(nranks, C.byref(group)) == 0
     out = [None]*nranks
     err = []
 
     def worker(rank):
         try:
-            h = E.HipEngine(spec, seq[0], rank=rank, nranks=nranks, local_group=group)
+            h = E.HipEngine(spec, seq[0], rank=rank, nranks=nranks, local_group=group if nranks > 1 else None)
             h.set_old(u0)
             h.set_dt(dt)
             h.set_state(u)
@@ -303,16 +305,20 @@ def _pc_sequence_on_slabs(spec, u0, u, dt, xs, nranks, seq):
     for t in ts:
         t.join(timeout=300)
     assert not any(t.is_alive() for t in ts), "slab worker hung"
-    lib.tp_local_group_destroy(group)
+    if nranks > 1:
+        lib.tp_local_group_destroy(group)
     assert not err, err
     return [np.concatenate([o[k] for o in out], axis=-3) for k in range(len(seq))]
 
 
-@pytest.mark.parametrize("seq_name", ["cptr_cptramg_cptr", "cpr_cptr"])
-def test_switching_pc_kinds_on_a_live_slab_group(seq_name):
+@pytest.mark.parametrize("seq_name,nranks", [("cptr_cptramg_cptr", 2), ("cpr_cptr", 2), ("cptr_cptramg_cptr", 1), ("cpr_cptr", 1)],
+                         ids=["cptr_cptramg_cptr", "cpr_cptr", "cptr_cptramg_cptr_one_slab", "cpr_cptr_one_slab"])
+def test_switching_pc_kinds_on_a_live_slab_group(seq_name, nranks):
     """tp_set_options on a live multi-slab context: the global-grid scratch buffers (gvec, gA00, gA01, gA10, gSm,
     gAt) are each sized from their own needs, so cptr -> cptramg -> cptr does not leave gvec with 4 planes where stage 1
-    writes 6, and cpr -> cptr does not leave gA01/gA10/gSm unallocated.  Every stage must equal a FRESH context's result."""
+    writes 6, and cpr -> cptr does not leave gA01/gA10/gSm unallocated.  Every stage must equal a FRESH context's result.
+    On one slab the same sequences show that an options change drops the recorded pc_apply program of the ("x", "y") pair:
+    replaying the old kind's program would not give the fresh context's result."""
     spec, u0, *_ = cases.c4_spe10_3d(Nx=8, Ny=21, Nz=7, nphase=2)
     u = cases.perturbed_state(spec, seed=5, amp=0.2)
     xs = np.random.default_rng(11).standard_normal(u.shape)
@@ -320,31 +326,32 @@ def test_switching_pc_kinds_on_a_live_slab_group(seq_name):
     seqs = {"cptr_cptramg_cptr": [dict(base, pc="cptr"), dict(base, pc="cptramg", decoup="QI"), dict(base, pc="cptr", decoup="No")],
             "cpr_cptr": [dict(base, pc="cpr", decoup="QI"), dict(base, pc="cptr", decoup="No")]}
     seq = seqs[seq_name]
-    got = _pc_sequence_on_slabs(spec, u0, u, 3000.0, xs, 2, seq)
+    got = _pc_sequence_on_slabs(spec, u0, u, 3000.0, xs, nranks, seq)
     for k, o in enumerate(seq):
-        fresh = _pc_sequence_on_slabs(spec, u0, u, 3000.0, xs, 2, [o])[0]
-        assert rel2(got[k], fresh) < 1e-12, (seq_name, k)
+        fresh = _pc_sequence_on_slabs(spec, u0, u, 3000.0, xs, nranks, [o])[0]
+        assert rel2(got[k], fresh) < 1e-12, (seq_name, nranks, k)
 
 
-@pytest.mark.parametrize("gather", [2000000, 0], ids=["replicated", "distributed"])
-def test_pc_apply_program_replay_on_slabs(gather):
-    """Multi-slab pc_apply runs as a recorded PROGRAM: hipGraph segments between the exchanges, the exchanges as host
-    closures (tp_common.hpp).  The recording pass must already produce the result, a replay on the same vector pair must
-    reproduce it bit for bit, and a replay with other CONTENTS in the same buffers must follow them (linearity)."""
+@pytest.mark.parametrize("nranks,gather", [(3, 2000000), (3, 0), (1, 2000000)], ids=["replicated", "distributed", "one_slab"])
+def test_pc_apply_program_replay_on_slabs(nranks, gather):
+    """pc_apply runs as a recorded PROGRAM: hipGraph segments between the exchanges, the exchanges as host closures
+    (tp_common.hpp); on one slab (a plain context, no group) the program is a single segment.  The recording pass must
+    already produce the result, a replay on the same vector pair must reproduce it bit for bit, and a replay with other
+    CONTENTS in the same buffers must follow them (linearity)."""
     from thermalporous_amd import engine as E
     spec, u0, *_ = cases.c4_spe10_3d(Nx=8, Ny=21, Nz=7, nphase=2)
     u = cases.perturbed_state(spec, seed=5, amp=0.2)
     xs = np.random.default_rng(11).standard_normal(u.shape)
     opts = dict(pc="cptr", ksp_rtol=1e-8, amg_gather_cells=gather)
-    nranks = 3
     lib = E.load_library()
     group = C.c_void_p()
-    assert lib.tp_local_group_create(nranks, C.byref(group)) == 0
+    if nranks > 1:
+        assert lib.tp_local_group_create(nranks, C.byref(group)) == 0
     out, err = [None]*nranks, []
 
     def worker(rank):
         try:
-            h = E.HipEngine(spec, opts, rank=rank, nranks=nranks, local_group=group)
+            h = E.HipEngine(spec, opts, rank=rank, nranks=nranks, local_group=group if nranks > 1 else None)
             h.set_old(u0)
             h.set_dt(3000.0)
             h.set_state(u)
@@ -365,7 +372,8 @@ def test_pc_apply_program_replay_on_slabs(gather):
     for t in ts:
         t.join(timeout=300)
     assert not any(t.is_alive() for t in ts), "slab worker hung"
-    lib.tp_local_group_destroy(group)
+    if nranks > 1:
+        lib.tp_local_group_destroy(group)
     assert not err, err
     y1, y2, y3 = (np.concatenate([o[k] for o in out], axis=-3) for k in range(3))
     assert np.array_equal(y1, y2)

@@ -63,7 +63,7 @@ struct HaloPub { const char *p; size_t fstride; int n2; };
     do {                                                                            \
         if ((c)->rec && !(c)->rec_in_comm) {                                        \
             seg_end(c);                                                             \
-            (c)->rec->steps.push_back({nullptr, [=]() { call; }});                  \
+            (c)->rec->steps.push_back({GraphExec(), [=]() { call; }});              \
             (c)->rec_in_comm = true;                                                \
             try { call; } catch (...) { (c)->rec_in_comm = false; throw; }          \
             (c)->rec_in_comm = false;                                               \
@@ -194,24 +194,27 @@ void gather_slabs(tp_ctx *c, const double *local, long lstride, double *global, 
     TP_NCCL(ncclGroupEnd());
 }
 
+// in-process group: copy out, barrier, combine in rank order (identical result on every rank), barrier, copy in
+template <class Op>
+static void lg_allreduce(tp_ctx *c, double *dev, int n, Op combine) {
+    LocalGroup *G = c->lgroup;
+    std::vector<double> &mine = G->red[c->grid.rank];
+    mine.resize(n);
+    TP_HIP(hipMemcpyAsync(mine.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    TP_HIP(hipStreamSynchronize(c->stream));
+    G->barrier();
+    std::vector<double> acc(n, 0.0);
+    for (int r = 0; r < G->n; ++r)
+        for (int i = 0; i < n; ++i) acc[i] = combine(acc[i], G->red[r][i]);
+    G->barrier();                                  // everybody has read before anybody overwrites
+    TP_HIP(hipMemcpyAsync(dev, acc.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    TP_HIP(hipStreamSynchronize(c->stream));
+}
+
 void allreduce_sum(tp_ctx *c, double *dev, int n) {
     if (!c->dist || n <= 0) return;
     TP_COMM_RECORD(c, allreduce_sum(c, dev, n));
-    if (c->lgroup) {
-        LocalGroup *G = c->lgroup;
-        std::vector<double> &mine = G->red[c->grid.rank];
-        mine.resize(n);
-        TP_HIP(hipMemcpyAsync(mine.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-        TP_HIP(hipStreamSynchronize(c->stream));
-        G->barrier();
-        std::vector<double> sum(n, 0.0);
-        for (int r = 0; r < G->n; ++r)                 // fixed order: identical result on every rank
-            for (int i = 0; i < n; ++i) sum[i] += G->red[r][i];
-        G->barrier();                                  // everybody has read before anybody overwrites
-        TP_HIP(hipMemcpyAsync(dev, sum.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        TP_HIP(hipStreamSynchronize(c->stream));
-        return;
-    }
+    if (c->lgroup) { lg_allreduce(c, dev, n, [](double a, double b) { return a + b; }); return; }
     TP_NCCL(ncclAllReduce(dev, dev, n, ncclDouble, ncclSum, (ncclComm_t)c->comm, c->stream));
 }
 
@@ -219,22 +222,15 @@ void allreduce_sum(tp_ctx *c, double *dev, int n) {
 void allreduce_max(tp_ctx *c, double *dev, int n) {
     if (!c->dist || n <= 0) return;
     TP_COMM_RECORD(c, allreduce_max(c, dev, n));
-    if (c->lgroup) {
-        LocalGroup *G = c->lgroup;
-        std::vector<double> &mine = G->red[c->grid.rank];
-        mine.resize(n);
-        TP_HIP(hipMemcpyAsync(mine.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-        TP_HIP(hipStreamSynchronize(c->stream));
-        G->barrier();
-        std::vector<double> mx(n, 0.0);
-        for (int r = 0; r < G->n; ++r)
-            for (int i = 0; i < n; ++i) mx[i] = std::max(mx[i], G->red[r][i]);
-        G->barrier();                                  // everybody has read before anybody overwrites
-        TP_HIP(hipMemcpyAsync(dev, mx.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        TP_HIP(hipStreamSynchronize(c->stream));
-        return;
-    }
+    if (c->lgroup) { lg_allreduce(c, dev, n, [](double a, double b) { return std::max(a, b); }); return; }
     TP_NCCL(ncclAllReduce(dev, dev, n, ncclDouble, ncclMax, (ncclComm_t)c->comm, c->stream));
+}
+
+// the AMG hierarchies follow the options and the fields they were built from: dropped, pc_setup rebuilds them
+static void drop_hierarchies(tp_ctx *c) {
+    delete c->amg_p; c->amg_p = nullptr;
+    delete c->amg_T; c->amg_T = nullptr;
+    delete c->bamg; c->bamg = nullptr;
 }
 
 }  // namespace tp
@@ -244,13 +240,8 @@ tp_ctx::~tp_ctx() {
         fprintf(stderr, "[tp] pipelined FGMRES: %ld speculative applications issued, %ld discarded, %ld iterations without one\n",
                 spec_issued, spec_wasted, spec_skipped);
     for (auto *v : vecs) delete v;
-    delete amg_p;
-    delete amg_T;
-    delete bamg;
-    for (auto &gph : pc_graphs) (void)hipGraphExecDestroy(gph.exec);
-    for (auto &pr : pc_programs)
-        for (auto &st : pr.steps)
-            if (st.exec) (void)hipGraphExecDestroy(st.exec);
+    tp::drop_hierarchies(this);
+    pc_programs.clear();                 // (the graph segments go before the stream they were captured on)
     if (comm) ncclCommDestroy((ncclComm_t)comm);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -385,10 +376,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
                              opt->schur_a11 != c->opt.schur_a11 || opt->fs_additive != c->opt.fs_additive;
     c->opt = *opt;
     if (tile_changed) c->ilu.slots = 0;
-    if (amg_changed) {
-        delete c->amg_p; c->amg_p = nullptr; delete c->amg_T; c->amg_T = nullptr;
-        if (c->bamg) { delete c->bamg; c->bamg = nullptr; }
-    }
+    if (amg_changed) drop_hierarchies(c);
     if (schur_of(*opt) && c->Sm.n == 0) c->Sm.alloc((size_t)7 * c->g.ntot);
     c->pc_ready = false;
     c->graph_epoch++;            // any option may change the captured kernel sequence: drop the pc_apply graphs
@@ -473,9 +461,7 @@ int tp_finalize_fields(tp_ctx *c) {
     compute_trans(c);
     TP_HIP(hipStreamSynchronize(c->stream));
     c->fields_ready = true;
-    delete c->amg_p; c->amg_p = nullptr;
-    delete c->amg_T; c->amg_T = nullptr;
-    if (c->bamg) { delete c->bamg; c->bamg = nullptr; }
+    drop_hierarchies(c);
     c->pc_ready = false;
     c->graph_epoch++;
     TP_API_END

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 #include <stdexcept>
 #include <functional>
@@ -141,6 +142,18 @@ struct DBuf {
     DBuf() = default;
     DBuf(const DBuf &) = delete;
     DBuf &operator=(const DBuf &) = delete;
+};
+
+// move-only owner of one instantiated hipGraph (a capture segment of a recorded pc_apply program)
+struct GraphExec {
+    hipGraphExec_t h = nullptr;
+    GraphExec() = default;
+    explicit GraphExec(hipGraphExec_t h_) : h(h_) {}
+    GraphExec(GraphExec &&o) noexcept : h(o.h) { o.h = nullptr; }
+    GraphExec &operator=(GraphExec &&o) noexcept { std::swap(h, o.h); return *this; }
+    GraphExec(const GraphExec &) = delete;
+    GraphExec &operator=(const GraphExec &) = delete;
+    ~GraphExec() { if (h) (void)hipGraphExecDestroy(h); }
 };
 
 // Layout of one semicoarsening hierarchy, shared by the scalar (tp_amg.hip) and the system (tp_amg_block.hip) AMG: pure host-side
@@ -339,15 +352,12 @@ struct tp_ctx {
     std::vector<double> hostbuf;
     // scratch vectors for PC apply
     tp::DBuf<double> w1, w2, w3, w4, dx;
-    // captured preconditioner application (hipGraph on fixed staging buffers)
-    // captured pc_apply graphs, one per (input, output) vector pair: FGMRES applies the preconditioner to basis
-    // vector j into Z_j, a handful of fixed address pairs that recur in every solve
-    struct PcGraph { const double *x; double *y; hipGraphExec_t exec; };
-    std::vector<PcGraph> pc_graphs;
-    // multi-GPU: a preconditioner application is recorded as a PROGRAM -- hipGraph segments (the kernel sequences between two
-    // exchanges) alternating with the exchanges themselves (RCCL calls / in-process copies, replayed as host closures on the
-    // same stream).  RCCL calls are never captured; only what lies between them is.
-    struct PcStep { hipGraphExec_t exec; std::function<void()> comm; };
+    // A preconditioner application is recorded as a PROGRAM, one per (input, output) vector pair: FGMRES applies the
+    // preconditioner to basis vector j into Z_j, a handful of fixed address pairs that recur in every solve.  A program is
+    // hipGraph segments (the kernel sequences between two exchanges) alternating with the exchanges themselves (RCCL calls /
+    // in-process copies, replayed as host closures on the same stream).  RCCL calls are never captured; only what lies between
+    // them is.  A single slab has no exchange: its program is one segment, one hipGraphLaunch per replay.
+    struct PcStep { tp::GraphExec exec; std::function<void()> comm; };     // a segment (exec.h set) or an exchange
     struct PcProgram { const double *x; double *y; std::vector<PcStep> steps; };
     std::vector<PcProgram> pc_programs;
     PcProgram *rec = nullptr;          // program being recorded (comm calls split the capture), else null

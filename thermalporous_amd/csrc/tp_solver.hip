@@ -81,6 +81,12 @@ static void refresh_pc_signature(tp_ctx *c) {
     if (h != c->pc_sig) { c->pc_sig = h; c->graph_epoch++; }
 }
 
+// several GPUs, hierarchy replicated from the top: stage 1 works on the system gathered on the global grid of every rank
+static bool replicated(const tp_ctx *c, const AmgPlan &plan) { return c->dist && plan.dist_levels == 0; }
+static bool stage1_replicated(const tp_ctx *c) { return c->dist && replicated(c, sysamg_of(c->opt) ? c->bamg->plan : c->amg_p->plan); }
+// the grid the stage-1 hierarchies are built on: the GLOBAL grid (one GPU: the slab is the whole grid)
+static GridDev hierarchy_grid(const tp_ctx *c) { return c->dist ? c->gfull : make_grid(c->g.n0, c->g.n1, c->g.n2, c->g.n2, 0); }
+
 // the inner solve's dot products are local: on several GPUs every rank must hold the whole stage-1 system
 static void require_replicated_for_inner(tp_ctx *c, const AmgPlan &plan) {
     if (c->opt.s1_ksp == 0 || !c->dist) return;
@@ -94,7 +100,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
     TP_REQUIRE(c->b == 3, "pc_cptramg is a two-phase preconditioner");
     TP_REQUIRE(c->opt.decoup >= 0 && c->opt.decoup <= 2, "pc_cptramg: decoupling No, QI or TI");
     decouple(c);
-    const GridDev gam = c->dist ? c->gfull : make_grid(c->g.n0, c->g.n1, c->g.n2, c->g.n2, 0);
+    const GridDev gam = hierarchy_grid(c);
     if (!c->bamg) {
         double st[3];
         face_strengths(c, st);             // the pressure's coarsening schedule
@@ -105,7 +111,7 @@ static void pc_setup_sysamg(tp_ctx *c) {
     BStencil A0;
     if (c->opt.decoup == 0) { A0.base = c->J.p; A0.ss = (long)c->b * c->b * nt; A0.rs = (long)c->b * nt; A0.cs = nt; }
     else { A0.base = c->At.p; A0.ss = 4 * nt; A0.rs = 2 * nt; A0.cs = nt; }
-    if (c->dist && c->bamg->plan.dist_levels == 0) {
+    if (replicated(c, c->bamg->plan)) {
         // small grids: the hierarchy lives on the gathered global grid, replicated on every rank (as small scalar hierarchies
         // do); larger ones keep their top levels on the slabs (tp_amg_block.hip) and work on the slab operator directly
         const size_t ng = (size_t)c->gfull.ntot;
@@ -148,7 +154,7 @@ void pc_setup(tp_ctx *c) {
     // so the preconditioner (and the iteration counts) are those of the single-GPU run and only stage 2 is
     // bjacobi.  Grids above amg_gather_cells keep their top levels distributed over the slabs (tp_amg.hip);
     // smaller ones are replicated from the top: every rank gathers the scalar stage-1 operators.
-    const GridDev gam = c->dist ? c->gfull : make_grid(c->g.n0, c->g.n1, c->g.n2, c->g.n2, 0);
+    const GridDev gam = hierarchy_grid(c);
     // selfp on several GPUs works on slab vectors (its exact-Sp sweep needs the slab's own Jacobian rows): the hierarchies
     // keep every level with >= 2 planes per rank distributed, whatever amg_gather_cells says
     const long gather_cells = (c->dist && cptr && c->opt.schur_a11 == 2) ? 0 : (long)c->opt.amg_gather_cells;
@@ -189,7 +195,7 @@ void pc_setup(tp_ctx *c) {
         if (c->opt.decoup == 0) Sl.base = c->J.p + (long)(c->b + 1) * c->g.ntot;
     }
     if (cptr && !selfp) TP_REQUIRE(Sl.base, "pc_cptr needs the S~ operator (assemble with want_schur)");
-    if (c->dist && c->amg_p->plan.dist_levels == 0) {
+    if (replicated(c, c->amg_p->plan)) {
         const size_t ng = (size_t)c->gfull.ntot;
         // every buffer is tested on its own size (an options switch cpr -> cptr, or cptr -> cptramg -> cptr, on a live
         // context must not find gvec shrunk or gA01/gA10/gSm missing because some OTHER buffer was already large enough)
@@ -254,13 +260,57 @@ void resolve_cycle_shapes(tp_ctx *c) {
     if (changed) c->graph_epoch++;
 }
 
+// The system one stage-1 application runs on: this rank's slab, or (several GPUs, replicated hierarchy) the system gathered
+// on the global grid of every rank.
+struct Stage1Sys {
+    GridDev g;
+    Stencil A00, A01, A10;
+    bool exchange;         // vectors need a halo exchange between the steps: slab vectors of a distributed context only
+};
+static Stage1Sys stage1_system(const tp_ctx *c, bool gathered) {
+    if (!gathered) return {c->g, c->opA00, c->opA01, c->opA10, c->dist};
+    const long ng = c->gfull.ntot;
+    return {c->gfull, {c->gA00.p, ng}, {c->gA01.p, ng}, {c->gA10.p, ng}, false};
+}
+
+// y = K r on system `s`; t and w are two work vectors of the system's grid.  npri == 1: y0 = K(A00) r0.  Else
+// PCFIELDSPLIT additive (pc_fieldsplit_diag, singlephase.py:371-375) or schur FULL on (p,T) (twophase.py:536-545):
+// K(A00), K(S~) = one V-cycle each (slab-distributed AMG levels: the V-cycles return owned cells, the couplings read halos)
+static void stage1_sequence(tp_ctx *c, const Stage1Sys &s, const double *r0, const double *r1, double *y0, double *y1,
+                            double *t, double *w) {
+    // K(A00): one V-cycle of the pressure hierarchy, or (s1_ksp) an inner solve preconditioned by it
+    InnerOp op;
+    op.g = s.g;
+    op.A[0][0] = s.A00;
+    const auto K00 = [&](const double *b, double *xx) { inner_solve(c, op, [&](const double *bb, double *xo) { amg_vcycle(c, c->amg_p, bb, xo); }, b, xx, 1); };
+    if (npri_of(c->opt) == 1) { K00(r0, y0); return; }
+    if (c->opt.fs_additive) {              // one V-cycle per field
+        K00(r0, y0);
+        amg_vcycle(c, c->amg_T, r1, y1);
+        return;
+    }
+    const long n = s.g.ntot;
+    K00(r0, w);                                                             // w = K(A00) r0
+    if (s.exchange) halo_exchange(c, s.g, w, 1, n);
+    spmv_scalar(c, s.g, s.A10, w, t, -1.0, r1);                             // t = r1 - A10 w
+    if (c->opt.schur_a11 == 2) {                                            // selfp (slab system only: pc_setup): V7 then one Jacobi sweep on the exact Sp
+        double *xv = c->spbuf.p + 9 * c->g.ntot;
+        amg_vcycle(c, c->amg_T, t, xv);
+        selfp_post(c, t, xv, y1);
+    } else {
+        amg_vcycle(c, c->amg_T, t, y1);                                     // y1 = K(S~) t
+    }
+    if (s.exchange) halo_exchange(c, s.g, y1, 1, n);
+    spmv_scalar(c, s.g, s.A01, y1, t, -1.0, r0);                            // t = r0 - A01 y1
+    K00(t, y0);                                                             // y0 = K(A00) t
+}
+
 // y = B1 x :  CPRStage1PC.apply (preconditioners.py:881-903) / CPTRStage1PC.apply (:1550-1567)
 void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
-    const GridDev &g = c->g;
-    const long nt = g.ntot;
+    const long nt = c->g.ntot;
     ensure_work(c);
     resolve_cycle_shapes(c);
-    double *r0 = c->w3.p, *r1 = c->w3.p + nt, *t = c->w3.p + 2 * nt;   // w3 has >= 3 planes
+    const double *r0 = c->w3.p, *r1 = c->w3.p + nt;                         // w3 has >= 3 planes
     // y_s = 0 for the non-primary fields (:902-903, :1566-1567)
     const int npri = npri_of(c->opt);
     if (zero_secondary)
@@ -268,94 +318,39 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
     if (c->opt.decoup == 0 && !c->dist) {
         // decoupling "No" (pc_cptr, pc_cpr, pc_fieldsplit_cd presets): the stage-1 right-hand sides ARE the
         // primary fields of x -- no copy (multi-GPU keeps the copy: the V-cycle's exchange writes b's halos)
-        r0 = const_cast<double *>(x);
-        r1 = const_cast<double *>(x) + nt;
+        r0 = x;
+        r1 = x + nt;
     } else {
-        stage1_rhs(c, x, 0, r0);                   // r_p = x_p - (D_ps D_ss^-1) x_s
-        if (npri == 2) stage1_rhs(c, x, 1, r1);
+        stage1_rhs(c, x, 0, c->w3.p);              // r_p = x_p - (D_ps D_ss^-1) x_s
+        if (npri == 2) stage1_rhs(c, x, 1, c->w3.p + nt);
+    }
+    // the system and its vectors: slab vectors, or the planes of gvec on the gathered global grid
+    const bool gathered = stage1_replicated(c);
+    const Stage1Sys s = stage1_system(c, gathered);
+    double *y0 = y, *y1 = y + nt, *t = c->w3.p + 2 * nt, *w = c->w4.p;
+    if (gathered) {
+        const long ng = s.g.ntot;
+        double *gv = c->gvec.p;
+        gather_slabs(c, r0, nt, gv, ng, npri);     // r0 (and r1: consecutive planes on both sides)
+        r0 = gv; r1 = gv + ng; y0 = gv + 2 * ng; y1 = gv + 3 * ng; t = gv + 4 * ng; w = gv + 5 * ng;
     }
     if (sysamg_of(c->opt)) {
-        // pc_cptramg: y_pT = K(Atilde_00) r_pT, one V-cycle of the 2x2-block system AMG (r0, r1 are adjacent planes), or
-        // (s1_ksp) an inner solve preconditioned by it
+        // pc_cptramg: y_pT = K(Atilde_00) r_pT, one V-cycle of the 2x2-block system AMG (r0, r1 and y0, y1 are adjacent
+        // planes), or (s1_ksp) an inner solve preconditioned by it
         InnerOp op;
-        op.g = (c->dist && c->bamg->plan.dist_levels == 0) ? c->gfull : g;
+        op.g = s.g;
         for (int q = 0; q < 2; ++q)
             for (int r = 0; r < 2; ++r) { op.A[q][r].base = c->opPT.at(0, q, r); op.A[q][r].slot_stride = c->opPT.ss; }
-        const auto KPT = [&](const double *b, double *xx) { inner_solve(c, op, [&](const double *bb, double *xo) { bamg_vcycle(c, c->bamg, bb, xo); }, b, xx, 2); };
-        if (c->dist && c->bamg->plan.dist_levels == 0) {
-            const long ng = c->gfull.ntot;
-            gather_slabs(c, r0, nt, c->gvec.p, ng, 2);
-            KPT(c->gvec.p, c->gvec.p + 2 * ng);
-            const long off = g.np * c->grid.off2;          // my slab INCLUDING its halo planes
-            vec_copy(c, c->gvec.p + 2 * ng + off, y, nt);
-            vec_copy(c, c->gvec.p + 3 * ng + off, y + nt, nt);
-        } else {
-            KPT(r0, y);
-        }
-        return;
-    }
-    // K(A00): one V-cycle of the pressure hierarchy, or (s1_ksp) an inner solve preconditioned by it
-    InnerOp op;
-    const bool gathered = c->dist && c->amg_p->plan.dist_levels == 0;
-    op.g = gathered ? c->gfull : g;
-    op.A[0][0] = c->opA00;
-    if (gathered) { op.A[0][0].base = c->gA00.p; op.A[0][0].slot_stride = c->gfull.ntot; }
-    const auto K00 = [&](const double *b, double *xx) { inner_solve(c, op, [&](const double *bb, double *xo) { amg_vcycle(c, c->amg_p, bb, xo); }, b, xx, 1); };
-    if (c->dist && c->amg_p->plan.dist_levels == 0) {
-        // gathered global system: work vectors gr0, gr1, gy0, gy1, gt, gw on the global grid
-        const GridDev &G = c->gfull;
-        const long ng = G.ntot;
-        double *gr0 = c->gvec.p, *gr1 = gr0 + ng, *gy0 = gr0 + 2 * ng, *gy1 = gr0 + 3 * ng, *gt = gr0 + 4 * ng,
-               *gw = gr0 + 5 * ng;
-        gather_slabs(c, r0, nt, gr0, ng, npri);    // r0 (and r1: consecutive planes on both sides)
-        if (npri == 1) {
-            K00(gr0, gy0);
-        } else {
-            Stencil A10, A01;
-            A10.base = c->gA10.p; A10.slot_stride = ng;
-            A01.base = c->gA01.p; A01.slot_stride = ng;
-            if (c->opt.fs_additive) {               // PCFIELDSPLIT additive: one V-cycle per field
-                K00(gr0, gy0);
-                amg_vcycle(c, c->amg_T, gr1, gy1);
-            } else {
-            K00(gr0, gw);
-            spmv_scalar(c, G, A10, gw, gt, -1.0, gr1);
-            amg_vcycle(c, c->amg_T, gt, gy1);
-            spmv_scalar(c, G, A01, gy1, gt, -1.0, gr0);
-            K00(gt, gy0);
-            }
-        }
-        // my slab of the result INCLUDING its halo planes (global planes lo-1 .. hi), so y needs no exchange
-        const long off = g.np * c->grid.off2;
-        vec_copy(c, gy0 + off, y, nt);
-        if (npri == 2) vec_copy(c, gy1 + off, y + nt, nt);
-        return;
-    }
-    if (npri == 1) {
-        K00(r0, y);
-        return;
-    }
-    // PCFIELDSPLIT schur FULL on (p,T) (twophase.py:536-545): K(A00), K(S~) = one V-cycle each
-    // (multi-GPU with distributed AMG levels: the V-cycles return owned cells, the couplings read halos)
-    double *y0 = y, *y1 = y + nt;
-    if (c->opt.fs_additive) {              // PCFIELDSPLIT additive (pc_fieldsplit_diag, singlephase.py:371-375)
-        K00(r0, y0);
-        amg_vcycle(c, c->amg_T, r1, y1);
-        return;
-    }
-    K00(r0, c->w4.p);                                  // y0 = K(A00) r0
-    if (c->dist) halo_exchange(c, g, c->w4.p, 1, nt);
-    spmv_scalar(c, g, c->opA10, c->w4.p, t, -1.0, r1);                      // t = r1 - A10 y0
-    if (c->opt.schur_a11 == 2) {                                            // selfp: V7 then one Jacobi sweep on the exact Sp
-        double *xv = c->spbuf.p + 9 * nt;
-        amg_vcycle(c, c->amg_T, t, xv);
-        selfp_post(c, t, xv, y1);
+        inner_solve(c, op, [&](const double *bb, double *xo) { bamg_vcycle(c, c->bamg, bb, xo); }, r0, y0, 2);
     } else {
-        amg_vcycle(c, c->amg_T, t, y1);                                     // y1 = K(S~) t
+        stage1_sequence(c, s, r0, r1, y0, y1, t, w);
     }
-    if (c->dist) halo_exchange(c, g, y1, 1, nt);
-    spmv_scalar(c, g, c->opA01, y1, t, -1.0, r0);                           // t = r0 - A01 y1
-    K00(t, y0);                                     // y0 = K(A00) t
+    if (gathered) {
+        // my slab of the result INCLUDING its halo planes (global planes lo-1 .. hi), so y needs no exchange
+        const long off = c->g.np * c->grid.off2;
+        vec_copy(c, y0 + off, y, nt);
+        if (npri == 2) vec_copy(c, y1 + off, y + nt, nt);
+    }
 }
 
 // composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r
@@ -364,15 +359,20 @@ static void pc_apply_body(tp_ctx *c, const double *x, double *y) {
     const int npri = npri_of(c->opt);
     // (y's secondary fields are left untouched: the second stage below never reads them and overwrites them)
     stage1_apply(c, x, y, false);                 // multi-GPU, replicated stage 1: y comes back with live halo planes
-    if (c->dist && ((c->amg_p && c->amg_p->plan.dist_levels > 0) || (sysamg_of(c->opt) && c->bamg && c->bamg->plan.dist_levels > 0)))
-        halo_exchange(c, c->g, y, npri, c->g.ntot);       // (slab-distributed hierarchies return owned cells only)
+    if (c->dist && !stage1_replicated(c)) halo_exchange(c, c->g, y, npri, c->g.ntot);       // (slab-distributed hierarchies return owned cells only)
     if (c->opt.pc_kind == 2) return;                          // pc_fieldsplit_cd: the Schur stage IS the preconditioner
     resid_block_cols(c, c->J.p, x, y, npri, c->w1.p);        // secondary fields of y are zero
     ilu_solve(c, c->w1.p, y, y, npri);                       // y = y + M^-1 r  (y's secondary fields are zero: not read)
 }
 
-// ---- recording of multi-GPU pc_apply programs: one capture segment between two exchanges -------------------------------
+// ---- recording of pc_apply programs: one capture segment between two exchanges ------------------------------------------
+// TP_DEBUG=2: one line per HIP graph call (used to locate the profiler crash described in DESIGN.md 6)
+static void pc_trace(const tp_ctx::PcProgram &pr, const char *what) {
+    static const bool trace = getenv("TP_DEBUG") && atoi(getenv("TP_DEBUG")) >= 2;
+    if (trace) { fprintf(stderr, "[tp] pc_apply(%p,%p): %s\n", (const void *)pr.x, (void *)pr.y, what); fflush(stderr); }
+}
 void seg_begin(tp_ctx *c) {
+    pc_trace(*c->rec, "begin capture");
     TP_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     c->rec_capturing = true;
 }
@@ -380,24 +380,30 @@ void seg_begin(tp_ctx *c) {
 // recording pass must still produce the result, and the exchange that follows reads what these kernels wrote)
 void seg_end(tp_ctx *c) {
     hipGraph_t graph = nullptr;
+    pc_trace(*c->rec, "end capture");
     c->rec_capturing = false;
     TP_HIP(hipStreamEndCapture(c->stream, &graph));
     size_t nnodes = 0;
-    TP_HIP(hipGraphGetNodes(graph, nullptr, &nnodes));
-    if (nnodes > 0) {
-        hipGraphExec_t exec = nullptr;
-        const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (e != hipSuccess) { (void)hipGraphDestroy(graph); TP_HIP(e); }
-        c->rec->steps.push_back({exec, nullptr});
-        TP_HIP(hipGraphLaunch(exec, c->stream));
+    hipGraphExec_t exec = nullptr;
+    hipError_t e = hipGraphGetNodes(graph, nullptr, &nnodes);
+    if (e == hipSuccess && nnodes > 0) {
+        pc_trace(*c->rec, "instantiate");
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     }
-    TP_HIP(hipGraphDestroy(graph));
+    (void)hipGraphDestroy(graph);
+    TP_HIP(e);
+    if (!exec) return;
+    c->rec->steps.push_back({GraphExec(exec), nullptr});
+    pc_trace(*c->rec, "launch");
+    TP_HIP(hipGraphLaunch(exec, c->stream));
+    pc_trace(*c->rec, "launched");
 }
 
 // One preconditioner application is ~100 short kernels (the V-cycles' coarse levels); issued eagerly
 // the host launch path (~3 us per kernel) is slower than the GPU executes them.  The whole sequence
-// is therefore captured into a hipGraph per (input, output) address pair -- FGMRES uses the fixed pairs
-// (V_j, Z_j) -- and replayed per Krylov iteration.
+// is therefore recorded once per (input, output) address pair -- FGMRES uses the fixed pairs (V_j, Z_j) --
+// as a program (tp_common.hpp) and replayed per Krylov iteration: on one slab a single hipGraph, on several
+// slabs graph segments between the exchanges with the exchanges themselves as host closures.
 void pc_apply(tp_ctx *c, const double *x, double *y) {
     TP_REQUIRE(c->pc_ready, "pc_apply before pc_setup");
     static const bool use_graph = !(getenv("TP_GRAPH") && atoi(getenv("TP_GRAPH")) == 0);
@@ -408,74 +414,38 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
         pc_apply_body(c, x, y);
         return;
     }
-    if (c->pc_graph_epoch != c->graph_epoch || c->pc_graphs.size() > 512 || c->pc_programs.size() > 512) {      // stale (or runaway) cache
-        for (auto &gph : c->pc_graphs) (void)hipGraphExecDestroy(gph.exec);
-        c->pc_graphs.clear();
-        for (auto &pr : c->pc_programs)
-            for (auto &st : pr.steps)
-                if (st.exec) (void)hipGraphExecDestroy(st.exec);
+    if (c->pc_graph_epoch != c->graph_epoch || c->pc_programs.size() > 512) {      // stale (or runaway) cache
         c->pc_programs.clear();
         c->pc_graph_epoch = c->graph_epoch;
     }
-    if (c->dist) {
-        // several GPUs: graph segments between the exchanges, the exchanges themselves as host closures (tp_common.hpp)
-        for (auto &pr : c->pc_programs)
-            if (pr.x == x && pr.y == y) {
-                for (auto &st : pr.steps) {
-                    if (st.exec) TP_HIP(hipGraphLaunch(st.exec, c->stream));
-                    else st.comm();
-                }
-                return;
+    for (auto &pr : c->pc_programs)
+        if (pr.x == x && pr.y == y) {
+            for (auto &st : pr.steps) {
+                if (!st.exec.h) { st.comm(); continue; }
+                pc_trace(pr, "launch");
+                TP_HIP(hipGraphLaunch(st.exec.h, c->stream));
+                pc_trace(pr, "launched");
             }
-        c->pc_programs.push_back({x, y, {}});
-        c->rec = &c->pc_programs.back();
-        try {
-            seg_begin(c);
-            pc_apply_body(c, x, y);
-            seg_end(c);
-        } catch (...) {
-            if (c->rec_capturing) {
-                hipGraph_t g = nullptr;
-                (void)hipStreamEndCapture(c->stream, &g);
-                if (g) (void)hipGraphDestroy(g);
-                c->rec_capturing = false;
-            }
-            for (auto &st : c->pc_programs.back().steps)
-                if (st.exec) (void)hipGraphExecDestroy(st.exec);
-            c->pc_programs.pop_back();
-            c->rec = nullptr;
-            throw;
+            return;
         }
+    c->pc_programs.push_back({x, y, {}});
+    c->rec = &c->pc_programs.back();
+    try {
+        seg_begin(c);
+        pc_apply_body(c, x, y);
+        seg_end(c);
+    } catch (...) {
+        if (c->rec_capturing) {              // a dangling capture: end it, so that the stream is usable again
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(c->stream, &g);
+            if (g) (void)hipGraphDestroy(g);
+        }
+        c->rec_capturing = c->rec_in_comm = false;
         c->rec = nullptr;
-        return;
+        c->pc_programs.pop_back();           // (destroys the segments recorded so far)
+        throw;
     }
-    // TP_DEBUG=2: one line per HIP graph call (used to locate the profiler crash described in DESIGN.md 6)
-    static const bool trace = getenv("TP_DEBUG") && atoi(getenv("TP_DEBUG")) >= 2;
-    auto say = [&](const char *what) { if (trace) { fprintf(stderr, "[tp] pc_apply(%p,%p): %s\n", (const void *)x, (void *)y, what); fflush(stderr); } };
-    hipGraphExec_t exec = nullptr;
-    for (auto &gph : c->pc_graphs)
-        if (gph.x == x && gph.y == y) { exec = gph.exec; break; }
-    if (!exec) {
-        hipGraph_t graph = nullptr;
-        say("begin capture");
-        TP_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        try {
-            pc_apply_body(c, x, y);
-        } catch (...) {
-            (void)hipStreamEndCapture(c->stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        say("end capture");
-        TP_HIP(hipStreamEndCapture(c->stream, &graph));
-        say("instantiate");
-        TP_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        TP_HIP(hipGraphDestroy(graph));
-        c->pc_graphs.push_back({x, y, exec});
-    }
-    say("launch");
-    TP_HIP(hipGraphLaunch(exec, c->stream));
-    say("launched");
+    c->rec = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------
