@@ -129,6 +129,10 @@ typedef struct tp_options {
                                 is a line level when it is above the single-workgroup tail, among the first L levels and has
                                 n0 >= 2; L <= amg_full_levels.  0 (default): off, the point-Jacobi launch sequence.  One slab
                                 only; not with amg_single, pc_kind 3 or schur_a11 = 2 (refused, never ignored) */
+    int32_t ksp_kind;        /* outer Krylov method of tp_newton_solve: 0 = restarted FGMRES (the default: ksp_type fgmres, or gmres with
+                                ksp_pc_side right), 1 = right-preconditioned (flexible) BiCGStab (ksp_type fbcgs, or bcgs with
+                                ksp_pc_side right): a short recurrence on seven vectors plus the shared scratch w2 (what tp_ksp_info
+                                reports), two preconditioner applications per iteration, every scalar on the device; ksp_restart has no effect on it */
     /* Inner solve of the stage-1 PRESSURE block K(A00) (pc_kind 0, 1, 2) or of the (p,T) SYSTEM block (pc_kind 3): what PETSc
      * does when the sub-solver's ksp_type is not preonly.  The V-cycle becomes the (right) preconditioner of a small
      * Krylov method whose every scalar stays on the device, so it lives inside the captured pc_apply graph:
@@ -257,6 +261,16 @@ int tp_inner_stats(tp_ctx *ctx, int64_t *applies, int64_t *its, int64_t *unconve
 /* Krylov / Newton (PETSc KSP fgmres + SNES newtonls in the reference: twophase.py:416-433, singlephase.py:289-301;
  * reasons use PETSc's numbering so that the host raises ConvergenceError where Firedrake does, thermalmodel.py:170) */
 int tp_fgmres(tp_ctx *ctx, int32_t b, int32_t x, int32_t *its, int32_t *reason, double *rnorm);
+/* Right-preconditioned BiCGStab from x0 = 0 with the same preconditioner and operator (ksp_type fbcgs); mirrors tp_fgmres and
+ * runs whatever tp_options.ksp_kind says.  its counts BiCGStab iterations (two preconditioner applications each); reason:
+ * 2 converged (also b = 0, with 0 iterations), -3 ksp_max_it reached, -5 breakdown ((r^,r) = 0, (r^,v) = 0, or J M s = 0 for an
+ * s above the tolerance), -9 NaN or Inf.  After -5 and -9 x holds the last iterate that was formed from finite numbers. */
+int tp_bcgs(tp_ctx *ctx, int32_t b, int32_t x, int32_t *its, int32_t *reason, double *rnorm);
+/* out = {ksp_kind in effect, device bytes of Krylov workspace currently allocated (the FGMRES bases V and Z and the BiCGStab
+ * vectors; the scratch vectors every method shares with the preconditioner are not counted), number of BiCGStab work vectors
+ * allocated (0 before the first BiCGStab solve), pc_apply programs recorded since the last set-up that invalidated them and
+ * still replayable (a set-up that leaves addresses and options alone keeps them): 2 for a context that runs BiCGStab only} */
+int tp_ksp_info(tp_ctx *ctx, int64_t out[4]);
 int tp_newton_solve(tp_ctx *ctx, tp_solve_info *info);
 
 /* measurement hooks for bench.py: average device time (ms, HIP events on the context's stream)

@@ -310,6 +310,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     TP_REQUIRE(ndev > 0, "no HIP device: the thermalporous hot path has no CPU fallback");
     TP_REQUIRE(device >= 0 && device < ndev, "bad device ordinal");
     inner_check_options(*opt);
+    bcgs_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
@@ -362,6 +363,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_levels), "ilu_single (fp32 factor) is implemented for block-ILU(0): not with ilu_levels 1");
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
     inner_check_options(*opt);
+    bcgs_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
@@ -796,6 +798,26 @@ int tp_fgmres(tp_ctx *c, int32_t b, int32_t x, int32_t *its, int32_t *reason, do
     if (its) *its = it;
     if (reason) *reason = r;
     if (rnorm) *rnorm = rn;
+    TP_API_END
+}
+
+int tp_bcgs(tp_ctx *c, int32_t b, int32_t x, int32_t *its, int32_t *reason, double *rnorm) {
+    TP_API_BEGIN
+    TP_REQUIRE(b != x, "b and x must differ");
+    if (!c->pc_ready) pc_setup(c);
+    int it = 0;
+    double rn = 0.0;
+    const int r = bcgs(c, vec_of(c, b).p, vec_of(c, x).p, &it, &rn);
+    if (its) *its = it;
+    if (reason) *reason = r;
+    if (rnorm) *rnorm = rn;
+    TP_API_END
+}
+
+int tp_ksp_info(tp_ctx *c, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "null argument");
+    ksp_info(c, out);
     TP_API_END
 }
 

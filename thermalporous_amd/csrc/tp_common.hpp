@@ -281,6 +281,15 @@ struct InnerWork {
     DBuf<long long> stats;     // applies, iterations used, unconverged (tp_inner_stats)
 };
 
+// workspace of the outer BiCGStab (tp_bcgs.hip, tp_options.ksp_kind = 1): a fixed set of vectors allocated once per context --
+// their addresses are the (input, output) pairs of the two pc_apply programs a set-up records -- and the device block that
+// holds every scalar of the iteration
+struct BcgsWork {
+    DBuf<double> vec;          // r^, r, p, v, s, p^, s^: 7 vectors of b*ntot (t lives in tp_ctx::w2)
+    DBuf<double> partial;      // per-wave partial sums, two outputs
+    DBuf<double> state;        // sums, rho, alpha, omega, beta, tol, latches
+};
+
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
@@ -349,6 +358,7 @@ struct tp_ctx {
     // FGMRES workspace
     tp::DBuf<double> V, Z, gs_partial, gs_h, red_out;
     int gs_cap = 0;
+    tp::BcgsWork bcgs;                 // ksp_kind 1: the BiCGStab work vectors and its device-resident scalars (tp_bcgs.hip)
     std::vector<double> hostbuf;
     // scratch vectors for PC apply
     tp::DBuf<double> w1, w2, w3, w4, dx;
@@ -474,5 +484,9 @@ void pc_setup(tp_ctx *c);
 void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary = true);
 void pc_apply(tp_ctx *c, const double *x, double *y);
 int fgmres(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
+// outer BiCGStab (tp_bcgs.hip): same contract as fgmres; reasons 2, -3, -5 (breakdown), -9
+int bcgs(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
+void bcgs_check_options(const tp_options &o);
+void ksp_info(tp_ctx *c, int64_t out[4]);
 void newton(tp_ctx *c, tp_solve_info *info);
 }  // namespace tp

@@ -450,6 +450,7 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
 
 // ------------------------------------------------------------------------------------------------
 // FGMRES(m) from x0 = 0.  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
+// (the other outer method, tp_options.ksp_kind = 1, is bcgs in tp_bcgs.hip)
 int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
     const GridDev &g = c->g;
     const int B = c->b;
@@ -617,7 +618,8 @@ void newton(tp_ctx *c, tp_solve_info *info) {
         pc_setup(c);
         int kits = 0;
         double rn = 0.0;
-        kreason = fgmres(c, c->R.p, dx->p, &kits, &rn);
+        // (lits counts Krylov iterations: a BiCGStab iteration applies the preconditioner twice, vcycles counts per application)
+        kreason = c->opt.ksp_kind == 1 ? bcgs(c, c->R.p, dx->p, &kits, &rn) : fgmres(c, c->R.p, dx->p, &kits, &rn);
         lits += kits;
         if (kreason < 0) { reason = -3; break; }                 // SNES_DIVERGED_LINEAR_SOLVE
         vec_axpy_owned(c, B, -1.0, dx->p, c->u.p);               // basic line search, lambda = 1

@@ -47,7 +47,7 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
-                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32),
+                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32), ("ksp_kind", C.c_int32),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
@@ -66,12 +66,14 @@ API_SYMBOLS = (
     "tp_well_rates", "tp_vec_create", "tp_vec_create_batch", "tp_vec_dot_batch", "tp_vec_axpy_batch", "tp_vec_norm2", "tp_set_ksp_monitor", "tp_vec_set", "tp_vec_get", "tp_vec_copy_residual", "tp_spmv", "tp_pc_setup",
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
-    "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info",
+    "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
 )
 
 DEFAULT_OPTS = dict(
     pc="cpr", decoup="No",
     ksp_rtol=1e-7, ksp_atol=1e-50, ksp_max_it=200, ksp_restart=200,
+    ksp="fgmres",           # outer Krylov method: "fgmres" (restarted, ksp_restart) | "bcgs": right-preconditioned BiCGStab, seven vectors
+                            # plus the shared scratch w2 whatever the iteration count, two preconditioner applications per iteration (tp_options.ksp_kind)
     snes_rtol=1e-8, snes_atol=1e-50, snes_stol=1e-8, snes_max_it=15,
     amg_omega=0.9,          # damped-Jacobi weight (round 3: 0.8 -> 0.9 buys 3 % fewer Krylov iterations on C4 at equal cycle cost, +4 % Newton steps/s
                             # over 80 time steps, measured twice; 0.88-0.9 is a plateau, 0.95 starts to fail solves, 1.0 loses 40 %; C1-C3 neutral)
@@ -279,6 +281,7 @@ def check_amg_line_options(o, nranks=1, exc=EngineError):
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
+_KSP = {"fgmres": 0, "bcgs": 1}
 
 
 def load_library(path=None):
@@ -382,9 +385,16 @@ class HipEngine:
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
                           int(bool(o.get("ilu_whole", False))),
                           (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
-                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)),
+                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
+
+    @staticmethod
+    def _ksp_kind(o):
+        k = o.get("ksp", "fgmres")
+        if k not in _KSP:
+            raise ValueError("ksp = %r: 'fgmres' or 'bcgs'" % (k,))
+        return _KSP[k]
 
     def set_options(self, **kw):
         check_amg_line_options({**self.opts, **kw}, self.nranks)
@@ -539,7 +549,7 @@ class HipEngine:
         return out.value
 
     def set_ksp_monitor(self, fn):
-        """fn(its, rnorm, field_norms) at every FGMRES iteration (the reference's ksp_monitor_residuals monitor,
+        """fn(its, rnorm, field_norms) at every iteration of the outer Krylov method (the reference's ksp_monitor_residuals monitor,
         thermalmodel.py:44-74); None removes it."""
         proto = C.CFUNCTYPE(None, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
         if fn is None:
@@ -587,6 +597,18 @@ class HipEngine:
         its, reason, rn = C.c_int32(), C.c_int32(), C.c_double()
         self._ck(self.lib.tp_fgmres(self.ctx, self.vec(b), self.vec(x), C.byref(its), C.byref(reason), C.byref(rn)))
         return its.value, reason.value, rn.value
+
+    def bcgs(self, b, x):
+        """Right-preconditioned BiCGStab from x0 = 0 (tp_bcgs): (iterations, KSP reason, recurrence residual norm)."""
+        its, reason, rn = C.c_int32(), C.c_int32(), C.c_double()
+        self._ck(self.lib.tp_bcgs(self.ctx, self.vec(b), self.vec(x), C.byref(its), C.byref(reason), C.byref(rn)))
+        return its.value, reason.value, rn.value
+
+    def ksp_info(self):
+        """The outer Krylov method in effect and its workspace (tp_ksp_info)."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_ksp_info(self.ctx, out))
+        return dict(kind=out[0], bytes=out[1], bcgs_vectors=out[2], pc_programs=out[3])
 
     def copy_residual_to(self, name):
         self._ck(self.lib.tp_vec_copy_residual(self.ctx, self.vec(name)))

@@ -7,6 +7,8 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
 
   snes_type newtonls  (line search `basic`: Firedrake's default, not settable in the reference)
   ksp_type fgmres|gmres (right preconditioning), ksp_rtol/atol/max_it, ksp_gmres_restart
+  ksp_type fbcgs | bcgs + ksp_pc_side right: right-preconditioned BiCGStab (engine key ksp = "bcgs"); ksp_gmres_restart is
+     consumed and has no effect on it
   pc_type composite, pc_composite_type multiplicative, pc_composite_pcs "python,bjacobi"
      sub_0_pc_python_type  ...CPRStage1PC | ...CPTRStage1PC   sub_0_cpr_decoup  No|QI|TI
      sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur-FULL with ConvDiffSchurTwoPhasesPC
@@ -227,12 +229,18 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     # (l2 only inside the FAS presets, twophase.py:437): anything but basic would silently change the algorithm
     _take(sp, used, "snes_linesearch_type", ("basic",))
     _take(sp, used, "mat_type", ("aij",))
-    ksp = _take(sp, used, "ksp_type", ("fgmres", "gmres"), "gmres")
+    ksp = _take(sp, used, "ksp_type", ("fgmres", "gmres", "fbcgs", "bcgs"), "gmres")
     side = _take(sp, used, "ksp_pc_side", ("right",))
     if ksp == "gmres" and side is None:
         raise NotImplementedError("ksp_type gmres without ksp_pc_side: PETSc would precondition from the LEFT; only "
                                   "right-preconditioned (F)GMRES is implemented (the reference sets ksp_pc_side right, "
                                   "singlephase.py:296)")
+    if ksp == "bcgs" and side is None:
+        raise NotImplementedError("ksp_type bcgs without ksp_pc_side: PETSc would precondition from the LEFT; only "
+                                  "right-preconditioned BiCGStab is implemented (ksp_type fbcgs, or bcgs with ksp_pc_side right)")
+    # outer Krylov method of the engine: restarted FGMRES, or BiCGStab (under which ksp_gmres_restart is consumed below and
+    # has no effect: the newton_krylov dicts carry it)
+    o["ksp"] = "bcgs" if ksp in ("fbcgs", "bcgs") else "fgmres"
     for k_src, k_dst in (("ksp_rtol", "ksp_rtol"), ("ksp_atol", "ksp_atol"), ("ksp_max_it", "ksp_max_it"),
                          ("ksp_gmres_restart", "ksp_restart"), ("snes_max_it", "snes_max_it"),
                          ("snes_rtol", "snes_rtol"), ("snes_atol", "snes_atol"), ("snes_stol", "snes_stol")):
