@@ -129,6 +129,17 @@ typedef struct tp_options {
                                 is a line level when it is above the single-workgroup tail, among the first L levels and has
                                 n0 >= 2; L <= amg_full_levels.  0 (default): off, the point-Jacobi launch sequence.  One slab
                                 only; not with amg_single, pc_kind 3 or schur_a11 = 2 (refused, never ignored) */
+    int32_t ksp_basis_single;/* 1: the two FGMRES bases V and Z stored in fp32 (compressed-basis GMRES): compact vectors of the owned
+                                entries, half the Krylov workspace and half the bytes Gram-Schmidt moves; every sum, the iterate,
+                                the residual and the preconditioner stay fp64.  z_j is rounded BEFORE J is applied to it, so only
+                                the rounding of v_{j+1} perturbs the Arnoldi relation.  A restart cycle also ends when its
+                                recurrence residual has fallen to ksp_single_floor times the true residual it started from, and
+                                convergence is declared only on a recomputed true residual ||b - J x||, which is the rnorm
+                                returned.  FGMRES only: refused with ksp_kind 1.  0 (default): the fp64 bases.  NOTE for ABI readers:
+                                this field and ksp_single_floor were added HERE, before ksp_kind, not at the struct's tail: every
+                                field from ksp_kind on moved by 16 bytes and sizeof(tp_options) grew; recompile callers */
+    double  ksp_single_floor;/* theta of ksp_basis_single, 2^-24 < theta < 1 (1e-7): what one cycle may reduce the residual by
+                                before the rounded basis has lost its orthogonality.  Ignored when ksp_basis_single is 0 */
     int32_t ksp_kind;        /* outer Krylov method of tp_newton_solve: 0 = restarted FGMRES (the default: ksp_type fgmres, or gmres with
                                 ksp_pc_side right), 1 = right-preconditioned (flexible) BiCGStab (ksp_type fbcgs, or bcgs with
                                 ksp_pc_side right): a short recurrence on seven vectors plus the shared scratch w2 (what tp_ksp_info
@@ -230,6 +241,17 @@ int tp_vec_create_batch(tp_ctx *ctx, int32_t n, int32_t *first_id);
 int tp_vec_dot_batch(tp_ctx *ctx, int32_t first, int32_t n, int32_t w, double *out);
 int tp_vec_axpy_batch(tp_ctx *ctx, int32_t first, int32_t n, const double *coef, int32_t w);
 int tp_vec_norm2(tp_ctx *ctx, int32_t x, double *out);
+/* The same kernels on a compact fp32 batch (the storage of ksp_basis_single; exported so that they can be tested alone):
+ *   tp_fvec_create_batch  n float vectors of b * owned cells entries (field-major, no halo planes) at the basis stride
+ *   tp_fvec_store         slot i <- (float) x, and x <- (double) slot i in the same pass: the solver's round-and-store kernel
+ *   tp_fvec_get           slot i -> host, b * owned cells floats
+ *   tp_fvec_dot_batch     out[i] = <slot_i, w>, i < n, fp64 sums of widened entries
+ *   tp_fvec_axpy_batch    w += sum_i coef[i] slot_i, i < n */
+int tp_fvec_create_batch(tp_ctx *ctx, int32_t n, int32_t *batch);
+int tp_fvec_store(tp_ctx *ctx, int32_t batch, int32_t i, int32_t x);
+int tp_fvec_get(tp_ctx *ctx, int32_t batch, int32_t i, float *host);
+int tp_fvec_dot_batch(tp_ctx *ctx, int32_t batch, int32_t n, int32_t w, double *out);
+int tp_fvec_axpy_batch(tp_ctx *ctx, int32_t batch, int32_t n, const double *coef, int32_t w);
 int tp_spmv(tp_ctx *ctx, int32_t x, int32_t y);            /* y = J x */
 int tp_pc_setup(tp_ctx *ctx);                              /* PCSetUp: decoupling, AMG setup, ILU factor */
 int tp_pc_apply(tp_ctx *ctx, int32_t x, int32_t y);        /* composite multiplicative (stage1, ILU0) */
@@ -266,17 +288,23 @@ int tp_fgmres(tp_ctx *ctx, int32_t b, int32_t x, int32_t *its, int32_t *reason, 
  * 2 converged (also b = 0, with 0 iterations), -3 ksp_max_it reached, -5 breakdown ((r^,r) = 0, (r^,v) = 0, or J M s = 0 for an
  * s above the tolerance), -9 NaN or Inf.  After -5 and -9 x holds the last iterate that was formed from finite numbers. */
 int tp_bcgs(tp_ctx *ctx, int32_t b, int32_t x, int32_t *its, int32_t *reason, double *rnorm);
-/* out = {ksp_kind in effect, device bytes of Krylov workspace currently allocated (the FGMRES bases V and Z and the BiCGStab
- * vectors; the scratch vectors every method shares with the preconditioner are not counted), number of BiCGStab work vectors
+/* out = {ksp_kind in effect, device bytes of Krylov workspace currently allocated (the FGMRES bases V and Z -- under
+ * ksp_basis_single the two fp32 bases and the fp64 staging vectors -- and the BiCGStab vectors; the scratch vectors every method shares with the preconditioner are not counted), number of BiCGStab work vectors
  * allocated (0 before the first BiCGStab solve), pc_apply programs recorded since the last set-up that invalidated them and
  * still replayable (a set-up that leaves addresses and options alone keeps them): 2 for a context that runs BiCGStab only} */
 int tp_ksp_info(tp_ctx *ctx, int64_t out[4]);
+/* The FGMRES bases under ksp_basis_single: out = {1 if the option is in effect else 0, capacity of each fp32 basis in vectors (0
+ * before the first such solve), stride between two stored vectors in entries (b * owned cells rounded up to a multiple of 64),
+ * fp64 staging vectors allocated (b * ntot doubles each), restart cycles of the last fp32-basis FGMRES solve, true-residual
+ * evaluations (one SpMV and one norm each) of that solve}.  tp_ksp_info's bytes count these buffers too. */
+int tp_ksp_basis_info(tp_ctx *ctx, int64_t out[6]);
 int tp_newton_solve(tp_ctx *ctx, tp_solve_info *info);
 
 /* measurement hooks for bench.py: average device time (ms, HIP events on the context's stream)
  * of `reps` launches of one hot kernel.  which: 0 block SpMV, 1 ILU solve, 2 AMG V-cycle (pressure),
  * 3 assembly (residual+Jacobian), 4 full pc_apply, 5 pc_setup, 6 ILU factorisation, 7 one classical Gram-Schmidt
- * step against 16 basis vectors (VecMDot + VecMAXPY + VecNorm; needs a Krylov basis from an earlier solve). */
+ * step against 16 basis vectors (VecMDot + VecMAXPY + VecNorm; needs a Krylov basis from an earlier solve), 8 the same step
+ * against 16 vectors of the fp32 basis (needs one from an earlier ksp_basis_single solve). */
 int tp_time_kernel(tp_ctx *ctx, int32_t which, int32_t reps, double *ms_avg);
 int tp_amg_info(tp_ctx *ctx, int32_t which, int32_t *nlevels, double *op_complexity);
 /* level at which hierarchy `which` ends with relaxation only (amg_dom_tau), -1: full V-cycle; ratio0 = the

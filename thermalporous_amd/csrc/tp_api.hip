@@ -240,6 +240,7 @@ tp_ctx::~tp_ctx() {
         fprintf(stderr, "[tp] pipelined FGMRES: %ld speculative applications issued, %ld discarded, %ld iterations without one\n",
                 spec_issued, spec_wasted, spec_skipped);
     for (auto *v : vecs) delete v;
+    for (auto *f : fbatches) delete f;
     tp::drop_hierarchies(this);
     pc_programs.clear();                 // (the graph segments go before the stream they were captured on)
     if (comm) ncclCommDestroy((ncclComm_t)comm);
@@ -311,6 +312,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     TP_REQUIRE(device >= 0 && device < ndev, "bad device ordinal");
     inner_check_options(*opt);
     bcgs_check_options(*opt);
+    basis_single_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
@@ -364,6 +366,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
     inner_check_options(*opt);
     bcgs_check_options(*opt);
+    basis_single_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
@@ -376,6 +379,8 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
                              opt->amg_dom_tau != c->opt.amg_dom_tau || opt->amg_line_levels != c->opt.amg_line_levels ||
                              opt->amg_single != c->opt.amg_single || opt->amg_gather_cells != c->opt.amg_gather_cells ||
                              opt->schur_a11 != c->opt.schur_a11 || opt->fs_additive != c->opt.fs_additive;
+    // the FGMRES bases exist in one representation at a time: the next solve allocates the one the option asks for
+    if ((opt->ksp_basis_single != 0) != (c->opt.ksp_basis_single != 0)) basis_single_release(c);
     c->opt = *opt;
     if (tile_changed) c->ilu.slots = 0;
     if (amg_changed) drop_hierarchies(c);
@@ -673,6 +678,56 @@ int tp_vec_axpy_batch(tp_ctx *c, int32_t first, int32_t n, const double *coef, i
     TP_API_END
 }
 
+static FBatch &fbatch_of(tp_ctx *c, int32_t id, int32_t n) {
+    TP_REQUIRE(id >= 0 && id < (int)c->fbatches.size(), "bad float batch id");
+    TP_REQUIRE(n >= 0 && n <= c->fbatches[id]->n, "float batch has fewer vectors");
+    return *c->fbatches[id];
+}
+
+int tp_fvec_create_batch(tp_ctx *c, int32_t n, int32_t *batch) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && n >= 1 && batch, "bad arguments");
+    auto *f = new FBatch();
+    c->fbatches.push_back(f);
+    f->buf.alloc((size_t)n * basis_stride(c));
+    f->n = n;
+    *batch = (int32_t)c->fbatches.size() - 1;
+    TP_API_END
+}
+
+int tp_fvec_store(tp_ctx *c, int32_t batch, int32_t i, int32_t x) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && i >= 0, "bad arguments");
+    FBatch &f = fbatch_of(c, batch, i + 1);
+    basis_round_store(c, c->b, vec_of(c, x).p, f.buf.p + (size_t)i * basis_stride(c));
+    TP_HIP(hipGetLastError());
+    TP_API_END
+}
+
+int tp_fvec_get(tp_ctx *c, int32_t batch, int32_t i, float *host) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && i >= 0 && host, "bad arguments");
+    FBatch &f = fbatch_of(c, batch, i + 1);
+    copy_sync(c, host, f.buf.p + (size_t)i * basis_stride(c), sizeof(float) * (size_t)c->b * c->g.nown, hipMemcpyDeviceToHost);
+    TP_API_END
+}
+
+int tp_fvec_dot_batch(tp_ctx *c, int32_t batch, int32_t n, int32_t w, double *out) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && n >= 1 && out, "bad arguments");
+    FBatch &f = fbatch_of(c, batch, n);
+    multi_dot_s(c, c->b, f.buf.p, basis_stride(c), n, vec_of(c, w).p, out);
+    TP_API_END
+}
+
+int tp_fvec_axpy_batch(tp_ctx *c, int32_t batch, int32_t n, const double *coef, int32_t w) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && n >= 1 && coef, "bad arguments");
+    FBatch &f = fbatch_of(c, batch, n);
+    multi_axpy_s(c, c->b, f.buf.p, basis_stride(c), n, coef, 1.0, vec_of(c, w).p);
+    TP_API_END
+}
+
 int tp_vec_norm2(tp_ctx *c, int32_t x, double *out) {
     TP_API_BEGIN
     TP_REQUIRE(c && out, "bad arguments");
@@ -821,6 +876,18 @@ int tp_ksp_info(tp_ctx *c, int64_t out[4]) {
     TP_API_END
 }
 
+int tp_ksp_basis_info(tp_ctx *c, int64_t out[6]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "null argument");
+    out[0] = c->opt.ksp_basis_single ? 1 : 0;
+    out[1] = c->gs_cap_s;
+    out[2] = basis_stride(c);
+    out[3] = (int64_t)(c->kstage.n / ((size_t)c->b * c->g.ntot));
+    out[4] = c->ksp_cycles;
+    out[5] = c->ksp_true_res;
+    TP_API_END
+}
+
 int tp_inner_stats(tp_ctx *c, int64_t *applies, int64_t *its, int64_t *unconverged) {
     TP_API_BEGIN
     TP_REQUIRE(c, "null argument");
@@ -864,6 +931,12 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
                 TP_REQUIRE(c->gs_cap >= 17, "Krylov basis smaller than 17 vectors: run a solve first");
                 std::vector<double> hh(18);
                 orthogonalize(c, c->b, c->V.p, (long)c->b * c->g.ntot, 16, c->w2.p, hh.data());
+                break;
+            }
+            case 8: {       // the same step against 16 vectors of the fp32 basis
+                TP_REQUIRE(c->gs_cap_s >= 17, "fp32 Krylov basis smaller than 17 vectors: run a ksp_basis_single solve first");
+                std::vector<double> hh(18);
+                orthogonalize_s(c, c->b, c->Vs.p, basis_stride(c), 16, c->w2.p, hh.data());
                 break;
             }
             default: throw Error("unknown kernel id");

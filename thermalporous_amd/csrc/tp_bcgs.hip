@@ -380,7 +380,7 @@ static void bcgs_ensure(tp_ctx *c) {
 
 void ksp_info(tp_ctx *c, int64_t out[4]) {
     out[0] = c->opt.ksp_kind;
-    out[1] = (int64_t)((c->V.n + c->Z.n + c->bcgs.vec.n) * sizeof(double));
+    out[1] = (int64_t)((c->V.n + c->Z.n + c->bcgs.vec.n + c->kstage.n) * sizeof(double) + (c->Vs.n + c->Zs.n) * sizeof(float));
     out[2] = c->bcgs.vec.n ? BCGS_NVEC : 0;
     out[3] = c->pc_graph_epoch == c->graph_epoch ? (int64_t)c->pc_programs.size() : 0;
 }

@@ -290,6 +290,12 @@ struct BcgsWork {
     DBuf<double> state;        // sums, rho, alpha, omega, beta, tol, latches
 };
 
+// a batch of n compact fp32 vectors at the basis stride (tp_fvec_create_batch: the kernels of ksp_basis_single, testable alone)
+struct FBatch {
+    DBuf<float> buf;
+    int n = 0;
+};
+
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
@@ -358,6 +364,17 @@ struct tp_ctx {
     // FGMRES workspace
     tp::DBuf<double> V, Z, gs_partial, gs_h, red_out;
     int gs_cap = 0;
+    // tp_options.ksp_basis_single: the two bases as COMPACT fp32 vectors (owned entries only, field-major, stride
+    // basis_stride()) plus a ring of KS_STAGE fp64 staging vectors in the ordinary halo layout at fixed addresses: slot 0 holds
+    // w = J z_j, orthogonalised and normalised in place into the widened stored v_{j+1}; slot 1 the widened stored z_j.  Every
+    // preconditioner application of a solve is the one (slot 0, slot 1) program.  Exactly one representation is allocated:
+    // tp_set_options frees both when the option changes.
+    static constexpr int KS_STAGE = 2;
+    tp::DBuf<float> Vs, Zs;
+    tp::DBuf<double> kstage;
+    int gs_cap_s = 0;
+    long ksp_cycles = 0, ksp_true_res = 0;   // restart cycles / true-residual evaluations of the last fp32-basis solve (tp_ksp_basis_info)
+    std::vector<tp::FBatch *> fbatches;      // fp32 vector batches of the C ABI (tp_fvec_*)
     tp::BcgsWork bcgs;                 // ksp_kind 1: the BiCGStab work vectors and its device-resident scalars (tp_bcgs.hip)
     std::vector<double> hostbuf;
     // scratch vectors for PC apply
@@ -423,6 +440,15 @@ void orthogonalize_enqueue(tp_ctx *c, int nf, const double *V, long vstride, int
 const double *orthogonalize_norm_dev(const tp_ctx *c, int k);
 void orthogonalize_wait(tp_ctx *c, int k, double *host_out);
 void vec_scale_dev_norm(tp_ctx *c, int nf, const double *n2_dev, double *x);   // x *= 1/sqrt(*n2_dev) (owned)
+// fp32 Krylov bases (tp_options.ksp_basis_single; tp_linalg.hip): Vs points at compact float vectors `vstride` entries apart
+long basis_stride(const tp_ctx *c);                                              // b*nown rounded up to 64 entries
+void basis_round_store(tp_ctx *c, int nf, double *z, float *slot);             // slot = (float) z ; z = (double) slot
+void basis_scale_store(tp_ctx *c, int nf, double a, const double *x, double *y, float *slot);   // slot = (float)(a x) ; y = (double) slot
+void basis_scale_store_dev(tp_ctx *c, int nf, const double *n2_dev, double *x, float *slot);    // the same in place, a = 1/sqrt(*n2_dev)
+void multi_dot_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *w, double *host_out);
+void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *hcoef_host, double sign, double *w);
+void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w, double *host_out);
+void orthogonalize_enqueue_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w);
 void field_minmax(tp_ctx *c, const double *x, double *lo, double *hi);
 void field_clamp01(tp_ctx *c, double *x);
 // stencil operators
@@ -488,5 +514,7 @@ int fgmres(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
 int bcgs(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
 void bcgs_check_options(const tp_options &o);
 void ksp_info(tp_ctx *c, int64_t out[4]);
+void basis_single_check_options(const tp_options &o);
+void basis_single_release(tp_ctx *c);     // frees the FGMRES bases of both representations (the option changed)
 void newton(tp_ctx *c, tp_solve_info *info);
 }  // namespace tp

@@ -332,7 +332,264 @@ __global__ __launch_bounds__(256) void k_multi_axpy_norm(GridDev g, int nf, cons
     if (lane == 0) partial[wave] = acc;
 }
 
-void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, double *host_out) {
+// ---- fp32 Krylov bases (tp_options.ksp_basis_single) ------------------------------------------------
+// The FGMRES bases stored as floats, all arithmetic fp64 on widened loads.  A stored vector is COMPACT: the
+// nf * nown owned entries only, field-major -- entry t = owned cell t % nown of field t / nown -- without halo planes, at a
+// stride of basis_stride() entries (a multiple of 64 = 256 bytes; the padding is zeroed once and never written).  The fp64
+// vector on the other side of every kernel (w, z, v) keeps the ordinary halo layout.
+// Lane mapping: a wave owns the same chunk of 64 * MD_CHUNK entries as in the fp64 kernels, but a lane takes VW ADJACENT entries
+// per load (VW = 4: one 16-byte load where the fp64 kernels issue one 8-byte load per entry), MD_CHUNK / VW loads per basis
+// vector: a 4-byte load per lane would put half the bytes of the fp64 kernels in flight per instruction.  Groups that start at
+// or beyond the stride (the last wave's) read entry 0 with weight 0.
+long basis_stride(const tp_ctx *c) { return ((long)c->b * c->g.nown + 63) / 64 * 64; }
+
+template <int VW> struct FLoad;
+template <> struct FLoad<1> { static __device__ __forceinline__ void ld(const float *p, float (&o)[1]) { o[0] = *p; } };
+template <> struct FLoad<2> {
+    static __device__ __forceinline__ void ld(const float *p, float (&o)[2]) { const float2 v = *(const float2 *)p; o[0] = v.x; o[1] = v.y; }
+};
+template <> struct FLoad<4> {
+    static __device__ __forceinline__ void ld(const float *p, float (&o)[4]) {
+        const float4 v = *(const float4 *)p;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+};
+
+// entry offsets and the w indices of this lane's MD_CHUNK / VW groups of wave `wave`
+template <int CH, int VW>
+__device__ __forceinline__ void bs_lane_entries(const GridDev &g, long nall, long vstride, long wave, int lane, long (&off)[CH / VW],
+                                                long (&idx)[CH / VW][VW], bool (&ok)[CH / VW][VW]) {
+#pragma unroll
+    for (int q = 0; q < CH / VW; ++q) {
+        const long t0 = wave * (64L * CH) + ((long)q * 64 + lane) * VW;
+        off[q] = t0 < vstride ? t0 : 0;             // (vstride is a multiple of 64: a group never straddles it)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            const long t = t0 + e;
+            ok[q][e] = t < nall;
+            const long tt = ok[q][e] ? t : 0;
+            const long f = tt / g.nown, i = tt - f * g.nown;
+            idx[q][e] = f * g.ntot + g.np + i;
+        }
+    }
+}
+
+template <int CH, int VW>
+__global__ __launch_bounds__(256) void k_multi_dot_s(GridDev g, int nf, const float *__restrict__ V, long vstride, int k,
+                                                     const double *__restrict__ w, double *__restrict__ partial, long nwaves) {
+    constexpr int NG = CH / VW;
+    const long wave = ((long)blockIdx.x * TP_BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wave >= nwaves) return;
+    long off[NG], idx[NG][VW];
+    bool ok[NG][VW];
+    double wv[NG][VW];
+    bs_lane_entries<CH, VW>(g, g.nown * nf, vstride, wave, lane, off, idx, ok);
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) wv[q][e] = ok[q][e] ? w[idx[q][e]] : 0.0;
+    int i = 0;
+    for (; i + MD_U <= k; i += MD_U) {
+        float v[MD_U][NG][VW];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u)
+#pragma unroll
+            for (int q = 0; q < NG; ++q) FLoad<VW>::ld(V + (long)(i + u) * vstride + off[q], v[u][q]);
+        double s[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+            s[u] = 0.0;
+#pragma unroll
+            for (int q = 0; q < NG; ++q)
+#pragma unroll
+                for (int e = 0; e < VW; ++e) s[u] += (double)v[u][q][e] * wv[q][e];
+        }
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) s[u] = wave_sum(s[u]);
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < MD_U; ++u) partial[(long)(i + u) * nwaves + wave] = s[u];
+        }
+    }
+    for (; i < k; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            float v[VW];
+            FLoad<VW>::ld(V + (long)i * vstride + off[q], v);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) s += (double)v[e] * wv[q][e];
+        }
+        s = wave_sum(s);
+        if (lane == 0) partial[(long)i * nwaves + wave] = s;
+    }
+}
+
+// w -= V h ; per-wave ||w||^2 (k_multi_axpy_norm on the fp32 basis: same chunks, same reverse traversal)
+template <int CH, int VW>
+__global__ __launch_bounds__(256) void k_multi_axpy_norm_s(GridDev g, int nf, const float *__restrict__ V, long vstride, int k,
+                                                           const double *__restrict__ h, double *w, double *__restrict__ partial,
+                                                           long nwaves, int rev) {
+    constexpr int NG = CH / VW;
+    const long wave_d = ((long)blockIdx.x * TP_BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wave_d >= nwaves) return;
+    const long wave = rev ? nwaves - 1 - wave_d : wave_d;
+    long off[NG], idx[NG][VW];
+    bool ok[NG][VW];
+    double s[NG][VW], w0[NG][VW];
+    bs_lane_entries<CH, VW>(g, g.nown * nf, vstride, wave, lane, off, idx, ok);
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { s[q][e] = 0.0; w0[q][e] = w[idx[q][e]]; }
+    int p = 0;
+    for (; p + MD_U <= k; p += MD_U) {
+        float v[MD_U][NG][VW];
+        double hp[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+            hp[u] = h[p + u];
+#pragma unroll
+            for (int q = 0; q < NG; ++q) FLoad<VW>::ld(V + (long)(p + u) * vstride + off[q], v[u][q]);
+        }
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u)
+#pragma unroll
+            for (int q = 0; q < NG; ++q)
+#pragma unroll
+                for (int e = 0; e < VW; ++e) s[q][e] += hp[u] * (double)v[u][q][e];
+    }
+    for (; p < k; ++p) {
+        const double hp = h[p];
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            float v[VW];
+            FLoad<VW>::ld(V + (long)p * vstride + off[q], v);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) s[q][e] += hp * (double)v[e];
+        }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            if (ok[q][e]) {
+                const double wn = w0[q][e] - s[q][e];
+                w[idx[q][e]] = wn;
+                acc += wn * wn;
+            }
+        }
+    acc = wave_sum(acc);
+    if (lane == 0) partial[wave] = acc;
+}
+
+// w += sign * sum_i h_i V_i on the fp32 basis (x += Z y at the end of a cycle: once per cycle, one entry per thread)
+__global__ __launch_bounds__(256) void k_multi_axpy_s(GridDev g, int nf, const float *__restrict__ V, long vstride, int k,
+                                                      const double *__restrict__ h, double sign, double *w) {
+    const long t = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
+    if (t >= g.nown * nf) return;
+    const long f = t / g.nown, i = t - f * g.nown;
+    const long c = f * g.ntot + g.np + i;
+    double s = 0.0;
+    int j = 0;
+    for (; j + MD_U <= k; j += MD_U) {
+        float v[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) v[u] = V[(long)(j + u) * vstride + t];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) s += h[j + u] * (double)v[u];
+    }
+    for (; j < k; ++j) s += h[j] * (double)V[(long)j * vstride + t];
+    w[c] += sign * s;
+}
+
+// slot = (float) z and z = (double) slot in one pass: the preconditioned vector is stored rounded, and J is then applied to
+// exactly what was stored (FGMRES is consistent with any z_j as long as w = J z_j)
+__global__ void k_round_store(GridDev g, int nf, double *z, float *__restrict__ slot) {
+    const long t = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
+    if (t >= g.nown * nf) return;
+    const long f = t / g.nown, i = t - f * g.nown;
+    const long c = f * g.ntot + g.np + i;
+    const float r = (float)z[c];
+    slot[t] = r;
+    z[c] = (double)r;
+}
+// slot = (float)(a x) and y = (double) slot: v_{j+1} = w / ||w|| stored rounded, the next v is exactly the stored one.
+// DEV: a = 1 / sqrt(*n2p) with the zero / non-finite guard of k_scale_dev_norm (the norm is still on the device)
+template <bool DEV>
+__global__ void k_scale_store(GridDev g, int nf, double a_host, const double *__restrict__ n2p, const double *x, double *y,
+                              float *__restrict__ slot) {
+    const long t = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
+    if (t >= g.nown * nf) return;
+    double a = a_host;
+    if (DEV) {
+        const double n2 = *n2p;
+        a = (n2 > 0.0 && isfinite(n2)) ? 1.0 / sqrt(n2) : 0.0;
+    }
+    const long f = t / g.nown, i = t - f * g.nown;
+    const long c = f * g.ntot + g.np + i;
+    const float r = (float)(a * x[c]);
+    slot[t] = r;
+    y[c] = (double)r;
+}
+
+void basis_round_store(tp_ctx *c, int nf, double *z, float *slot) {
+    hipLaunchKernelGGL(k_round_store, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, z, slot);
+}
+void basis_scale_store(tp_ctx *c, int nf, double a, const double *x, double *y, float *slot) {
+    hipLaunchKernelGGL(k_scale_store<false>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, a, (const double *)nullptr, x, y, slot);
+}
+void basis_scale_store_dev(tp_ctx *c, int nf, const double *n2_dev, double *x, float *slot) {
+    hipLaunchKernelGGL(k_scale_store<true>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, 0.0, n2_dev, (const double *)x, x, slot);
+}
+
+// adjacent floats per load in the two Gram-Schmidt passes over the fp32 basis: 4 (one 16-byte load), or TP_BASIS_VEC = 1 | 2
+// (the mappings measured against it)
+static int basis_vec() {
+    static const int vw = [] {
+        const int v = getenv("TP_BASIS_VEC") ? atoi(getenv("TP_BASIS_VEC")) : 4;
+        return (v == 1 || v == 2) ? v : 4;
+    }();
+    return vw;
+}
+#define TP_MDS_LAUNCH(KERNEL, ...)                                                                             \
+    do {                                                                                                       \
+        const int vw_ = basis_vec();                                                                           \
+        if (md_chunk() == 4) {                                                                                 \
+            if (vw_ == 4) hipLaunchKernelGGL((KERNEL<4, 4>), __VA_ARGS__);                                     \
+            else if (vw_ == 2) hipLaunchKernelGGL((KERNEL<4, 2>), __VA_ARGS__);                                \
+            else hipLaunchKernelGGL((KERNEL<4, 1>), __VA_ARGS__);                                              \
+        } else {                                                                                               \
+            if (vw_ == 4) hipLaunchKernelGGL((KERNEL<8, 4>), __VA_ARGS__);                                     \
+            else if (vw_ == 2) hipLaunchKernelGGL((KERNEL<8, 2>), __VA_ARGS__);                                \
+            else hipLaunchKernelGGL((KERNEL<8, 1>), __VA_ARGS__);                                              \
+        }                                                                                                      \
+    } while (0)
+
+void multi_dot_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *w, double *host_out) {
+    const long nw = md_nwaves(c, nf);
+    if ((long)c->gs_partial.n < (long)k * nw) c->gs_partial.alloc((size_t)(k + 32) * nw);
+    if ((long)c->red_out.n < k) c->red_out.alloc(k + 64);
+    TP_MDS_LAUNCH(k_multi_dot_s, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, Vs, vstride, k, w, c->gs_partial.p, nw);
+    reduce_to_host(c, nw, k, host_out);
+}
+
+void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *hcoef_host, double sign, double *w) {
+    if (k <= 0) return;
+    if ((int)c->gs_h.n < k) c->gs_h.alloc(k + 64);
+    TP_HIP(hipMemcpyAsync(c->gs_h.p, hcoef_host, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_multi_axpy_s, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, Vs, vstride, k,
+                       c->gs_h.p, sign, w);
+    TP_HIP(hipGetLastError());
+    TP_HIP(hipStreamSynchronize(c->stream));      // the host buffer may be reused by the caller right away
+}
+
+// (Vs != nullptr: the basis is the compact fp32 one of tp_options.ksp_basis_single and the two passes are its kernels below;
+// everything around them -- partial sums, second stages, all-reduces, hand-over to the host -- is the same)
+static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *Vs, long vstride, int k, double *w, double *host_out) {
     const long nw = md_nwaves(c, nf);
     if ((long)c->gs_partial.n < (long)(k + 1) * nw) c->gs_partial.alloc((size_t)(k + 33) * nw);
     if ((long)c->red_out.n < k + 1) c->red_out.alloc(k + 65);
@@ -343,16 +600,19 @@ void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, doub
     // ||w||^2 / h_{j+1,j}^2 per iteration, the mis-normalised v_{j+1} feeds that back, and FGMRES stalls (the 2-slab case of
     // tests/test_gpu_slabs.py: DIVERGED_ITS where two messages converge in 12 iterations).  The exact one-message form needs
     // a lagged normalisation (two more vector passes and one wasted iteration per solve) for ~10 us of ~700: not adopted.
-    TP_MD_LAUNCH(k_multi_dot, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k, w,
-                 (const double *)nullptr, c->gs_partial.p, nw);
+    if (Vs) TP_MDS_LAUNCH(k_multi_dot_s, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, Vs, vstride, k, w, c->gs_partial.p, nw);
+    else TP_MD_LAUNCH(k_multi_dot, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k, w,
+                      (const double *)nullptr, c->gs_partial.p, nw);
     // one GPU: the sums also go straight to pinned host memory (no copy between the last kernel and the host's wake-up)
     static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
     double *pin = (use_pin && !c->dist && k + 1 <= tp_ctx::H_PIN) ? c->h_pin : nullptr;
     hipLaunchKernelGGL(k_reduce_partials, dim3(k), dim3(1024), 0, c->stream, c->gs_partial.p, nw, c->red_out.p, pin);
     allreduce_sum(c, c->red_out.p, k);
     static const int gs_rev = !(getenv("TP_GS_REVERSE") && atoi(getenv("TP_GS_REVERSE")) == 0);
-    TP_MD_LAUNCH(k_multi_axpy_norm, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k,
-                 c->red_out.p, w, c->gs_partial.p, nw, gs_rev);
+    if (Vs) TP_MDS_LAUNCH(k_multi_axpy_norm_s, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, Vs, vstride, k,
+                          c->red_out.p, w, c->gs_partial.p, nw, gs_rev);
+    else TP_MD_LAUNCH(k_multi_axpy_norm, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k,
+                      c->red_out.p, w, c->gs_partial.p, nw, gs_rev);
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->gs_partial.p, nw, c->red_out.p + k,
                        pin ? pin + k : (double *)nullptr);
     TP_HIP(hipGetLastError());
@@ -376,6 +636,13 @@ void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, doub
     TP_HIP(hipStreamSynchronize(c->stream));
 }
 
+void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, double *host_out) {
+    orthogonalize_any(c, nf, V, nullptr, vstride, k, w, host_out);
+}
+void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w, double *host_out) {
+    orthogonalize_any(c, nf, nullptr, Vs, vstride, k, w, host_out);
+}
+
 // The same in two halves for the pipelined FGMRES loop: enqueue the kernels (and all-reduces) and record an event; later wait
 // for that event only -- whatever was enqueued behind it (the next iteration's preconditioner application) keeps running -- and
 // read the k dots and ||w||^2 from the pinned buffer.  ||w||^2 also stays on the device at orthogonalize_norm_dev(c, k).
@@ -387,6 +654,9 @@ bool orthogonalize_can_split(const tp_ctx *c, int k) {
 }
 void orthogonalize_enqueue(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w) {
     orthogonalize(c, nf, V, vstride, k, w, nullptr);
+}
+void orthogonalize_enqueue_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w) {
+    orthogonalize_s(c, nf, Vs, vstride, k, w, nullptr);
 }
 const double *orthogonalize_norm_dev(const tp_ctx *c, int k) { return c->red_out.p + k; }
 void orthogonalize_wait(tp_ctx *c, int k, double *host_out) {

@@ -449,9 +449,178 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// FGMRES with the bases stored in fp32 (tp_options.ksp_basis_single; compressed-basis GMRES).
+void basis_single_check_options(const tp_options &o) {
+    if (!o.ksp_basis_single) return;
+    TP_REQUIRE(o.ksp_kind == 0, "ksp_basis_single with ksp_kind 1 (bcgs): BiCGStab has no basis to store in fp32");
+    TP_REQUIRE(o.ksp_single_floor > 0x1p-24 && o.ksp_single_floor < 1.0, "ksp_single_floor must lie in (2^-24, 1)");
+}
+void basis_single_release(tp_ctx *c) {
+    c->V.free(); c->Z.free(); c->gs_cap = 0;
+    c->Vs.free(); c->Zs.free(); c->kstage.free(); c->gs_cap_s = 0;
+}
+
+// column j of the Hessenberg matrix from the Gram-Schmidt coefficients hcol[0..j] and hn = ||w||: the previous Givens rotations,
+// the new one, the rotated right-hand side.  Returns the recurrence residual norm |g_{j+1}|
+static double givens_column(std::vector<double> &H, std::vector<double> &cs, std::vector<double> &sn, std::vector<double> &gvec,
+                            const double *hcol, double hn, int m, int j) {
+    for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = hcol[i];
+    H[(size_t)(j + 1) * m + j] = hn;
+    for (int i = 0; i < j; ++i) {
+        const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
+        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
+        H[(size_t)i * m + j] = t;
+    }
+    const double d = std::hypot(H[(size_t)j * m + j], H[(size_t)(j + 1) * m + j]);
+    cs[j] = H[(size_t)j * m + j] / d;
+    sn[j] = H[(size_t)(j + 1) * m + j] / d;
+    H[(size_t)j * m + j] = d;
+    H[(size_t)(j + 1) * m + j] = 0.0;
+    gvec[j + 1] = -sn[j] * gvec[j];
+    gvec[j] = cs[j] * gvec[j];
+    return std::fabs(gvec[j + 1]);
+}
+// y = H(0:k,0:k)^-1 g(0:k)
+static void hessenberg_solve(const std::vector<double> &H, const std::vector<double> &gvec, int m, int k, std::vector<double> &y) {
+    y.assign(k, 0.0);
+    for (int i = k - 1; i >= 0; --i) {
+        double s = gvec[i];
+        for (int q = i + 1; q < k; ++q) s -= H[(size_t)i * m + q] * y[q];
+        y[i] = s / H[(size_t)i * m + i];
+    }
+}
+
+// The loop of fgmres() below with three differences.  (1) Storage: Vs_j, Zs_j are floats; the fp64 vectors the preconditioner,
+// the SpMV and the orthogonalisation work on are the two staging vectors W and Zt.  z_j = M^-1 v_j is rounded into Zs_j and Zt
+// widened back BEFORE w = J Zt, so FGMRES stays exactly consistent with the stored Z; w is orthogonalised in W against the
+// widened Vs, then W <- widen(Vs_{j+1} = (float)(w/||w||)) in place, which is the next v.  (2) A cycle also ends when its
+// recurrence residual reaches theta * beta_cycle: below that the rounded basis has lost its orthogonality and the recurrence
+// no longer tracks the residual.  (3) Convergence is only ever declared on the recomputed r = b - J x at a cycle's end.
+static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
+    const GridDev &g = c->g;
+    const int B = c->b;
+    const long nv = (long)B * g.ntot, vs = basis_stride(c);
+    const int maxit = c->opt.ksp_max_it;
+    const int restart = std::max(1, std::min(c->opt.ksp_restart, maxit));
+    const double theta = c->opt.ksp_single_floor;
+    ensure_work(c);
+    c->ksp_cycles = c->ksp_true_res = 0;
+    if (c->kstage.n < (size_t)tp_ctx::KS_STAGE * nv) c->kstage.alloc((size_t)tp_ctx::KS_STAGE * nv);
+    double *W = c->kstage.p, *Zt = c->kstage.p + nv;
+    // growth on demand as in fgmres(); the padding between two vectors arrives zeroed and is never written
+    auto ensure_basis = [&](int need) {
+        if (c->gs_cap_s >= need) return;
+        const int cap = std::max(need, std::min(restart + 1, std::max(32, 2 * c->gs_cap_s)));
+        DBuf<float> nV, nZ;
+        nV.alloc((size_t)cap * vs);
+        nZ.alloc((size_t)cap * vs);
+        if (c->gs_cap_s > 0) {
+            TP_HIP(hipMemcpyAsync(nV.p, c->Vs.p, sizeof(float) * c->gs_cap_s * vs, hipMemcpyDeviceToDevice, c->stream));
+            TP_HIP(hipMemcpyAsync(nZ.p, c->Zs.p, sizeof(float) * c->gs_cap_s * vs, hipMemcpyDeviceToDevice, c->stream));
+            TP_HIP(hipStreamSynchronize(c->stream));
+        }
+        std::swap(c->Vs.p, nV.p); std::swap(c->Vs.n, nV.n);
+        std::swap(c->Zs.p, nZ.p); std::swap(c->Zs.n, nZ.n);
+        c->gs_cap_s = cap;
+    };
+    vec_zero(c, x, nv);
+    const double bnorm = norm2(c, B, bvec);
+    int its = 0;
+    if (bnorm == 0.0) { *its_out = 0; *rnorm_out = 0.0; return 2; }
+    if (!std::isfinite(bnorm)) { *its_out = 0; *rnorm_out = bnorm; return -9; }
+    const double tol = std::max(c->opt.ksp_rtol * bnorm, c->opt.ksp_atol);
+    double beta = bnorm;
+    const double *rsrc = bvec;
+    std::vector<double> H, cs, sn, gvec, hcol, yk;
+    static const bool pipe_on = !(getenv("TP_FGMRES_PIPE") && atoi(getenv("TP_FGMRES_PIPE")) == 0);
+    static const double spec_margin = getenv("TP_SPEC_MARGIN") ? atof(getenv("TP_SPEC_MARGIN")) : 4.0;
+    while (true) {
+        const int m = std::min(restart, maxit - its);
+        H.assign((size_t)(m + 1) * m, 0.0);
+        cs.assign(m, 0.0); sn.assign(m, 0.0); gvec.assign(m + 1, 0.0);
+        hcol.resize(m + 2);
+        gvec[0] = beta;
+        const double stop = std::max(tol, theta * beta);                    // this cycle's stopping threshold
+        ++c->ksp_cycles;
+        ensure_basis(2);
+        basis_scale_store(c, B, 1.0 / beta, rsrc, W, c->Vs.p);             // Vs_0 = (float)(r/beta), W = v_0
+        int k = 0;
+        bool nonfinite = false;
+        double res = beta, res_prev = beta, rate = 1.0;
+        bool have_w = false;               // z_j, w = J z_j already enqueued by the previous iteration (pipelining: see fgmres())
+        for (int j = 0; j < m; ++j) {
+            const bool pipe = pipe_on && !c->monitor && orthogonalize_can_split(c, j + 2);
+            ensure_basis(j + (pipe ? 3 : 2));
+            if (!have_w) {
+                pc_apply(c, W, Zt);                                         // z_j = M^-1 v_j
+                basis_round_store(c, B, Zt, c->Zs.p + (long)j * vs);
+                spmv_block_halo(c, c->J.p, Zt, W);                          // w = J (stored z_j)
+            }
+            have_w = false;
+            bool spec = false;
+            if (pipe) {
+                orthogonalize_enqueue_s(c, B, c->Vs.p, vs, j + 1, W);
+                spec = j + 1 < m && its + 1 < maxit && res_prev * std::min(rate, 1.0) > spec_margin * stop;
+                if (spec) ++c->spec_issued; else ++c->spec_skipped;
+                if (spec) {
+                    basis_scale_store_dev(c, B, orthogonalize_norm_dev(c, j + 1), W, c->Vs.p + (long)(j + 1) * vs);
+                    pc_apply(c, W, Zt);
+                    basis_round_store(c, B, Zt, c->Zs.p + (long)(j + 1) * vs);
+                    spmv_block_halo(c, c->J.p, Zt, W);
+                    have_w = true;
+                }
+                orthogonalize_wait(c, j + 1, hcol.data());
+            } else {
+                orthogonalize_s(c, B, c->Vs.p, vs, j + 1, W, hcol.data());
+            }
+            const double hn = std::sqrt(hcol[j + 1]);
+            res = givens_column(H, cs, sn, gvec, hcol.data(), hn, m, j);
+            ++its;
+            k = j + 1;
+            if (c->monitor) {
+                // x_j = x + Zs y_j, r = b - J x_j, ||r_f|| per field (as in fgmres())
+                std::vector<double> ym, fn(B, 0.0);
+                hessenberg_solve(H, gvec, m, k, ym);
+                double *xm = c->w4.p, *rm = c->w2.p;                        // free between pc_apply calls (this cycle's r is already in W)
+                vec_copy(c, x, xm, nv);
+                multi_axpy_s(c, B, c->Zs.p, vs, k, ym.data(), 1.0, xm);
+                if (c->dist) halo_exchange(c, g, xm, B, g.ntot);
+                resid_block_cols(c, c->J.p, bvec, xm, B, rm);
+                for (int f = 0; f < B; ++f) { const double *one[1] = {rm + (long)f * g.ntot}; multi_norm2sq(c, 1, 1, one, &fn[f]); fn[f] = std::sqrt(fn[f]); }
+                c->monitor(its, res, fn.data(), B, c->monitor_user);
+            }
+            rate = res_prev > 0.0 ? res / res_prev : 1.0;
+            res_prev = res;
+            if (!std::isfinite(res) || res <= stop || hn == 0.0) {
+                if (have_w) ++c->spec_wasted;
+                if (have_w) c->vcycles -= vcycles_per_apply(c);   // (discarded application)
+                nonfinite = !std::isfinite(res);
+                break;
+            }
+            if (!spec) basis_scale_store(c, B, 1.0 / hn, W, W, c->Vs.p + (long)(j + 1) * vs);       // Vs_{j+1} = (float)(w/||w||), W = v_{j+1}
+        }
+        hessenberg_solve(H, gvec, m, k, yk);
+        multi_axpy_s(c, B, c->Zs.p, vs, k, yk.data(), 1.0, x);               // x += Zs y
+        if (nonfinite) { *its_out = its; *rnorm_out = res; return -9; }     // KSP_DIVERGED_NANORINF
+        // the true residual decides: r = b - J x
+        if (c->dist) halo_exchange(c, g, x, B, g.ntot);
+        resid_block_cols(c, c->J.p, bvec, x, B, c->w2.p);
+        beta = norm2(c, B, c->w2.p);
+        ++c->ksp_true_res;
+        rsrc = c->w2.p;
+        *its_out = its; *rnorm_out = beta;
+        if (!std::isfinite(beta)) return -9;
+        if (beta <= tol) return 2;
+        if (its >= maxit) return -3;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // FGMRES(m) from x0 = 0.  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
 // (the other outer method, tp_options.ksp_kind = 1, is bcgs in tp_bcgs.hip)
+// (tp_options.ksp_basis_single: the fp32-basis form above; with the option off the loop below is untouched)
 int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
+    if (c->opt.ksp_basis_single) return fgmres_single(c, bvec, x, its_out, rnorm_out);
     const GridDev &g = c->g;
     const int B = c->b;
     const long nv = (long)B * g.ntot;

@@ -47,7 +47,8 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
-                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32), ("ksp_kind", C.c_int32),
+                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32),
+                ("ksp_basis_single", C.c_int32), ("ksp_single_floor", C.c_double), ("ksp_kind", C.c_int32),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
 
@@ -67,6 +68,7 @@ API_SYMBOLS = (
     "tp_pc_apply", "tp_stage1_update", "tp_stage1_apply", "tp_ilu0_factor", "tp_ilu0_solve", "tp_ilu_layout", "tp_amg_setup",
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
+    "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
 )
 
 DEFAULT_OPTS = dict(
@@ -74,6 +76,10 @@ DEFAULT_OPTS = dict(
     ksp_rtol=1e-7, ksp_atol=1e-50, ksp_max_it=200, ksp_restart=200,
     ksp="fgmres",           # outer Krylov method: "fgmres" (restarted, ksp_restart) | "bcgs": right-preconditioned BiCGStab, seven vectors
                             # plus the shared scratch w2 whatever the iteration count, two preconditioner applications per iteration (tp_options.ksp_kind)
+    ksp_basis_single=False, # FGMRES only: the bases V and Z stored in fp32, compact (compressed-basis GMRES), all arithmetic fp64: half the
+                            # Krylov workspace and half the bytes Gram-Schmidt moves; convergence only on a recomputed true residual
+    ksp_single_floor=1e-7,  # theta of ksp_basis_single, in (2^-24, 1): a restart cycle ends once its recurrence residual has fallen
+                            # to theta times the true residual it started from (check_ksp_basis_options)
     snes_rtol=1e-8, snes_atol=1e-50, snes_stol=1e-8, snes_max_it=15,
     amg_omega=0.9,          # damped-Jacobi weight (round 3: 0.8 -> 0.9 buys 3 % fewer Krylov iterations on C4 at equal cycle cost, +4 % Newton steps/s
                             # over 80 time steps, measured twice; 0.88-0.9 is a plateau, 0.95 starts to fail solves, 1.0 loses 40 %; C1-C3 neutral)
@@ -278,6 +284,18 @@ def check_amg_line_options(o, nranks=1, exc=EngineError):
         raise exc("amg_line_levels with nranks = %d: line relaxation is implemented for one slab" % int(nranks))
 
 
+def check_ksp_basis_options(o):
+    """ksp_basis_single / ksp_single_floor (tp_options) against the range of theta and the method that has no basis."""
+    th = o.get("ksp_single_floor", 1e-7)
+    # (checked whether or not ksp_basis_single is on: a value that could never be used is a mistake in the options either way;
+    # the library itself, which C callers may hand a zeroed field, checks it only with the option on)
+    if isinstance(th, (bool, np.bool_)) or not isinstance(th, (int, float, np.integer, np.floating)) or not 2.0**-24 < float(th) < 1.0:
+        raise ValueError("ksp_single_floor = %r: a number in (2^-24, 1)" % (th,))
+    if o.get("ksp_basis_single") and o.get("ksp", "fgmres") == "bcgs":
+        raise NotImplementedError("ksp_basis_single with ksp = 'bcgs' (ksp_type fbcgs): BiCGStab keeps no Krylov basis to store "
+                                  "in fp32; ksp_basis_single is an option of the restarted FGMRES")
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -325,6 +343,7 @@ class HipEngine:
         self.opts.update(opts or {})
         self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
         check_amg_line_options(self.opts, nranks)
+        check_ksp_basis_options(self.opts)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -363,6 +382,7 @@ class HipEngine:
         self._set_sources(spec.get("sources"))
         self.last = {}
         self._vec_ids = {}
+        self._fbatch_ids = {}
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc):
@@ -385,7 +405,8 @@ class HipEngine:
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
                           int(bool(o.get("ilu_whole", False))),
                           (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
-                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)), HipEngine._ksp_kind(o),
+                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)),
+                          int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
 
@@ -398,6 +419,7 @@ class HipEngine:
 
     def set_options(self, **kw):
         check_amg_line_options({**self.opts, **kw}, self.nranks)
+        check_ksp_basis_options({**self.opts, **kw})
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
         self._ck(self.lib.tp_set_options(self.ctx, C.byref(self._opt)))
@@ -609,6 +631,44 @@ class HipEngine:
         out = (C.c_int64*4)()
         self._ck(self.lib.tp_ksp_info(self.ctx, out))
         return dict(kind=out[0], bytes=out[1], bcgs_vectors=out[2], pc_programs=out[3])
+
+    def ksp_basis_info(self):
+        """The fp32 FGMRES bases of ksp_basis_single (tp_ksp_basis_info): whether the option is in effect, the capacity of each
+        basis in vectors, the stride between two stored vectors in entries, the fp64 staging vectors, and the restart cycles and
+        true-residual evaluations of the last such solve."""
+        out = (C.c_int64*6)()
+        self._ck(self.lib.tp_ksp_basis_info(self.ctx, out))
+        return dict(single=bool(out[0]), capacity=out[1], stride=out[2], staging=out[3], cycles=out[4], true_residuals=out[5])
+
+    # compact fp32 vector batches: the kernels of ksp_basis_single on their own (tp_fvec_*)
+    def fvec_batch(self, name, n):
+        """A batch of n compact float vectors (b * owned cells entries each, field-major, no halo planes)."""
+        if name not in self._fbatch_ids:
+            i = C.c_int32()
+            self._ck(self.lib.tp_fvec_create_batch(self.ctx, int(n), C.byref(i)))
+            self._fbatch_ids[name] = (i.value, int(n))
+        if self._fbatch_ids[name][1] < n:
+            raise EngineError("float batch %r holds %d vectors" % (name, self._fbatch_ids[name][1]))
+        return self._fbatch_ids[name][0]
+
+    def fvec_store(self, name, i, x):
+        """Slot i <- vector x rounded to fp32; x itself becomes the widened stored value (the solver's round-and-store kernel)."""
+        self._ck(self.lib.tp_fvec_store(self.ctx, self.fvec_batch(name, i + 1), int(i), self.vec(x)))
+
+    def fvec_get(self, name, i):
+        """Slot i as a float32 array of shape (b, n2_local, n1, n0)."""
+        out = np.empty(self.b*self.np_*self.n[2], dtype=np.float32)
+        self._ck(self.lib.tp_fvec_get(self.ctx, self.fvec_batch(name, i + 1), int(i), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out.reshape(self.b, self.n[2], self.n[1], self.n[0])
+
+    def fdot_batch(self, name, n, w):
+        out = np.zeros(n)
+        self._ck(self.lib.tp_fvec_dot_batch(self.ctx, self.fvec_batch(name, n), int(n), self.vec(w), _dptr(out)))
+        return out
+
+    def faxpy_batch(self, name, n, coef, w):
+        coef = np.ascontiguousarray(coef, dtype=float)
+        self._ck(self.lib.tp_fvec_axpy_batch(self.ctx, self.fvec_batch(name, n), int(n), _dptr(coef), self.vec(w)))
 
     def copy_residual_to(self, name):
         self._ck(self.lib.tp_vec_copy_residual(self.ctx, self.vec(name)))

@@ -151,9 +151,10 @@ def _check_ilu_single(o):
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import check_amg_line_options
+    from .engine import check_amg_line_options, check_ksp_basis_options
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
+    check_ksp_basis_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
         raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
@@ -219,7 +220,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     used = set()
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
-                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol")
+                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor")
     for k in build_keys:
         if k in sp:
             o[k] = sp.pop(k)
