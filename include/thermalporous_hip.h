@@ -123,6 +123,25 @@ typedef struct tp_options {
     int32_t ilu_single;      /* 1: the block-ILU(0) factor stream stored in fp32 (the factorisation, the sweeps' arithmetic and
                                 every vector stay fp64): half the factor's memory and 43 % fewer bytes per sweep.  The default
                                 per-tile ILU(0) only: not with ilu_levels 1, ilu_whole or an ilu_block of several tiles */
+    /* Line search of tp_newton_solve (snes_linesearch_type).  NOTE for ABI readers: these fields stand HERE, between
+     * ilu_single and amg_line_levels, not at the struct's tail (the tests of earlier options pin the order of every field from
+     * amg_line_levels on): every field from amg_line_levels on moved and sizeof(tp_options) grew; recompile callers.
+     * ls_kind 0 `basic` (the default): every Krylov correction is applied at full length; the launch sequence is unchanged.
+     * ls_kind 1 `bt`: Armijo backtracking.  From iterate u0 with residual F0 and correction dx, trial t sets u = u0 - lambda dx
+     * and accepts when ||F(u)||^2 is finite and <= (1 - 2 ls_alpha lambda) ||F0||^2; a rejected trial shrinks lambda by the
+     * minimiser of the quadratic (ls_order 2, or only one finite rejected trial) or cubic (ls_order 3) interpolant clamped to
+     * [0.1, 0.5] lambda, a non-finite trial halves it.  The slope is taken as -||F0||^2 (exact for an exact linear solve, within
+     * ksp_rtol otherwise: no mat-vec is spent on it).  The first trial uses the fused residual+Jacobian assembly, later trials
+     * the residual only, and an iteration accepted after several trials re-assembles the Jacobian once at the accepted state.
+     * A search that fails (ls_max_it trials, or lambda < ls_minlambda) restores u0 and ends the solve with reason -6
+     * (SNES_DIVERGED_LINE_SEARCH).  Every bt field below must keep its default while ls_kind is 0 (refused, never ignored). */
+    int32_t ls_kind;         /* 0 basic, 1 bt */
+    int32_t ls_order;        /* 2 quadratic, 3 cubic (snes_linesearch_order; default 3) */
+    int32_t ls_max_it;       /* most trials per Newton iteration, >= 1 (snes_linesearch_max_it; default 40) */
+    double  ls_alpha;        /* Armijo parameter in (0, 0.5) (snes_linesearch_alpha; default 1e-4) */
+    double  ls_maxstep;      /* first trial: lambda <= ls_maxstep / ||dx||_2, > 0 (snes_linesearch_maxstep; default 1e8) */
+    double  ls_minlambda;    /* ABSOLUTE smallest lambda in [0, 1) (snes_linesearch_minlambda; default 1e-12) */
+    double  ls_max_change[3];/* first trial: lambda <= ls_max_change[f] / max|dx_f| per field (p, T, S_o); <= 0: off (default) */
     int32_t amg_line_levels; /* L >= 0: the first L levels of the scalar hierarchies (pressure, S~ / A_11) smooth with line-Jacobi
                                 along internal axis 0, x <- x + amg_omega T^-1 (b - A x), T = the tridiagonal part of the level's
                                 operator along that axis (one Thomas solve per line), instead of damped point Jacobi.  A level
@@ -299,6 +318,20 @@ int tp_ksp_info(tp_ctx *ctx, int64_t out[4]);
  * evaluations (one SpMV and one norm each) of that solve}.  tp_ksp_info's bytes count these buffers too. */
 int tp_ksp_basis_info(tp_ctx *ctx, int64_t out[6]);
 int tp_newton_solve(tp_ctx *ctx, tp_solve_info *info);
+/* The line search: out = {ls_kind in effect, device bytes of line-search workspace allocated (the saved iterate u0
+ * only: the reductions use the scratch they share with the Krylov loop; 0 until the first bt solve), residual evaluations of the
+ * last Newton solve's searches (= trials; the re-assembly at an accepted shortened step repeats the accepted trial's state and is
+ * not counted), non-finite trials among them} */
+int tp_ls_info(tp_ctx *ctx, int64_t out[4]);
+/* Per Newton iteration of the last solve, at most cap entries: the accepted lambda, ||F|| after it and the trials spent; *n =
+ * the number of iterations recorded (a failed search is not an iteration).  n = 0 after a basic solve. */
+int tp_ls_history(tp_ctx *ctx, int32_t cap, double *lambda, double *fnorm, int32_t *trials, int32_t *n);
+/* The two kernels of the search on their own, on tp_vec ids:
+ *   tp_ls_step_stats  out = {||dx||_2^2, max|dx_p|, max|dx_T|, max|dx_S|} over owned cells, summed / maxed over the slabs
+ *                     (single-phase: out[3] = 0)
+ *   tp_ls_trial       out_vec = u0_vec - lambda dx_vec on owned cells of all fields; halo planes of out_vec are not written */
+int tp_ls_step_stats(tp_ctx *ctx, int32_t dx, double out[4]);
+int tp_ls_trial(tp_ctx *ctx, int32_t u0, int32_t dx, double lambda, int32_t out);
 
 /* measurement hooks for bench.py: average device time (ms, HIP events on the context's stream)
  * of `reps` launches of one hot kernel.  which: 0 block SpMV, 1 ILU solve, 2 AMG V-cycle (pressure),

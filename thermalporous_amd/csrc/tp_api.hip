@@ -313,6 +313,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     inner_check_options(*opt);
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
+    ls_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
@@ -367,6 +368,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     inner_check_options(*opt);
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
+    ls_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
@@ -381,6 +383,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
                              opt->schur_a11 != c->opt.schur_a11 || opt->fs_additive != c->opt.fs_additive;
     // the FGMRES bases exist in one representation at a time: the next solve allocates the one the option asks for
     if ((opt->ksp_basis_single != 0) != (c->opt.ksp_basis_single != 0)) basis_single_release(c);
+    if (opt->ls_kind == 0) c->ls_u0.free();          // the saved iterate belongs to the bt search: the next bt solve allocates it
     c->opt = *opt;
     if (tile_changed) c->ilu.slots = 0;
     if (amg_changed) drop_hierarchies(c);
@@ -903,6 +906,39 @@ int tp_newton_solve(tp_ctx *c, tp_solve_info *info) {
     TP_API_BEGIN
     TP_REQUIRE(c && info, "null argument");
     newton(c, info);
+    TP_HIP(hipStreamSynchronize(c->stream));
+    TP_API_END
+}
+
+int tp_ls_info(tp_ctx *c, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "bad arguments");
+    out[0] = c->opt.ls_kind;
+    out[1] = (int64_t)(c->ls_u0.n * sizeof(double));
+    out[2] = c->ls_evals;
+    out[3] = c->ls_nonfinite;
+    TP_API_END
+}
+
+int tp_ls_history(tp_ctx *c, int32_t cap, double *lambda, double *fnorm, int32_t *trials, int32_t *n) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && n && cap >= 0 && (cap == 0 || (lambda && fnorm && trials)), "bad arguments");
+    *n = (int32_t)c->ls_lambda.size();
+    for (int i = 0; i < std::min<int>(cap, *n); ++i) { lambda[i] = c->ls_lambda[i]; fnorm[i] = c->ls_fnorm[i]; trials[i] = c->ls_trials[i]; }
+    TP_API_END
+}
+
+int tp_ls_step_stats(tp_ctx *c, int32_t dx, double out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "bad arguments");
+    ls_step_stats(c, vec_of(c, dx).p, out);
+    TP_API_END
+}
+
+int tp_ls_trial(tp_ctx *c, int32_t u0, int32_t dx, double lambda, int32_t out) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "bad arguments");
+    ls_trial(c, vec_of(c, u0).p, vec_of(c, dx).p, lambda, vec_of(c, out).p);
     TP_HIP(hipStreamSynchronize(c->stream));
     TP_API_END
 }

@@ -404,6 +404,12 @@ struct tp_ctx {
     static constexpr int H_PIN = 1024;   // doubles of pinned, device-mapped host memory the reductions write their results to
     double *h_pin = nullptr;
     hipEvent_t ev_h = nullptr;           // recorded behind the reductions of an orthogonalisation (pipelined FGMRES loop)
+    // line search of newton() (tp_options.ls_kind = 1): the saved iterate u0 (b*ntot doubles, allocated by the first bt solve) and
+    // what tp_ls_info / tp_ls_history report about the last solve
+    tp::DBuf<double> ls_u0;
+    std::vector<double> ls_lambda, ls_fnorm;
+    std::vector<int32_t> ls_trials;
+    long ls_evals = 0, ls_nonfinite = 0;
     tp_ksp_monitor_fn monitor = nullptr;      // per-field true-residual monitor (ksp_monitor_residuals)
     void *monitor_user = nullptr;
     ~tp_ctx();
@@ -449,6 +455,10 @@ void multi_dot_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const 
 void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *hcoef_host, double sign, double *w);
 void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w, double *host_out);
 void orthogonalize_enqueue_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w);
+// line search (tp_options.ls_kind = 1): host_out = {||dx||^2, max|dx_f| f < 3} over owned cells, all slabs (one host sync);
+// u = u0 - lambda dx on owned cells of all fields
+void ls_step_stats(tp_ctx *c, const double *dx, double *host_out);
+void ls_trial(tp_ctx *c, const double *u0, const double *dx, double lambda, double *u);
 void field_minmax(tp_ctx *c, const double *x, double *lo, double *hi);
 void field_clamp01(tp_ctx *c, double *x);
 // stencil operators
@@ -516,5 +526,7 @@ void bcgs_check_options(const tp_options &o);
 void ksp_info(tp_ctx *c, int64_t out[4]);
 void basis_single_check_options(const tp_options &o);
 void basis_single_release(tp_ctx *c);     // frees the FGMRES bases of both representations (the option changed)
+void ls_check_options(const tp_options &o);
+double ls_next_lambda(int order, double g0, double f0, double lam, double phi, bool have_prev, double lam_p, double phi_p);
 void newton(tp_ctx *c, tp_solve_info *info);
 }  // namespace tp

@@ -708,6 +708,123 @@ void field_clamp01(tp_ctx *c, double *x) {
     TP_HIP(hipGetLastError());
 }
 
+// ---- backtracking line search (tp_options.ls_kind = 1; newton() in tp_solver.hip) ------------------
+// Step statistics in one launch: block (bx, f) takes LS_PER owned entries per thread of field f, strided by the block, and
+// leaves one partial sum of squares and one partial max|.| -- wave reduction (DPP shuffles), then the 4 waves through LDS.
+// partial = [nf*nbx sums | nf*nbx maxima]; k_ls_final reduces them in a fixed order (no atomics on doubles): block 0 the sum
+// over all fields, block 1 + f the maximum of field f (0 for a field the model does not have).  Inputs are finite (dx of a
+// Krylov solve that did not diverge); fmax would drop a NaN, so a non-finite dx shows in the sum, which the caller tests.
+constexpr int LS_PER = 4;
+__global__ __launch_bounds__(TP_BLOCK) void k_ls_step_stats(GridDev g, const double *__restrict__ dx, double *__restrict__ partial,
+                                                           int nbx, int nf) {
+    __shared__ double ssum[TP_BLOCK / 64], smax[TP_BLOCK / 64];
+    const int f = blockIdx.y;
+    const double *p = dx + (long)f * g.ntot + g.np;
+    const long base = (long)blockIdx.x * (TP_BLOCK * LS_PER) + threadIdx.x;
+    double v[LS_PER];
+#pragma unroll
+    for (int j = 0; j < LS_PER; ++j) {
+        const long i = base + (long)j * TP_BLOCK;
+        v[j] = i < g.nown ? p[i] : 0.0;
+    }
+    double s = 0.0, m = 0.0;
+#pragma unroll
+    for (int j = 0; j < LS_PER; ++j) { s += v[j] * v[j]; m = fmax(m, fabs(v[j])); }
+    s = wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) { ssum[threadIdx.x >> 6] = s; smax[threadIdx.x >> 6] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long slot = (long)f * nbx + blockIdx.x;
+        partial[slot] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
+        partial[(long)nf * nbx + slot] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+    }
+}
+__global__ __launch_bounds__(1024) void k_ls_final(const double *__restrict__ partial, int nbx, int nf, double *__restrict__ out,
+                                                   double *__restrict__ out2) {
+    __shared__ double sh[16];
+    const int which = blockIdx.x;                          // 0: sum, 1 + f: maximum of field f
+    const long n = which == 0 ? (long)nf * nbx : (which - 1 < nf ? nbx : 0);
+    const double *p = which == 0 ? partial : partial + (long)nf * nbx + (long)(which - 1) * nbx;
+    double s = 0.0;
+    for (long i = threadIdx.x; i < n; i += 1024) s = which == 0 ? s + p[i] : fmax(s, p[i]);
+    if (which == 0) s = wave_sum(s);
+    else {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s = fmax(s, __shfl_down(s, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) t = which == 0 ? t + sh[w] : fmax(t, sh[w]);
+        out[which] = t;
+        if (out2) out2[which] = t;
+    }
+}
+
+void ls_step_stats(tp_ctx *c, const double *dx, double *host_out) {
+    const GridDev &g = c->g;
+    const int nf = c->b;
+    const int nbx = (int)((g.nown + (long)TP_BLOCK * LS_PER - 1) / ((long)TP_BLOCK * LS_PER));
+    if ((long)c->gs_partial.n < 2L * nf * nbx) c->gs_partial.alloc((size_t)2 * nf * nbx + 64);
+    if ((long)c->red_out.n < 4) c->red_out.alloc(64);
+    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    double *pin = (use_pin && !c->dist) ? c->h_pin : nullptr;
+    hipLaunchKernelGGL(k_ls_step_stats, dim3(nbx, nf), dim3(TP_BLOCK), 0, c->stream, g, dx, c->gs_partial.p, nbx, nf);
+    hipLaunchKernelGGL(k_ls_final, dim3(4), dim3(1024), 0, c->stream, (const double *)c->gs_partial.p, nbx, nf, c->red_out.p, pin);
+    TP_HIP(hipGetLastError());
+    allreduce_sum(c, c->red_out.p, 1);
+    allreduce_max(c, c->red_out.p + 1, 3);
+    if (pin) {
+        TP_HIP(hipStreamSynchronize(c->stream));
+        memcpy(host_out, pin, sizeof(double) * 4);
+        return;
+    }
+    if (use_pin) {                         // several slabs: the all-reduced values through the pinned buffer (reduce_to_host)
+        TP_HIP(hipMemcpyAsync(c->h_pin, c->red_out.p, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+        TP_HIP(hipStreamSynchronize(c->stream));
+        memcpy(host_out, c->h_pin, sizeof(double) * 4);
+        return;
+    }
+    TP_HIP(hipMemcpyAsync(host_out, c->red_out.p, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    TP_HIP(hipStreamSynchronize(c->stream));
+}
+
+// u = u0 - lambda dx over the owned cells of all fields (nf <= 3); halo planes are not touched.  One item per thread: W = 2
+// doubles as one 16-byte access when the plane size is even and every pointer 16-byte aligned (the owned range of every field
+// then starts on an even entry and holds an even number of them), else single doubles (odd planes: W = 1 covers any count).
+// Elementwise, so u may be u0 or dx (no __restrict__).
+template <int W>
+struct alignas(8 * W) LsPack {
+    double v[W];
+};
+template <int W>
+__global__ __launch_bounds__(TP_BLOCK) void k_ls_trial(GridDev g, int nf, double lambda, const double *u0, const double *dx, double *u) {
+    const long t = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
+    if (t >= g.nown * nf / W) return;
+    const long e = t * W;
+    const long f = (long)(e >= g.nown) + (long)(e >= 2 * g.nown);
+    const long i = f * g.ntot + g.np + (e - f * g.nown);
+    const LsPack<W> a = *reinterpret_cast<const LsPack<W> *>(u0 + i), d = *reinterpret_cast<const LsPack<W> *>(dx + i);
+    LsPack<W> r;
+#pragma unroll
+    for (int q = 0; q < W; ++q) r.v[q] = a.v[q] - lambda * d.v[q];
+    *reinterpret_cast<LsPack<W> *>(u + i) = r;
+}
+void ls_trial(tp_ctx *c, const double *u0, const double *dx, double lambda, double *u) {
+    const GridDev &g = c->g;
+    const int nf = c->b;
+    TP_REQUIRE(nf <= 3, "ls_trial: at most three fields");
+    bool wide = g.np % 2 == 0;
+    for (const double *q : {u0, dx, (const double *)u}) wide = wide && ((uintptr_t)q % 16 == 0);
+    if (wide) hipLaunchKernelGGL(k_ls_trial<2>, grid_for(g.nown * nf / 2), dim3(TP_BLOCK), 0, c->stream, g, nf, lambda, u0, dx, u);
+    else hipLaunchKernelGGL(k_ls_trial<1>, grid_for(g.nown * nf), dim3(TP_BLOCK), 0, c->stream, g, nf, lambda, u0, dx, u);
+    TP_HIP(hipGetLastError());
+}
+
 // ---- block stencil mat-vec: y = J x  (MatMult) ----------------------------------------------------
 // MODE 0: y = J x ; MODE 1: r = x0 - J[:, :NC] y   (stage-1 output has zero secondary fields)
 // (first, count): the owned cells [first, first + count) -- the whole slab, or a range of planes when the boundary planes

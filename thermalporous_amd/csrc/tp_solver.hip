@@ -6,7 +6,7 @@
 //   fgmres               = KSP fgmres, right PC, restart/max_it 200, classical Gram-Schmidt without
 //                          refinement (twophase.py:426-432)
 //   newton               = SNES newtonls with Firedrake's default `basic` line search
-//                          (thermalmodel.py:36-42,165)
+//                          (thermalmodel.py:36-42,165), or the opt-in backtracking search `bt` (tp_options.ls_kind)
 // The loops live here (C++) rather than in Python so that one Krylov iteration costs kernel time,
 // not interpreter time; the Python PC classes call the same stage functions through the C ABI.
 #include "tp_common.hpp"
@@ -764,6 +764,113 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
 }
 
 // ------------------------------------------------------------------------------------------------
+// Backtracking line search (tp_options.ls_kind = 1, snes_linesearch_type bt).
+void ls_check_options(const tp_options &o) {
+    TP_REQUIRE(o.ls_kind == 0 || o.ls_kind == 1, "ls_kind must be 0 (basic) or 1 (bt)");
+    if (o.ls_kind == 0) {
+        // the bt fields at their defaults (or zeroed, as a C caller that never heard of them leaves them): refused, never ignored
+        TP_REQUIRE(o.ls_order == 0 || o.ls_order == 3, "ls_order is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        TP_REQUIRE(o.ls_max_it == 0 || o.ls_max_it == 40, "ls_max_it is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        TP_REQUIRE(o.ls_alpha == 0.0 || o.ls_alpha == 1e-4, "ls_alpha is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        TP_REQUIRE(o.ls_maxstep == 0.0 || o.ls_maxstep == 1e8, "ls_maxstep is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        TP_REQUIRE(o.ls_minlambda == 0.0 || o.ls_minlambda == 1e-12, "ls_minlambda is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        for (int f = 0; f < 3; ++f)
+            TP_REQUIRE(!(o.ls_max_change[f] > 0.0), "ls_max_change is set but ls_kind is 0 (basic): the field belongs to the bt search");
+        return;
+    }
+    TP_REQUIRE(o.ls_order == 2 || o.ls_order == 3, "ls_order must be 2 (quadratic) or 3 (cubic)");
+    TP_REQUIRE(o.ls_alpha > 0.0 && o.ls_alpha < 0.5, "ls_alpha must lie in (0, 0.5)");
+    TP_REQUIRE(o.ls_max_it >= 1, "ls_max_it must be >= 1");
+    TP_REQUIRE(o.ls_maxstep > 0.0, "ls_maxstep must be > 0");
+    TP_REQUIRE(o.ls_minlambda >= 0.0 && o.ls_minlambda < 1.0, "ls_minlambda must lie in [0, 1)");
+    for (int f = 0; f < 3; ++f) TP_REQUIRE(o.ls_max_change[f] == o.ls_max_change[f], "ls_max_change must not be NaN");
+}
+
+// The next trial length after the finite rejected trial (lam, phi = ||F||^2); (lam_p, phi_p): the finite rejected trial before
+// it, if any since the start or the last non-finite trial.  f = phi / 2, f0 = ||F0||^2 / 2, slope g0 = -||F0||^2.  Written
+// operation by operation as tests/newton_ls_ref.py:next_lambda is: same inputs, same bits.
+double ls_next_lambda(int order, double g0, double f0, double lam, double phi, bool have_prev, double lam_p, double phi_p) {
+    double nl;
+    const double f = 0.5 * phi;
+    if (order == 2 || !have_prev) {
+        nl = -g0 * lam * lam / (2.0 * (f - f0 - g0 * lam));                 // minimiser of the quadratic through f0, g0, f
+    } else {
+        // Dennis & Schnabel, A6.3.1: minimiser of the cubic through f0, g0 and the last two trials
+        const double fp = 0.5 * phi_p;
+        const double t1 = f - f0 - lam * g0, t2 = fp - f0 - lam_p * g0;
+        const double a = (t1 / (lam * lam) - t2 / (lam_p * lam_p)) / (lam - lam_p);
+        const double b = (-lam_p * t1 / (lam * lam) + lam * t2 / (lam_p * lam_p)) / (lam - lam_p);
+        const double d = b * b - 3.0 * a * g0;
+        if (d < 0.0) nl = 0.5 * lam;
+        else if (a == 0.0) nl = -g0 / (2.0 * b);
+        else nl = (-b + std::sqrt(d)) / (3.0 * a);
+    }
+    if (!(nl >= 0.1 * lam)) nl = 0.1 * lam;                                 // (also catches a NaN)
+    if (nl > 0.5 * lam) nl = 0.5 * lam;
+    return nl;
+}
+
+// One search from u0 = c->u (residual norm fnorm_in, correction dx).  On success c->u is the accepted iterate, R and J are
+// assembled there, and lam, ynorm, phi = ||F||^2, xsq = ||u||^2 describe the step.  On failure c->u is u0 again.
+static bool ls_backtrack(tp_ctx *c, bool schur, const double *dx, double fnorm_in, double *lam_out, double *ynorm_out,
+                         double *phi_out, double *xsq_out, int *trials_out) {
+    const GridDev &g = c->g;
+    const int B = c->b;
+    const long nv = (long)B * g.ntot;
+    const tp_options &o = c->opt;
+    if (c->ls_u0.n < (size_t)nv) c->ls_u0.alloc(nv);
+    double st[4];
+    ls_step_stats(c, dx, st);                                               // (all-reduced: every slab decides alike)
+    vec_copy(c, c->u.p, c->ls_u0.p, nv);
+    const double ynorm = std::sqrt(st[0]);
+    double lam = 1.0;
+    if (o.ls_maxstep / ynorm < lam) lam = o.ls_maxstep / ynorm;
+    for (int f = 0; f < B; ++f)
+        if (o.ls_max_change[f] > 0.0 && o.ls_max_change[f] / st[1 + f] < lam) lam = o.ls_max_change[f] / st[1 + f];
+    const double ff = fnorm_in * fnorm_in, f0 = 0.5 * ff, g0 = -ff;
+    bool have = false, have_prev = false;                                   // finite rejected trials since the last non-finite one
+    double lam_1 = 0.0, phi_1 = 0.0, lam_2 = 0.0, phi_2 = 0.0;
+    *ynorm_out = ynorm;
+    bool ok = std::isfinite(ynorm);
+    for (int t = 1; ok; ++t) {
+        ls_trial(c, c->ls_u0.p, dx, lam, c->u.p);
+        if (c->dist) halo_exchange(c, g, c->u.p, B, g.ntot);
+        if (t == 1) assemble(c, true, schur);                               // an accepted first trial costs what the basic step costs
+        else assemble(c, false, false);
+        double nrm[2];
+        const double *v2[2] = {c->R.p, c->u.p};
+        multi_norm2sq(c, B, 2, v2, nrm);                                    // the one host wait of a trial
+        const double phi = nrm[0];
+        ++c->ls_evals;
+        *trials_out = t;
+        const bool finite = std::isfinite(phi);
+        if (!finite) ++c->ls_nonfinite;
+        if (finite && phi <= (1.0 - 2.0 * o.ls_alpha * lam) * ff) {
+            // INVARIANT: a rejected first trial left J (and S~) of a state that was thrown away, possibly non-finite, and later
+            // trials wrote R only.  The fused assembly below rewrites EVERY owned entry of R, J and S~ from the accepted
+            // state -- the assembly kernels store, they never accumulate into what they find -- so nothing of a rejected
+            // trial reaches pc_setup.  (Halo planes of J are written by nobody and exchanged where they are read.)
+            if (t > 1) assemble(c, true, schur);
+            *lam_out = lam; *phi_out = phi; *xsq_out = nrm[1];
+            return true;
+        }
+        if (t >= o.ls_max_it) break;
+        if (!finite) {
+            lam = 0.5 * lam;
+            have = have_prev = false;
+        } else {
+            if (have) { lam_2 = lam_1; phi_2 = phi_1; have_prev = true; }
+            lam_1 = lam; phi_1 = phi; have = true;
+            lam = ls_next_lambda(o.ls_order, g0, f0, lam_1, phi_1, have_prev, lam_2, phi_2);
+        }
+        if (lam < o.ls_minlambda) break;
+    }
+    vec_copy(c, c->ls_u0.p, c->u.p, nv);                                    // u <- u0, bitwise (halo planes included)
+    c->jac_ready = c->pc_ready = false;                                     // R, J: whatever the last trial left
+    return false;
+}
+
+// ------------------------------------------------------------------------------------------------
 void newton(tp_ctx *c, tp_solve_info *info) {
     const GridDev &g = c->g;
     const int B = c->b;
@@ -780,6 +887,8 @@ void newton(tp_ctx *c, tp_solve_info *info) {
     double fnorm = norm2(c, B, c->R.p);
     const double fnorm0 = fnorm;
     int nits = 0, lits = 0, reason = 0, kreason = 0;
+    c->ls_lambda.clear(); c->ls_fnorm.clear(); c->ls_trials.clear();
+    c->ls_evals = c->ls_nonfinite = 0;
     if (!std::isfinite(fnorm)) reason = -4;                      // SNES_DIVERGED_FNORM_NAN
     else if (fnorm < c->opt.snes_atol) reason = 2;               // SNES_CONVERGED_FNORM_ABS
     while (reason == 0) {
@@ -791,6 +900,19 @@ void newton(tp_ctx *c, tp_solve_info *info) {
         kreason = c->opt.ksp_kind == 1 ? bcgs(c, c->R.p, dx->p, &kits, &rn) : fgmres(c, c->R.p, dx->p, &kits, &rn);
         lits += kits;
         if (kreason < 0) { reason = -3; break; }                 // SNES_DIVERGED_LINEAR_SOLVE
+        if (c->opt.ls_kind == 1) {                               // bt: backtracking from the full step (ls_backtrack above)
+            double lam = 0.0, ynorm = 0.0, phi = 0.0, xsq = 0.0;
+            int trials = 0;
+            if (!ls_backtrack(c, schur, dx->p, fnorm, &lam, &ynorm, &phi, &xsq, &trials)) { reason = -6; break; }   // SNES_DIVERGED_LINE_SEARCH
+            ++nits;
+            fnorm = std::sqrt(phi);
+            c->ls_lambda.push_back(lam); c->ls_fnorm.push_back(fnorm); c->ls_trials.push_back(trials);
+            const double snorm = lam * ynorm, xnorm = std::sqrt(xsq);
+            if (fnorm < c->opt.snes_atol) reason = 2;            // (an accepted phi is finite)
+            else if (fnorm <= c->opt.snes_rtol * fnorm0) reason = 3;
+            else if (snorm < c->opt.snes_stol * xnorm) reason = 4;
+            continue;
+        }
         vec_axpy_owned(c, B, -1.0, dx->p, c->u.p);               // basic line search, lambda = 1
         if (c->dist) halo_exchange(c, g, c->u.p, B, g.ntot);
         assemble(c, true, schur);

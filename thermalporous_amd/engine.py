@@ -47,7 +47,10 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
-                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32), ("amg_line_levels", C.c_int32),
+                ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
+                ("ls_kind", C.c_int32), ("ls_order", C.c_int32), ("ls_max_it", C.c_int32), ("ls_alpha", C.c_double),
+                ("ls_maxstep", C.c_double), ("ls_minlambda", C.c_double), ("ls_max_change", C.c_double*3),
+                ("amg_line_levels", C.c_int32),
                 ("ksp_basis_single", C.c_int32), ("ksp_single_floor", C.c_double), ("ksp_kind", C.c_int32),
                 ("s1_ksp", C.c_int32), ("s1_max_it", C.c_int32), ("s1_rtol", C.c_double), ("s1_atol", C.c_double)]
 
@@ -69,6 +72,7 @@ API_SYMBOLS = (
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
+    "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial",
 )
 
 DEFAULT_OPTS = dict(
@@ -112,7 +116,55 @@ DEFAULT_OPTS = dict(
     s1_ksp="preonly",       # "preonly": one V-cycle | "richardson": s1_max_it V-cycles from x0 = 0 | "fgmres": GMRES(s1_max_it <= 32)
     s1_max_it=1,
     s1_rtol=0.0, s1_atol=0.0,   # fgmres: latch on the recurrence residual <= max(s1_rtol*||rhs||, s1_atol); 0, 0 = fixed count
+    # line search of the Newton solver (include/thermalporous_hip.h: tp_options.ls_kind; check_linesearch_options)
+    linesearch="basic",     # "basic": every correction at full length | "bt": Armijo backtracking (snes_linesearch_type bt)
+    ls_order=3,             # bt: 2 quadratic | 3 cubic interpolation of the next trial length
+    ls_alpha=1e-4,          # bt: Armijo parameter in (0, 0.5)
+    ls_max_it=40,           # bt: most trials per Newton iteration
+    ls_maxstep=1e8,         # bt: first trial length <= ls_maxstep / ||dx||
+    ls_minlambda=1e-12,     # bt: absolute smallest trial length, in [0, 1)
+    ls_max_change=None,     # bt: (dp, dT, dS) caps on the change of p, T, S_o per Newton iteration (<= 0: no cap); None: off
 )
+_LS = {"basic": 0, "bt": 1}
+_LS_DEFAULTS = dict(ls_order=3, ls_alpha=1e-4, ls_max_it=40, ls_maxstep=1e8, ls_minlambda=1e-12, ls_max_change=None)
+
+
+def _is_number(v):
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def check_linesearch_options(o):
+    """linesearch and the ls_* keys (tp_options.ls_kind ...): ranges under "bt"; under "basic" every ls_* key must keep its
+    default -- a value that would be ignored is refused."""
+    kind = o.get("linesearch", "basic")
+    if kind not in _LS:
+        raise NotImplementedError("linesearch = %r: 'basic' or 'bt'" % (kind,))
+    mc = o.get("ls_max_change")
+    if mc is not None:
+        mc = tuple(mc)
+        if len(mc) != 3 or not all(_is_number(v) and float(v) == float(v) for v in mc):
+            raise ValueError("ls_max_change = %r: None or a (dp, dT, dS) triple of numbers (<= 0: no cap on that field)" % (o["ls_max_change"],))
+    if kind == "basic":
+        for k, d in _LS_DEFAULTS.items():
+            v = o.get(k, d)
+            if k == "ls_max_change":
+                if mc is not None and any(float(x) > 0 for x in mc):
+                    raise ValueError("ls_max_change = %r with linesearch = 'basic': the key belongs to the bt search" % (v,))
+            elif v != d:
+                raise ValueError("%s = %r with linesearch = 'basic': the key belongs to the bt search" % (k, v))
+        return
+    order, it = o.get("ls_order", 3), o.get("ls_max_it", 40)
+    if isinstance(order, (bool, np.bool_)) or order not in (2, 3):
+        raise ValueError("ls_order = %r: 2 (quadratic) or 3 (cubic)" % (order,))
+    if not _is_number(it) or int(it) != it or it < 1:
+        raise ValueError("ls_max_it = %r: a count >= 1" % (it,))
+    a, ms, ml = o.get("ls_alpha", 1e-4), o.get("ls_maxstep", 1e8), o.get("ls_minlambda", 1e-12)
+    if not _is_number(a) or not 0.0 < float(a) < 0.5:
+        raise ValueError("ls_alpha = %r: a number in (0, 0.5)" % (a,))
+    if not _is_number(ms) or not float(ms) > 0.0:
+        raise ValueError("ls_maxstep = %r: a number > 0" % (ms,))
+    if not _is_number(ml) or not 0.0 <= float(ml) < 1.0:
+        raise ValueError("ls_minlambda = %r: a number in [0, 1)" % (ml,))
 
 def default_ilu_tile(n, nslabs=1, ncu=256):
     """bjacobi tile (t0, t1, t2) for a grid of internal extents n = (n0, n1, n2) cut into `nslabs` slabs along axis 2.
@@ -344,6 +396,7 @@ class HipEngine:
         self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
         check_amg_line_options(self.opts, nranks)
         check_ksp_basis_options(self.opts)
+        check_linesearch_options(self.opts)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -397,7 +450,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        return tp_options(_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
+        # (the line-search fields stand in the middle of the struct: they are set by name, everything else in declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith("ls_")]
+        vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
                           0 if t[0] >= (1 << 30) else int(t[0]), int(o["amg_full_levels"]), int(o["amg_coarse_pre"]),
@@ -409,6 +464,10 @@ class HipEngine:
                           int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
+        return tp_options(**dict(zip(rest, vals)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
+                          ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
+                          ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
+                          ls_max_change=(C.c_double*3)(*[float(v) for v in (o.get("ls_max_change") or (0.0, 0.0, 0.0))]))
 
     @staticmethod
     def _ksp_kind(o):
@@ -420,6 +479,7 @@ class HipEngine:
     def set_options(self, **kw):
         check_amg_line_options({**self.opts, **kw}, self.nranks)
         check_ksp_basis_options({**self.opts, **kw})
+        check_linesearch_options({**self.opts, **kw})
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
         self._ck(self.lib.tp_set_options(self.ctx, C.byref(self._opt)))
@@ -731,11 +791,38 @@ class HipEngine:
         self._ck(self.lib.tp_inner_stats(self.ctx, C.byref(a), C.byref(i), C.byref(u)))
         return a.value, i.value, u.value
 
+    def ls_info(self):
+        """The line search (tp_ls_info): kind in effect, device bytes of its workspace, residual evaluations (= trials) of the last
+        Newton solve's searches and the non-finite ones among them."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_ls_info(self.ctx, out))
+        return dict(kind=out[0], bytes=out[1], evaluations=out[2], nonfinite=out[3])
+
+    def ls_history(self, cap=256):
+        """Per Newton iteration of the last solve (tp_ls_history): accepted lambda, ||F|| after it, trials spent.  Empty after a
+        basic solve."""
+        lam, fn = np.zeros(cap), np.zeros(cap)
+        tr = np.zeros(cap, dtype=np.int32)
+        n = C.c_int32()
+        self._ck(self.lib.tp_ls_history(self.ctx, int(cap), _dptr(lam), _dptr(fn), tr.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        k = min(n.value, cap)
+        return dict(n=n.value, lam=lam[:k].copy(), fnorm=fn[:k].copy(), trials=[int(t) for t in tr[:k]])
+
+    def ls_step_stats(self, dx):
+        """(||dx||^2, [max|dx_f| per field]) of vector `dx` over owned cells of all slabs (tp_ls_step_stats)."""
+        out = np.zeros(4)
+        self._ck(self.lib.tp_ls_step_stats(self.ctx, self.vec(dx), _dptr(out)))
+        return out[0], out[1:1 + self.b].copy()
+
+    def ls_trial(self, u0, dx, lam, out):
+        """out = u0 - lam*dx on owned cells (tp_ls_trial); the halo planes of `out` are not written."""
+        self._ck(self.lib.tp_ls_trial(self.ctx, self.vec(u0), self.vec(dx), C.c_double(float(lam)), self.vec(out)))
+
     def newton_solve(self):
         info = tp_solve_info()
         self._ck(self.lib.tp_newton_solve(self.ctx, C.byref(info)))
         self.last = dict(nits=info.nits, lits=info.lits, reason=info.reason, fnorm=info.fnorm, fnorm0=info.fnorm0,
-                         ksp_reason=info.last_ksp_reason, vcycles=info.vcycles)
+                         ksp_reason=info.last_ksp_reason, vcycles=info.vcycles, ls_trials=self.ls_info()["evaluations"])
         return self.last
 
     def close(self):

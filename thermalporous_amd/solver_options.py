@@ -5,7 +5,10 @@ The reference configures its whole linear/nonlinear stack through PETSc option d
 subset that selects the solvers it implements and rejects everything else loudly -- every key is either
 CONSUMED (and its value checked against what is implemented), purely cosmetic (monitors/views), or an error:
 
-  snes_type newtonls  (line search `basic`: Firedrake's default, not settable in the reference)
+  snes_type newtonls, snes_linesearch_type basic (Firedrake's default) | bt: Armijo backtracking (engine key linesearch = "bt")
+     with snes_linesearch_order 2|3 (default 3, PETSc's), snes_linesearch_alpha, snes_linesearch_max_it,
+     snes_linesearch_maxstep, snes_linesearch_minlambda (absolute here) -> ls_order, ls_alpha, ls_max_it, ls_maxstep,
+     ls_minlambda; any of them without bt raises.  l2 and cp are not implemented
   ksp_type fgmres|gmres (right preconditioning), ksp_rtol/atol/max_it, ksp_gmres_restart
   ksp_type fbcgs | bcgs + ksp_pc_side right: right-preconditioned BiCGStab (engine key ksp = "bcgs"); ksp_gmres_restart is
      consumed and has no effect on it
@@ -21,7 +24,8 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
 Defaults the reference inherits silently from Firedrake/PETSc are fixed here explicitly
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
 ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
-Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol.  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol, linesearch,
+ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -151,10 +155,11 @@ def _check_ilu_single(o):
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import check_amg_line_options, check_ksp_basis_options
+    from .engine import check_amg_line_options, check_ksp_basis_options, check_linesearch_options
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_ksp_basis_options(o)
+    check_linesearch_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
         raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
@@ -220,7 +225,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     used = set()
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
-                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor")
+                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor",
+                  "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
     for k in build_keys:
         if k in sp:
             o[k] = sp.pop(k)
@@ -228,7 +234,22 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     _take(sp, used, "snes_type", ("newtonls",))
     # Firedrake's default line search is `basic`; the reference never sets another one on its Newton-Krylov path
     # (l2 only inside the FAS presets, twophase.py:437): anything but basic would silently change the algorithm
-    _take(sp, used, "snes_linesearch_type", ("basic",))
+    # the engine's own backtracking search is `bt` (PETSc's newtonls default); l2 / cp are not implemented
+    ls = _take(sp, used, "snes_linesearch_type", ("basic", "bt"))
+    ls_keys = (("snes_linesearch_order", "ls_order"), ("snes_linesearch_alpha", "ls_alpha"), ("snes_linesearch_max_it", "ls_max_it"),
+               ("snes_linesearch_maxstep", "ls_maxstep"), ("snes_linesearch_minlambda", "ls_minlambda"))
+    if ls is not None:
+        if "linesearch" in solver_parameters and o["linesearch"] != ls:
+            raise ValueError("the line search is configured twice and differently: linesearch = %r, snes_linesearch_type = %r"
+                             % (o["linesearch"], ls))
+        o["linesearch"] = ls
+    for k_src, k_dst in ls_keys:
+        if k_src in sp:
+            if o["linesearch"] != "bt":
+                raise NotImplementedError("%s without snes_linesearch_type bt: the key belongs to the backtracking search "
+                                          "(it would be silently ignored)" % k_src)
+            o[k_dst] = sp[k_src]
+            used.add(k_src)
     _take(sp, used, "mat_type", ("aij",))
     ksp = _take(sp, used, "ksp_type", ("fgmres", "gmres", "fbcgs", "bcgs"), "gmres")
     side = _take(sp, used, "ksp_pc_side", ("right",))
