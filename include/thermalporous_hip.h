@@ -111,6 +111,18 @@ typedef struct tp_options {
                                 reference's `sub_1_pc_bjacobi_blocks: 1` (tests/test_homo_wells.py:112, pc_cptr_a11
                                 twophase.py:612): couplings between the tiles are kept; the tiles (ilu_t0 x ilu_t1 x ilu_t2,
                                 now only the unit of the sweep) are swept one tile-diagonal T0+T1+T2 per launch.  ILU(0) only. */
+    /* Red-black Gauss-Seidel on the top levels of the scalar hierarchies (pressure, S~ / A_11).  NOTE for ABI readers: the two
+     * fields stand HERE, between ilu_whole and ilu_block (the tests of earlier options pin the order of every field from ilu_block
+     * on): every field from ilu_block on moved and sizeof(tp_options) grew; recompile callers.
+     * Level l is a GS level when l < amg_gs_levels and it has more than 1024 cells (above the single-workgroup tail); every other
+     * level keeps damped Jacobi.  Cell (i0, i1, i2) of a level is red when i0 + i1 + i2 is even; a half-sweep of one colour sets
+     * x_i <- x_i + (b_i - (A x)_i) / a0_i on its cells (no damping: amg_omega is not used); forward sweep = red then black,
+     * backward = black then red.  A GS level is V(g, g), g = amg_gs_sweeps: g forward sweeps from the zero guess, residual,
+     * coarse correction, g backward sweeps; as the relaxation-only level of amg_dom_tau it returns B^g F^g 0.
+     * Scope limits of this implementation (refused naming both options, never ignored; the context stays usable): one slab only;
+     * not with amg_line_levels > 0, amg_single, pc_kind 3 or schur_a11 = 2. */
+    int32_t amg_gs_levels;   /* L >= 0, <= amg_full_levels.  0 (default): off, the point-Jacobi launch sequence */
+    int32_t amg_gs_sweeps;   /* g in 1..4 (default 1); must be 1 while amg_gs_levels is 0 */
     int32_t ilu_block[3];    /* bjacobi block = a BOX of ilu_block[0] x [1] x [2] whole cells (internal axis order), independent of the
                                 sweep tile: `sub_1_pc_bjacobi_blocks N` for blocks larger than one tile (tests/test_homo_wells.py:112,125,
                                 twophase.py:612).  Blocks start at the slab's origin (the last one along an axis is the ragged one);
@@ -357,6 +369,9 @@ int tp_amg_tail_info(tp_ctx *ctx, int32_t which, int64_t out[6]);
 /* line relaxation of hierarchy `which` (0 pressure, 1 S~) as planned from amg_line_levels: out = {line levels in effect, lines
  * per workgroup on level 0 (0 if level 0 is no line level), n0 of level 0, device bytes of the factor streams of all line levels} */
 int tp_amg_line_info(tp_ctx *ctx, int32_t which, int64_t out[4]);
+/* red-black Gauss-Seidel of hierarchy `which` (0 pressure, 1 S~) as planned from amg_gs_levels / amg_gs_sweeps: out = {GS levels
+ * in effect, sweeps per leg g, red cells of level 0, black cells of level 0}; all zero when the hierarchy has no GS level */
+int tp_amg_gs_info(tp_ctx *ctx, int32_t which, int64_t out[4]);
 
 #ifdef __cplusplus
 }

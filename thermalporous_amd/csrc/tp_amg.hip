@@ -716,6 +716,56 @@ __global__ __launch_bounds__(TP_BLOCK) void k_amg_line_sweep(LevelDevT<R> L, Lin
     }
 }
 
+// ---- red-black Gauss-Seidel (tp_options.amg_gs_levels) ---------------------------------------------------------
+// Cell (i0, i1, i2) is red (colour 0) when i0 + i1 + i2 is even, black (colour 1) otherwise: the six neighbours of a cell of a
+// 7-point stencil have the other colour, so the cells of one colour do not couple and a half-sweep over one colour,
+//     x_i <- x_i + (b_i - (A x)_i) / a0_i      (no damping),
+// is order-independent.  The colour comes from the cell's indices, not from the parity of its linear index (they differ as
+// soon as n0 or n0 n1 is even).  One thread per cell in the XCD-aware order, like k_amg_jacobi, and the same cache lines: every
+// lane loads its stencil row, b and the seven x values unconditionally (the halo planes make every address valid); a lane of the
+// other colour stores its x unchanged, so the stores are whole lines and the level's x / x2 ping-pong as in the Jacobi path.
+template <class R>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_gs_half(LevelDevT<R> L, int colour, const double *__restrict__ b,
+                                                          const double *__restrict__ x, double *__restrict__ out) {
+    const long tid = xcd_tid();
+    if (tid >= L.g.nown) return;
+    int i0, i1, i2;
+    cell_ijk(L.g, tid, i0, i1, i2);
+    const long c = L.g.np + tid;
+    long off[7];
+    nb_offsets(L.g, off);
+    const double a0 = (double)L.op.slot(0)[c], xc = x[c];
+    double s = a0 * xc;
+#pragma unroll
+    for (int k = 1; k < 7; ++k) s += (double)L.op.slot(k)[c] * x[c + off[k]];
+    const double upd = xc + (b[c] - s) / a0;
+    out[c] = (((i0 + i1 + i2) & 1) == colour) ? upd : xc;
+}
+
+// the whole first forward sweep from the zero guess in one launch (the pattern of pre2_cell): red  x = b / a0;  black
+// x = (b - sum_k a_k x_n) / a0  with the six red neighbours' x_n = b_n / a0_n recomputed from b and the neighbours' diagonals.
+// A neighbour outside the box (its coefficient is zero) is read at the cell's own address, so that no quotient is formed from a
+// halo plane's zero diagonal.
+template <class R>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_gs_first(LevelDevT<R> L, const double *__restrict__ b, double *__restrict__ out) {
+    const long tid = xcd_tid();
+    if (tid >= L.g.nown) return;
+    int i0, i1, i2;
+    cell_ijk(L.g, tid, i0, i1, i2);
+    const long c = L.g.np + tid;
+    long off[7];
+    nb_offsets(L.g, off);
+    const bool in[7] = {true, i0 > 0, i0 + 1 < L.g.n0, i1 > 0, i1 + 1 < L.g.n1, i2 > 0, i2 + 1 < L.g.n2};
+    const double a0 = (double)L.op.slot(0)[c], bc = b[c];
+    double s = 0.0;
+#pragma unroll
+    for (int k = 1; k < 7; ++k) {
+        const long n = in[k] ? c + off[k] : c;
+        s += (double)L.op.slot(k)[c] * (b[n] / (double)L.op.slot(0)[n]);
+    }
+    out[c] = (((i0 + i1 + i2) & 1) ? bc - s : bc) / a0;
+}
+
 // ---- the tail: all small levels in one workgroup --------------------------------------------------------
 // down-sweep, coarse solve and up-sweep of the levels [l0, nlev) by one workgroup of 1024 threads; `lv`: descriptors in LDS.
 // Ends behind a workgroup barrier.
@@ -942,6 +992,21 @@ void amg_line_check_options(const tp_options &o, int nranks) {
     TP_REQUIRE(nranks <= 1, "amg_line_levels (line relaxation) is implemented for one slab: not with nranks > 1");
 }
 
+// Red-black Gauss-Seidel (tp_options.amg_gs_levels / amg_gs_sweeps): ranges and what this implementation excludes.
+void amg_gs_check_options(const tp_options &o, int nranks) {
+    const int L = o.amg_gs_levels, g = o.amg_gs_sweeps;
+    TP_REQUIRE(L >= 0, "amg_gs_levels must be >= 0");
+    TP_REQUIRE(g >= 1 && g <= 4, "amg_gs_sweeps must be in 1..4");
+    TP_REQUIRE(L > 0 || g == 1, "amg_gs_sweeps must be 1 while amg_gs_levels is 0: the sweep count would be ignored");
+    if (L == 0) return;
+    TP_REQUIRE(L <= o.amg_full_levels, "amg_gs_levels must not exceed amg_full_levels: Gauss-Seidel levels are V(g,g) levels, never pure-transfer or paired ones");
+    TP_REQUIRE(o.amg_line_levels == 0, "amg_gs_levels (red-black Gauss-Seidel) and amg_line_levels (line relaxation) exclude one another: one smoother per level");
+    TP_REQUIRE(!o.amg_single, "amg_gs_levels (red-black Gauss-Seidel) is implemented for fp64 operators: not with amg_single");
+    TP_REQUIRE(o.pc_kind != 3, "amg_gs_levels (red-black Gauss-Seidel) is implemented for the scalar hierarchies: not with pc_kind 3 (pc_cptramg, the system AMG)");
+    TP_REQUIRE(o.schur_a11 != 2, "amg_gs_levels (red-black Gauss-Seidel) is not implemented for schur_a11 = 2 (schur_selfp)");
+    TP_REQUIRE(nranks <= 1, "amg_gs_levels (red-black Gauss-Seidel) is implemented for one slab: not with nranks > 1");
+}
+
 // g0: the grid the hierarchy coarsens -- the slab itself on one GPU, the GLOBAL grid on several.  There the top
 // levels (more than gather_cells cells, at least two planes on every rank) stay distributed over the slabs
 // and the rest of the hierarchy is built on the gathered global grid, replicated on every rank; a problem
@@ -1009,6 +1074,10 @@ AmgPlan amg_plan(const GridDev &g0, const double strength[3], const tp_options &
             P.lv[l].line_g = line_group(P.lv[l].g);
             TP_REQUIRE(P.lv[l].line_g >= 1, "amg_line_levels: a line of this level does not fit the LDS budget of the line sweep");
         }
+    // Gauss-Seidel levels: above the tail, among the first amg_gs_levels levels (all of them full levels: amg_gs_check_options);
+    // such a level is V(g, g)
+    for (int l = 0; l < std::min(o.amg_gs_levels, P.tail_level); ++l)
+        P.lv[l].gs = P.lv[l].pre = P.lv[l].post = o.amg_gs_sweeps;
     return P;
 }
 
@@ -1027,6 +1096,18 @@ void amg_line_info(const Amg *amg, int64_t out[4]) {
         if (amg->plan.lv[l].line_g > 0) { out[0]++; out[3] += (int64_t)amg->lv[l]->linef.n * (int64_t)sizeof(double); }
     out[1] = amg->plan.lv[0].line_g;
     out[2] = amg->plan.lv[0].g.n0;
+}
+
+void amg_gs_info(const Amg *amg, int64_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (size_t l = 0; l < amg->lv.size(); ++l)
+        if (amg->plan.lv[l].gs > 0) { out[0]++; out[1] = amg->plan.lv[l].gs; }
+    if (amg->plan.lv[0].gs > 0) {          // even and odd index sums of a box differ by one cell exactly when every extent is odd
+        const GridDev &g = amg->plan.lv[0].g;
+        const int64_t n = (int64_t)g.n0 * g.n1 * g.n2;
+        out[2] = (n + ((g.n0 & 1) && (g.n1 & 1) && (g.n2 & 1) ? 1 : 0)) / 2;
+        out[3] = n - out[2];
+    }
 }
 
 template <class R>
@@ -1322,6 +1403,31 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             throw Error("line relaxation (amg_line_levels) with fp32 operators (amg_single)");
         }
     };
+    // Gauss-Seidel levels (amg_gs_levels; one slab, fp64 operators: amg_gs_check_options): g forward sweeps (red, black) from the
+    // zero guess on the way down, g backward sweeps (black, red) on the way up; the iterate ping-pongs between x and x2
+    auto is_gs = [&](int l) { return amg->plan.lv[l].gs > 0; };
+    auto gs_half = [&](int l, int colour, const double *bb, const double *xin, double *xout) {
+        hipLaunchKernelGGL(k_amg_gs_half<R>, xcd_grid(amg->lv[l]->g.nown), bl, 0, c->stream, dev_of<R>(amg, l), colour, bb, xin, xout);
+    };
+    auto gs_forward = [&](int l, const double *bb) {        // F^g(0); returns the buffer that holds it
+        AmgLevel *L = amg->lv[l];
+        double *cur = L->x.p, *oth = L->x2.p;
+        hipLaunchKernelGGL(k_amg_gs_first<R>, xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, l), bb, cur);
+        for (int h = 2; h < 2 * amg->plan.lv[l].gs; ++h) {
+            gs_half(l, h & 1, bb, cur, oth);
+            std::swap(cur, oth);
+        }
+        return cur;
+    };
+    auto gs_backward = [&](int l, const double *bb, double *src, double *out) {      // out = B^g(src)
+        AmgLevel *L = amg->lv[l];
+        const int nh = 2 * amg->plan.lv[l].gs;
+        for (int h = 0; h < nh; ++h) {
+            double *dst = (h == nh - 1) ? out : (src == L->x.p ? L->x2.p : L->x.p);
+            gs_half(l, 1 - (h & 1), bb, src, dst);
+            src = dst;
+        }
+    };
     // down-sweep over the big levels
     for (int l = 0; l < ltop; ++l) {
         AmgLevel *L = amg->lv[l];
@@ -1344,7 +1450,10 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             hipLaunchKernelGGL(k_amg_restrict<R>, xcd_grid(cv.g.nown), bl, 0, c->stream, Ld, cv.g, bl_, bc);
         } else {
             double *cur = L->x.p, *oth = L->x2.p;
-            if (is_line(l)) {                       // the sweep from the zero guess, then plain line sweeps
+            if (is_gs(l)) {
+                cur = gs_forward(l, bl_);
+                oth = (cur == L->x.p) ? L->x2.p : L->x.p;
+            } else if (is_line(l)) {                // the sweep from the zero guess, then plain line sweeps
                 line_sweep(l, bl_, nullptr, cur);
                 for (int k = 1; k < Ld.pre; ++k) {
                     line_sweep(l, bl_, cur, oth);
@@ -1378,7 +1487,9 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         AmgLevel *L = amg->lv[trunc];
         const double *bt = (trunc == 0) ? b : L->b.p;
         double *et = (trunc == 0) ? x : L->e.p;
-        if (is_line(trunc)) {                       // its two sweeps as line sweeps
+        if (is_gs(trunc)) {                         // B^g F^g 0
+            gs_backward(trunc, bt, gs_forward(trunc, bt), et);
+        } else if (is_line(trunc)) {                // its two sweeps as line sweeps
             line_sweep(trunc, bt, nullptr, L->x.p);
             line_sweep(trunc, bt, L->x.p, et);
         } else {
@@ -1436,6 +1547,12 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         hx(l + 1, Lc->e.p);                         // distributed coarse level: parents across the boundary
         if (Ld.post == 0) {                         // pure transfer level
             hipLaunchKernelGGL(k_amg_prolong_set<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, out);
+            continue;
+        }
+        if (is_gs(l)) {                             // the unfused sequence whatever fuse_below says: x += P ec, then the half-sweeps
+            TP_REQUIRE(src, "a Gauss-Seidel level has pre-smoothing sweeps");
+            hipLaunchKernelGGL(k_amg_prolong_add<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, src);
+            gs_backward(l, bl_, src, out);
             continue;
         }
         if (is_line(l)) {                           // the unfused sequence whatever fuse_below says: x += P ec, then line sweeps

@@ -315,6 +315,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     basis_single_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
+    amg_gs_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
     c->grid = *grid; c->prm = *prm; c->opt = *opt; c->device = device;
@@ -370,6 +371,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     basis_single_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
+    amg_gs_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
                               (opt->ilu_single != 0) != (c->opt.ilu_single != 0) ||
@@ -379,6 +381,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
                              opt->amg_coarse_pre != c->opt.amg_coarse_pre || opt->amg_coarse_post != c->opt.amg_coarse_post ||
                              opt->amg_tail_post != c->opt.amg_tail_post || opt->amg_mid_skip != c->opt.amg_mid_skip ||
                              opt->amg_dom_tau != c->opt.amg_dom_tau || opt->amg_line_levels != c->opt.amg_line_levels ||
+                             opt->amg_gs_levels != c->opt.amg_gs_levels || opt->amg_gs_sweeps != c->opt.amg_gs_sweeps ||
                              opt->amg_single != c->opt.amg_single || opt->amg_gather_cells != c->opt.amg_gather_cells ||
                              opt->schur_a11 != c->opt.schur_a11 || opt->fs_additive != c->opt.fs_additive;
     // the FGMRES bases exist in one representation at a time: the next solve allocates the one the option asks for
@@ -1054,6 +1057,15 @@ int tp_amg_line_info(tp_ctx *c, int32_t which, int64_t out[4]) {
     Amg *amg = which == 0 ? c->amg_p : c->amg_T;
     TP_REQUIRE(amg, "AMG hierarchy not built");
     amg_line_info(amg, out);
+    TP_API_END
+}
+
+int tp_amg_gs_info(tp_ctx *c, int32_t which, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out && (which == 0 || which == 1), "bad arguments");
+    Amg *amg = which == 0 ? c->amg_p : c->amg_T;
+    TP_REQUIRE(amg, "AMG hierarchy not built");
+    amg_gs_info(amg, out);
     TP_API_END
 }
 

@@ -167,6 +167,8 @@ struct AmgPlan {
         // line relaxation (tp_options.amg_line_levels): the level's sweeps are line-Jacobi along axis 0, one workgroup per
         // line_g consecutive lines (flattened line index i1 + n1 i2); line_g == 0: point Jacobi
         int line_g = 0;
+        // red-black Gauss-Seidel (tp_options.amg_gs_levels): gs > 0: the level's sweeps are GS sweeps, pre == post == gs
+        int gs = 0;
     };
     std::vector<int> sched;    // axis of every coarsening step
     std::vector<Level> lv;     // sched.size() + 1 levels
@@ -487,6 +489,8 @@ void amg_setup(tp_ctx *c, Amg *amg, const Stencil &A0);
 void amg_vcycle(tp_ctx *c, Amg *amg, const double *b, double *x);
 void amg_line_check_options(const tp_options &o, int nranks);      // what amg_line_levels excludes (throws, naming both options)
 void amg_line_info(const Amg *amg, int64_t out[4]);
+void amg_gs_check_options(const tp_options &o, int nranks);        // what amg_gs_levels excludes (throws, naming both options)
+void amg_gs_info(const Amg *amg, int64_t out[4]);
 bool amg_resolve_trunc(tp_ctx *c, Amg *amg);      // waits for the set-up's dominance ratios; true if the cycle shape changed
 // system AMG (2x2 blocks on (p,T))
 void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[3]);

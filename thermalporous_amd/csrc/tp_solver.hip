@@ -73,7 +73,7 @@ static void refresh_pc_signature(tp_ctx *c) {
                              (uintptr_t)c->Sm.p, (uintptr_t)c->ilu.fwd.p, (uintptr_t)c->ilu.fwd32.p, (uintptr_t)c->ilu.fwdp.p, (uintptr_t)c->amg_p, (uintptr_t)c->amg_T, (uintptr_t)c->bamg,
                              (uintptr_t)c->w1.p, (uintptr_t)c->w3.p, (uintptr_t)c->w4.p, (uintptr_t)c->dcoef.p, (uintptr_t)c->spbuf.p,
                              (uintptr_t)c->opt.amg_nu, (uintptr_t)c->opt.pc_kind, (uintptr_t)c->opt.decoup,
-                             (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip, (uintptr_t)c->opt.amg_line_levels,
+                             (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip, (uintptr_t)c->opt.amg_line_levels, (uintptr_t)c->opt.amg_gs_levels, (uintptr_t)c->opt.amg_gs_sweeps,
                              (uintptr_t)c->opt.s1_ksp, (uintptr_t)c->opt.s1_max_it, (uintptr_t)c->inner.V.p, (uintptr_t)c->inner.Z.p,
                              (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole};
     uintptr_t h = 1469598103934665603ull;
@@ -133,6 +133,7 @@ void pc_setup(tp_ctx *c) {
     TP_REQUIRE(c->jac_ready, "pc_setup needs an assembled Jacobian");
     ensure_work(c);
     amg_line_check_options(c->opt, c->grid.nranks);
+    amg_gs_check_options(c->opt, c->grid.nranks);
     if (c->opt.s1_ksp) inner_reset_stats(c);      // tp_inner_stats counts since the last set-up
     if (c->ilu.slots == 0) ilu_setup(c);          // (a stage-2 layout the options do not allow fails here, before the streams fork)
     if (c->opt.pc_kind == 4) {               // pc_bilu (twophase.py:758-762): bjacobi + ILU is the whole preconditioner

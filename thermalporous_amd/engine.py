@@ -47,6 +47,7 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
+                ("amg_gs_levels", C.c_int32), ("amg_gs_sweeps", C.c_int32),
                 ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
                 ("ls_kind", C.c_int32), ("ls_order", C.c_int32), ("ls_max_it", C.c_int32), ("ls_alpha", C.c_double),
                 ("ls_maxstep", C.c_double), ("ls_minlambda", C.c_double), ("ls_max_change", C.c_double*3),
@@ -72,7 +73,7 @@ API_SYMBOLS = (
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
-    "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial",
+    "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -92,6 +93,11 @@ DEFAULT_OPTS = dict(
     amg_line_levels=0,      # L: line-Jacobi along internal axis 0 (Thomas solve per line) instead of point Jacobi on the first L levels of
                             # the scalar hierarchies that lie above the single-workgroup tail (L <= amg_full_levels).  0: off.  One slab,
                             # fp64 operators, not pc cptramg, not schur_selfp (check_amg_line_options)
+    amg_gs_levels=0,        # L: red-black Gauss-Seidel (no damping, amg_omega unused) instead of damped Jacobi on the first L levels of the
+                            # scalar hierarchies that lie above the single-workgroup tail (L <= amg_full_levels); such a level is V(g, g) with
+    amg_gs_sweeps=1,        # g = 1..4 sweeps per leg: forward (red, black) before the coarse correction, backward (black, red) after it.
+                            # L = 0: off (g must then be 1).  One slab, fp64 operators, not amg_line_levels, pc cptramg or schur_selfp
+                            # (check_amg_gs_options)
     # multi-GPU: AMG levels with more cells than this stay distributed over the slabs.  Cost model: a V(2,2)
     # level streams ~6 sweeps x 104 B per cell (5.5 TB/s on one GPU) and needs 6 halo exchanges when distributed; with N
     # slabs it saves (1 - 1/N) of its streaming time and pays 6 x t_exchange (~10 us per grouped RCCL send/recv): the
@@ -336,6 +342,33 @@ def check_amg_line_options(o, nranks=1, exc=EngineError):
         raise exc("amg_line_levels with nranks = %d: line relaxation is implemented for one slab" % int(nranks))
 
 
+def check_amg_gs_options(o, nranks=1, exc=EngineError):
+    """amg_gs_levels / amg_gs_sweeps (tp_options) against their ranges and the options they exclude: refused naming both, never
+    ignored."""
+    L, g = o.get("amg_gs_levels", 0), o.get("amg_gs_sweeps", 1)
+    if isinstance(L, bool) or int(L) != L or L < 0:
+        raise ValueError("amg_gs_levels = %r: an integer >= 0" % (L,))
+    if isinstance(g, bool) or int(g) != g or not 1 <= g <= 4:
+        raise ValueError("amg_gs_sweeps = %r: an integer in 1..4" % (g,))
+    if L == 0:
+        if g != 1:
+            raise ValueError("amg_gs_sweeps = %d with amg_gs_levels = 0: the sweep count would be ignored" % g)
+        return
+    if L > int(o["amg_full_levels"]):
+        raise ValueError("amg_gs_levels = %d exceeds amg_full_levels = %d: Gauss-Seidel levels are V(g,g) levels, never "
+                         "pure-transfer or paired ones" % (L, o["amg_full_levels"]))
+    if o.get("amg_line_levels", 0):
+        raise exc("amg_gs_levels with amg_line_levels: one smoother per level, choose one")
+    if o.get("amg_single"):
+        raise exc("amg_gs_levels with amg_single: the red-black sweeps are implemented for fp64 operators")
+    if o.get("pc") == "cptramg":
+        raise exc("amg_gs_levels with pc cptramg (pc_kind 3): red-black Gauss-Seidel is implemented for the scalar hierarchies")
+    if o.get("schur_selfp"):
+        raise exc("amg_gs_levels with schur_selfp (schur_a11 = 2): not implemented")
+    if int(nranks) > 1:
+        raise exc("amg_gs_levels with nranks = %d: red-black Gauss-Seidel is implemented for one slab" % int(nranks))
+
+
 def check_ksp_basis_options(o):
     """ksp_basis_single / ksp_single_floor (tp_options) against the range of theta and the method that has no basis."""
     th = o.get("ksp_single_floor", 1e-7)
@@ -395,6 +428,7 @@ class HipEngine:
         self.opts.update(opts or {})
         self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
         check_amg_line_options(self.opts, nranks)
+        check_amg_gs_options(self.opts, nranks)
         check_ksp_basis_options(self.opts)
         check_linesearch_options(self.opts)
         self.nph = int(spec["nphase"])
@@ -458,7 +492,7 @@ class HipEngine:
                           0 if t[0] >= (1 << 30) else int(t[0]), int(o["amg_full_levels"]), int(o["amg_coarse_pre"]),
                           int(o["amg_coarse_post"]), int(bool(o["amg_mid_skip"])), int(o["amg_tail_post"]), int(bool(o["amg_single"])), 2 if o.get("schur_selfp") else int(bool(o["schur_a11"])),
                           int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
-                          int(bool(o.get("ilu_whole", False))),
+                          int(bool(o.get("ilu_whole", False))), int(o.get("amg_gs_levels", 0)), int(o.get("amg_gs_sweeps", 1)),
                           (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
                           int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)),
                           int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
@@ -478,6 +512,7 @@ class HipEngine:
 
     def set_options(self, **kw):
         check_amg_line_options({**self.opts, **kw}, self.nranks)
+        check_amg_gs_options({**self.opts, **kw}, self.nranks)
         check_ksp_basis_options({**self.opts, **kw})
         check_linesearch_options({**self.opts, **kw})
         self.opts.update(kw)
@@ -763,6 +798,13 @@ class HipEngine:
         out = (C.c_int64*4)()
         self._ck(self.lib.tp_amg_line_info(self.ctx, which, out))
         return dict(levels=out[0], group=out[1], n0=out[2], bytes=out[3])
+
+    def amg_gs_info(self, which=0):
+        """Red-black Gauss-Seidel of hierarchy `which` (tp_amg_gs_info): GS levels in effect, sweeps per leg, red and black cells of
+        level 0 (all zero when the option is off or no level qualifies)."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_amg_gs_info(self.ctx, which, out))
+        return dict(levels=out[0], sweeps=out[1], red=out[2], black=out[3])
 
     def amg_layout(self, which=0):
         """(number of slab-distributed top levels, coarsening axis of every level)."""

@@ -155,9 +155,10 @@ def _check_ilu_single(o):
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import check_amg_line_options, check_ksp_basis_options, check_linesearch_options
+    from .engine import check_amg_gs_options, check_amg_line_options, check_ksp_basis_options, check_linesearch_options
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
+    check_amg_gs_options(o, exc=NotImplementedError)
     check_ksp_basis_options(o)
     check_linesearch_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
@@ -223,7 +224,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     o["schur_selfp"] = False
     o["fs_additive"] = False
     used = set()
-    build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels",
+    build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor",
                   "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
