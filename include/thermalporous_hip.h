@@ -107,6 +107,17 @@ typedef struct tp_options {
                                 take 4 steps of skew per axis-2 plane and 2 per axis-1 line instead of 1 and 1 */
     int32_t fs_additive;     /* pc_kind 2: 1 = PCFIELDSPLIT additive on (p,T) -- y_p = V(A_pp) x_p, y_T = V(A_TT) x_T, no coupling
                                 (pc_fieldsplit_diag, singlephase.py:371-375) -- instead of Schur FULL */
+    /* Gram-Schmidt refinement of the outer FGMRES (ksp_gmres_cgs_refinement_type).  NOTE for ABI readers: the
+     * two fields stand HERE, between fs_additive and ilu_whole, not at the struct's tail (the tests of earlier options pin the
+     * order of every field from ilu_whole on): every field from ilu_whole on moved and sizeof(tp_options) grew; recompile callers.
+     * One orthogonalisation step is h = V^T w ; w <- w - V h ; n1 = ||w||^2 (classical Gram-Schmidt in one pass).  A SECOND pass
+     * c = V^T w ; w <- w - V c ; h <- h + c ; n2 = ||w||^2 follows when a flag on the device is set: by ksp_reorth 2 always, by
+     * ksp_reorth 1 when n1 < eta^2 (||h||^2 + n1) with every sum finite (the vector lost more than 1 - eta of its length: the
+     * DGKS / Rutishauser rule).  The host neither decides nor waits: the second pass's kernels are always enqueued and return
+     * at once when the flag is clear, and everything the loop reads afterwards (the k coefficients, ||w||^2) holds the final
+     * values in the same places.  FGMRES with fp64 bases only: refused with ksp_kind 1 and with ksp_basis_single. */
+    int32_t ksp_reorth;      /* 0 never (default: the launch sequence is unchanged), 1 if needed, 2 always */
+    double  ksp_reorth_eta;  /* eta in (0, 1) (default 2^-1/2): the rule of ksp_reorth 1; range-checked whenever ksp_reorth is not 0 */
     int32_t ilu_whole;       /* 1: ONE bjacobi block per rank = block-ILU(0) of the whole slab, PETSc's default bjacobi and the
                                 reference's `sub_1_pc_bjacobi_blocks: 1` (tests/test_homo_wells.py:112, pc_cptr_a11
                                 twophase.py:612): couplings between the tiles are kept; the tiles (ilu_t0 x ilu_t1 x ilu_t2,
@@ -272,6 +283,13 @@ int tp_vec_create_batch(tp_ctx *ctx, int32_t n, int32_t *first_id);
 int tp_vec_dot_batch(tp_ctx *ctx, int32_t first, int32_t n, int32_t w, double *out);
 int tp_vec_axpy_batch(tp_ctx *ctx, int32_t first, int32_t n, const double *coef, int32_t w);
 int tp_vec_norm2(tp_ctx *ctx, int32_t x, double *out);
+/* One Gram-Schmidt step of the outer FGMRES on user vectors (the kernels of tp_options.ksp_reorth, testable alone, and the
+ * orthogonalisation for callers who drive their own Krylov method over the kernels above): basis = the vectors first..first+k-1
+ * of one batch, w = any vector outside them.  mode 0 | 1 | 2 and eta as ksp_reorth / ksp_reorth_eta (the context's options are
+ * not read).  On return w holds the orthogonalised vector (NOT normalised), h[0..k) the coefficients (h + c after a second
+ * pass), *norm2 the final ||w||^2 and *refined 1 if the second pass ran, else 0.  The step counts in tp_ksp_reorth_info. */
+int tp_vec_orth_step(tp_ctx *ctx, int32_t first, int32_t k, int32_t w, int32_t mode, double eta, double *h, double *norm2,
+                     int32_t *refined);
 /* The same kernels on a compact fp32 batch (the storage of ksp_basis_single; exported so that they can be tested alone):
  *   tp_fvec_create_batch  n float vectors of b * owned cells entries (field-major, no halo planes) at the basis stride
  *   tp_fvec_store         slot i <- (float) x, and x <- (double) slot i in the same pass: the solver's round-and-store kernel
@@ -329,6 +347,11 @@ int tp_ksp_info(tp_ctx *ctx, int64_t out[4]);
  * fp64 staging vectors allocated (b * ntot doubles each), restart cycles of the last fp32-basis FGMRES solve, true-residual
  * evaluations (one SpMV and one norm each) of that solve}.  tp_ksp_info's bytes count these buffers too. */
 int tp_ksp_basis_info(tp_ctx *ctx, int64_t out[6]);
+/* Gram-Schmidt refinement (tp_options.ksp_reorth): out = {ksp_reorth in effect, orthogonalisation steps since tp_create (every
+ * mode, tp_vec_orth_step included), second passes executed, second passes enqueued but skipped by the device flag}.  The last
+ * two are counters on the device, written by the kernel that takes the decision and copied out only by this call (one stream
+ * synchronisation); on several slabs every rank counts the same decisions. */
+int tp_ksp_reorth_info(tp_ctx *ctx, int64_t out[4]);
 int tp_newton_solve(tp_ctx *ctx, tp_solve_info *info);
 /* The line search: out = {ls_kind in effect, device bytes of line-search workspace allocated (the saved iterate u0
  * only: the reductions use the scratch they share with the Krylov loop; 0 until the first bt solve), residual evaluations of the

@@ -313,6 +313,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     inner_check_options(*opt);
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
+    reorth_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     amg_gs_check_options(*opt, grid->nranks);
@@ -369,6 +370,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     inner_check_options(*opt);
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
+    reorth_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     amg_gs_check_options(*opt, c->grid.nranks);
@@ -684,6 +686,23 @@ int tp_vec_axpy_batch(tp_ctx *c, int32_t first, int32_t n, const double *coef, i
     TP_API_END
 }
 
+int tp_vec_orth_step(tp_ctx *c, int32_t first, int32_t k, int32_t w, int32_t mode, double eta, double *h, double *norm2,
+                     int32_t *refined) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && k >= 1 && h && norm2 && refined, "bad arguments");
+    TP_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (never), 1 (if needed) or 2 (always)");
+    TP_REQUIRE(mode != 1 || (eta > 0.0 && eta < 1.0), "eta must lie in (0, 1)");
+    const double *V = batch_base(c, first, k);
+    TP_REQUIRE(w < first || w >= first + k, "w must not be one of the k basis vectors");
+    std::vector<double> out((size_t)k + 1);
+    int ran = 0;
+    orthogonalize_mode(c, c->b, V, (long)c->b * c->g.ntot, k, vec_of(c, w).p, mode, eta, out.data(), &ran);
+    std::memcpy(h, out.data(), sizeof(double) * k);
+    *norm2 = out[k];
+    *refined = ran;
+    TP_API_END
+}
+
 static FBatch &fbatch_of(tp_ctx *c, int32_t id, int32_t n) {
     TP_REQUIRE(id >= 0 && id < (int)c->fbatches.size(), "bad float batch id");
     TP_REQUIRE(n >= 0 && n <= c->fbatches[id]->n, "float batch has fewer vectors");
@@ -891,6 +910,18 @@ int tp_ksp_basis_info(tp_ctx *c, int64_t out[6]) {
     out[3] = (int64_t)(c->kstage.n / ((size_t)c->b * c->g.ntot));
     out[4] = c->ksp_cycles;
     out[5] = c->ksp_true_res;
+    TP_API_END
+}
+
+int tp_ksp_reorth_info(tp_ctx *c, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "null argument");
+    long long h[4] = {0, 0, 0, 0};
+    if (c->ro_stat.n >= 4) copy_sync(c, h, c->ro_stat.p, sizeof(h), hipMemcpyDeviceToHost);
+    out[0] = c->opt.ksp_reorth;
+    out[1] = c->ro_steps;
+    out[2] = h[1];
+    out[3] = h[2];
     TP_API_END
 }
 

@@ -375,6 +375,11 @@ struct tp_ctx {
     tp::DBuf<float> Vs, Zs;
     tp::DBuf<double> kstage;
     int gs_cap_s = 0;
+    // tp_options.ksp_reorth: the second Gram-Schmidt pass's sums c (k) and its ||w||^2, and the device-resident latch
+    // {flag of the step in flight, second passes executed, second passes skipped} (tp_linalg.hip; tp_ksp_reorth_info)
+    tp::DBuf<double> ro_c;
+    tp::DBuf<long long> ro_stat;
+    long ro_steps = 0;                       // orthogonalisation steps since create
     long ksp_cycles = 0, ksp_true_res = 0;   // restart cycles / true-residual evaluations of the last fp32-basis solve (tp_ksp_basis_info)
     std::vector<tp::FBatch *> fbatches;      // fp32 vector batches of the C ABI (tp_fvec_*)
     tp::BcgsWork bcgs;                 // ksp_kind 1: the BiCGStab work vectors and its device-resident scalars (tp_bcgs.hip)
@@ -447,6 +452,11 @@ bool orthogonalize_can_split(const tp_ctx *c, int k);
 void orthogonalize_enqueue(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w);
 const double *orthogonalize_norm_dev(const tp_ctx *c, int k);
 void orthogonalize_wait(tp_ctx *c, int k, double *host_out);
+// the same step with the refinement mode and eta given by the caller instead of tp_options (tp_vec_orth_step); *refined = the
+// device flag of this step
+void orthogonalize_mode(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, int mode, double eta, double *host_out,
+                        int *refined);
+void reorth_check_options(const tp_options &o);
 void vec_scale_dev_norm(tp_ctx *c, int nf, const double *n2_dev, double *x);   // x *= 1/sqrt(*n2_dev) (owned)
 // fp32 Krylov bases (tp_options.ksp_basis_single; tp_linalg.hip): Vs points at compact float vectors `vstride` entries apart
 long basis_stride(const tp_ctx *c);                                              // b*nown rounded up to 64 entries

@@ -332,6 +332,210 @@ __global__ __launch_bounds__(256) void k_multi_axpy_norm(GridDev g, int nf, cons
     if (lane == 0) partial[wave] = acc;
 }
 
+// ---- Gram-Schmidt refinement (tp_options.ksp_reorth) ---------------------------------
+// A second pass c = V^T w ; w -= V c ; h += c ; ||w||^2 behind the first, PREDICATED on a flag in device memory: the host
+// enqueues the second pass's kernels on every step and neither takes the decision nor waits for it.  stat = {flag of the step
+// in flight, second passes executed, second passes skipped}.  The kernels below are siblings of k_multi_dot, k_reduce_partials
+// and k_multi_axpy_norm (same chunks, same load batching, same summation orders), kept apart from them so that the one-pass
+// path runs the code it always ran; with the flag clear each returns before it has touched w, red_out, the pinned buffer or
+// the partial sums.
+
+// The decision, one wave behind the (all-reduced) sums of the first pass: red[0..k) = h, red[k] = n1 = ||w - V h||^2.
+// mode 2: always.  mode 1: n1 < eta^2 (||h||^2 + n1), i.e. ||w'|| < eta ||w||, with ||w||^2 taken as ||h||^2 + n1 (no further
+// pass over memory); a sum that is not finite never refines, so the loop's NaN handling sees the first pass's values.
+__global__ __launch_bounds__(64) void k_reorth_decide(const double *__restrict__ red, int k, int mode, double eta2,
+                                                      long long *__restrict__ stat) {
+    const int lane = threadIdx.x;
+    double hh = 0.0;
+    for (int i = lane; i < k; i += 64) {
+        const double h = red[i];
+        hh += h * h;
+    }
+    hh = wave_sum(hh);
+    if (lane == 0) {
+        const double n1 = red[k];
+        const bool go = mode == 2 || (isfinite(hh) && isfinite(n1) && n1 < eta2 * (hh + n1));
+        stat[0] = go ? 1 : 0;
+        stat[go ? 1 : 2] += 1;
+    }
+}
+
+// k_multi_dot without the norm output, predicated, traversal direction selectable (rev as in k_multi_axpy_norm)
+template <int CH>
+__global__ __launch_bounds__(256) void k_multi_dot_p(const long long *__restrict__ flag, GridDev g, int nf,
+                                                     const double *__restrict__ V, long vstride, int k,
+                                                     const double *__restrict__ w, double *__restrict__ partial, long nwaves,
+                                                     int rev) {
+    constexpr int MD_CHUNK = CH;
+    const long wave_d = ((long)blockIdx.x * TP_BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wave_d >= nwaves || *flag == 0) return;
+    const long wave = rev ? nwaves - 1 - wave_d : wave_d;
+    const long nall = g.nown * nf;
+    long idx[MD_CHUNK];
+    double wv[MD_CHUNK];
+#pragma unroll
+    for (int j = 0; j < MD_CHUNK; ++j) {
+        const long t = (wave * MD_CHUNK + j) * 64 + lane;
+        const bool ok = t < nall;
+        const long tt = ok ? t : 0;
+        const long f = tt / g.nown, i = tt - f * g.nown;
+        idx[j] = f * g.ntot + g.np + i;              // (tail lanes: entry 0 -- a valid address, weight 0)
+        wv[j] = ok ? w[idx[j]] : 0.0;
+    }
+    int i = 0;
+    for (; i + MD_U <= k; i += MD_U) {
+        double v[MD_U][MD_CHUNK];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u)
+#pragma unroll
+            for (int j = 0; j < MD_CHUNK; ++j) v[u][j] = V[(long)(i + u) * vstride + idx[j]];
+        double s[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+            s[u] = 0.0;
+#pragma unroll
+            for (int j = 0; j < MD_CHUNK; ++j) s[u] += v[u][j] * wv[j];
+        }
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) s[u] = wave_sum(s[u]);
+        if (lane == 0) {
+#pragma unroll
+            for (int u = 0; u < MD_U; ++u) partial[(long)(i + u) * nwaves + wave] = s[u];
+        }
+    }
+    for (; i < k; ++i) {
+        const double *Vi = V + (long)i * vstride;
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < MD_CHUNK; ++j) s += Vi[idx[j]] * wv[j];
+        s = wave_sum(s);
+        if (lane == 0) partial[(long)i * nwaves + wave] = s;
+    }
+}
+
+// k_reduce_partials, predicated: out[i] = sum of partials i, or 0 with the flag clear (out is the second pass's own buffer:
+// on several slabs its all-reduce is enqueued either way and must then add zeros)
+__global__ __launch_bounds__(1024) void k_reduce_partials_p(const long long *__restrict__ flag, const double *__restrict__ partial,
+                                                            long nwaves, double *__restrict__ out) {
+    __shared__ double sh[16];
+    if (*flag == 0) {
+        if (threadIdx.x == 0) out[blockIdx.x] = 0.0;
+        return;
+    }
+    const double *p = partial + (long)blockIdx.x * nwaves;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    long i = threadIdx.x;
+    for (; i + 3 * 1024 < nwaves; i += 4 * 1024) {
+        s0 += p[i]; s1 += p[i + 1024]; s2 += p[i + 2 * 1024]; s3 += p[i + 3 * 1024];
+    }
+    for (; i < nwaves; i += 1024) s0 += p[i];
+    double s = wave_sum((s0 + s1) + (s2 + s3));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) t += sh[w];
+        out[blockIdx.x] = t;
+    }
+}
+
+// k_multi_axpy_norm, predicated (h = the second pass's sums c)
+template <int CH>
+__global__ __launch_bounds__(256) void k_multi_axpy_norm_p(const long long *__restrict__ flag, GridDev g, int nf,
+                                                           const double *__restrict__ V, long vstride, int k,
+                                                           const double *__restrict__ h, double *w,
+                                                           double *__restrict__ partial, long nwaves, int rev) {
+    constexpr int MD_CHUNK = CH;
+    const long wave_d = ((long)blockIdx.x * TP_BLOCK + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (wave_d >= nwaves || *flag == 0) return;
+    const long wave = rev ? nwaves - 1 - wave_d : wave_d;
+    const long nall = g.nown * nf;
+    long idx[MD_CHUNK];
+    bool ok[MD_CHUNK];
+    double s[MD_CHUNK], w0[MD_CHUNK];
+#pragma unroll
+    for (int j = 0; j < MD_CHUNK; ++j) {
+        const long t = (wave * MD_CHUNK + j) * 64 + lane;
+        ok[j] = t < nall;
+        const long tt = ok[j] ? t : 0;
+        const long f = tt / g.nown, i = tt - f * g.nown;
+        idx[j] = f * g.ntot + g.np + i;
+        s[j] = 0.0;
+        w0[j] = w[idx[j]];
+    }
+    int q = 0;
+    for (; q + MD_U <= k; q += MD_U) {
+        double v[MD_U][MD_CHUNK], hq[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+            hq[u] = h[q + u];
+#pragma unroll
+            for (int j = 0; j < MD_CHUNK; ++j) v[u][j] = V[(long)(q + u) * vstride + idx[j]];
+        }
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u)
+#pragma unroll
+            for (int j = 0; j < MD_CHUNK; ++j) s[j] += hq[u] * v[u][j];
+    }
+    for (; q < k; ++q) {
+        const double hq = h[q];
+#pragma unroll
+        for (int j = 0; j < MD_CHUNK; ++j) s[j] += hq * V[(long)q * vstride + idx[j]];
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < MD_CHUNK; ++j) {
+        if (ok[j]) {
+            const double wn = w0[j] - s[j];
+            w[idx[j]] = wn;
+            acc += wn * wn;
+        }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) partial[wave] = acc;
+}
+
+// The hand-over of an executed second pass, one workgroup: red[i] <- h_i + c_i, red[k] <- n2, mirrored into the pinned buffer
+// where that path is in use -- the places the loop, orthogonalize_norm_dev and the host read the first pass's values from.
+// n2 is summed here from the update pass's partials (k_reduce_partials' order) on one slab; on several slabs partial is null
+// and n2 = c2[k], already reduced and all-reduced.
+__global__ __launch_bounds__(1024) void k_reorth_commit(const long long *__restrict__ flag, const double *__restrict__ partial,
+                                                        long nwaves, int k, const double *__restrict__ c2,
+                                                        double *__restrict__ red, double *__restrict__ pin) {
+    __shared__ double sh[16];
+    if (*flag == 0) return;
+    double n2 = 0.0;
+    if (partial) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        long i = threadIdx.x;
+        for (; i + 3 * 1024 < nwaves; i += 4 * 1024) {
+            s0 += partial[i]; s1 += partial[i + 1024]; s2 += partial[i + 2 * 1024]; s3 += partial[i + 3 * 1024];
+        }
+        for (; i < nwaves; i += 1024) s0 += partial[i];
+        const double s = wave_sum((s0 + s1) + (s2 + s3));
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int w = 0; w < 16; ++w) n2 += sh[w];
+        }
+    } else if (threadIdx.x == 0) {
+        n2 = c2[k];
+    }
+    for (int i = threadIdx.x; i < k; i += 1024) {
+        const double t = red[i] + c2[i];
+        red[i] = t;
+        if (pin) pin[i] = t;
+    }
+    if (threadIdx.x == 0) {
+        red[k] = n2;
+        if (pin) pin[k] = n2;
+    }
+}
+
 // ---- fp32 Krylov bases (tp_options.ksp_basis_single) ------------------------------------------------
 // The FGMRES bases stored as floats, all arithmetic fp64 on widened loads.  A stored vector is COMPACT: the
 // nf * nown owned entries only, field-major -- entry t = owned cell t % nown of field t / nown -- without halo planes, at a
@@ -587,10 +791,45 @@ void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const
     TP_HIP(hipStreamSynchronize(c->stream));      // the host buffer may be reused by the caller right away
 }
 
+// The second Gram-Schmidt pass of tp_options.ksp_reorth, enqueued behind the first pass's last all-reduce and in
+// front of whatever hands the sums to the host (the event of the split form included): one wave takes the decision from the
+// sums in red_out, the four kernels behind it return at once when it says no.  Several slabs: the sums are all-reduced, so
+// every rank sets the same flag; the two all-reduces of this pass are enqueued whatever the flag says -- every rank must issue
+// the same sequence of collectives -- on the pass's own buffer ro_c, which a skipped pass fills with zeros.
+// Traversal: the first update pass walks back to front (TP_GS_REVERSE) and so ends at the front of the vectors; the second dot
+// pass therefore starts there, front to back, and the second update pass again walks back to front.  TP_REORTH_DOT_REVERSE=1
+// turns the second dot pass round (for measuring; same sums either way).
+static void reorth_pass(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, long nw, double *pin, int mode,
+                        double eta, int gs_rev) {
+    TP_REQUIRE(V, "ksp_reorth needs the fp64 Krylov basis");
+    if (c->ro_stat.n < 4) c->ro_stat.alloc(4);
+    if ((long)c->ro_c.n < k + 1) c->ro_c.alloc(k + 65);
+    static const int dot_flip = getenv("TP_REORTH_DOT_REVERSE") && atoi(getenv("TP_REORTH_DOT_REVERSE")) != 0;
+    const int dot_rev = (gs_rev ? 0 : 1) ^ dot_flip;
+    const long long *flag = c->ro_stat.p;
+    hipLaunchKernelGGL(k_reorth_decide, dim3(1), dim3(64), 0, c->stream, (const double *)c->red_out.p, k, mode, eta * eta, c->ro_stat.p);
+    TP_MD_LAUNCH(k_multi_dot_p, md_grid(nw), dim3(256), 0, c->stream, flag, c->g, nf, V, vstride, k, (const double *)w,
+                 c->gs_partial.p, nw, dot_rev);
+    hipLaunchKernelGGL(k_reduce_partials_p, dim3(k), dim3(1024), 0, c->stream, flag, (const double *)c->gs_partial.p, nw, c->ro_c.p);
+    allreduce_sum(c, c->ro_c.p, k);
+    TP_MD_LAUNCH(k_multi_axpy_norm_p, md_grid(nw), dim3(256), 0, c->stream, flag, c->g, nf, V, vstride, k,
+                 (const double *)c->ro_c.p, w, c->gs_partial.p, nw, gs_rev);
+    if (c->dist) {
+        hipLaunchKernelGGL(k_reduce_partials_p, dim3(1), dim3(1024), 0, c->stream, flag, (const double *)c->gs_partial.p, nw, c->ro_c.p + k);
+        allreduce_sum(c, c->ro_c.p + k, 1);
+    }
+    hipLaunchKernelGGL(k_reorth_commit, dim3(1), dim3(1024), 0, c->stream, flag,
+                       c->dist ? (const double *)nullptr : (const double *)c->gs_partial.p, nw, k, (const double *)c->ro_c.p,
+                       c->red_out.p, pin);
+    TP_HIP(hipGetLastError());
+}
+
 // (Vs != nullptr: the basis is the compact fp32 one of tp_options.ksp_basis_single and the two passes are its kernels below;
 // everything around them -- partial sums, second stages, all-reduces, hand-over to the host -- is the same)
-static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *Vs, long vstride, int k, double *w, double *host_out) {
+static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *Vs, long vstride, int k, double *w, double *host_out,
+                              int ro = 0, double ro_eta = 0.0) {
     const long nw = md_nwaves(c, nf);
+    ++c->ro_steps;
     if ((long)c->gs_partial.n < (long)(k + 1) * nw) c->gs_partial.alloc((size_t)(k + 33) * nw);
     if ((long)c->red_out.n < k + 1) c->red_out.alloc(k + 65);
     // Several GPUs: TWO all-reduces per Krylov iteration (the k dots, then the norm of the orthogonalised vector), ONE host
@@ -617,6 +856,7 @@ static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *V
                        pin ? pin + k : (double *)nullptr);
     TP_HIP(hipGetLastError());
     allreduce_sum(c, c->red_out.p + k, 1);
+    if (ro) reorth_pass(c, nf, V, vstride, k, w, nw, pin, ro, ro_eta, gs_rev);
     if (pin) {
         if (!host_out) {                   // split form (orthogonalize_enqueue / orthogonalize_wait): the caller goes on enqueueing
             TP_HIP(hipEventRecord(c->ev_h, c->stream));
@@ -637,7 +877,14 @@ static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *V
 }
 
 void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, double *host_out) {
-    orthogonalize_any(c, nf, V, nullptr, vstride, k, w, host_out);
+    orthogonalize_any(c, nf, V, nullptr, vstride, k, w, host_out, c->opt.ksp_reorth, c->opt.ksp_reorth_eta);
+}
+void orthogonalize_mode(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, int mode, double eta, double *host_out,
+                        int *refined) {
+    orthogonalize_any(c, nf, V, nullptr, vstride, k, w, host_out, mode, eta);
+    long long flag = 0;
+    if (mode) copy_sync(c, &flag, c->ro_stat.p, sizeof(flag), hipMemcpyDeviceToHost);
+    *refined = flag != 0;
 }
 void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w, double *host_out) {
     orthogonalize_any(c, nf, nullptr, Vs, vstride, k, w, host_out);

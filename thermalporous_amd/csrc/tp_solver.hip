@@ -456,6 +456,15 @@ void basis_single_check_options(const tp_options &o) {
     TP_REQUIRE(o.ksp_kind == 0, "ksp_basis_single with ksp_kind 1 (bcgs): BiCGStab has no basis to store in fp32");
     TP_REQUIRE(o.ksp_single_floor > 0x1p-24 && o.ksp_single_floor < 1.0, "ksp_single_floor must lie in (2^-24, 1)");
 }
+// Gram-Schmidt refinement of the fp64-basis FGMRES (tp_options.ksp_reorth)
+void reorth_check_options(const tp_options &o) {
+    TP_REQUIRE(o.ksp_reorth >= 0 && o.ksp_reorth <= 2, "ksp_reorth must be 0 (never), 1 (if needed) or 2 (always)");
+    if (!o.ksp_reorth) return;
+    TP_REQUIRE(o.ksp_kind == 0, "ksp_reorth with ksp_kind 1 (bcgs): BiCGStab has no basis to orthogonalise against");
+    TP_REQUIRE(!o.ksp_basis_single, "ksp_reorth with ksp_basis_single: a basis rounded to fp32 cannot be orthonormal below 2^-24, "
+               "a second Gram-Schmidt pass buys nothing");
+    TP_REQUIRE(o.ksp_reorth_eta > 0.0 && o.ksp_reorth_eta < 1.0, "ksp_reorth_eta must lie in (0, 1)");
+}
 void basis_single_release(tp_ctx *c) {
     c->V.free(); c->Z.free(); c->gs_cap = 0;
     c->Vs.free(); c->Zs.free(); c->kstage.free(); c->gs_cap_s = 0;

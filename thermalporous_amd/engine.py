@@ -46,7 +46,8 @@ class tp_options(C.Structure):
                 ("ilu_t1", C.c_int32), ("ilu_t2", C.c_int32), ("ilu_t0", C.c_int32),
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
-                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("ilu_whole", C.c_int32),
+                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32),
+                ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double), ("ilu_whole", C.c_int32),
                 ("amg_gs_levels", C.c_int32), ("amg_gs_sweeps", C.c_int32),
                 ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
                 ("ls_kind", C.c_int32), ("ls_order", C.c_int32), ("ls_max_it", C.c_int32), ("ls_alpha", C.c_double),
@@ -73,7 +74,7 @@ API_SYMBOLS = (
     "tp_amg_vcycle", "tp_schur_apply", "tp_fgmres", "tp_newton_solve", "tp_time_kernel", "tp_amg_info", "tp_amg_layout", "tp_amg_trunc",
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
-    "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info",
+    "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -85,6 +86,10 @@ DEFAULT_OPTS = dict(
                             # Krylov workspace and half the bytes Gram-Schmidt moves; convergence only on a recomputed true residual
     ksp_single_floor=1e-7,  # theta of ksp_basis_single, in (2^-24, 1): a restart cycle ends once its recurrence residual has fallen
                             # to theta times the true residual it started from (check_ksp_basis_options)
+    ksp_reorth="never",     # FGMRES, fp64 bases: a second classical Gram-Schmidt pass (CGS2) per iteration -- "never" | "ifneeded" (when
+                            # the first pass left less than ksp_reorth_eta of the vector's length) | "always"; decided and predicated
+                            # on the device, no further host wait (ksp_gmres_cgs_refinement_type; check_ksp_reorth_options)
+    ksp_reorth_eta=2.0**-0.5,   # eta of "ifneeded", in (0, 1): refine when ||w - V h|| < eta ||w|| (the DGKS / Rutishauser value)
     snes_rtol=1e-8, snes_atol=1e-50, snes_stol=1e-8, snes_max_it=15,
     amg_omega=0.9,          # damped-Jacobi weight (round 3: 0.8 -> 0.9 buys 3 % fewer Krylov iterations on C4 at equal cycle cost, +4 % Newton steps/s
                             # over 80 time steps, measured twice; 0.88-0.9 is a plateau, 0.95 starts to fail solves, 1.0 loses 40 %; C1-C3 neutral)
@@ -381,6 +386,28 @@ def check_ksp_basis_options(o):
                                   "in fp32; ksp_basis_single is an option of the restarted FGMRES")
 
 
+_REORTH = {"never": 0, "ifneeded": 1, "always": 2}
+
+
+def check_ksp_reorth_options(o):
+    """ksp_reorth / ksp_reorth_eta (tp_options) against the range of eta and the configurations that have no fp64 basis."""
+    eta = o.get("ksp_reorth_eta", 2.0**-0.5)
+    # (checked whether or not the refinement is on, as ksp_single_floor is)
+    if not _is_number(eta) or not 0.0 < float(eta) < 1.0:
+        raise ValueError("ksp_reorth_eta = %r: a number in (0, 1)" % (eta,))
+    mode = o.get("ksp_reorth", "never")
+    if mode not in _REORTH:
+        raise ValueError("ksp_reorth = %r: 'never', 'ifneeded' or 'always'" % (mode,))
+    if mode == "never":
+        return
+    if o.get("ksp", "fgmres") == "bcgs":
+        raise NotImplementedError("ksp_reorth = %r with ksp = 'bcgs' (ksp_type fbcgs): BiCGStab keeps no Krylov basis to "
+                                  "orthogonalise against; ksp_reorth is an option of the restarted FGMRES" % (mode,))
+    if o.get("ksp_basis_single"):
+        raise NotImplementedError("ksp_reorth = %r with ksp_basis_single: a basis rounded to fp32 cannot be orthonormal below "
+                                  "2^-24, so a second Gram-Schmidt pass buys nothing; ksp_reorth needs the fp64 bases" % (mode,))
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -430,6 +457,7 @@ class HipEngine:
         check_amg_line_options(self.opts, nranks)
         check_amg_gs_options(self.opts, nranks)
         check_ksp_basis_options(self.opts)
+        check_ksp_reorth_options(self.opts)
         check_linesearch_options(self.opts)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
@@ -484,8 +512,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        # (the line-search fields stand in the middle of the struct: they are set by name, everything else in declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith("ls_")]
+        # (the line-search and refinement fields stand in the middle of the struct: they are set by name, everything else in
+        # declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth"))]
         vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
@@ -498,7 +527,8 @@ class HipEngine:
                           int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
-        return tp_options(**dict(zip(rest, vals)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
+        return tp_options(**dict(zip(rest, vals)), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
+                          ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
                           ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
                           ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
                           ls_max_change=(C.c_double*3)(*[float(v) for v in (o.get("ls_max_change") or (0.0, 0.0, 0.0))]))
@@ -514,6 +544,7 @@ class HipEngine:
         check_amg_line_options({**self.opts, **kw}, self.nranks)
         check_amg_gs_options({**self.opts, **kw}, self.nranks)
         check_ksp_basis_options({**self.opts, **kw})
+        check_ksp_reorth_options({**self.opts, **kw})
         check_linesearch_options({**self.opts, **kw})
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
@@ -734,6 +765,26 @@ class HipEngine:
         out = (C.c_int64*6)()
         self._ck(self.lib.tp_ksp_basis_info(self.ctx, out))
         return dict(single=bool(out[0]), capacity=out[1], stride=out[2], staging=out[3], cycles=out[4], true_residuals=out[5])
+
+    def ksp_reorth_info(self):
+        """The Gram-Schmidt refinement of ksp_reorth (tp_ksp_reorth_info): the mode in effect, the orthogonalisation steps since
+        the engine was created, and the second passes executed / enqueued but skipped by the device flag."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_ksp_reorth_info(self.ctx, out))
+        return dict(mode=("never", "ifneeded", "always")[out[0]], steps=out[1], refined=out[2], skipped=out[3])
+
+    def orth_step(self, prefix, k, w, mode="never", eta=2.0**-0.5):
+        """One Gram-Schmidt step of the outer FGMRES on user vectors (tp_vec_orth_step): w is orthogonalised in place against the
+        first k vectors of batch `prefix` (which must hold them already: vec_batch); returns (h[0..k), final ||w||^2, whether
+        the second pass ran)."""
+        if mode not in _REORTH:
+            raise ValueError("mode = %r: 'never', 'ifneeded' or 'always'" % (mode,))
+        if prefix + str(int(k) - 1) not in self._vec_ids:
+            raise EngineError("batch %r holds fewer than %d vectors" % (prefix, k))
+        h, n2, ran = np.zeros(int(k)), C.c_double(), C.c_int32()
+        self._ck(self.lib.tp_vec_orth_step(self.ctx, self._vec_ids[prefix + "0"], int(k), self.vec(w), _REORTH[mode], C.c_double(float(eta)),
+                                           _dptr(h), C.byref(n2), C.byref(ran)))
+        return h, n2.value, bool(ran.value)
 
     # compact fp32 vector batches: the kernels of ksp_basis_single on their own (tp_fvec_*)
     def fvec_batch(self, name, n):

@@ -10,6 +10,9 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
      snes_linesearch_maxstep, snes_linesearch_minlambda (absolute here) -> ls_order, ls_alpha, ls_max_it, ls_maxstep,
      ls_minlambda; any of them without bt raises.  l2 and cp are not implemented
   ksp_type fgmres|gmres (right preconditioning), ksp_rtol/atol/max_it, ksp_gmres_restart
+  ksp_gmres_cgs_refinement_type refine_never (PETSc's and this build's default) | refine_ifneeded | refine_always -> engine key
+     ksp_reorth = "never" | "ifneeded" | "always" (a second classical Gram-Schmidt pass, decided on the device; eta of the
+     ifneeded rule is the build key ksp_reorth_eta).  FGMRES with fp64 bases only.  ksp_gmres_modifiedgramschmidt is not consumed
   ksp_type fbcgs | bcgs + ksp_pc_side right: right-preconditioned BiCGStab (engine key ksp = "bcgs"); ksp_gmres_restart is
      consumed and has no effect on it
   pc_type composite, pc_composite_type multiplicative, pc_composite_pcs "python,bjacobi"
@@ -25,7 +28,7 @@ Defaults the reference inherits silently from Firedrake/PETSc are fixed here exp
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
 ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
 Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol, linesearch,
-ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+ksp_reorth, ksp_reorth_eta, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -43,6 +46,7 @@ _SCHUR_WHY = ("an iterative solver on the Schur split is not implemented: PETSc 
               "the (p,T) system solver of pc_cptramg) can be an inner iteration")
 _ADDITIVE_WHY = ("an iterative solver on the temperature block of the additive split is not implemented: only the pressure "
                  "solver K(A00) is wired to the inner iteration")
+_CGS_REFINE = {"refine_never": "never", "refine_ifneeded": "ifneeded", "refine_always": "always"}
 _S1_MAXK = 32              # GMRES(k) without restart: k basis vectors of the stage-1 block are stored
 
 
@@ -155,11 +159,13 @@ def _check_ilu_single(o):
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import check_amg_gs_options, check_amg_line_options, check_ksp_basis_options, check_linesearch_options
+    from .engine import (check_amg_gs_options, check_amg_line_options, check_ksp_basis_options, check_ksp_reorth_options,
+                         check_linesearch_options)
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_amg_gs_options(o, exc=NotImplementedError)
     check_ksp_basis_options(o)
+    check_ksp_reorth_options(o)
     check_linesearch_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
@@ -226,7 +232,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     used = set()
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
-                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor",
+                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
                   "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
     for k in build_keys:
         if k in sp:
@@ -264,6 +270,13 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     # outer Krylov method of the engine: restarted FGMRES, or BiCGStab (under which ksp_gmres_restart is consumed below and
     # has no effect: the newton_krylov dicts carry it)
     o["ksp"] = "bcgs" if ksp in ("fbcgs", "bcgs") else "fgmres"
+    # Gram-Schmidt refinement of the outer GMRES (PETSc: KSPGMRESSetCGSRefinementType)
+    ref = _take(sp, used, "ksp_gmres_cgs_refinement_type", tuple(_CGS_REFINE))
+    if ref is not None:
+        if "ksp_reorth" in solver_parameters and o["ksp_reorth"] != _CGS_REFINE[ref]:
+            raise ValueError("the Gram-Schmidt refinement is configured twice and differently: ksp_reorth = %r, "
+                             "ksp_gmres_cgs_refinement_type = %r" % (o["ksp_reorth"], ref))
+        o["ksp_reorth"] = _CGS_REFINE[ref]
     for k_src, k_dst in (("ksp_rtol", "ksp_rtol"), ("ksp_atol", "ksp_atol"), ("ksp_max_it", "ksp_max_it"),
                          ("ksp_gmres_restart", "ksp_restart"), ("snes_max_it", "snes_max_it"),
                          ("snes_rtol", "snes_rtol"), ("snes_atol", "snes_atol"), ("snes_stol", "snes_stol")):
