@@ -107,6 +107,16 @@ typedef struct tp_options {
                                 take 4 steps of skew per axis-2 plane and 2 per axis-1 line instead of 1 and 1 */
     int32_t fs_additive;     /* pc_kind 2: 1 = PCFIELDSPLIT additive on (p,T) -- y_p = V(A_pp) x_p, y_T = V(A_TT) x_T, no coupling
                                 (pc_fieldsplit_diag, singlephase.py:371-375) -- instead of Schur FULL */
+    /* Order of the composite's stages (pc_composite_pcs).  NOTE for ABI readers: the field stands HERE, between
+     * fs_additive and ksp_reorth (the tests of earlier options pin the order of every field from ksp_reorth on).  It fills the four
+     * bytes of padding that preceded ksp_reorth_eta: ksp_reorth moved by 4 bytes, no other field moved and sizeof(tp_options) is
+     * unchanged; recompile callers.
+     * PCCOMPOSITE multiplicative over a sequence s_1 .. s_m of the two stages S (CPR / CPTR / the system V-cycle) and I (bjacobi +
+     * block-ILU): y = 0; for k = 1..m: r = x - J y (k = 1: r = x), y += B_{s_k} r.  The residual is taken over all b rows and all b
+     * columns of y.  B_I r is the configured stage-2 solve (one factorisation per set-up, shared by both I stages of 2); B_S r is
+     * what tp_stage1_apply computes for r: as a later stage it ADDS into y's primary fields and leaves the secondary ones alone.
+     * Refused, naming both options, with pc_kind 2 (no second stage) and 4 (no first stage) unless 0. */
+    int32_t pc_order;        /* 0 SI (default: the launch sequence is unchanged), 1 IS, 2 ISI, 3 SIS */
     /* Gram-Schmidt refinement of the outer FGMRES (ksp_gmres_cgs_refinement_type).  NOTE for ABI readers: the
      * two fields stand HERE, between fs_additive and ilu_whole, not at the struct's tail (the tests of earlier options pin the
      * order of every field from ilu_whole on): every field from ilu_whole on moved and sizeof(tp_options) grew; recompile callers.
@@ -308,6 +318,11 @@ int tp_stage1_update(tp_ctx *ctx);                         /* CPRStage1PC/CPTRSt
 int tp_stage1_apply(tp_ctx *ctx, int32_t x, int32_t y);    /* ....apply (preconditioners.py:881,1550) */
 int tp_ilu0_factor(tp_ctx *ctx);                           /* sub_1: bjacobi + ILU(0) numeric factorisation (singlephase.py:348-349) */
 int tp_ilu0_solve(tp_ctx *ctx, int32_t x, int32_t y);
+/* The stage-1 right-hand side of a LATER S stage of the composite (tp_options.pc_order), one kernel: for every primary field q
+ * out_q = [x - J y]_q - sum_s d_{q,s} [x - J y]_s, with the decoupling coefficients d of the last tp_pc_setup (none for decoupling
+ * "No").  y is read in all b fields (several slabs: its halo planes are exchanged first); only the npri primary planes of `out`
+ * are written, owned cells only.  x, y and out must be three different vectors.  pc_kind 0, 1 or 3. */
+int tp_stage_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);
 /* the stage-2 layout that was built from the options (read-only; sets the layout up if no factorisation has yet):
  * out = {B0, B1, B2, number of bjacobi blocks, number of tiles, block-local tile-diagonals, most tiles in one launch,
  * launches per sweep direction}.  One tile per block (the default): B = the tile, blocks = tiles, 1, tiles, 1. */
@@ -372,7 +387,9 @@ int tp_ls_trial(tp_ctx *ctx, int32_t u0, int32_t dx, double lambda, int32_t out)
  * of `reps` launches of one hot kernel.  which: 0 block SpMV, 1 ILU solve, 2 AMG V-cycle (pressure),
  * 3 assembly (residual+Jacobian), 4 full pc_apply, 5 pc_setup, 6 ILU factorisation, 7 one classical Gram-Schmidt
  * step against 16 basis vectors (VecMDot + VecMAXPY + VecNorm; needs a Krylov basis from an earlier solve), 8 the same step
- * against 16 vectors of the fp32 basis (needs one from an earlier ksp_basis_single solve). */
+ * against 16 vectors of the fp32 basis (needs one from an earlier ksp_basis_single solve), 9 the stage-1 right-hand side of a later
+ * S stage in one launch (tp_stage_rhs), 10 the pair of launches it replaces (block residual over all b rows and columns + the
+ * decoupled right-hand side per primary field), 11 that block residual alone.  4 times the pc_order in force. */
 int tp_time_kernel(tp_ctx *ctx, int32_t which, int32_t reps, double *ms_avg);
 int tp_amg_info(tp_ctx *ctx, int32_t which, int32_t *nlevels, double *op_complexity);
 /* level at which hierarchy `which` ends with relaxation only (amg_dom_tau), -1: full V-cycle; ratio0 = the

@@ -1,0 +1,216 @@
+"""Stage orders of the composite preconditioner (pc_order): what can be checked without a GPU -- the option
+plumbing through every layer, the parsing of pc_composite_pcs by position, the rejections, and the numpy reference
+tests/pc_order_ref.py on the small single-phase system the GPU tests use (tests/test_gpu_pc_order.py)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import pc_order_ref as PR
+from thermalporous_amd.engine import (API_SYMBOLS, DEFAULT_OPTS, HipEngine, check_pc_order_options, tp_options)
+from thermalporous_amd.solver_options import engine_options
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "thermalporous_hip.h")
+CODES = {"SI": 0, "IS": 1, "ISI": 2, "SIS": 3}
+
+
+# ---- options ------------------------------------------------------------------------------------------------------------------
+def test_defaults_struct_field_and_export():
+    assert DEFAULT_OPTS["pc_order"] == "SI"
+    names = [f[0] for f in tp_options._fields_]
+    assert dict(tp_options._fields_)["pc_order"] is C.c_int32
+    i = names.index("pc_order")
+    assert names[i - 1] == "fs_additive" and names[i + 1] == "ksp_reorth"
+    assert "tp_stage_rhs" in API_SYMBOLS
+    text = open(HEADER).read()
+    assert "int tp_stage_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);" in text
+    assert "int32_t pc_order;" in text
+    base = dict(DEFAULT_OPTS, ilu_tile=(1 << 30, 8, 8))
+    base.pop("pc_order")
+    a = HipEngine._make_options(base)                       # without the key
+    assert a.pc_order == 0
+    for order, code in CODES.items():
+        b = HipEngine._make_options(dict(base, pc_order=order))
+        assert b.pc_order == code
+        # every other field is what it was without the key
+        assert all(bytes(C.string_at(C.addressof(a) + getattr(tp_options, n).offset, getattr(tp_options, n).size)) ==
+                   bytes(C.string_at(C.addressof(b) + getattr(tp_options, n).offset, getattr(tp_options, n).size))
+                   for n in names if n != "pc_order")
+
+
+def test_unknown_order_raises():
+    for bad in ("SS", "II", "SISI", "", "si", 1, None):
+        with pytest.raises(ValueError, match="pc_order"):
+            check_pc_order_options(dict(DEFAULT_OPTS, pc_order=bad))
+
+
+@pytest.mark.parametrize("order", ["IS", "ISI", "SIS"])
+def test_refused_combinations_name_both(order):
+    with pytest.raises(NotImplementedError, match=r"pc_order.*fieldsplit_cd"):
+        check_pc_order_options(dict(DEFAULT_OPTS, pc="fieldsplit_cd", pc_order=order))
+    with pytest.raises(NotImplementedError, match=r"pc_order.*bilu"):
+        check_pc_order_options(dict(DEFAULT_OPTS, pc="bilu", pc_order=order))
+    # the default order goes with both, and every order with the composites
+    check_pc_order_options(dict(DEFAULT_OPTS, pc="fieldsplit_cd"))
+    check_pc_order_options(dict(DEFAULT_OPTS, pc="bilu"))
+    for pc in ("cpr", "cptr", "cptramg"):
+        check_pc_order_options(dict(DEFAULT_OPTS, pc=pc, pc_order=order))
+    # through the PETSc dicts, with the build key
+    with pytest.raises(NotImplementedError, match=r"pc_order.*bilu"):
+        engine_options({"snes_type": "newtonls", "ksp_type": "fgmres", "mat_type": "aij", "pc_type": "bjacobi", "sub_pc_type": "ilu",
+                        "pc_order": order}, "Two-phase")
+
+
+# ---- pc_composite_pcs by position -----------------------------------------------------------------------------------------------
+V = {"ksp_type": "preonly", "pc_type": "hypre", "pc_hypre_type": "boomeramg", "pc_hypre_boomeramg_max_iter": 1}
+BASE = {"snes_type": "newtonls", "ksp_type": "fgmres", "mat_type": "aij", "pc_type": "composite", "pc_composite_type": "multiplicative"}
+
+
+def s_python_cpr(k, decoup=None):
+    d = {"sub_%d_pc_python_type" % k: "thermalporous.preconditioners.CPRStage1PC", "sub_%d_cpr_stage1" % k: dict(V)}
+    if decoup:
+        d["sub_%d_cpr_decoup" % k] = decoup
+    return d
+
+
+def s_python_cptr(k):
+    p = "sub_%d_" % k
+    return {p + "pc_python_type": "thermalporous.preconditioners.CPTRStage1PC", p + "cpr_stage1_pc_type": "fieldsplit",
+            p + "cpr_stage1_pc_fieldsplit_type": "schur", p + "cpr_stage1_pc_fieldsplit_schur_fact_type": "FULL",
+            p + "cpr_stage1_fieldsplit_0": dict(V), p + "cpr_stage1_fieldsplit_1_ksp_type": "preonly",
+            p + "cpr_stage1_fieldsplit_1_pc_type": "python",
+            p + "cpr_stage1_fieldsplit_1_pc_python_type": "thermalporous.preconditioners.ConvDiffSchurTwoPhasesPC",
+            p + "cpr_stage1_fieldsplit_1_schur": dict(V)}
+
+
+def s_fieldsplit_cpr(k, fields=("0", "1")):
+    p = "sub_%d_" % k
+    return {p + "pc_fieldsplit_type": "additive", p + "pc_fieldsplit_0_fields": fields[0], p + "pc_fieldsplit_1_fields": fields[1],
+            p + "fieldsplit_0": dict(V), p + "fieldsplit_1_ksp_type": "gmres", p + "fieldsplit_1_ksp_max_it": 0,
+            p + "fieldsplit_1_pc_type": "none"}
+
+
+def s_fieldsplit_cptr(k):
+    p = "sub_%d_" % k
+    return {p + "pc_fieldsplit_type": "additive", p + "pc_fieldsplit_0_fields": "0,1", p + "pc_fieldsplit_1_fields": "2",
+            p + "fieldsplit_0_pc_type": "fieldsplit", p + "fieldsplit_0_pc_fieldsplit_type": "schur",
+            p + "fieldsplit_0_pc_fieldsplit_schur_fact_type": "FULL", p + "fieldsplit_0_fieldsplit_0": dict(V),
+            p + "fieldsplit_0_fieldsplit_1_ksp_type": "preonly", p + "fieldsplit_0_fieldsplit_1_pc_type": "python",
+            p + "fieldsplit_0_fieldsplit_1_pc_python_type": "thermalporous.preconditioners.ConvDiffSchurTwoPhasesPC",
+            p + "fieldsplit_0_fieldsplit_1_schur": dict(V),
+            p + "fieldsplit_1_ksp_type": "gmres", p + "fieldsplit_1_ksp_max_it": 0, p + "fieldsplit_1_pc_type": "none"}
+
+
+def i_stage(k, levels=0, blocks=None):
+    d = {"sub_%d_sub_pc_type" % k: "ilu", "sub_%d_sub_pc_factor_levels" % k: levels}
+    if blocks is not None:
+        d["sub_%d_pc_bjacobi_blocks" % k] = blocks
+    return d
+
+
+def composite(x_name, order, s_entry, trailing=False, **ikw):
+    """The dict of `order` with the S entries built by s_entry(position) and named x_name."""
+    names = [x_name if s == "S" else "bjacobi" for s in order]
+    d = dict(BASE, pc_composite_pcs=",".join(names) + ("," if trailing else ""))
+    for k, s in enumerate(order):
+        d.update(s_entry(k) if s == "S" else i_stage(k, **ikw))
+    return d
+
+
+SHAPES = [("python", s_python_cpr, "Single phase", "cpr"), ("fieldsplit", s_fieldsplit_cpr, "Single phase", "cpr"),
+          ("python", s_python_cptr, "Two-phase", "cptr"), ("fieldsplit", s_fieldsplit_cptr, "Two-phase", "cptr")]
+
+
+@pytest.mark.parametrize("x_name,s_entry,model,pc", SHAPES, ids=["py_cpr_1ph", "fs_cpr_1ph", "py_cptr_2ph", "fs_cptr_2ph"])
+@pytest.mark.parametrize("order", PR.ORDERS)
+@pytest.mark.parametrize("trailing", [False, True], ids=["plain", "trailing_comma"])
+def test_composite_pcs_maps_onto_the_order(x_name, s_entry, model, pc, order, trailing):
+    o = engine_options(composite(x_name, order, s_entry, trailing), model)
+    assert (o["pc_order"], o["pc"], o["ilu_levels"], o["decoup"]) == (order, pc, 0, "No")
+    # the same dict in the presets' order gives the same options but for the order
+    ref = engine_options(composite(x_name, "SI", s_entry), model)
+    assert {k: v for k, v in o.items() if k != "pc_order"} == {k: v for k, v in ref.items() if k != "pc_order"}
+
+
+def test_stage_keys_are_parsed_by_position():
+    # the reference's spelling of ILU -> AMG -> ILU, blanks and the trailing comma included; ILU(1) and a block count on the I entries
+    d = composite("fieldsplit", "ISI", s_fieldsplit_cpr, levels=1, blocks=4)
+    d["pc_composite_pcs"] = "bjacobi, fieldsplit ,bjacobi,"
+    o = engine_options(d, "Two-phase")
+    assert (o["pc_order"], o["pc"], o["ilu_levels"], o["bjacobi_blocks"]) == ("ISI", "cpr", 1, 4)
+    # a python S entry at position 1 carries its own decoupling key
+    o = engine_options(composite("python", "IS", lambda k: s_python_cpr(k, "QI")), "Single phase")
+    assert (o["pc_order"], o["decoup"]) == ("IS", "QI")
+    # an inner solve spelled under the S entry's prefix, wherever it stands
+    d = composite("python", "SIS", s_python_cpr)
+    for k in (0, 2):
+        d["sub_%d_cpr_stage1" % k] = dict(V, pc_hypre_boomeramg_max_iter=3)
+    o = engine_options(d, "Single phase")
+    assert (o["pc_order"], o["s1_ksp"], o["s1_max_it"]) == ("SIS", "richardson", 3)
+    # every key is consumed or rejected: a stray key of an entry, and a key of an entry that does not exist
+    d = composite("python", "IS", s_python_cpr)
+    d["sub_1_bogus"] = 1
+    with pytest.raises(KeyError, match="bogus"):
+        engine_options(d, "Single phase")
+    d = composite("python", "IS", s_python_cpr)
+    d["sub_2_sub_pc_type"] = "ilu"
+    with pytest.raises(KeyError, match="sub_2_sub_pc_type"):
+        engine_options(d, "Single phase")
+    # the build key re-orders a dict in the presets' order; against a dict that spells another order it must agree
+    assert engine_options(dict(composite("python", "SI", s_python_cpr), pc_order="ISI"), "Single phase")["pc_order"] == "ISI"
+    assert engine_options(dict(composite("python", "IS", s_python_cpr), pc_order="IS"), "Single phase")["pc_order"] == "IS"
+    with pytest.raises(ValueError, match="twice"):
+        engine_options(dict(composite("python", "IS", s_python_cpr), pc_order="SIS"), "Single phase")
+
+
+def test_differing_duplicate_stages_raise_with_the_keys():
+    d = composite("fieldsplit", "ISI", s_fieldsplit_cpr)
+    d["sub_2_sub_pc_factor_levels"] = 1
+    with pytest.raises(NotImplementedError, match=r"bjacobi entries differ.*sub_0_sub_pc_factor_levels / sub_2_sub_pc_factor_levels"):
+        engine_options(d, "Two-phase")
+    d = composite("fieldsplit", "ISI", s_fieldsplit_cpr)
+    d["sub_2_pc_bjacobi_blocks"] = 2
+    with pytest.raises(NotImplementedError, match=r"differ.*pc_bjacobi_blocks"):
+        engine_options(d, "Two-phase")
+    d = composite("python", "SIS", s_python_cpr)
+    d["sub_2_cpr_decoup"] = "QI"
+    with pytest.raises(NotImplementedError, match=r"python entries differ.*sub_0_cpr_decoup / sub_2_cpr_decoup"):
+        engine_options(d, "Single phase")
+    # an unset fill level is PETSc's default 0: the same as an explicit 0
+    d = composite("fieldsplit", "ISI", s_fieldsplit_cpr)
+    del d["sub_2_sub_pc_factor_levels"]
+    assert engine_options(d, "Two-phase")["pc_order"] == "ISI"
+    # other sequences
+    for pcs in ("bjacobi,bjacobi", "python,python", "python,bjacobi,python,bjacobi", "python,bjacobi,fieldsplit", "bjacobi,lu", "bjacobi"):
+        with pytest.raises(NotImplementedError, match="pc_composite_pcs"):
+            engine_options(dict(BASE, pc_composite_pcs=pcs), "Two-phase")
+
+
+@pytest.mark.parametrize("first", ["fieldsplit", "python"])
+def test_temperature_only_third_stage_is_named(first):
+    d = dict(BASE, pc_composite_pcs=first + ",bjacobi,fieldsplit")
+    d.update(s_fieldsplit_cpr(0, ("0", "1,2")) if first == "fieldsplit" else s_python_cpr(0, "TI"))
+    d.update(i_stage(1))
+    d.update(s_fieldsplit_cpr(2, ("1", "0,2")))
+    with pytest.raises(NotImplementedError, match=r"temperature-only stage.*not implemented"):
+        engine_options(d, "Two-phase")
+
+
+# ---- the reference ----------------------------------------------------------------------------------------------------------
+def test_oracle_sequences_converge_with_the_recorded_counts():
+    """The 14 x 19 single-phase system: apply_seq("SI") IS TwoStagePC.apply, and the oracle FGMRES converges under every order
+    after 4, 4, 3, 3 iterations."""
+    name, builder, kw, opts = PR.PARITY[2]
+    spec, u0, u, o, J, F = PR.oracle_system(builder, kw, opts)
+    x = np.random.default_rng(11).standard_normal(J.shape[1:2] + J.shape[3:])
+    PR.check_si_is_apply(o.pc, x)
+    got = []
+    for order in PR.ORDERS:
+        d, its, reason = PR.fgmres_seq(o, J, F, order)
+        assert reason == 2, order
+        got.append(its)
+    assert tuple(got) == PR.COUNTS[name] == (4, 4, 3, 3)
+    # the right-hand side of a later S stage is what stage1 forms from the residual: with y = 0 the decoupled x itself
+    assert np.array_equal(PR.stage_rhs_ref(o.pc, x, np.zeros_like(x)), x[:1])

@@ -314,6 +314,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
+    pc_order_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     amg_gs_check_options(*opt, grid->nranks);
@@ -371,6 +372,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     bcgs_check_options(*opt);
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
+    pc_order_check_options(*opt);
     ls_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     amg_gs_check_options(*opt, c->grid.nranks);
@@ -832,6 +834,16 @@ int tp_ilu0_solve(tp_ctx *c, int32_t x, int32_t y) {
     TP_API_END
 }
 
+int tp_stage_rhs(tp_ctx *c, int32_t x, int32_t y, int32_t out) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && c->pc_ready, "tp_stage_rhs: preconditioner not set up (the decoupling coefficients are those of tp_pc_setup)");
+    TP_REQUIRE(c->opt.pc_kind == 0 || c->opt.pc_kind == 1 || c->opt.pc_kind == 3, "tp_stage_rhs: pc_kind 0, 1 or 3 (a first stage with a second one behind it)");
+    TP_REQUIRE(x != y && x != out && y != out, "tp_stage_rhs: x, y and out must differ");
+    if (c->dist) halo_exchange(c, c->g, vec_of(c, y).p, c->b, c->g.ntot);
+    stage_rhs(c, vec_of(c, x).p, vec_of(c, y).p, vec_of(c, out).p);
+    TP_API_END
+}
+
 int tp_amg_setup(tp_ctx *c, int32_t which) {
     TP_API_BEGIN
     (void)which;
@@ -982,7 +994,8 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
     TP_REQUIRE(reps > 0 && ms_avg, "bad arguments");
     ensure_work(c);          // (w3 needs three planes even when b == 2: tp_solver.hip)
     if (which != 3) TP_REQUIRE(c->jac_ready, "Jacobian not assembled");
-    if (which == 1 || which == 2 || which == 4) TP_REQUIRE(c->pc_ready, "preconditioner not set up");
+    if (which == 1 || which == 2 || which == 4 || which == 9 || which == 10) TP_REQUIRE(c->pc_ready, "preconditioner not set up");
+    if (which == 9 || which == 10) TP_REQUIRE(c->opt.pc_kind == 0 || c->opt.pc_kind == 1 || c->opt.pc_kind == 3, "pc_kind 0, 1 or 3");
     auto run = [&]() {
         switch (which) {
             case 0: spmv_block(c, c->J.p, c->R.p, c->w2.p); break;
@@ -1009,6 +1022,12 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
                 orthogonalize_s(c, c->b, c->Vs.p, basis_stride(c), 16, c->w2.p, hh.data());
                 break;
             }
+            case 9: stage_rhs(c, c->R.p, c->dx.p, c->w3.p); break;      // (dx: whatever the last application left; the time does not depend on it)
+            case 10:
+                resid_block_cols(c, c->J.p, c->R.p, c->dx.p, c->b, c->w1.p);
+                for (int q = 0; q < npri_of(c->opt); ++q) stage1_rhs(c, c->w1.p, q, c->w3.p + (long)q * c->g.ntot);
+                break;
+            case 11: resid_block_cols(c, c->J.p, c->R.p, c->dx.p, c->b, c->w1.p); break;
             default: throw Error("unknown kernel id");
         }
     };

@@ -457,6 +457,7 @@ void orthogonalize_wait(tp_ctx *c, int k, double *host_out);
 void orthogonalize_mode(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, int mode, double eta, double *host_out,
                         int *refined);
 void reorth_check_options(const tp_options &o);
+void pc_order_check_options(const tp_options &o);
 void vec_scale_dev_norm(tp_ctx *c, int nf, const double *n2_dev, double *x);   // x *= 1/sqrt(*n2_dev) (owned)
 // fp32 Krylov bases (tp_options.ksp_basis_single; tp_linalg.hip): Vs points at compact float vectors `vstride` entries apart
 long basis_stride(const tp_ctx *c);                                              // b*nown rounded up to 64 entries
@@ -482,6 +483,7 @@ void decouple(tp_ctx *c);
 void selfp_build(tp_ctx *c);                                                           // S7, w/diag(Sp) into spbuf
 void selfp_post(tp_ctx *c, const double *b, const double *x, double *y);                  // y = x + w D^-1 (b - Sp x)
 void stage1_rhs(tp_ctx *c, const double *x, int q, double *out);                        // out = x_q - d_q x_s
+void stage_rhs(tp_ctx *c, const double *x, const double *y, double *out);                // out_q = [x - J y]_q - d_q [x - J y]_s, q < npri
 // ILU
 void ilu_setup(tp_ctx *c);
 void ilu_factor(tp_ctx *c);

@@ -322,9 +322,10 @@ void inner_check_options(const tp_options &o) {
 int vcycles_per_apply(const tp_ctx *c) {
     if (c->opt.pc_kind == 4) return 0;
     const int extra = c->opt.s1_ksp ? c->opt.s1_max_it - 1 : 0;      // per inner solve
-    if (c->opt.fs_additive) return 2 + extra;
-    if (schur_of(c->opt)) return 3 + 2 * extra;                       // K(A00) is applied twice
-    return 1 + extra;
+    const int stages = c->opt.pc_order == 3 ? 2 : 1;                  // S stages of the order (pc_order 3 = SIS)
+    if (c->opt.fs_additive) return stages * (2 + extra);
+    if (schur_of(c->opt)) return stages * (3 + 2 * extra);            // K(A00) is applied twice
+    return stages * (1 + extra);
 }
 
 void inner_ensure(tp_ctx *c) {

@@ -1159,6 +1159,78 @@ void resid_block_cols(tp_ctx *c, const double *J, const double *x, const double 
     TP_HIP(hipGetLastError());
 }
 
+// ---- stage-1 right-hand side of a LATER S stage of the composite (tp_options.pc_order) ----------------
+// out_q = [x - J y]_q - sum_s d_{q,s} [x - J y]_s for the NPRI primary fields q, in one launch: the block residual restricted to
+// the rows stage 1 reads, with the decoupling of k_stage1_rhs / k_stage1_rhs_temp applied in registers.  y is read in all B
+// columns.  DEC 0: decoupling No, the NPRI primary rows; DEC 1: QI / TI, the primary rows and the last row (s = B - 1);
+// DEC 2: QI_temp / TI_temp (B = 3, NPRI = 1), the pressure row and both secondary rows.  Indexing, plane order and the
+// per-slot batch of loads are those of k_spmv_block: every Jacobian plane that is read is streamed exactly once, coalesced.
+template <int B, int NS, int NPRI, int DEC>
+__global__ __launch_bounds__(256) void k_stage_rhs(GridDev g, const double *__restrict__ J, const double *__restrict__ x,
+                                                   const double *__restrict__ y, const double *__restrict__ d,
+                                                   double *__restrict__ out) {
+    static_assert(NPRI + DEC <= B && (DEC < 2 || NPRI == 1), "rows of the stage-1 right-hand side");
+    constexpr int NR = NPRI + DEC;                     // Jacobian rows read: the primary ones first, then the secondary ones
+    const long tid = xcd_tid();
+    if (tid >= g.nown) return;
+    const long c = g.np + tid, nt = g.ntot;
+    const long off[7] = {0, -1, 1, -(long)g.n0, (long)g.n0, -g.np, g.np};
+    double acc[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) acc[i] = 0.0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double yv[B];
+#pragma unroll
+        for (int k = 0; k < B; ++k) yv[k] = y[(long)k * nt + c + off[s]];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int r = (DEC == 1 && i == NPRI) ? B - 1 : i;
+#pragma unroll
+            for (int k = 0; k < B; ++k) acc[i] += J[((long)(s * B + r) * B + k) * nt + c] * yv[k];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int r = (DEC == 1 && i == NPRI) ? B - 1 : i;
+        acc[i] = x[(long)r * nt + c] - acc[i];         // [x - J y]_r
+    }
+#pragma unroll
+    for (int q = 0; q < NPRI; ++q) {
+        double v = acc[q];
+        if constexpr (DEC == 1) v -= d[(long)q * nt + c] * acc[NPRI];
+        if constexpr (DEC == 2) v = v - d[c] * acc[1] - d[nt + c] * acc[2];
+        out[(long)q * nt + c] = v;
+    }
+}
+
+// out[0 .. npri) = the stage-1 right-hand sides of x - J y (all b columns of y: its halo planes must be live); `out` holds
+// npri planes and aliases neither x nor y
+void stage_rhs(tp_ctx *c, const double *x, const double *y, double *out) {
+    const GridDev &g = c->g;
+    const dim3 gr = xcd_grid(g.nown), bl(256);
+    const bool d3 = g.gn2 > 1;
+    const int npri = npri_of(c->opt), dec = c->opt.decoup == 0 ? 0 : c->opt.decoup >= 3 ? 2 : 1;
+    const double *d = c->dcoef.p;
+    TP_REQUIRE(dec == 0 || d, "stage_rhs: no decoupling coefficients (pc_setup)");
+#define SR(B, NP, DC)                                                                                                   \
+    do {                                                                                                                \
+        if (d3) hipLaunchKernelGGL((k_stage_rhs<B, 7, NP, DC>), gr, bl, 0, c->stream, g, c->J.p, x, y, d, out);         \
+        else    hipLaunchKernelGGL((k_stage_rhs<B, 5, NP, DC>), gr, bl, 0, c->stream, g, c->J.p, x, y, d, out);         \
+    } while (0)
+    if (c->b == 3 && npri == 2) {
+        TP_REQUIRE(dec < 2, "stage_rhs: the _temp decouplings are pressure-only (pc_cpr)");
+        if (dec) SR(3, 2, 1); else SR(3, 2, 0);
+    } else if (c->b == 3) {
+        if (dec == 2) SR(3, 1, 2); else if (dec) SR(3, 1, 1); else SR(3, 1, 0);
+    } else {
+        TP_REQUIRE(npri == 1 && dec < 2, "stage_rhs: single-phase systems have one primary and one secondary field");
+        if (dec) SR(2, 1, 1); else SR(2, 1, 0);
+    }
+#undef SR
+    TP_HIP(hipGetLastError());
+}
+
 // ---- scalar stencil: y = z + alpha * A x ----------------------------------------------------------
 __global__ __launch_bounds__(256) void k_spmv_scalar(GridDev g, Stencil A, const double *__restrict__ x,
                                                      double *__restrict__ y, double alpha,

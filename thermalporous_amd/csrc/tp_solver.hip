@@ -72,7 +72,7 @@ static void refresh_pc_signature(tp_ctx *c) {
     const uintptr_t sig[] = {(uintptr_t)c->opA00.base, (uintptr_t)c->opA01.base, (uintptr_t)c->opA10.base,
                              (uintptr_t)c->Sm.p, (uintptr_t)c->ilu.fwd.p, (uintptr_t)c->ilu.fwd32.p, (uintptr_t)c->ilu.fwdp.p, (uintptr_t)c->amg_p, (uintptr_t)c->amg_T, (uintptr_t)c->bamg,
                              (uintptr_t)c->w1.p, (uintptr_t)c->w3.p, (uintptr_t)c->w4.p, (uintptr_t)c->dcoef.p, (uintptr_t)c->spbuf.p,
-                             (uintptr_t)c->opt.amg_nu, (uintptr_t)c->opt.pc_kind, (uintptr_t)c->opt.decoup,
+                             (uintptr_t)c->opt.amg_nu, (uintptr_t)c->opt.pc_kind, (uintptr_t)c->opt.pc_order, (uintptr_t)c->opt.decoup,
                              (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip, (uintptr_t)c->opt.amg_line_levels, (uintptr_t)c->opt.amg_gs_levels, (uintptr_t)c->opt.amg_gs_sweeps,
                              (uintptr_t)c->opt.s1_ksp, (uintptr_t)c->opt.s1_max_it, (uintptr_t)c->inner.V.p, (uintptr_t)c->inner.Z.p,
                              (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole};
@@ -306,6 +306,8 @@ static void stage1_sequence(tp_ctx *c, const Stage1Sys &s, const double *r0, con
     K00(t, y0);                                                             // y0 = K(A00) t
 }
 
+static void stage1_run(tp_ctx *c, const double *r0, const double *r1, double *y);
+
 // y = B1 x :  CPRStage1PC.apply (preconditioners.py:881-903) / CPTRStage1PC.apply (:1550-1567)
 void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
     const long nt = c->g.ntot;
@@ -325,6 +327,14 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
         stage1_rhs(c, x, 0, c->w3.p);              // r_p = x_p - (D_ps D_ss^-1) x_s
         if (npri == 2) stage1_rhs(c, x, 1, c->w3.p + nt);
     }
+    stage1_run(c, r0, r1, y);
+}
+
+// the stage-1 solver on prepared right-hand sides r0 (, r1): y_0 (, y_1) = K r; y holds npri planes of the slab.  Scratch: the third
+// plane of w3, w4 and (replicated hierarchy on several GPUs) gvec -- r and y may be anything else, the first two planes of w3 included
+static void stage1_run(tp_ctx *c, const double *r0, const double *r1, double *y) {
+    const long nt = c->g.ntot;
+    const int npri = npri_of(c->opt);
     // the system and its vectors: slab vectors, or the planes of gvec on the gathered global grid
     const bool gathered = stage1_replicated(c);
     const Stage1Sys s = stage1_system(c, gathered);
@@ -354,16 +364,58 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary) {
     }
 }
 
-// composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r
+// ---- the composite's stage orders (tp_options.pc_order) ------------------------------------------------
+void pc_order_check_options(const tp_options &o) {
+    TP_REQUIRE(o.pc_order >= 0 && o.pc_order <= 3, "pc_order must be 0 (SI), 1 (IS), 2 (ISI) or 3 (SIS)");
+    if (!o.pc_order) return;
+    TP_REQUIRE(o.pc_kind != 2, "pc_order other than 0 (SI) with pc_kind 2 (pc_fieldsplit_cd): that preconditioner has no second stage to order");
+    TP_REQUIRE(o.pc_kind != 4, "pc_order other than 0 (SI) with pc_kind 4 (pc_bilu): that preconditioner has no first stage to order");
+}
+
+// A later S stage: y_q += [B_S (x - J y)]_q on the primary fields q; y's secondary fields stay as they are.
+// Invariants (every supported order puts an I stage right before a later S stage):
+//  - the residual behind the right-hand side reads ALL b columns of y.  That is correct only because the I stage before wrote
+//    every field of y (ilu_solve writes all b fields, whatever nadd says about what it reads);
+//  - that I stage wrote owned cells only: on several slabs all b fields of y need live halo planes first;
+//  - scratch: the right-hand sides go to the first npri planes of w3 (where the decoupled first stage keeps them), stage1_run
+//    works in w3's third plane, w4 and gvec, and the stage's result e lands in the first npri planes of w1 -- free here, the
+//    residual the I stage solved for is dead once ilu_solve has returned.  None of them is x or y;
+//  - the accumulation covers owned cells: y's primary halo planes are stale afterwards (pc_stage_I_full exchanges them).
+static void pc_stage_S_later(tp_ctx *c, const double *x, double *y) {
+    const long nt = c->g.ntot;
+    const int npri = npri_of(c->opt);
+    if (c->dist) halo_exchange(c, c->g, y, c->b, nt);
+    stage_rhs(c, x, y, c->w3.p);                            // one launch: only the Jacobian rows stage 1 needs
+    stage1_run(c, c->w3.p, c->w3.p + nt, c->w1.p);
+    vec_axpy_owned(c, npri, 1.0, c->w1.p, y);               // y_q += e_q
+}
+// A later I stage behind a later S stage (ISI): y += B_I (x - J y) with all b columns of y -- every field is nonzero by now.
+// Several slabs: the S stage before changed the owned cells of the primary fields; the secondary halo planes are still those of
+// the exchange in front of that S stage.  w1 (the S stage's result, already added) is free again for the residual.
+static void pc_stage_I_full(tp_ctx *c, const double *x, double *y) {
+    if (c->dist) halo_exchange(c, c->g, y, npri_of(c->opt), c->g.ntot);
+    resid_block_cols(c, c->J.p, x, y, c->b, c->w1.p);
+    ilu_solve(c, c->w1.p, y, y, c->b);                      // y = y + M^-1 r, all fields of y read
+}
+
+// composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r  (pc_order 0 = SI; 1..3: the same two stages as IS, ISI, SIS)
 static void pc_apply_body(tp_ctx *c, const double *x, double *y) {
     if (c->opt.pc_kind == 4) { ilu_solve(c, x, y, nullptr, 0); return; }
     const int npri = npri_of(c->opt);
+    if (c->opt.pc_order == 1 || c->opt.pc_order == 2) {      // IS, ISI
+        ilu_solve(c, x, y, nullptr, 0);                      // y = B_I x: every field of y written, nothing of it read
+        pc_stage_S_later(c, x, y);
+        if (c->opt.pc_order == 2) pc_stage_I_full(c, x, y);
+        return;
+    }
     // (y's secondary fields are left untouched: the second stage below never reads them and overwrites them)
     stage1_apply(c, x, y, false);                 // multi-GPU, replicated stage 1: y comes back with live halo planes
     if (c->dist && !stage1_replicated(c)) halo_exchange(c, c->g, y, npri, c->g.ntot);       // (slab-distributed hierarchies return owned cells only)
     if (c->opt.pc_kind == 2) return;                          // pc_fieldsplit_cd: the Schur stage IS the preconditioner
     resid_block_cols(c, c->J.p, x, y, npri, c->w1.p);        // secondary fields of y are zero
     ilu_solve(c, c->w1.p, y, y, npri);                       // y = y + M^-1 r  (y's secondary fields are zero: not read)
+    // SIS: "y's secondary fields are never read" held while S was first only; the I stage above has now written every field
+    if (c->opt.pc_order == 3) pc_stage_S_later(c, x, y);
 }
 
 // ---- recording of pc_apply programs: one capture segment between two exchanges ------------------------------------------

@@ -46,7 +46,7 @@ class tp_options(C.Structure):
                 ("ilu_t1", C.c_int32), ("ilu_t2", C.c_int32), ("ilu_t0", C.c_int32),
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
-                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32),
+                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("pc_order", C.c_int32),
                 ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double), ("ilu_whole", C.c_int32),
                 ("amg_gs_levels", C.c_int32), ("amg_gs_sweeps", C.c_int32),
                 ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
@@ -75,10 +75,14 @@ API_SYMBOLS = (
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
+    "tp_stage_rhs",
 )
 
 DEFAULT_OPTS = dict(
     pc="cpr", decoup="No",
+    pc_order="SI",          # order of the composite's stages, S = the CPR / CPTR / system-AMG stage, I = bjacobi + block-ILU: "SI" (the
+                            # presets' order) | "IS" | "ISI" | "SIS" -- PCCOMPOSITE multiplicative, a block residual over all fields between
+                            # two stages (pc_composite_pcs "bjacobi,fieldsplit", ...; check_pc_order_options).  Not pc fieldsplit_cd / bilu
     ksp_rtol=1e-7, ksp_atol=1e-50, ksp_max_it=200, ksp_restart=200,
     ksp="fgmres",           # outer Krylov method: "fgmres" (restarted, ksp_restart) | "bcgs": right-preconditioned BiCGStab, seven vectors
                             # plus the shared scratch w2 whatever the iteration count, two preconditioner applications per iteration (tp_options.ksp_kind)
@@ -387,6 +391,23 @@ def check_ksp_basis_options(o):
 
 
 _REORTH = {"never": 0, "ifneeded": 1, "always": 2}
+_PC_ORDER = {"SI": 0, "IS": 1, "ISI": 2, "SIS": 3}
+
+
+def check_pc_order_options(o):
+    """pc_order (tp_options) against its values and the preconditioners that have only one of the two stages: refused naming
+    both, never ignored."""
+    order = o.get("pc_order", "SI")
+    if not isinstance(order, str) or order not in _PC_ORDER:
+        raise ValueError("pc_order = %r: 'SI', 'IS', 'ISI' or 'SIS'" % (order,))
+    if order == "SI":
+        return
+    if o.get("pc") == "fieldsplit_cd":
+        raise NotImplementedError("pc_order = %r with pc = 'fieldsplit_cd' (pc_kind 2): that preconditioner has no second stage "
+                                  "to order" % (order,))
+    if o.get("pc") == "bilu":
+        raise NotImplementedError("pc_order = %r with pc = 'bilu' (pc_kind 4): that preconditioner has no first stage to order"
+                                  % (order,))
 
 
 def check_ksp_reorth_options(o):
@@ -458,6 +479,7 @@ class HipEngine:
         check_amg_gs_options(self.opts, nranks)
         check_ksp_basis_options(self.opts)
         check_ksp_reorth_options(self.opts)
+        check_pc_order_options(self.opts)
         check_linesearch_options(self.opts)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
@@ -512,9 +534,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        # (the line-search and refinement fields stand in the middle of the struct: they are set by name, everything else in
-        # declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth"))]
+        # (the line-search, refinement and stage-order fields stand in the middle of the struct: they are set by name, everything
+        # else in declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order"))]
         vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
@@ -527,7 +549,7 @@ class HipEngine:
                           int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
-        return tp_options(**dict(zip(rest, vals)), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
+        return tp_options(**dict(zip(rest, vals)), pc_order=_PC_ORDER[o.get("pc_order", "SI")], ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
                           ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
                           ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
                           ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
@@ -545,6 +567,7 @@ class HipEngine:
         check_amg_gs_options({**self.opts, **kw}, self.nranks)
         check_ksp_basis_options({**self.opts, **kw})
         check_ksp_reorth_options({**self.opts, **kw})
+        check_pc_order_options({**self.opts, **kw})
         check_linesearch_options({**self.opts, **kw})
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
@@ -718,6 +741,11 @@ class HipEngine:
 
     def stage1_apply(self, x, y):
         self._ck(self.lib.tp_stage1_apply(self.ctx, self.vec(x), self.vec(y)))
+
+    def stage_rhs(self, x, y, out):
+        """out_q = [x - J y]_q - d_q [x - J y]_s on the primary fields q (tp_stage_rhs): the right-hand side of a later S stage of
+        the composite (pc_order), one kernel; the other fields of `out` are not written."""
+        self._ck(self.lib.tp_stage_rhs(self.ctx, self.vec(x), self.vec(y), self.vec(out)))
 
     def ilu_factor(self):
         self._ck(self.lib.tp_ilu0_factor(self.ctx))

@@ -16,6 +16,8 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
   ksp_type fbcgs | bcgs + ksp_pc_side right: right-preconditioned BiCGStab (engine key ksp = "bcgs"); ksp_gmres_restart is
      consumed and has no effect on it
   pc_type composite, pc_composite_type multiplicative, pc_composite_pcs "python,bjacobi"
+     also "bjacobi,X" | "bjacobi,X,bjacobi" | "X,bjacobi,X", X = python or fieldsplit (blanks and one trailing comma ignored): the
+     engine key pc_order = "IS" | "ISI" | "SIS"; the k-th entry's keys carry sub_k_, a repeated entry must be configured identically
      sub_0_pc_python_type  ...CPRStage1PC | ...CPTRStage1PC   sub_0_cpr_decoup  No|QI|TI
      sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur-FULL with ConvDiffSchurTwoPhasesPC
      sub_1_sub_pc_type ilu, sub_1_sub_pc_factor_levels 0, sub_1_pc_bjacobi_blocks
@@ -160,12 +162,13 @@ def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
     from .engine import (check_amg_gs_options, check_amg_line_options, check_ksp_basis_options, check_ksp_reorth_options,
-                         check_linesearch_options)
+                         check_linesearch_options, check_pc_order_options)
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_amg_gs_options(o, exc=NotImplementedError)
     check_ksp_basis_options(o)
     check_ksp_reorth_options(o)
+    check_pc_order_options(o)
     check_linesearch_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
@@ -233,7 +236,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
-                  "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
+                  "pc_order", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
     for k in build_keys:
         if k in sp:
             o[k] = sp.pop(k)
@@ -348,9 +351,93 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         return o
     # ---- composite multiplicative (stage 1, bjacobi/ILU(0)) -----------------------------------------------------
     _take(sp, used, "pc_composite_type", ("multiplicative",))
-    pcs = _take(sp, used, "pc_composite_pcs", ("python,bjacobi", "fieldsplit,bjacobi"))
-    if pcs is None:
+    sp, pcs, order, given = _composite_stages(sp, used)
+    # the build key pc_order re-orders a dict written in the presets' order "S,I"; a dict that spells another order must agree
+    if "pc_order" in solver_parameters and order != "SI" and o["pc_order"] != order:
+        raise ValueError("the order of the composite's stages is configured twice and differently: pc_order = %r, "
+                         "pc_composite_pcs = %r" % (o["pc_order"], given))
+    if "pc_order" not in solver_parameters:
+        o["pc_order"] = order
+    if order != "SI":
+        # the stages were renamed to the places they have in "S,I" (sub_0_ = S, sub_1_ = I): say so in whatever is raised below
+        try:
+            return _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=not order.startswith("S"))
+        except (KeyError, NotImplementedError, ValueError) as e:
+            msg = e.args[0] if e.args else ""
+            raise type(e)("%s [pc_composite_pcs = %r: keys are named here by stage, sub_0_ = the %s entry's sub_%d_, sub_1_ = "
+                          "the bjacobi entry's sub_%d_]" % (msg, given, pcs.split(",")[0], order.index("S"), order.index("I"))) from e
+    return _engine_options_composite(sp, used, o, pcs, model_name, vector)
+
+
+_STAGE_OF = {"python": "S", "fieldsplit": "S", "bjacobi": "I"}
+_ORDERS = ("SI", "IS", "ISI", "SIS")
+
+
+def _composite_stages(sp, used):
+    """pc_composite_pcs by PETSc's grammar: a comma-separated list of PC type names (blanks ignored, one trailing comma allowed)
+    whose k-th entry is configured under the prefix sub_k_.  The hot path has two stages, S = the python / fieldsplit entry
+    (CPR, CPTR, the system V-cycle) and I = bjacobi, in the orders S,I | I,S | I,S,I | S,I,S.  Returns the options with every
+    stage's keys moved to the prefix it has in "S,I" (S: sub_0_, I: sub_1_), the value in that canonical spelling, the order
+    and the value as given.  An entry that appears twice must be configured identically both times: one set-up serves both."""
+    if "pc_composite_pcs" not in sp:
         raise NotImplementedError("pc_composite_pcs missing")
+    given = sp["pc_composite_pcs"]
+    used.add("pc_composite_pcs")
+    text = "".join(str(given).split())
+    names = (text[:-1] if text.endswith(",") else text).split(",")
+    kinds = "".join(_STAGE_OF.get(n, "?") for n in names)
+    s_names = sorted({n for n in names if _STAGE_OF.get(n) == "S"})
+    prefixes = ["sub_%d_" % k for k in range(len(names))]
+    entry = [{k[len(pre):]: v for k, v in sp.items() if k.startswith(pre)} for pre in prefixes]
+    # (the reference's cprctr dicts: a third entry that is one V-cycle on field 1 alone, behind a stage on field 0)
+    for k, n in enumerate(names):
+        if n == "fieldsplit" and "".join(str(entry[k].get("pc_fieldsplit_0_fields", "")).split()) == "1":
+            raise NotImplementedError("pc_composite_pcs = %r: entry %d (sub_%d_) is a temperature-only stage, a V-cycle on field 1 "
+                                      "alone (sub_%d_pc_fieldsplit_0_fields = \"1\"): a third kind of stage is not implemented"
+                                      % (given, k, k, k))
+    if "?" in kinds or kinds not in _ORDERS or len(s_names) != 1:
+        raise NotImplementedError("pc_composite_pcs = %r is not implemented on the hot path (supported, X = python or fieldsplit: "
+                                  "'X,bjacobi', 'bjacobi,X', 'bjacobi,X,bjacobi', 'X,bjacobi,X')" % (given,))
+    first = {"S": kinds.index("S"), "I": kinds.index("I")}
+    for k, kind in enumerate(kinds):
+        j = first[kind]
+        if k == j:
+            continue
+        a, b = dict(entry[j]), dict(entry[k])
+        if kind == "I":         # PETSc's defaults where a key is unset: the same fill level and block count is what matters
+            for e in (a, b):
+                e.setdefault("sub_pc_type", "ilu")
+                e["sub_pc_factor_levels"] = int(e.get("sub_pc_factor_levels", 0))
+        diff = sorted(q for q in set(a) | set(b) if a.get(q, _MISSING) != b.get(q, _MISSING))
+        if diff:
+            raise NotImplementedError("pc_composite_pcs = %r: the two %s entries differ in %s; one set-up serves both, so they "
+                                      "must be configured identically" % (given, names[k],
+                                      ", ".join("sub_%d_%s / sub_%d_%s" % (j, q, k, q) for q in diff)))
+    out = {k: v for k, v in sp.items() if not k.startswith("sub_")}
+    for k, v in sp.items():
+        if not k.startswith("sub_"):
+            continue
+        for i, pre in enumerate(prefixes):
+            if k.startswith(pre):
+                if i == first[kinds[i]]:                 # (a repeated entry equals its first occurrence: dropped)
+                    out[("sub_0_" if kinds[i] == "S" else "sub_1_") + k[len(pre):]] = v
+                break
+        else:
+            out[k] = v                                   # no entry has this prefix: left for _reject_unused
+    return out, s_names[0] + ",bjacobi", kinds, given
+
+
+_MISSING = object()
+
+
+def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=False):
+    """The composite's two stages, S under sub_0_ and I under sub_1_ (engine_options)."""
+    if s_moved and "sub_0_cpr_decoup" in sp:
+        # the model class reads sub_0_cpr_decoup, the S entry's key only when S comes first: elsewhere the entry's own key decides
+        if o["decoup"] not in ("No", sp["sub_0_cpr_decoup"]):
+            raise ValueError("the decoupling is configured twice and differently: %r and the stage's cpr_decoup = %r"
+                             % (o["decoup"], sp["sub_0_cpr_decoup"]))
+        o["decoup"] = sp["sub_0_cpr_decoup"]
     # stage 2: bjacobi + ILU(0) (singlephase.py:348-349); block count: see engine.tiles_for_blocks
     _take(sp, used, "sub_1_sub_pc_type", ("ilu",))
     levels = int(_take(sp, used, "sub_1_sub_pc_factor_levels", None, 0))
