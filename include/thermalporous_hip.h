@@ -128,6 +128,28 @@ typedef struct tp_options {
      * values in the same places.  FGMRES with fp64 bases only: refused with ksp_kind 1 and with ksp_basis_single. */
     int32_t ksp_reorth;      /* 0 never (default: the launch sequence is unchanged), 1 if needed, 2 always */
     double  ksp_reorth_eta;  /* eta in (0, 1) (default 2^-1/2): the rule of ksp_reorth 1; range-checked whenever ksp_reorth is not 0 */
+    /* Eisenstat-Walker inexact Newton (snes_ksp_ew): tp_newton_solve chooses the relative tolerance eta_k of its k-th
+     * linear solve from the nonlinear residuals instead of solving every system to ksp_rtol.  NOTE for ABI readers: the seven fields
+     * stand HERE, between ksp_reorth_eta and ilu_whole, not at the struct's tail (the tests of earlier options pin the order of every
+     * field from ilu_whole on, and that of pc_order, ksp_reorth, ksp_reorth_eta before): every field from ilu_whole on moved and
+     * sizeof(tp_options) grew; recompile callers.
+     * With ||F_k|| the residual norm where system k is formed, rho_k the residual norm the Krylov solver returned for it:
+     *   k == 0:     eta = ew_rtol0
+     *   version 1:  eta = | ||F_k|| - rho_{k-1} | / ||F_{k-1}|| ;            s = pow(eta_{k-1}, ew_alpha2)
+     *   version 2:  eta = ew_gamma pow(||F_k|| / ||F_{k-1}||, ew_alpha) ;    s = ew_gamma pow(eta_{k-1}, ew_alpha)
+     *   k > 0:      if s > ew_threshold: eta = max(eta, s)                   (safeguard)
+     *   always:     eta = min(eta, ew_rtolmax); eta = max(eta, ksp_rtol)     (cap, then floor)
+     * and solve k stops at max(eta_k ||F_k||, ksp_atol).  One deliberate difference from PETSc: the configured ksp_rtol stays as a
+     * FLOOR (PETSc overwrites it); the two differ only where the formula asks for more digits than the user ever wanted.  ksp_rtol >
+     * ew_rtolmax is refused.  PETSc's version 3 is not implemented.  The option lives in tp_newton_solve only: tp_fgmres and tp_bcgs
+     * called on their own use ksp_rtol.  Every ew_* field must keep its default (or 0) while ksp_ew is 0 (refused, never ignored). */
+    int32_t ksp_ew;          /* 0 off (default: the launch sequence and every result are unchanged), 1 or 2: the version */
+    double  ew_rtol0;        /* eta_0 in [0, 1) (snes_ksp_ew_rtol0; default 0.3) */
+    double  ew_rtolmax;      /* the cap in [0, 1), >= ksp_rtol (snes_ksp_ew_rtolmax; default 0.9) */
+    double  ew_gamma;        /* in [0, 1] (snes_ksp_ew_gamma; default 1) */
+    double  ew_alpha;        /* in (1, 2] (snes_ksp_ew_alpha; default (1 + sqrt 5) / 2) */
+    double  ew_alpha2;       /* in (1, 2] (snes_ksp_ew_alpha2; default (1 + sqrt 5) / 2) */
+    double  ew_threshold;    /* in (0, 1) (snes_ksp_ew_threshold; default 0.1) */
     int32_t ilu_whole;       /* 1: ONE bjacobi block per rank = block-ILU(0) of the whole slab, PETSc's default bjacobi and the
                                 reference's `sub_1_pc_bjacobi_blocks: 1` (tests/test_homo_wells.py:112, pc_cptr_a11
                                 twophase.py:612): couplings between the tiles are kept; the tiles (ilu_t0 x ilu_t1 x ilu_t2,
@@ -382,6 +404,20 @@ int tp_ls_history(tp_ctx *ctx, int32_t cap, double *lambda, double *fnorm, int32
  *   tp_ls_trial       out_vec = u0_vec - lambda dx_vec on owned cells of all fields; halo planes of out_vec are not written */
 int tp_ls_step_stats(tp_ctx *ctx, int32_t dx, double out[4]);
 int tp_ls_trial(tp_ctx *ctx, int32_t u0, int32_t dx, double lambda, int32_t out);
+
+/* Eisenstat-Walker (tp_options.ksp_ew).  tp_ew_next_rtol is the chooser on its own: the tolerance of linear solve k of a Newton
+ * solve from fnorm = ||F_k||, fnorm_last = ||F_{k-1}||, lresid_last = rho_{k-1} and rtol_last = eta_{k-1} (the last three are not
+ * read for k = 0), with the parameters and ksp_rtol of *opt (opt->ksp_ew must be 1 or 2; ranges are checked).  It needs no context
+ * and no GPU.
+ * tp_ew_info: out = {version in effect (0: off), Newton solves run under it since tp_create, linear solves among them, linear
+ * solves whose eta the safeguard raised}.
+ * tp_ew_history: per linear solve of the last Newton solve, at most cap entries: eta_k, ||F_k||, rho_k, the Krylov iterations and
+ * the KSP reason of solve k; *n = the number of solves recorded.  n = 0 after a solve with ksp_ew 0. */
+int tp_ew_next_rtol(const tp_options *opt, int32_t k, double fnorm, double fnorm_last, double lresid_last, double rtol_last,
+                    double *rtol);
+int tp_ew_info(tp_ctx *ctx, int64_t out[4]);
+int tp_ew_history(tp_ctx *ctx, int32_t cap, double *rtol, double *fnorm, double *lresid, int32_t *kits, int32_t *kreason,
+                  int32_t *n);
 
 /* measurement hooks for bench.py: average device time (ms, HIP events on the context's stream)
  * of `reps` launches of one hot kernel.  which: 0 block SpMV, 1 ILU solve, 2 AMG V-cycle (pressure),

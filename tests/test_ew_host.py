@@ -1,0 +1,327 @@
+"""The opt-in Eisenstat-Walker inexact Newton (ksp_ew / snes_ksp_ew), everything that needs no GPU: the C++ chooser against the
+numpy one, the options in both spellings and their refusals, the numpy reference tests/ew_ref.py on the inputs the GPU tests
+compare against (and the conditions those inputs must meet, the sensitivity floor among them), and the host time loop on an
+oracle engine that runs the reference."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases
+import ew_ref as R
+import newton_ls_ref as L
+from thermalporous_amd import engine as E
+from thermalporous_amd.solver_options import engine_options
+from thermalporous_amd.twophase import TwoPhase
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "thermalporous_hip.h")
+ALPHA = (1.0 + math.sqrt(5.0))/2.0
+_CACHE = {}
+
+
+def ramp(name):
+    """The reference on the ramp, computed once and shared (never modified): name -> (per-step results, final state)."""
+    if name not in _CACHE:
+        version, scale = {"fixed": (0, 1.0), "v1": (1, 1.0), "v2": (2, 1.0), "v1_half": (1, 0.5), "v2_half": (2, 0.5)}[name]
+        _CACHE[name] = R.ref_ramp(version, scale)
+    return _CACHE[name]
+
+
+def c_next_rtol(version, k, fnorm, fnorm_last, lresid_last, rtol_last, ksp_rtol, **p):
+    opts = dict(ksp_ew=version, ksp_rtol=ksp_rtol, **{"ew_" + q: v for q, v in p.items()})
+    return E.HipEngine.ew_next_rtol(opts, k, fnorm, fnorm_last, lresid_last, rtol_last)
+
+
+# ---- chooser against chooser ---------------------------------------------------------------------------------------------------
+def test_chooser_matches_the_reference_over_a_seeded_sweep(hip_lib):
+    rng = np.random.default_rng(20261019)
+    seen = 0
+    for _ in range(1500):
+        version = int(rng.integers(1, 3))
+        k = int(rng.integers(0, 6))
+        p = dict(rtol0=float(rng.uniform(0.0, 0.999)), rtolmax=float(rng.uniform(1e-3, 0.999)), gamma=float(rng.uniform(0.0, 1.0)),
+                 alpha=float(rng.uniform(1.0001, 2.0)), alpha2=float(rng.uniform(1.0001, 2.0)), threshold=float(rng.uniform(1e-3, 0.999)))
+        ksp_rtol = float(min(10.0**rng.uniform(-12, -1), p["rtolmax"]))
+        f_last = float(10.0**rng.uniform(-6, 6))
+        fnorm = f_last*float(10.0**rng.uniform(-4, 0.5))
+        eta_last = float(10.0**rng.uniform(-8, math.log10(0.9)))
+        rho_last = eta_last*f_last*float(rng.uniform(0.05, 1.0))
+        want, fl = R.next_rtol(version, k, fnorm, f_last, rho_last, eta_last, ksp_rtol, **p)
+        got = c_next_rtol(version, k, fnorm, f_last, rho_last, eta_last, ksp_rtol, **p)
+        # both call the same libm pow; four ulp of slack covers a differing contraction
+        assert abs(got - want) <= 1e-14*abs(want), (version, k, fnorm, f_last, rho_last, eta_last, ksp_rtol, p, got, want)
+        seen |= fl
+    assert seen == R.FIRST | R.SAFE_TESTED | R.SAFE_RAISED | R.CAPPED | R.FLOORED
+
+
+def test_hand_made_inputs_take_every_branch(hip_lib):
+    """(name, version, k, ||F_k||, ||F_k-1||, rho_k-1, eta_k-1, ksp_rtol, parameters) -> (eta, the branches taken)."""
+    thr = 0.1
+    just_below = math.nextafter(thr**(1.0/ALPHA), 0.0)         # s = pow(eta_last, alpha) <= threshold: safeguard not consulted
+    while math.pow(just_below, ALPHA) > thr:
+        just_below = math.nextafter(just_below, 0.0)
+    just_above = just_below
+    while not math.pow(just_above, ALPHA) > thr:
+        just_above = math.nextafter(just_above, 1.0)
+    table = [
+        ("k0", 2, 0, 5.0, 0.0, 0.0, 0.0, 1e-8, {}, 0.3, R.FIRST),
+        ("k0_v1_rtol0", 1, 0, 5.0, 0.0, 0.0, 0.0, 1e-8, dict(rtol0=0.01), 0.01, R.FIRST),
+        # version 1: | 0.5 - 0.25 | / 10 = 0.025; s = 0.01^alpha < threshold
+        ("v1", 1, 1, 0.5, 10.0, 0.25, 0.01, 1e-8, {}, abs(0.5 - 0.25)/10.0, 0),
+        # version 2: (0.5/10)^alpha; s as above
+        ("v2", 2, 2, 0.5, 10.0, 0.25, 0.01, 1e-8, {}, math.pow(0.5/10.0, ALPHA), 0),
+        ("v2_gamma", 2, 2, 0.5, 10.0, 0.25, 0.01, 1e-8, dict(gamma=0.5), 0.5*math.pow(0.5/10.0, ALPHA), 0),
+        # the safeguard just below its threshold: the formula's small eta stands
+        ("safe_below", 2, 1, 1e-3, 1.0, 0.1, just_below, 1e-8, {}, math.pow(1e-3, ALPHA), 0),
+        # ... and just above: eta is raised to s
+        ("safe_above", 2, 1, 1e-3, 1.0, 0.1, just_above, 1e-8, {}, math.pow(just_above, ALPHA), R.SAFE_TESTED | R.SAFE_RAISED),
+        # consulted but not raising: the formula's eta is already above s
+        ("safe_tested", 2, 1, 0.8, 1.0, 0.1, 0.3, 1e-8, {}, math.pow(0.8, ALPHA), R.SAFE_TESTED),
+        ("safe_v1", 1, 1, 0.101, 1.0, 0.1, 0.5, 1e-8, dict(alpha2=1.5), math.pow(0.5, 1.5), R.SAFE_TESTED | R.SAFE_RAISED),
+        # the cap: the residual grew
+        ("cap", 2, 1, 3.0, 1.0, 0.1, 0.01, 1e-8, {}, 0.9, R.CAPPED),
+        ("cap_v1", 1, 3, 3.0, 1.0, 0.1, 0.01, 1e-8, dict(rtolmax=0.5), 0.5, R.CAPPED),
+        # the floor: the formula asks for more digits than ksp_rtol
+        ("floor", 2, 1, 1e-7, 1.0, 1e-9, 1e-3, 1e-6, {}, 1e-6, R.FLOORED),
+        ("floor_k0", 2, 0, 1.0, 0.0, 0.0, 0.0, 0.5, {}, 0.5, R.FIRST | R.FLOORED),
+    ]
+    taken = 0
+    for name, version, k, fn, fl_, rho, eta_last, ksp_rtol, p, want, flags in table:
+        ref, fl = R.next_rtol(version, k, fn, fl_, rho, eta_last, ksp_rtol, **{**R.DEFAULTS, **p})
+        assert fl == flags, (name, fl, flags)
+        assert ref == pytest.approx(want, rel=1e-15), name
+        got = c_next_rtol(version, k, fn, fl_, rho, eta_last, ksp_rtol, **p)
+        assert abs(got - ref) <= 1e-14*ref, (name, got, ref)
+        taken |= fl
+    assert taken == R.FIRST | R.SAFE_TESTED | R.SAFE_RAISED | R.CAPPED | R.FLOORED
+    # the two sides of the threshold really are neighbours, and give different answers
+    assert 0.0 < just_above - just_below < 1e-15 and math.pow(just_above, ALPHA) > 50*math.pow(1e-3, ALPHA)
+
+
+def test_the_export_checks_its_options(hip_lib):
+    t = E.HipEngine._make_options({**E.DEFAULT_OPTS, "ilu_tile": (1 << 30, 8, 8)})
+    out = C.c_double()
+    args = (C.c_int32(0), C.c_double(1.0), C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.byref(out))
+    assert hip_lib.tp_ew_next_rtol(C.byref(t), *args) != 0 and b"ksp_ew" in hip_lib.tp_last_error()      # off: nothing to choose
+    t.ksp_ew = 2
+    assert hip_lib.tp_ew_next_rtol(C.byref(t), *args) == 0 and out.value == 0.3
+    t.ew_alpha = 1.0
+    assert hip_lib.tp_ew_next_rtol(C.byref(t), *args) != 0 and b"ew_alpha" in hip_lib.tp_last_error()
+    t.ew_alpha, t.ksp_ew = ALPHA, 3
+    assert hip_lib.tp_ew_next_rtol(C.byref(t), *args) != 0 and b"snes_ksp_ew_version 3" in hip_lib.tp_last_error()
+    t.ksp_ew, t.ksp_rtol = 1, 0.95
+    assert hip_lib.tp_ew_next_rtol(C.byref(t), *args) != 0 and b"ew_rtolmax" in hip_lib.tp_last_error()
+
+
+# ---- options -------------------------------------------------------------------------------------------------------------------
+def cptr_parameters():
+    spec, u0, p, g, c = cases.c3_spe10_2d(6, 8, 2)
+    from oracle.engine import OracleEngine
+    m = TwoPhase(g, c, p, end=0.01, maxdt=0.01, solver_parameters="pc_cptr", filename=None, verbosity=False, _engine_factory=OracleEngine)
+    return dict(m.solver_parameters)
+
+
+EW_KEYS = ("ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
+OTHER = dict(ew_rtol0=0.1, ew_rtolmax=0.5, ew_gamma=0.9, ew_alpha=2.0, ew_alpha2=1.5, ew_threshold=0.2)
+
+
+def test_defaults_struct_fields_and_exports():
+    assert E.DEFAULT_OPTS["ksp_ew"] is False
+    assert [E.DEFAULT_OPTS[k] for k in EW_KEYS] == [0.3, 0.9, 1.0, ALPHA, ALPHA, 0.1]
+    names = [f[0] for f in E.tp_options._fields_]
+    i = names.index("ksp_ew")               # (between ksp_reorth_eta and ilu_whole: the fields around keep the order earlier tests pin)
+    assert names[i:i + 7] == ["ksp_ew"] + list(EW_KEYS)
+    assert names[i - 1] == "ksp_reorth_eta" and names[i + 7] == "ilu_whole" and names[-1] == "s1_atol"
+    types = dict(E.tp_options._fields_)
+    assert types["ksp_ew"] is C.c_int32 and all(types[k] is C.c_double for k in EW_KEYS)
+    assert all(getattr(E.tp_options, k).offset % 8 == 0 for k in EW_KEYS)
+    o = E.resolve_ilu_options(dict(E.DEFAULT_OPTS), (12, 16, 1))
+    t = E.HipEngine._make_options(o)
+    assert t.ksp_ew == 0 and [getattr(t, k) for k in EW_KEYS] == [0.3, 0.9, 1.0, ALPHA, ALPHA, 0.1]
+    for given, code in ((False, 0), (0, 0), (1, 1), (2, 2), (True, 2)):
+        assert E.HipEngine._make_options({**o, "ksp_ew": given}).ksp_ew == code
+    t = E.HipEngine._make_options({**o, "ksp_ew": 1, **OTHER})
+    assert [getattr(t, k) for k in EW_KEYS] == [OTHER[k] for k in EW_KEYS]
+    # every other field is what it was without the keys
+    a, b = E.HipEngine._make_options(o), E.HipEngine._make_options({**o, "ksp_ew": 2, **OTHER})
+    assert all(bytes(C.string_at(C.addressof(a) + getattr(E.tp_options, n).offset, getattr(E.tp_options, n).size)) ==
+               bytes(C.string_at(C.addressof(b) + getattr(E.tp_options, n).offset, getattr(E.tp_options, n).size))
+               for n in names if n != "ksp_ew" and n not in EW_KEYS)
+    for sym in ("tp_ew_next_rtol", "tp_ew_info", "tp_ew_history"):
+        assert sym in E.API_SYMBOLS
+    text = open(HEADER).read()
+    assert re.search(r"int32_t\s+ksp_ew\s*;", text) and all(re.search(r"double\s+%s\s*;" % k, text) for k in EW_KEYS)
+    assert "int tp_ew_info(tp_ctx *ctx, int64_t out[4]);" in text
+    assert re.search(r"int tp_ew_next_rtol\(const tp_options \*opt, int32_t k, double fnorm, double fnorm_last, double lresid_last, "
+                     r"double rtol_last,\s*double \*rtol\);", text)
+    assert re.search(r"int tp_ew_history\(tp_ctx \*ctx, int32_t cap, double \*rtol, double \*fnorm, double \*lresid, int32_t \*kits, "
+                     r"int32_t \*kreason,\s*int32_t \*n\);", text)
+
+
+def test_petsc_keys_translate_in_both_spellings():
+    d = cptr_parameters()
+    o = engine_options(d, "Two-phase")
+    assert o["ksp_ew"] is False and [o[k] for k in EW_KEYS] == [0.3, 0.9, 1.0, ALPHA, ALPHA, 0.1]
+    for flag in (None, True):
+        o = engine_options({**d, "snes_ksp_ew": flag}, "Two-phase")              # (raises without the feature)
+        assert o["ksp_ew"] == 2 and [o[k] for k in EW_KEYS] == [0.3, 0.9, 1.0, ALPHA, ALPHA, 0.1]
+    assert not engine_options({**d, "snes_ksp_ew": False}, "Two-phase")["ksp_ew"]
+    assert engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_version": 1}, "Two-phase")["ksp_ew"] == 1
+    assert engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_version": 2}, "Two-phase")["ksp_ew"] == 2
+    petsc = {"snes_ksp_ew_" + k[3:]: v for k, v in OTHER.items()}
+    o = engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_version": 1, **petsc}, "Two-phase")
+    assert o["ksp_ew"] == 1 and {k: o[k] for k in EW_KEYS} == OTHER
+    # the build keys, alone or agreeing with the PETSc keys
+    o = engine_options({**d, "ksp_ew": 1, **OTHER}, "Two-phase")
+    assert o["ksp_ew"] == 1 and {k: o[k] for k in EW_KEYS} == OTHER
+    assert E.ew_version(engine_options({**d, "ksp_ew": True}, "Two-phase")["ksp_ew"]) == 2
+    o = engine_options({**d, "ksp_ew": 2, "snes_ksp_ew": None, "ew_rtol0": 0.1, "snes_ksp_ew_rtol0": 0.1}, "Two-phase")
+    assert o["ksp_ew"] == 2 and o["ew_rtol0"] == 0.1
+    # it combines with everything else
+    o = engine_options({**d, "snes_ksp_ew": None, "ksp_type": "fbcgs", "snes_linesearch_type": "bt", "pc_order": "ISI"}, "Two-phase")
+    assert (o["ksp_ew"], o["ksp"], o["linesearch"], o["pc_order"]) == (2, "bcgs", "bt", "ISI")
+    o = engine_options({**d, "ksp_ew": 1, "ksp_basis_single": True, "s1_ksp": "fgmres", "s1_max_it": 4}, "Two-phase")
+    assert o["ksp_ew"] == 1 and o["ksp_basis_single"] and o["s1_ksp"] == "fgmres"
+
+
+def test_every_refusal_raises():
+    d = cptr_parameters()
+    with pytest.raises(NotImplementedError, match="snes_ksp_ew_version 3"):
+        engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_version": 3}, "Two-phase")
+    with pytest.raises(NotImplementedError, match="snes_ksp_ew_version 3"):
+        engine_options({**d, "ksp_ew": 3}, "Two-phase")
+    for bad in (0, 4, -1, 1.5, "2", True):
+        with pytest.raises(ValueError):
+            engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_version": bad}, "Two-phase")
+    for bad in (4, -1, 1.5, "2"):
+        with pytest.raises(ValueError):
+            engine_options({**d, "ksp_ew": bad}, "Two-phase")
+    with pytest.raises(ValueError):
+        engine_options({**d, "snes_ksp_ew": 2}, "Two-phase")                      # the flag is no version
+    # a snes_ksp_ew_* key without the flag names the flag
+    for k, v in [("snes_ksp_ew_version", 1)] + [("snes_ksp_ew_" + q[3:], v) for q, v in OTHER.items()]:
+        with pytest.raises(NotImplementedError, match="without snes_ksp_ew"):
+            engine_options({**d, k: v}, "Two-phase")
+        with pytest.raises(NotImplementedError, match="without snes_ksp_ew"):
+            engine_options({**d, "snes_ksp_ew": False, k: v}, "Two-phase")
+    # an ew_* build key away from its default while the option is off
+    for k, v in OTHER.items():
+        with pytest.raises(ValueError, match=k):
+            engine_options({**d, k: v}, "Two-phase")
+        with pytest.raises(ValueError, match=k):
+            E.check_ew_options({**E.DEFAULT_OPTS, k: v})
+    E.check_ew_options(dict(E.DEFAULT_OPTS))
+    # both spellings, disagreeing
+    for kw in (dict(ksp_ew=1, snes_ksp_ew=None), dict(ksp_ew=2, snes_ksp_ew=False), dict(ksp_ew=False, snes_ksp_ew=None),
+               dict(ksp_ew=2, snes_ksp_ew=None, snes_ksp_ew_version=1), dict(ksp_ew=2, snes_ksp_ew=None, ew_rtol0=0.2, snes_ksp_ew_rtol0=0.1)):
+        with pytest.raises(ValueError, match="twice"):
+            engine_options({**d, **kw}, "Two-phase")
+    # the floor above the cap
+    with pytest.raises(ValueError, match="ew_rtolmax"):
+        engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_rtolmax": 1e-9, "ksp_rtol": 1e-8}, "Two-phase")
+    with pytest.raises(ValueError, match="ew_rtolmax"):
+        E.check_ew_options({**E.DEFAULT_OPTS, "ksp_ew": 2, "ksp_rtol": 0.95})
+    with pytest.raises(KeyError):
+        engine_options({**d, "snes_ksp_ew": None, "snes_ksp_ew_safeguard": True}, "Two-phase")
+
+
+@pytest.mark.parametrize("bad", [dict(ew_rtol0=-0.1), dict(ew_rtol0=1.0), dict(ew_rtolmax=-0.1), dict(ew_rtolmax=1.0), dict(ew_gamma=-0.1),
+                                 dict(ew_gamma=1.01), dict(ew_alpha=1.0), dict(ew_alpha=2.01), dict(ew_alpha2=1.0), dict(ew_alpha2=2.5),
+                                 dict(ew_threshold=0.0), dict(ew_threshold=1.0), dict(ew_rtol0=True), dict(ew_gamma=float("nan")),
+                                 dict(ew_alpha="2")])
+def test_check_ew_options_ranges(bad):
+    for version in (1, 2, True):
+        E.check_ew_options({**E.DEFAULT_OPTS, "ksp_ew": version})
+        E.check_ew_options({**E.DEFAULT_OPTS, "ksp_ew": version, "ew_rtol0": 0.0, "ew_gamma": 0.0, "ew_alpha": 2.0, "ew_alpha2": 2.0})
+        with pytest.raises(ValueError):
+            E.check_ew_options({**E.DEFAULT_OPTS, "ksp_ew": version, **bad})
+
+
+# ---- the reference on the ramp: where the inputs are chosen ------------------------------------------------------------------------
+def test_reference_converges_and_halves_the_krylov_work():
+    fixed = ramp("fixed")[0]
+    assert len(fixed) == len(R.RAMP_DT) and all(s["reason"] == 3 for s in fixed)
+    kfixed = sum(s["lits"] for s in fixed)
+    for v in ("v1", "v2"):
+        steps = ramp(v)[0]
+        assert len(steps) == len(R.RAMP_DT) and all(s["reason"] == 3 for s in steps), v
+        assert all(r > 0 for s in steps for r in s["ew"]["kreason"])
+        k = sum(s["lits"] for s in steps)
+        print("%s: Newton %d (fixed %d), Krylov %d (fixed %d), safeguard raised %d" %
+              (v, sum(s["nits"] for s in steps), sum(s["nits"] for s in fixed), k, kfixed, sum(s["safeguarded"] for s in steps)))
+        # measured 92 (v1) and 94 (v2) against 191: at most 0.75 x, so that +-1 iteration per solve on the GPU (32 / 35 solves)
+        # cannot flip the GPU's strict comparison
+        assert k <= 0.75*kfixed
+        assert sum(s["safeguarded"] for s in steps) >= 1
+        assert R.EXPECT_NITS[v] == [s["nits"] for s in steps]
+        # the record is consistent: eta recomputed from the recorded norms, tolerance honoured and not over-solved by the formula
+        for s in steps:
+            e = s["ew"]
+            assert e["fnorm"] == [s["fnorm0"]] + s["hist"][:-1] and sum(e["kits"]) == s["lits"]
+            for k_ in range(len(e["rtol"])):
+                last = (e["fnorm"][k_ - 1], e["lresid"][k_ - 1], e["rtol"][k_ - 1]) if k_ else (0.0, 0.0, 0.0)
+                assert e["rtol"][k_] == R.next_rtol(int(v[1]), k_, e["fnorm"][k_], *last, R.RAMP_OPTS["ksp_rtol"])[0]
+                assert e["lresid"][k_] <= e["rtol"][k_]*e["fnorm"][k_]
+    assert R.EXPECT_NITS["fixed"] == [s["nits"] for s in fixed]
+
+
+def test_sensitivity_floor_of_the_ramp():
+    """Floor 1 per field = the larger of |EW - fixed| and |EW - EW with every eta halved| on the final state, over both versions."""
+    ufixed = ramp("fixed")[1]
+    worst = [0.0, 0.0, 0.0]
+    for v in ("v1", "v2"):
+        steps, u = ramp(v)
+        hsteps, uh = ramp(v + "_half")
+        assert len(hsteps) == len(steps) and all(s["reason"] == 3 for s in hsteps)
+        # the halved run is a second legitimate run of the same problem: its Newton counts stay within +-1
+        assert all(abs(a["nits"] - b["nits"]) <= 1 for a, b in zip(steps, hsteps)), v
+        d_fixed, d_half = R.state_diff(u, ufixed), R.state_diff(u, uh)
+        print("%s: vs fixed %s, vs halved %s" % (v, ["%.3e" % x for x in d_fixed], ["%.3e" % x for x in d_half]))
+        worst = [max(w, a, b) for w, a, b in zip(worst, d_fixed, d_half)]
+    print("floor 1 %s  tolerance %s" % (["%.3e" % x for x in worst], ["%.3e" % x for x in R.PARITY_TOL]))
+    for f in range(3):
+        assert worst[f] <= R.FLOOR1[f] <= 1.25*worst[f]                 # the constant is the measured floor, rounded up
+        assert R.PARITY_TOL[f] == pytest.approx(10*R.FLOOR1[f], rel=1e-12) and R.PARITY_TOL[f] <= 1e-8
+
+
+def test_the_small_inputs_meet_their_conditions():
+    """c3 (12 x 16), the first two ramp steps: 4 and 5 Newton iterations under version 2, eta above rtol0 once.  The bt input:
+    a step is shortened, and its final state is no more sensitive than the ramp's."""
+    steps, _ = R.ref_ramp(2, case=R.c3_case, opts=R.C3_OPTS, dts=R.RAMP_DT[:2])
+    assert [s["reason"] for s in steps] == [3, 3] and [s["nits"] for s in steps] == R.C3_EXPECT_NITS == [4, 5]
+    assert sum(1 for s in steps for e in s["ew"]["rtol"] if e > 0.3) == 1
+    runs = {}
+    for name, (version, scale) in {"fixed": (0, 1.0), "ew": (2, 1.0), "half": (2, 0.5)}.items():
+        _, _, eng = L.cold_engine("c3", R.BT_OPTS, R.BT_DT)
+        runs[name] = R.newton_ew_ref(eng, version=version, eta_scale=scale, linesearch="bt")
+        assert runs[name]["reason"] == 3
+    assert max(runs["ew"]["trials"]) > 1 and runs["ew"]["trials"] == R.BT_EXPECT_TRIALS
+    d = [max(a, b) for a, b in zip(R.state_diff(runs["ew"]["u"], runs["fixed"]["u"]), R.state_diff(runs["ew"]["u"], runs["half"]["u"]))]
+    print("bt input: floor %s" % ["%.3e" % x for x in d])
+    assert all(d[f] <= R.FLOOR1[f] for f in range(3))
+
+
+# ---- the host time loop ----------------------------------------------------------------------------------------------------------
+def test_host_time_loop_runs_the_ramp_and_writes_the_results_file(tmp_path):
+    spec, u0, p, g, c = R.ramp_case()
+    d = cptr_parameters()
+    d.update({"snes_ksp_ew": None, "ksp_rtol": 1e-8})
+    out = tmp_path/"ew_results.txt"
+    m = TwoPhase(g, c, p, end=1.0, maxdt=0.03, solver_parameters=d, filename=str(out), verbosity=True, _engine_factory=R.EwOracleEngine)
+    m.start()
+    for dt in R.RAMP_DT:
+        m.dt.assign(dt*R.DAY)
+        m.step()
+    m.finish()
+    assert m.engine.opts["ksp_ew"] == 2 and m.failed_solves == 0
+    steps = ramp("v2")[0]
+    assert m.nits_vec == [s["nits"] for s in steps] and m.lits_vec == [s["lits"] for s in steps]
+    assert m.dt_vec == [dt*R.DAY for dt in R.RAMP_DT]
+    assert len(m.engine.last["ew_rtol"]) == m.nits_vec[-1] and m.engine.last["ew_rtol"][0] == 0.3
+    text = out.read_text()
+    for col in ("nits = ", "lits = ", "dts = ", "timings = ", "snes_ksp_ew", "Total Linear iterations:  %d" % sum(m.lits_vec),
+                "Total Nonlinear iterations:  %d" % sum(m.nits_vec), "Number of time-steps:  8"):
+        assert col in text, col

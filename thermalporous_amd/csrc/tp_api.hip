@@ -316,6 +316,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
     ls_check_options(*opt);
+    ew_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
     amg_gs_check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
@@ -374,6 +375,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
     ls_check_options(*opt);
+    ew_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
     amg_gs_check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
@@ -886,7 +888,7 @@ int tp_fgmres(tp_ctx *c, int32_t b, int32_t x, int32_t *its, int32_t *reason, do
     if (!c->pc_ready) pc_setup(c);
     int it = 0;
     double rn = 0.0;
-    const int r = fgmres(c, vec_of(c, b).p, vec_of(c, x).p, &it, &rn);
+    const int r = fgmres(c, vec_of(c, b).p, vec_of(c, x).p, &it, &rn, c->opt.ksp_rtol);
     if (its) *its = it;
     if (reason) *reason = r;
     if (rnorm) *rnorm = rn;
@@ -899,7 +901,7 @@ int tp_bcgs(tp_ctx *c, int32_t b, int32_t x, int32_t *its, int32_t *reason, doub
     if (!c->pc_ready) pc_setup(c);
     int it = 0;
     double rn = 0.0;
-    const int r = bcgs(c, vec_of(c, b).p, vec_of(c, x).p, &it, &rn);
+    const int r = bcgs(c, vec_of(c, b).p, vec_of(c, x).p, &it, &rn, c->opt.ksp_rtol);
     if (its) *its = it;
     if (reason) *reason = r;
     if (rnorm) *rnorm = rn;
@@ -971,6 +973,38 @@ int tp_ls_history(tp_ctx *c, int32_t cap, double *lambda, double *fnorm, int32_t
     TP_REQUIRE(c && n && cap >= 0 && (cap == 0 || (lambda && fnorm && trials)), "bad arguments");
     *n = (int32_t)c->ls_lambda.size();
     for (int i = 0; i < std::min<int>(cap, *n); ++i) { lambda[i] = c->ls_lambda[i]; fnorm[i] = c->ls_fnorm[i]; trials[i] = c->ls_trials[i]; }
+    TP_API_END
+}
+
+int tp_ew_next_rtol(const tp_options *opt, int32_t k, double fnorm, double fnorm_last, double lresid_last, double rtol_last,
+                    double *rtol) {
+    TP_API_BEGIN
+    TP_REQUIRE(opt && rtol && k >= 0, "bad arguments");
+    TP_REQUIRE(opt->ksp_ew != 0, "tp_ew_next_rtol needs ksp_ew 1 or 2");
+    ew_check_options(*opt);
+    *rtol = ew_next_rtol(*opt, k, fnorm, fnorm_last, lresid_last, rtol_last);
+    TP_API_END
+}
+
+int tp_ew_info(tp_ctx *c, int64_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "bad arguments");
+    out[0] = c->opt.ksp_ew;
+    out[1] = c->ew_solves;
+    out[2] = c->ew_lsolves;
+    out[3] = c->ew_safeguard;
+    TP_API_END
+}
+
+int tp_ew_history(tp_ctx *c, int32_t cap, double *rtol, double *fnorm, double *lresid, int32_t *kits, int32_t *kreason,
+                  int32_t *n) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && n && cap >= 0 && (cap == 0 || (rtol && fnorm && lresid && kits && kreason)), "bad arguments");
+    *n = (int32_t)c->ew_rtol.size();
+    for (int i = 0; i < std::min<int>(cap, *n); ++i) {
+        rtol[i] = c->ew_rtol[i]; fnorm[i] = c->ew_fnorm[i]; lresid[i] = c->ew_lresid[i];
+        kits[i] = c->ew_kits[i]; kreason[i] = c->ew_kreason[i];
+    }
     TP_API_END
 }
 

@@ -2,7 +2,7 @@
 // bcgs with ksp_pc_side right).  A short recurrence: seven vectors plus the shared scratch w2 whatever the iteration count, no basis, no
 // Gram-Schmidt.
 //
-//   r = b; r^ = b; rho = (b,b); tol = max(ksp_rtol ||b||, ksp_atol)
+//   r = b; r^ = b; rho = (b,b); tol = max(rtol ||b||, ksp_atol)      (rtol: ksp_rtol, or the solve's eta under ksp_ew)
 //   repeat:  p = r + beta (p - omega v)            (first iteration: beta = 0, p = r)
 //            p^ = M p;  v = J p^;  alpha = rho / (r^,v)
 //            s = r - alpha v;  ||s|| <= tol: half-step exit, omega := 0
@@ -391,8 +391,8 @@ void ksp_info(tp_ctx *c, int64_t out[4]) {
         else hipLaunchKernelGGL(KERNEL<1>, gw, bl, 0, c->stream, __VA_ARGS__);                   \
     } while (0)
 
-// BiCGStab from x0 = 0.  Returns the KSP reason: 2 converged, -3 ksp_max_it reached, -5 breakdown, -9 NaN or Inf.
-int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
+// BiCGStab from x0 = 0 to the relative tolerance rtol (the latch on the device receives it through k_bcgs_init).  Returns the KSP reason: 2 converged, -3 ksp_max_it reached, -5 breakdown, -9 NaN or Inf.
+int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
     const GridDev &g = c->g;
     const int B = c->b;
     const long nv = (long)B * g.ntot;
@@ -438,7 +438,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
     vec_zero(c, x, nv);
     BC_LAUNCH(k_bcgs_start, g, B, bvec, r, rh, part, nw);
     reduce(1);
-    hipLaunchKernelGGL(k_bcgs_init, one, wv, 0, c->stream, st, c->opt.ksp_rtol, c->opt.ksp_atol, pin);
+    hipLaunchKernelGGL(k_bcgs_init, one, wv, 0, c->stream, st, rtol, c->opt.ksp_atol, pin);
     TP_HIP(hipGetLastError());
     wait();
     *its_out = 0;

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <functional>
 #include "../../include/thermalporous_hip.h"
+#include "tp_ew.hpp"
 
 struct ncclComm;
 
@@ -417,6 +418,11 @@ struct tp_ctx {
     std::vector<double> ls_lambda, ls_fnorm;
     std::vector<int32_t> ls_trials;
     long ls_evals = 0, ls_nonfinite = 0;
+    // Eisenstat-Walker (tp_options.ksp_ew; tp_ew.hpp): per linear solve of the last Newton solve eta_k, ||F_k||, rho_k, the Krylov
+    // iterations and reason (tp_ew_history), and the counters of tp_ew_info since tp_create.  Host data only.
+    std::vector<double> ew_rtol, ew_fnorm, ew_lresid;
+    std::vector<int32_t> ew_kits, ew_kreason;
+    long ew_solves = 0, ew_lsolves = 0, ew_safeguard = 0;
     tp_ksp_monitor_fn monitor = nullptr;      // per-field true-residual monitor (ksp_monitor_residuals)
     void *monitor_user = nullptr;
     ~tp_ctx();
@@ -535,9 +541,12 @@ void ensure_work(tp_ctx *c);          // scratch vectors w1..w4, dx of the preco
 void pc_setup(tp_ctx *c);
 void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary = true);
 void pc_apply(tp_ctx *c, const double *x, double *y);
-int fgmres(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
+// rtol: the relative tolerance of THIS solve (tp_fgmres / tp_bcgs pass tp_options.ksp_rtol, newton() the same or, under ksp_ew, eta_k):
+// every reader of the tolerance -- both FGMRES loops, the speculation margin, the fp32-basis loop's true-residual test, the
+// BiCGStab latch on the device -- follows it; tp_options is never written
+int fgmres(tp_ctx *c, const double *b, double *x, int *its, double *rnorm, double rtol);
 // outer BiCGStab (tp_bcgs.hip): same contract as fgmres; reasons 2, -3, -5 (breakdown), -9
-int bcgs(tp_ctx *c, const double *b, double *x, int *its, double *rnorm);
+int bcgs(tp_ctx *c, const double *b, double *x, int *its, double *rnorm, double rtol);
 void bcgs_check_options(const tp_options &o);
 void ksp_info(tp_ctx *c, int64_t out[4]);
 void basis_single_check_options(const tp_options &o);

@@ -6,7 +6,8 @@
 //   fgmres               = KSP fgmres, right PC, restart/max_it 200, classical Gram-Schmidt without
 //                          refinement (twophase.py:426-432)
 //   newton               = SNES newtonls with Firedrake's default `basic` line search
-//                          (thermalmodel.py:36-42,165), or the opt-in backtracking search `bt` (tp_options.ls_kind)
+//                          (thermalmodel.py:36-42,165), or the opt-in backtracking search `bt` (tp_options.ls_kind); opt-in
+//                          Eisenstat-Walker tolerances per linear solve (tp_options.ksp_ew, tp_ew.hpp)
 // The loops live here (C++) rather than in Python so that one Krylov iteration costs kernel time,
 // not interpreter time; the Python PC classes call the same stage functions through the C ABI.
 #include "tp_common.hpp"
@@ -558,7 +559,7 @@ static void hessenberg_solve(const std::vector<double> &H, const std::vector<dou
 // widened Vs, then W <- widen(Vs_{j+1} = (float)(w/||w||)) in place, which is the next v.  (2) A cycle also ends when its
 // recurrence residual reaches theta * beta_cycle: below that the rounded basis has lost its orthogonality and the recurrence
 // no longer tracks the residual.  (3) Convergence is only ever declared on the recomputed r = b - J x at a cycle's end.
-static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
+static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
     const GridDev &g = c->g;
     const int B = c->b;
     const long nv = (long)B * g.ntot, vs = basis_stride(c);
@@ -590,7 +591,7 @@ static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out,
     int its = 0;
     if (bnorm == 0.0) { *its_out = 0; *rnorm_out = 0.0; return 2; }
     if (!std::isfinite(bnorm)) { *its_out = 0; *rnorm_out = bnorm; return -9; }
-    const double tol = std::max(c->opt.ksp_rtol * bnorm, c->opt.ksp_atol);
+    const double tol = std::max(rtol * bnorm, c->opt.ksp_atol);
     double beta = bnorm;
     const double *rsrc = bvec;
     std::vector<double> H, cs, sn, gvec, hcol, yk;
@@ -678,11 +679,11 @@ static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out,
 }
 
 // ------------------------------------------------------------------------------------------------
-// FGMRES(m) from x0 = 0.  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
+// FGMRES(m) from x0 = 0 to the relative tolerance rtol (ksp_rtol, or the solve's eta under ksp_ew: tp_common.hpp).  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
 // (the other outer method, tp_options.ksp_kind = 1, is bcgs in tp_bcgs.hip)
 // (tp_options.ksp_basis_single: the fp32-basis form above; with the option off the loop below is untouched)
-int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out) {
-    if (c->opt.ksp_basis_single) return fgmres_single(c, bvec, x, its_out, rnorm_out);
+int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
+    if (c->opt.ksp_basis_single) return fgmres_single(c, bvec, x, its_out, rnorm_out, rtol);
     const GridDev &g = c->g;
     const int B = c->b;
     const long nv = (long)B * g.ntot;
@@ -710,7 +711,7 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
     int its = 0;
     if (bnorm == 0.0) { *its_out = 0; *rnorm_out = 0.0; return 2; }
     if (!std::isfinite(bnorm)) { *its_out = 0; *rnorm_out = bnorm; return -9; }
-    const double tol = std::max(c->opt.ksp_rtol * bnorm, c->opt.ksp_atol);
+    const double tol = std::max(rtol * bnorm, c->opt.ksp_atol);
     double beta = bnorm;
     const double *rsrc = bvec;
     std::vector<double> H, cs, sn, gvec, hcol, yk;
@@ -951,6 +952,12 @@ void newton(tp_ctx *c, tp_solve_info *info) {
     int nits = 0, lits = 0, reason = 0, kreason = 0;
     c->ls_lambda.clear(); c->ls_fnorm.clear(); c->ls_trials.clear();
     c->ls_evals = c->ls_nonfinite = 0;
+    // Eisenstat-Walker (tp_options.ksp_ew, tp_ew.hpp): eta_k of linear solve k from ||F_k||, ||F_{k-1}||, rho_{k-1}, eta_{k-1}.  The
+    // norms are the all-reduced ones, so every slab computes the same eta bit for bit.  Off: rtol below is ksp_rtol, as ever.
+    const bool ew = c->opt.ksp_ew != 0;
+    double ew_f_last = 0.0, ew_rho_last = 0.0, ew_eta_last = 0.0;
+    c->ew_rtol.clear(); c->ew_fnorm.clear(); c->ew_lresid.clear(); c->ew_kits.clear(); c->ew_kreason.clear();
+    if (ew) ++c->ew_solves;
     if (!std::isfinite(fnorm)) reason = -4;                      // SNES_DIVERGED_FNORM_NAN
     else if (fnorm < c->opt.snes_atol) reason = 2;               // SNES_CONVERGED_FNORM_ABS
     while (reason == 0) {
@@ -959,8 +966,21 @@ void newton(tp_ctx *c, tp_solve_info *info) {
         int kits = 0;
         double rn = 0.0;
         // (lits counts Krylov iterations: a BiCGStab iteration applies the preconditioner twice, vcycles counts per application)
-        kreason = c->opt.ksp_kind == 1 ? bcgs(c, c->R.p, dx->p, &kits, &rn) : fgmres(c, c->R.p, dx->p, &kits, &rn);
+        double rtol = c->opt.ksp_rtol;
+        if (ew) {
+            int fl = 0;
+            rtol = ew_next_rtol(c->opt, (int)c->ew_rtol.size(), fnorm, ew_f_last, ew_rho_last, ew_eta_last, &fl);
+            ++c->ew_lsolves;
+            if (fl & EW_SAFE_RAISED) ++c->ew_safeguard;
+        }
+        kreason = c->opt.ksp_kind == 1 ? bcgs(c, c->R.p, dx->p, &kits, &rn, rtol) : fgmres(c, c->R.p, dx->p, &kits, &rn, rtol);
         lits += kits;
+        if (ew) {
+            // (after an accepted bt step fnorm is the accepted trial's norm: the next eta sees it as ||F_{k+1}||)
+            c->ew_rtol.push_back(rtol); c->ew_fnorm.push_back(fnorm); c->ew_lresid.push_back(rn);
+            c->ew_kits.push_back(kits); c->ew_kreason.push_back(kreason);
+            ew_f_last = fnorm; ew_rho_last = rn; ew_eta_last = rtol;
+        }
         if (kreason < 0) { reason = -3; break; }                 // SNES_DIVERGED_LINEAR_SOLVE
         if (c->opt.ls_kind == 1) {                               // bt: backtracking from the full step (ls_backtrack above)
             double lam = 0.0, ynorm = 0.0, phi = 0.0, xsq = 0.0;

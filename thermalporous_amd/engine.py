@@ -9,6 +9,7 @@ Slab layout: each rank owns planes [off2, off2+n2) along internal axis 2 and sto
 with one halo plane per side (include/thermalporous_hip.h).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -47,7 +48,9 @@ class tp_options(C.Structure):
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("pc_order", C.c_int32),
-                ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double), ("ilu_whole", C.c_int32),
+                ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double),
+                ("ksp_ew", C.c_int32), ("ew_rtol0", C.c_double), ("ew_rtolmax", C.c_double), ("ew_gamma", C.c_double),
+                ("ew_alpha", C.c_double), ("ew_alpha2", C.c_double), ("ew_threshold", C.c_double), ("ilu_whole", C.c_int32),
                 ("amg_gs_levels", C.c_int32), ("amg_gs_sweeps", C.c_int32),
                 ("ilu_block", C.c_int32*3), ("ilu_single", C.c_int32),
                 ("ls_kind", C.c_int32), ("ls_order", C.c_int32), ("ls_max_it", C.c_int32), ("ls_alpha", C.c_double),
@@ -75,7 +78,7 @@ API_SYMBOLS = (
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
-    "tp_stage_rhs",
+    "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history",
 )
 
 DEFAULT_OPTS = dict(
@@ -139,13 +142,70 @@ DEFAULT_OPTS = dict(
     ls_maxstep=1e8,         # bt: first trial length <= ls_maxstep / ||dx||
     ls_minlambda=1e-12,     # bt: absolute smallest trial length, in [0, 1)
     ls_max_change=None,     # bt: (dp, dT, dS) caps on the change of p, T, S_o per Newton iteration (<= 0: no cap); None: off
+    # Eisenstat-Walker inexact Newton (include/thermalporous_hip.h: tp_options.ksp_ew; check_ew_options): the tolerance of every
+    # linear solve of a Newton solve chosen from the nonlinear residuals, ksp_rtol kept as its floor (snes_ksp_ew)
+    ksp_ew=False,           # False / 0: every linear solve to ksp_rtol | 1 | 2: the version (True: 2, PETSc's default)
+    ew_rtol0=0.3,           # eta of the first linear solve, in [0, 1)
+    ew_rtolmax=0.9,         # cap on eta, in [0, 1); ksp_rtol may not exceed it
+    ew_gamma=1.0,           # version 2: eta = gamma (||F_k|| / ||F_k-1||)^alpha, gamma in [0, 1]
+    ew_alpha=(1.0 + math.sqrt(5.0))/2.0,    # version 2: alpha in (1, 2]
+    ew_alpha2=(1.0 + math.sqrt(5.0))/2.0,   # version 1: the safeguard's exponent, in (1, 2]
+    ew_threshold=0.1,       # the safeguard acts when its term exceeds this, in (0, 1)
 )
 _LS = {"basic": 0, "bt": 1}
 _LS_DEFAULTS = dict(ls_order=3, ls_alpha=1e-4, ls_max_it=40, ls_maxstep=1e8, ls_minlambda=1e-12, ls_max_change=None)
 
 
+_EW_DEFAULTS = dict(ew_rtol0=0.3, ew_rtolmax=0.9, ew_gamma=1.0, ew_alpha=(1.0 + math.sqrt(5.0))/2.0,
+                    ew_alpha2=(1.0 + math.sqrt(5.0))/2.0, ew_threshold=0.1)
+
+
 def _is_number(v):
     return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def ew_version(v):
+    """ksp_ew as the version in effect: False / 0 -> 0 (off), True -> 2, 1 | 2 -> itself; 3 is PETSc's third version, not
+    implemented; anything else is a ValueError."""
+    if v is None or v is False or (isinstance(v, np.bool_) and not v):
+        return 0
+    if v is True or (isinstance(v, np.bool_) and v):
+        return 2
+    if _is_number(v) and float(v) == int(v):
+        if int(v) == 3:
+            raise NotImplementedError("ksp_ew = 3 (snes_ksp_ew_version 3) is not implemented: it needs the line search's predicted "
+                                      "and actual reduction; versions 1 and 2 are")
+        if int(v) in (0, 1, 2):
+            return int(v)
+    raise ValueError("ksp_ew = %r: False / 0 (off), 1, 2 or True (= 2)" % (v,))
+
+
+def check_ew_options(o):
+    """ksp_ew and the ew_* keys (tp_options.ksp_ew ...): ranges (PETSc's) with the option on; off, every ew_* key must keep its
+    default -- a value that would be ignored is refused."""
+    ver = ew_version(o.get("ksp_ew", False))
+    vals = {k: o.get(k, d) for k, d in _EW_DEFAULTS.items()}
+    if ver == 0:
+        for k, d in _EW_DEFAULTS.items():
+            if isinstance(vals[k], (bool, np.bool_)) or vals[k] != d:
+                raise ValueError("%s = %r with ksp_ew off: the key belongs to Eisenstat-Walker (it would be ignored)" % (k, vals[k]))
+        return
+    for k, v in vals.items():
+        if not _is_number(v) or float(v) != float(v):
+            raise ValueError("%s = %r: a number" % (k, v))
+    for k in ("ew_rtol0", "ew_rtolmax"):
+        if not 0.0 <= float(vals[k]) < 1.0:
+            raise ValueError("%s = %r: a number in [0, 1)" % (k, vals[k]))
+    if not 0.0 <= float(vals["ew_gamma"]) <= 1.0:
+        raise ValueError("ew_gamma = %r: a number in [0, 1]" % (vals["ew_gamma"],))
+    for k in ("ew_alpha", "ew_alpha2"):
+        if not 1.0 < float(vals[k]) <= 2.0:
+            raise ValueError("%s = %r: a number in (1, 2]" % (k, vals[k]))
+    if not 0.0 < float(vals["ew_threshold"]) < 1.0:
+        raise ValueError("ew_threshold = %r: a number in (0, 1)" % (vals["ew_threshold"],))
+    if float(o.get("ksp_rtol", 1e-7)) > float(vals["ew_rtolmax"]):
+        raise ValueError("ksp_rtol = %r exceeds ew_rtolmax = %r: ksp_rtol is the floor of the Eisenstat-Walker tolerance and "
+                         "would lie above its cap" % (o.get("ksp_rtol", 1e-7), vals["ew_rtolmax"]))
 
 
 def check_linesearch_options(o):
@@ -481,6 +541,7 @@ class HipEngine:
         check_ksp_reorth_options(self.opts)
         check_pc_order_options(self.opts)
         check_linesearch_options(self.opts)
+        check_ew_options(self.opts)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -534,9 +595,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        # (the line-search, refinement and stage-order fields stand in the middle of the struct: they are set by name, everything
-        # else in declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order"))]
+        # (the line-search, refinement, stage-order and Eisenstat-Walker fields stand in the middle of the struct: they are set by
+        # name, everything else in declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "ksp_ew", "ew_"))]
         vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
@@ -549,7 +610,8 @@ class HipEngine:
                           int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
-        return tp_options(**dict(zip(rest, vals)), pc_order=_PC_ORDER[o.get("pc_order", "SI")], ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
+        ew = {k: float(o.get(k, d)) for k, d in _EW_DEFAULTS.items()}
+        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
                           ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
                           ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
                           ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
@@ -569,6 +631,7 @@ class HipEngine:
         check_ksp_reorth_options({**self.opts, **kw})
         check_pc_order_options({**self.opts, **kw})
         check_linesearch_options({**self.opts, **kw})
+        check_ew_options({**self.opts, **kw})
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
         self._ck(self.lib.tp_set_options(self.ctx, C.byref(self._opt)))
@@ -939,11 +1002,47 @@ class HipEngine:
         """out = u0 - lam*dx on owned cells (tp_ls_trial); the halo planes of `out` are not written."""
         self._ck(self.lib.tp_ls_trial(self.ctx, self.vec(u0), self.vec(dx), C.c_double(float(lam)), self.vec(out)))
 
+    def ew_info(self):
+        """Eisenstat-Walker (tp_ew_info): the version in effect (0: off), Newton solves run under it since the engine was created,
+        linear solves among them, and those whose tolerance the safeguard raised."""
+        out = (C.c_int64*4)()
+        self._ck(self.lib.tp_ew_info(self.ctx, out))
+        return dict(version=out[0], newton_solves=out[1], linear_solves=out[2], safeguarded=out[3])
+
+    def ew_history(self, cap=256):
+        """Per linear solve of the last Newton solve (tp_ew_history): its tolerance eta, ||F|| where the system was formed, the
+        residual norm the Krylov solver returned, its iterations and KSP reason.  Empty after a solve with ksp_ew off."""
+        eta, fn, rho = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        kits, kre = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        n = C.c_int32()
+        ip = C.POINTER(C.c_int32)
+        self._ck(self.lib.tp_ew_history(self.ctx, int(cap), _dptr(eta), _dptr(fn), _dptr(rho), kits.ctypes.data_as(ip),
+                                        kre.ctypes.data_as(ip), C.byref(n)))
+        k = min(n.value, cap)
+        return dict(n=n.value, rtol=eta[:k].copy(), fnorm=fn[:k].copy(), lresid=rho[:k].copy(), kits=[int(v) for v in kits[:k]],
+                    kreason=[int(v) for v in kre[:k]])
+
+    @staticmethod
+    def ew_next_rtol(opts, k, fnorm, fnorm_last=0.0, lresid_last=0.0, rtol_last=0.0):
+        """The Eisenstat-Walker chooser on its own (tp_ew_next_rtol): the tolerance of linear solve k from engine options `opts`
+        (ksp_ew, the ew_* keys, ksp_rtol; anything missing at its default) and the norms.  No engine and no GPU needed."""
+        o = {**DEFAULT_OPTS, "ilu_tile": (1 << 30, 8, 8), **opts}
+        check_ew_options(o)
+        t = HipEngine._make_options(o)
+        out = C.c_double()
+        lib = load_library()
+        if lib.tp_ew_next_rtol(C.byref(t), C.c_int32(int(k)), C.c_double(float(fnorm)), C.c_double(float(fnorm_last)),
+                               C.c_double(float(lresid_last)), C.c_double(float(rtol_last)), C.byref(out)) != 0:
+            raise EngineError(lib.tp_last_error().decode())
+        return out.value
+
     def newton_solve(self):
         info = tp_solve_info()
         self._ck(self.lib.tp_newton_solve(self.ctx, C.byref(info)))
         self.last = dict(nits=info.nits, lits=info.lits, reason=info.reason, fnorm=info.fnorm, fnorm0=info.fnorm0,
                          ksp_reason=info.last_ksp_reason, vcycles=info.vcycles, ls_trials=self.ls_info()["evaluations"])
+        if self.opts.get("ksp_ew"):
+            self.last["ew_rtol"] = [float(v) for v in self.ew_history()["rtol"]]
         return self.last
 
     def close(self):

@@ -26,11 +26,16 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
   right), ksp_max_it k <= 32, ksp_rtol, ksp_atol -- also spelled pc_type ksp + ksp_<the same keys> -> s1_ksp, s1_max_it,
   s1_rtol, s1_atol.  The Schur / temperature solvers stay one V-cycle.
 
+  snes_ksp_ew (flag): Eisenstat-Walker inexact Newton, the tolerance of every linear solve chosen from the nonlinear residuals
+     (engine key ksp_ew = 1 | 2, True = 2), with snes_ksp_ew_version 1|2 (default 2; 3 is not implemented), snes_ksp_ew_rtol0,
+     _rtolmax, _gamma, _alpha, _alpha2, _threshold (PETSc's defaults and ranges) -> ew_rtol0 ... ew_threshold; any of them without
+     the flag raises.  Unlike PETSc the configured ksp_rtol stays as the tolerance's floor; ksp_rtol > rtolmax is a ValueError
+
 Defaults the reference inherits silently from Firedrake/PETSc are fixed here explicitly
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
 ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
 Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol, linesearch,
-ksp_reorth, ksp_reorth_eta, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+ksp_reorth, ksp_reorth_eta, ksp_ew, ew_rtol0, ew_rtolmax, ew_gamma, ew_alpha, ew_alpha2, ew_threshold, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -161,8 +166,8 @@ def _check_ilu_single(o):
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import (check_amg_gs_options, check_amg_line_options, check_ksp_basis_options, check_ksp_reorth_options,
-                         check_linesearch_options, check_pc_order_options)
+    from .engine import (check_amg_gs_options, check_amg_line_options, check_ew_options, check_ksp_basis_options,
+                         check_ksp_reorth_options, check_linesearch_options, check_pc_order_options)
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_amg_gs_options(o, exc=NotImplementedError)
@@ -170,6 +175,7 @@ def _check_inner(o):
     check_ksp_reorth_options(o)
     check_pc_order_options(o)
     check_linesearch_options(o)
+    check_ew_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
         raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
@@ -195,6 +201,51 @@ def _take(sp, used, key, allowed=None, default=None):
                                   % (key, v, ", ".join(repr(a) for a in allowed)))
     used.add(key)
     return v
+
+
+_EW_KEYS = (("snes_ksp_ew_rtol0", "ew_rtol0"), ("snes_ksp_ew_rtolmax", "ew_rtolmax"), ("snes_ksp_ew_gamma", "ew_gamma"),
+            ("snes_ksp_ew_alpha", "ew_alpha"), ("snes_ksp_ew_alpha2", "ew_alpha2"), ("snes_ksp_ew_threshold", "ew_threshold"))
+
+
+def _take_ew(sp, used, o, given):
+    """snes_ksp_ew (a flag: None or True; False is off) and snes_ksp_ew_version / _rtol0 / _rtolmax / _gamma / _alpha / _alpha2 /
+    _threshold -> ksp_ew and the ew_* keys.  A snes_ksp_ew_* key without the flag raises, as PETSc would silently ignore it; both
+    spellings given and disagreeing is a ValueError."""
+    from .engine import ew_version
+    flag = None
+    if "snes_ksp_ew" in sp:
+        v = sp["snes_ksp_ew"]
+        if not (v is None or isinstance(v, bool)):
+            raise ValueError("snes_ksp_ew = %r: a flag (None or True), or False for off; the version is snes_ksp_ew_version" % (v,))
+        flag = v is None or v
+        used.add("snes_ksp_ew")
+    sub_keys = [k for k in sp if k.startswith("snes_ksp_ew_")]
+    if sub_keys and not flag:
+        raise NotImplementedError("%s without snes_ksp_ew: the key belongs to the Eisenstat-Walker tolerances, which the flag "
+                                  "snes_ksp_ew switches on (it would be silently ignored)" % sorted(sub_keys)[0])
+    if flag is None:
+        return
+    ver = 0
+    if flag:
+        ver = sp.get("snes_ksp_ew_version", 2)
+        if "snes_ksp_ew_version" in sp:
+            used.add("snes_ksp_ew_version")
+        if isinstance(ver, bool) or ver not in (1, 2, 3):
+            raise ValueError("snes_ksp_ew_version = %r: 1 or 2 (3 is not implemented)" % (ver,))
+        if ver == 3:
+            raise NotImplementedError("snes_ksp_ew_version 3 is not implemented: it needs the line search's predicted and actual "
+                                      "reduction; versions 1 and 2 are")
+    if "ksp_ew" in given and ew_version(o["ksp_ew"]) != ver:
+        raise ValueError("Eisenstat-Walker is configured twice and differently: ksp_ew = %r, but snes_ksp_ew = %r%s says %s"
+                         % (o["ksp_ew"], sp["snes_ksp_ew"], " with snes_ksp_ew_version %r" % sp["snes_ksp_ew_version"]
+                            if "snes_ksp_ew_version" in sp else "", "version %d" % ver if ver else "off"))
+    o["ksp_ew"] = ver
+    for k_src, k_dst in _EW_KEYS:
+        if k_src in sp:
+            if k_dst in given and o[k_dst] != sp[k_src]:
+                raise ValueError("Eisenstat-Walker is configured twice and differently: %s = %r, %s = %r" % (k_dst, o[k_dst], k_src, sp[k_src]))
+            o[k_dst] = sp[k_src]
+            used.add(k_src)
 
 
 def _reject_schur_krylov(sp, prefix):
@@ -236,7 +287,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
-                  "pc_order", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
+                  "pc_order", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
+                  "ksp_ew", "ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
     for k in build_keys:
         if k in sp:
             o[k] = sp.pop(k)
@@ -260,6 +312,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
                                           "(it would be silently ignored)" % k_src)
             o[k_dst] = sp[k_src]
             used.add(k_src)
+    _take_ew(sp, used, o, solver_parameters)
     _take(sp, used, "mat_type", ("aij",))
     ksp = _take(sp, used, "ksp_type", ("fgmres", "gmres", "fbcgs", "bcgs"), "gmres")
     side = _take(sp, used, "ksp_pc_side", ("right",))
