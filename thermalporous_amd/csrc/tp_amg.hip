@@ -316,7 +316,18 @@ struct LevelDevT {
     int axis;
     int pre, post;           // smoothing sweeps of this level: V(pre, post); post == 0: pure transfer level
     int pad_;
+    double omega;            // damping the set-up built invd with: invd[c] = (R)(omega / diag[c]) at every owned cell (k_amg_weights)
 };
+
+// omega / diag of an OWNED cell c without reading the stored plane: a kernel that streams the diagonal anyway recomputes in
+// registers what k_amg_weights stored -- the same correctly rounded division, the same rounding to R, so the same bits -- and
+// saves one plane in eleven of a Jacobi sweep.  (REG = false: the stored plane, TP_AMG_INVD_LOAD=1; kernels that read invd at
+// neighbours -- halo cells have a zero diagonal -- and the line, Gauss-Seidel and tail kernels always read the plane.)
+template <class R, bool REG>
+__device__ __forceinline__ double invd_at(const LevelDevT<R> &L, long c) {
+    if constexpr (REG) return (double)(R)(L.omega / (double)L.op.slot(0)[c]);
+    else return (double)L.invd[c];
+}
 
 __device__ __forceinline__ void nb_offsets(const GridDev &g, long (&off)[7]) {
     off[0] = 0; off[1] = -1; off[2] = 1; off[3] = -(long)g.n0; off[4] = g.n0; off[5] = -g.np; off[6] = g.np;
@@ -338,7 +349,7 @@ __device__ __forceinline__ double pre2_cell(const LevelDevT<R> &L, const double 
     return x1 + L.invd[c] * (b[c] - s);
 }
 
-template <class R>
+template <class R, bool REG = false>
 __device__ __forceinline__ double jacobi_cell(const LevelDevT<R> &L, const double *__restrict__ b,
                                               const double *__restrict__ x, long tid) {
     const long c = L.g.np + tid;
@@ -347,7 +358,7 @@ __device__ __forceinline__ double jacobi_cell(const LevelDevT<R> &L, const doubl
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) s += L.op.slot(k)[c] * x[c + off[k]];
-    return x[c] + L.invd[c] * (b[c] - s);
+    return x[c] + invd_at<R, REG>(L, c) * (b[c] - s);
 }
 
 template <class R>
@@ -436,7 +447,7 @@ __device__ __forceinline__ double prolong_val(const LevelDevT<R> &Lf, const Grid
     return (1.0 - fF) * e0 + fF * (wm * e0 + fR * (wp * e1));
 }
 
-template <class R>
+template <class R, bool REG = false>
 __device__ __forceinline__ double prolong_jacobi_cell(const LevelDevT<R> &Lf, const GridDev &gc,
                                                       const double *__restrict__ b, const double *x,
                                                       const double *__restrict__ ec, long tid) {
@@ -465,7 +476,7 @@ __device__ __forceinline__ double prolong_jacobi_cell(const LevelDevT<R> &Lf, co
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) s += (double)Lf.op.slot(k)[c] * v[k];
-    return v[0] + (double)Lf.invd[c] * (b[c] - s);
+    return v[0] + invd_at<R, REG>(Lf, c) * (b[c] - s);
 }
 
 // ---- two levels at once: a smoothed level l followed by a pure transfer level l+1 (amg_mid_skip) ------------
@@ -527,7 +538,7 @@ __device__ __forceinline__ double prolong2_val(const LevelDevT<R> &L0, const Lev
     return (1.0 - fF) * v0 + fF * (wm * v0 + fR * (wp * v1));
 }
 // x' = P_l P_{l+1} e2 ;  out = x' + invd (b - A x')     (level l has no pre-smoothing)
-template <class R>
+template <class R, bool REG = false>
 __device__ __forceinline__ double prolong2_jacobi_cell(const LevelDevT<R> &L0, const LevelDevT<R> &L1, const GridDev &g2,
                                                        const double *__restrict__ b, const double *__restrict__ e2,
                                                        long tid) {
@@ -549,7 +560,7 @@ __device__ __forceinline__ double prolong2_jacobi_cell(const LevelDevT<R> &L0, c
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) s += (double)L0.op.slot(k)[c] * v[k];
-    return v[0] + (double)L0.invd[c] * (b[c] - s);
+    return v[0] + invd_at<R, REG>(L0, c) * (b[c] - s);
 }
 
 // ---- per-level kernels (big levels) -----------------------------------------------------------------
@@ -560,11 +571,11 @@ __global__ __launch_bounds__(256) void k_amg_pre(LevelDevT<R> L, const double *b
     const long c = L.g.np + tid;
     out[c] = two ? pre2_cell(L, b, tid) : L.invd[c] * b[c];
 }
-template <class R>
+template <class R, bool REG>
 __global__ __launch_bounds__(256) void k_amg_jacobi(LevelDevT<R> L, const double *b, const double *x, double *out) {
     const long tid = xcd_tid();
     if (tid >= L.g.nown) return;
-    out[L.g.np + tid] = jacobi_cell(L, b, x, tid);
+    out[L.g.np + tid] = jacobi_cell<R, REG>(L, b, x, tid);
 }
 template <class R>
 __global__ __launch_bounds__(256) void k_amg_resid_restrict(LevelDevT<R> Lf, GridDev gc, const double *b,
@@ -573,12 +584,12 @@ __global__ __launch_bounds__(256) void k_amg_resid_restrict(LevelDevT<R> Lf, Gri
     if (tid >= gc.nown) return;
     rc[gc.np + tid] = resid_restrict_cell(Lf, gc, b, x, tid);
 }
-template <class R>
+template <class R, bool REG>
 __global__ __launch_bounds__(256) void k_amg_prolong_jacobi(LevelDevT<R> Lf, GridDev gc, const double *b,
                                                             const double *x, const double *ec, double *out) {
     const long tid = xcd_tid();
     if (tid >= Lf.g.nown) return;
-    out[Lf.g.np + tid] = prolong_jacobi_cell(Lf, gc, b, x, ec, tid);
+    out[Lf.g.np + tid] = prolong_jacobi_cell<R, REG>(Lf, gc, b, x, ec, tid);
 }
 
 template <class R>
@@ -588,12 +599,12 @@ __global__ __launch_bounds__(256) void k_amg_restrict2(LevelDevT<R> L0, LevelDev
     if (tid >= g2.nown) return;
     rc[g2.np + tid] = restrict2_cell(L0, L1, g2, r, tid);
 }
-template <class R>
+template <class R, bool REG>
 __global__ __launch_bounds__(256) void k_amg_prolong2_jacobi(LevelDevT<R> L0, LevelDevT<R> L1, GridDev g2, const double *b,
                                                              const double *e2, double *out) {
     const long tid = xcd_tid();
     if (tid >= L0.g.nown) return;
-    out[L0.g.np + tid] = prolong2_jacobi_cell(L0, L1, g2, b, e2, tid);
+    out[L0.g.np + tid] = prolong2_jacobi_cell<R, REG>(L0, L1, g2, b, e2, tid);
 }
 
 // unfused variants for the top levels, where the fused kernels are issue-bound rather than HBM-bound
@@ -1123,6 +1134,7 @@ static LevelDevT<R> dev_of(const Amg *amg, int level) {
     d.invd = (const R *)L->invd.p; d.wm = (const R *)L->wm.p; d.wp = (const R *)L->wp.p;
     d.b = L->b.p; d.x = L->x.p; d.x2 = L->x2.p; d.e = L->e.p;
     d.axis = L->axis;
+    d.omega = amg->omega;
     return d;
 }
 
@@ -1253,6 +1265,7 @@ template <class R>
 static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     AmgLevel *L0 = amg->lv[0];
     const int lg = amg->plan.dist_levels;
+    amg->omega = c->opt.amg_omega;      // what k_amg_weights below builds invd with (LevelDevT::omega)
     if (sizeof(R) == sizeof(double)) {
         L0->op = A0;                     // zero-copy view of the Jacobian planes
     } else {
@@ -1380,6 +1393,13 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     std::vector<double *> xs(nlev, nullptr);       // pre-smoothed iterate of each big level (null: none)
     // level l (smoothed, no pre-sweeps) + level l+1 (pure transfer): both transfers in one launch each way
     static const bool pair_on = !(getenv("TP_AMG_PAIR") && atoi(getenv("TP_AMG_PAIR")) == 0);
+    // the sweeps' centre-cell omega / diag: recomputed in registers (invd_at), or TP_AMG_INVD_LOAD=1: read from the stored plane
+    static const bool invd_reg = !(getenv("TP_AMG_INVD_LOAD") && atoi(getenv("TP_AMG_INVD_LOAD")) != 0);
+#define TP_AMG_REG_LAUNCH(KERNEL, ...)                                                                         \
+    do {                                                                                                       \
+        if (invd_reg) hipLaunchKernelGGL((KERNEL<R, true>), __VA_ARGS__);                                      \
+        else hipLaunchKernelGGL((KERNEL<R, false>), __VA_ARGS__);                                              \
+    } while (0)
     auto paired = [&](int l) {
         if (!pair_on || l < lg || l + 2 > lt || amg->lv[l]->g.nown >= amg->fuse_below) return false;
         if (trunc >= 0 && l + 2 > trunc) return false;          // (the truncation level is among the V(nu,nu) levels: never paired)
@@ -1464,7 +1484,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             hipLaunchKernelGGL(k_amg_pre<R>, gr, bl, 0, c->stream, Ld, bl_, Ld.pre >= 2 ? 1 : 0, cur);
             for (int k = 2; k < Ld.pre; ++k) {
                 hx(l, cur);
-                hipLaunchKernelGGL(k_amg_jacobi<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)cur, oth);
+                TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)cur, oth);
                 std::swap(cur, oth);
             }
             }
@@ -1535,12 +1555,12 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         if (l >= 1 && paired(l - 1)) continue;      // transfer-only level folded into its parent's launch
         if (paired(l)) {
             AmgLevel *L2 = amg->lv[l + 2];
-            hipLaunchKernelGGL(k_amg_prolong2_jacobi<R>, gr, bl, 0, c->stream, Ld, dev_of<R>(amg, l + 1), L2->g, bl_,
+            TP_AMG_REG_LAUNCH(k_amg_prolong2_jacobi, gr, bl, 0, c->stream, Ld, dev_of<R>(amg, l + 1), L2->g, bl_,
                                (const double *)L2->e.p, dst);
             for (int k = 1; k < Ld.post; ++k) {
                 src = dst;
                 dst = (k == Ld.post - 1) ? out : (src == L->x.p ? L->x2.p : L->x.p);
-                hipLaunchKernelGGL(k_amg_jacobi<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
+                TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
             }
             continue;
         }
@@ -1569,17 +1589,18 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         if (src && L->g.nown >= amg->fuse_below) {
             hipLaunchKernelGGL(k_amg_prolong_add<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, src);
             hx(l, src);
-            hipLaunchKernelGGL(k_amg_jacobi<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
+            TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
         } else {
-            hipLaunchKernelGGL(k_amg_prolong_jacobi<R>, gr, bl, 0, c->stream, Ld, cv.g, bl_, (const double *)src, ec, dst);
+            TP_AMG_REG_LAUNCH(k_amg_prolong_jacobi, gr, bl, 0, c->stream, Ld, cv.g, bl_, (const double *)src, ec, dst);
         }
         for (int k = 1; k < Ld.post; ++k) {
             src = dst;
             dst = (k == Ld.post - 1) ? out : (src == L->x.p ? L->x2.p : L->x.p);
             hx(l, src);
-            hipLaunchKernelGGL(k_amg_jacobi<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
+            TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
         }
     }
+#undef TP_AMG_REG_LAUNCH
     TP_HIP(hipGetLastError());
 }
 

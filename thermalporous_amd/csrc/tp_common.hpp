@@ -214,6 +214,7 @@ struct Amg {
     DBuf<double> coarse_inv;   // dense inverse on the coarsest grid
     int ncoarse = 0;
     bool single = false;       // operators / weights / inverse diagonals stored in fp32
+    double omega = 0.0;        // amg_omega of the last set-up: invd = omega / diag (LevelDevT::omega)
     int tail_lds = 0;          // doubles per LDS-resident vector set of the tail (0: tail vectors stay in global memory)
     long fuse_below = 200000;  // levels with fewer cells use the fused (launch-saving) kernels
     // relaxation-only truncation (tp_options.amg_dom_tau): dominance ratios of the V(nu,nu) levels, measured by the set-up

@@ -17,6 +17,11 @@ __global__ void k_copy(const double *x, double *y, long n) {
     const long i = (long)blockIdx.x * TP_BLOCK + threadIdx.x;
     if (i < n) y[i] = x[i];
 }
+// field of owned entry t in [0, nf * nown) for nf <= 3 (every launch site: nf = tp_ctx::b): two comparisons.  A 64-bit division
+// is ~150 instructions on this ISA, and in the Gram-Schmidt kernels every chunk's first load waited behind its own
+// (k_ls_trial below has always done it this way)
+__device__ __forceinline__ long field_of(long t, long nown) { return (long)(t >= nown) + (long)(t >= 2 * nown); }
+#define TP_REQUIRE_NF3(nf) TP_REQUIRE((nf) >= 1 && (nf) <= 3, "the vector kernels take the field index from two comparisons: at most 3 fields")
 // y[f][c] (+)= a*x[f][c] over owned cells of nf fields
 template <bool ACC>
 __global__ void k_axpy_owned(GridDev g, int nf, double a, const double *x, double *y) {
@@ -45,11 +50,12 @@ __global__ void k_scale_dev_norm(GridDev g, int nf, const double *__restrict__ n
     if (t >= g.nown * nf) return;
     const double n2 = *n2p;
     const double a = (n2 > 0.0 && isfinite(n2)) ? 1.0 / sqrt(n2) : 0.0;
-    const long f = t / g.nown, i = t - f * g.nown;
+    const long f = field_of(t, g.nown), i = t - f * g.nown;
     const long c = f * g.ntot + g.np + i;
     x[c] = a * x[c];
 }
 void vec_scale_dev_norm(tp_ctx *c, int nf, const double *n2_dev, double *x) {
+    TP_REQUIRE_NF3(nf);
     hipLaunchKernelGGL(k_scale_dev_norm, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, n2_dev, x);
 }
 
@@ -93,7 +99,7 @@ __global__ __launch_bounds__(256) void k_multi_dot(GridDev g, int nf, const doub
         const long t = (wave * MD_CHUNK + j) * 64 + lane;
         ok[j] = t < nall;
         const long tt = ok[j] ? t : 0;
-        const long f = tt / g.nown, i = tt - f * g.nown;
+        const long f = field_of(tt, g.nown), i = tt - f * g.nown;
         idx[j] = f * g.ntot + g.np + i;              // (tail lanes: entry 0 -- a valid address, weight 0)
         wv[j] = ok[j] ? w[idx[j]] : 0.0;
     }
@@ -210,6 +216,7 @@ static void reduce_to_host(tp_ctx *c, long nw, int n, double *host_out) {
 
 void multi_dot(tp_ctx *c, int nf, const double *V, long vstride, int k, const double *w, const double *w2,
                double *host_out) {
+    TP_REQUIRE_NF3(nf);
     const long nw = md_nwaves(c, nf);
     const int nout = k + (w2 ? 1 : 0);
     if ((long)c->gs_partial.n < (long)nout * nw) c->gs_partial.alloc((size_t)(nout + 32) * nw);
@@ -222,6 +229,7 @@ void multi_dot(tp_ctx *c, int nf, const double *V, long vstride, int k, const do
 // ||x_i||^2 of several vectors with ONE reduction launch, ONE all-reduce and ONE host sync (the three norms of SNES's
 // convergence test: ||F||, ||dx||, ||u||; each used to cost its own sync and -- on several GPUs -- its own all-reduce)
 void multi_norm2sq(tp_ctx *c, int nf, int nvec, const double *const *x, double *host_out) {
+    TP_REQUIRE_NF3(nf);
     const long nw = md_nwaves(c, nf);
     if ((long)c->gs_partial.n < (long)nvec * nw) c->gs_partial.alloc((size_t)(nvec + 32) * nw);
     if ((long)c->red_out.n < nvec) c->red_out.alloc(nvec + 64);
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(256) void k_multi_axpy_norm(GridDev g, int nf, cons
         const long t = (wave * MD_CHUNK + j) * 64 + lane;
         ok[j] = t < nall;
         const long tt = ok[j] ? t : 0;
-        const long f = tt / g.nown, i = tt - f * g.nown;
+        const long f = field_of(tt, g.nown), i = tt - f * g.nown;
         idx[j] = f * g.ntot + g.np + i;
         s[j] = 0.0;
         w0[j] = w[idx[j]];
@@ -379,7 +387,7 @@ __global__ __launch_bounds__(256) void k_multi_dot_p(const long long *__restrict
         const long t = (wave * MD_CHUNK + j) * 64 + lane;
         const bool ok = t < nall;
         const long tt = ok ? t : 0;
-        const long f = tt / g.nown, i = tt - f * g.nown;
+        const long f = field_of(tt, g.nown), i = tt - f * g.nown;
         idx[j] = f * g.ntot + g.np + i;              // (tail lanes: entry 0 -- a valid address, weight 0)
         wv[j] = ok ? w[idx[j]] : 0.0;
     }
@@ -461,7 +469,7 @@ __global__ __launch_bounds__(256) void k_multi_axpy_norm_p(const long long *__re
         const long t = (wave * MD_CHUNK + j) * 64 + lane;
         ok[j] = t < nall;
         const long tt = ok[j] ? t : 0;
-        const long f = tt / g.nown, i = tt - f * g.nown;
+        const long f = field_of(tt, g.nown), i = tt - f * g.nown;
         idx[j] = f * g.ntot + g.np + i;
         s[j] = 0.0;
         w0[j] = w[idx[j]];
@@ -572,7 +580,7 @@ __device__ __forceinline__ void bs_lane_entries(const GridDev &g, long nall, lon
             const long t = t0 + e;
             ok[q][e] = t < nall;
             const long tt = ok[q][e] ? t : 0;
-            const long f = tt / g.nown, i = tt - f * g.nown;
+            const long f = field_of(tt, g.nown), i = tt - f * g.nown;
             idx[q][e] = f * g.ntot + g.np + i;
         }
     }
@@ -733,7 +741,7 @@ __global__ void k_scale_store(GridDev g, int nf, double a_host, const double *__
         const double n2 = *n2p;
         a = (n2 > 0.0 && isfinite(n2)) ? 1.0 / sqrt(n2) : 0.0;
     }
-    const long f = t / g.nown, i = t - f * g.nown;
+    const long f = field_of(t, g.nown), i = t - f * g.nown;
     const long c = f * g.ntot + g.np + i;
     const float r = (float)(a * x[c]);
     slot[t] = r;
@@ -744,9 +752,11 @@ void basis_round_store(tp_ctx *c, int nf, double *z, float *slot) {
     hipLaunchKernelGGL(k_round_store, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, z, slot);
 }
 void basis_scale_store(tp_ctx *c, int nf, double a, const double *x, double *y, float *slot) {
+    TP_REQUIRE_NF3(nf);
     hipLaunchKernelGGL(k_scale_store<false>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, a, (const double *)nullptr, x, y, slot);
 }
 void basis_scale_store_dev(tp_ctx *c, int nf, const double *n2_dev, double *x, float *slot) {
+    TP_REQUIRE_NF3(nf);
     hipLaunchKernelGGL(k_scale_store<true>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, 0.0, n2_dev, (const double *)x, x, slot);
 }
 
@@ -774,6 +784,7 @@ static int basis_vec() {
     } while (0)
 
 void multi_dot_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *w, double *host_out) {
+    TP_REQUIRE_NF3(nf);
     const long nw = md_nwaves(c, nf);
     if ((long)c->gs_partial.n < (long)k * nw) c->gs_partial.alloc((size_t)(k + 32) * nw);
     if ((long)c->red_out.n < k) c->red_out.alloc(k + 64);
@@ -801,6 +812,7 @@ void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const
 // turns the second dot pass round (for measuring; same sums either way).
 static void reorth_pass(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, long nw, double *pin, int mode,
                         double eta, int gs_rev) {
+    TP_REQUIRE_NF3(nf);
     TP_REQUIRE(V, "ksp_reorth needs the fp64 Krylov basis");
     if (c->ro_stat.n < 4) c->ro_stat.alloc(4);
     if ((long)c->ro_c.n < k + 1) c->ro_c.alloc(k + 65);
@@ -828,6 +840,7 @@ static void reorth_pass(tp_ctx *c, int nf, const double *V, long vstride, int k,
 // everything around them -- partial sums, second stages, all-reduces, hand-over to the host -- is the same)
 static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *Vs, long vstride, int k, double *w, double *host_out,
                               int ro = 0, double ro_eta = 0.0) {
+    TP_REQUIRE_NF3(nf);
     const long nw = md_nwaves(c, nf);
     ++c->ro_steps;
     if ((long)c->gs_partial.n < (long)(k + 1) * nw) c->gs_partial.alloc((size_t)(k + 33) * nw);
