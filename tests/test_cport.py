@@ -189,3 +189,66 @@ def test_cport_fgmres_restart_and_limit_match_numpy_oracle(restart, maxit):
     assert (reason_c, its_c) == (reason_o, its_o)
     assert abs(rn_c - hist[-1]) <= 1e-10*np.linalg.norm(F)
     assert rel2(d_c, d_o) < 1e-8
+
+
+# ---- the hand-built source lists and edge states of tests/edge_cases.py ------------------------------------------------
+# (the full-size GPU tests use this port as their checker: it must be right where the rate laws switch branch too)
+def _twins(spec, opts, u, dt):
+    o, c = OracleEngine(spec, opts), CPortEngine(spec, opts)
+    for e in (o, c):
+        e.set_old(u)
+        e.set_dt(dt)
+        e.set_state(u)
+    return o, c
+
+
+@pytest.mark.parametrize("nphase,pc", [(1, "fieldsplit_cd"), (2, "cptr")])
+def test_cport_matches_numpy_oracle_on_isolated_source_branches(nphase, pc):
+    """Every branch of the rate laws (edge_cases.branch_sources: 70 groups, 91 entries) with all fluxes switched off and S at
+    0, 1, -0.05, 1.05: residual and diagonal block per cell, scaled by the cell's own block row (edge_cases.per_cell_scales)."""
+    import edge_cases as ec
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=7, Nz=5, nphase=nphase)
+    u = ec.edge_state(spec, 3, "sat")
+    spec = ec.sources_only(ec.branch_sources(spec, 7, 70, u))
+    npea, ncap, nshut = ec.check_cap_margin(spec, u)
+    assert npea >= 8 and ncap >= 8 and nshut >= 8 + 2
+    if nphase == 2:
+        assert len(ec.sat_pairs_across_faces(spec, u)) == 6
+        assert set(ec.SAT_EDGES) <= set(u[2].reshape(-1)[spec["sources"]["cell"]])
+    o, c = _twins(spec, dict(pc=pc), u, ec.SOURCES_ONLY_DT)
+    Ro, (Jo, So) = o.residual(), o.jacobian(want_schur=True)
+    Rc, (Jc, Sc) = c.residual(), c.jacobian(want_schur=True)
+    assert np.isfinite(Ro).all() and np.isfinite(Jo).all() and np.isfinite(So).all()
+    assert np.abs(Jo[1:]).max() == 0.0 and np.abs(Jc[1:]).max() == 0.0 and np.abs(Sc[1:]).max() == 0.0
+    eR, eJ = ec.per_cell_errors(o.prob, u, Rc, Jc, Ro, Jo)
+    # 1e-12, not the 1e-13 of the per-plane checks: nothing larger in the plane hides a cell here, and dS of a producer's
+    # water/oil split carries the rounding of both viscosity laws times mu_o/mu_w ~ 1e3 (measured: 3e-13 at S = 1)
+    assert eR <= 1e-12 and eJ <= 1e-12, (eR, eJ)
+    assert (np.abs(Sc[0] - So[0]) <= 1e-12*np.abs(So[0])).all()
+
+
+@pytest.mark.parametrize("nphase", [1, 2])
+@pytest.mark.parametrize("kind", ["sat", "ties", "dead"])
+def test_cport_matches_numpy_oracle_at_edge_states(nphase, kind):
+    """The whole operator with the branch sources at the assembly's edge states: S outside [0, 1], exact upwind ties that carry
+    information, an interior block of zero transmissibility (and zero conductivity / porosity 0 and 1)."""
+    import edge_cases as ec
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=7, Nz=5, nphase=nphase)
+    if kind == "dead":
+        spec = ec.dead_block(spec)
+        u = cases.perturbed_state(spec, seed=3)
+    else:
+        u = ec.edge_state(spec, 3, kind)
+    spec = ec.branch_sources(spec, 7, 70, u)
+    ec.check_cap_margin(spec, u)
+    if kind == "ties":
+        assert ec.check_ties(spec, u) > 0
+    o, c = _twins(spec, dict(pc="cptr" if nphase == 2 else "fieldsplit_cd"), u, 8640.0)
+    Ro, (Jo, So) = o.residual(), o.jacobian(want_schur=True)
+    Rc, (Jc, Sc) = c.residual(), c.jacobian(want_schur=True)
+    assert np.isfinite(Ro).all() and np.isfinite(Jo).all() and np.isfinite(So).all()
+    for f in range(o.b):
+        assert np.abs(Rc[f] - Ro[f]).max() <= 1e-13*np.abs(Ro[f]).max()
+        for q in range(o.b):
+            assert np.abs(Jc[:, f, q] - Jo[:, f, q]).max() <= 1e-13*np.abs(Jo[:, f, q]).max()
+    assert np.abs(Sc - So).max() <= 1e-13*np.abs(So).max()

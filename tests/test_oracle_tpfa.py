@@ -158,3 +158,47 @@ def test_schur_operator_is_frozen_energy_block():
     # off-diagonal entries: pure conduction (no flow): identical in S~ and J_TT
     for s in range(1, 5):
         assert np.allclose(Sm[s], J[s, 1, 1], rtol=1e-12, atol=1e-14*np.abs(Sm).max())
+
+
+@pytest.mark.parametrize("nphase", [1, 2])
+@pytest.mark.parametrize("kind", ["sat", "ties", "dead"])
+def test_analytic_jacobian_equals_complex_step_at_edge_states(nphase, kind):
+    """The reference of the GPU edge tests is well defined where they look: with every rate branch present
+    (edge_cases.branch_sources), at S = 0, 1, -0.05, 1.05, at exact upwind ties and around a block of zero transmissibility
+    the analytic Jacobian equals the complex-step one and everything stays finite."""
+    import edge_cases as ec
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=7, Nz=5, nphase=nphase)
+    if kind == "dead":
+        spec = ec.dead_block(spec)
+        u = cases.perturbed_state(spec, seed=3)
+    else:
+        u = ec.edge_state(spec, 3, kind)
+    spec = ec.branch_sources(spec, 7, 70, u)
+    ec.check_cap_margin(spec, u)
+    P = Problem(spec)
+    P.set_old(u)
+    P.set_dt(8640.0)
+    R, J = P.residual(u), P.jacobian(u)
+    Jc = P.jacobian_complex_step(u)
+    assert np.isfinite(R).all() and np.isfinite(J).all()
+    assert np.abs(J - Jc).max() <= 1e-13*np.abs(Jc).max()
+
+
+@pytest.mark.parametrize("nphase", [1, 2])
+def test_exact_upwind_ties_carry_information(nphase):
+    """At edge_state("ties") at least 10 % of the faces of every non-gravity axis have Phi == 0 exactly with different T on both
+    sides, and sending those ties to the '+' side instead of the '-' side changes the Jacobian's energy row: agreement with
+    this oracle distinguishes gt from ge in the upwind choice."""
+    import edge_cases as ec
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=7, Nz=5, nphase=nphase)
+    u = ec.edge_state(spec, 3, "ties")
+    assert ec.check_ties(spec, u) > 0
+    Js = []
+    for cls in (Problem, ec.PlusTieProblem):
+        P = cls(spec)
+        P.set_old(u)
+        P.set_dt(8640.0)
+        Js.append(P.jacobian(u))
+    # (at a tie F == 0 and only dF/dp = T^K L_up dPhi/dp is left: the p column of every row sees the upwind side)
+    for r in range(P.b):
+        assert np.abs(Js[1][:, r, 0] - Js[0][:, r, 0]).max() > 1e-3*np.abs(Js[0][:, r, 0]).max(), r

@@ -24,6 +24,7 @@ namespace tp {
 template <int NPH>
 struct Props {
     double p, T, S;
+    double rf1, rf2;              // ro = rf1 * rf2 (oil_rho_factors)
     double ro, ro_p, ro_T;
     double Lo[4];                 // kr_o rho_o / mu_o and d/d(p,T,S)
     double rw, rw_p, rw_T;
@@ -37,7 +38,8 @@ __device__ __forceinline__ Props<NPH> eval_props(double p, double T, double S, d
                                                  const DevPrm &q) {
     Props<NPH> r;
     r.p = p; r.T = T; r.S = S;
-    oil_rho(p, T, q, r.ro, r.ro_p, r.ro_T);
+    oil_rho_factors(p, T, q, r.rf1, r.rf2);
+    oil_rho_from(r.rf1, r.rf2, r.ro, r.ro_p, r.ro_T);
     double mo, mo_T;
     oil_mu(T, q, mo, mo_T);
     r.mo = mo;
@@ -262,21 +264,24 @@ __global__ __launch_bounds__(256) void k_assemble(AsmArgs a) {
 // A workgroup of 256 threads owns a 16 x 4 x 4 tile of cells.  Phase 1 evaluates the closures ONCE per cell of the tile and
 // of its six face halos (544 evaluations for 256 cells: 2.1 per cell instead of the 7 of k_assemble) into an LDS image,
 // structure-of-arrays [value][slot of the 18 x 6 x 6 box]; phase 2 is k_assemble's cell body with every Props read from the
-// LDS.  Same functions on the same inputs: results are bitwise those of k_assemble.  Measured on C4.
+// LDS.  Same functions on the same inputs: results are bitwise those of k_assemble (tests/test_gpu_assembly_edges.py).  For that
+// the image holds the oil density as its two factors, not as their product: rho_o goes straight into the sum rho+ + rho- of the
+// driving force, and under -ffp-contract=fast k_assemble, which inlines eval_props, contracts product and sum into one fma; a
+// product rounded into the image first gave another last bit in a few entries.  Measured on C4.
 constexpr int ATX = 16, ATY = 4, ATZ = 4, ABX = ATX + 2, ABY = ATY + 2, ABZ = ATZ + 2, ANS = ABX * ABY * ABZ;
 template <int NPH> struct PropsLds {
-    static constexpr int NV = NPH == 2 ? 19 : 9;
+    static constexpr int NV = NPH == 2 ? 18 : 8;
     static __device__ __forceinline__ void put(double *l, int s, const Props<NPH> &r) {
         int v = 0;
         auto w = [&](double x) { l[(v++) * ANS + s] = x; };
-        w(r.p); w(r.T); w(r.ro); w(r.ro_p); w(r.ro_T); w(r.Lo[0]); w(r.Lo[1]); w(r.Lo[2]); w(r.kT);
+        w(r.p); w(r.T); w(r.rf1); w(r.rf2); w(r.Lo[0]); w(r.Lo[1]); w(r.Lo[2]); w(r.kT);
         if (NPH == 2) { w(r.S); w(r.Lo[3]); w(r.rw); w(r.rw_p); w(r.rw_T); w(r.Lw[0]); w(r.Lw[1]); w(r.Lw[2]); w(r.Lw[3]); w(r.kT_S); }
     }
     static __device__ __forceinline__ Props<NPH> get(const double *l, int s) {
         Props<NPH> r;
         int v = 0;
         auto rd = [&]() { return l[(v++) * ANS + s]; };
-        r.p = rd(); r.T = rd(); r.ro = rd(); r.ro_p = rd(); r.ro_T = rd(); r.Lo[0] = rd(); r.Lo[1] = rd(); r.Lo[2] = rd(); r.kT = rd();
+        r.p = rd(); r.T = rd(); r.rf1 = rd(); r.rf2 = rd(); oil_rho_from(r.rf1, r.rf2, r.ro, r.ro_p, r.ro_T); r.Lo[0] = rd(); r.Lo[1] = rd(); r.Lo[2] = rd(); r.kT = rd();
         if (NPH == 2) {
             r.S = rd(); r.Lo[3] = rd(); r.rw = rd(); r.rw_p = rd(); r.rw_T = rd();
             r.Lw[0] = rd(); r.Lw[1] = rd(); r.Lw[2] = rd(); r.Lw[3] = rd(); r.kT_S = rd();

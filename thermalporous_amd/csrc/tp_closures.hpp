@@ -7,11 +7,23 @@
 namespace tp {
 
 // oil_rho = rho_ref * e^(c(10p - p0)) * e^(-e1 (T - T0))            (:37-46)
-__device__ __forceinline__ void oil_rho(double p, double T, const DevPrm &q, double &r, double &r_p, double &r_T) {
+// (in two halves: r is the PRODUCT of the two factors, and where r goes straight into a sum the compiler contracts that
+// product into the sum.  k_assemble_lds keeps the factors in its LDS image and forms r where it is used, like k_assemble.)
+__device__ __forceinline__ void oil_rho_factors(double p, double T, const DevPrm &q, double &f1, double &f2) {
     constexpr double c = 5.5e-5, p0 = 1.01325, e1 = 2.5e-4, T0 = 15.5556 + 273.15;
-    r = q.rho_ref * exp(c * (p * 1e1 - p0)) * exp(-e1 * (T - T0));
+    f1 = q.rho_ref * exp(c * (p * 1e1 - p0));
+    f2 = exp(-e1 * (T - T0));
+}
+__device__ __forceinline__ void oil_rho_from(double f1, double f2, double &r, double &r_p, double &r_T) {
+    constexpr double c = 5.5e-5, e1 = 2.5e-4;
+    r = f1 * f2;
     r_p = (10.0 * c) * r;
     r_T = (-e1) * r;
+}
+__device__ __forceinline__ void oil_rho(double p, double T, const DevPrm &q, double &r, double &r_p, double &r_T) {
+    double f1, f2;
+    oil_rho_factors(p, T, q, f1, f2);
+    oil_rho_from(f1, f2, r, r_p, r_T);
 }
 
 // oil_mu = 1e-3 * 10^(A1 API + A2) * Tf^(A3 API + A4), Tf = 1.8 (T - 273.15) + 32     (:48-57)
