@@ -105,6 +105,16 @@ typedef struct tp_options {
     int32_t ilu_levels;      /* stage 2 fill level: 0 = block-ILU(0) (sub_1_sub_pc_factor_levels 0, the presets' default),
                                 1 = block-ILU(1) (pc_cprilu1_gmres, twophase.py:653-668): 13-block rows, the sweeps
                                 take 4 steps of skew per axis-2 plane and 2 per axis-1 line instead of 1 and 1 */
+    /* Temperature stage of the composite (the reference's cprctr composites, CTRStage1PC).  NOTE for ABI readers:
+     * the field stands HERE, between ilu_levels and fs_additive (the tests of earlier options pin the order of every field from
+     * fs_additive on): every field from fs_additive on moved and sizeof(tp_options) grew by 8; recompile callers.
+     * 1 appends one stage T behind the last stage of pc_order (SIT, IST, ISIT, SIST): r = x - J y over all b columns of y,
+     * y_T += V(A_TT) r_T, one V-cycle of a scalar hierarchy set up on the T-T block of the UNDECOUPLED Jacobian (the composite's
+     * own operator), coarsened by the conduction strengths vol / h^2; every other field of y stays as it is.  The hierarchy follows
+     * the amg_* options like the other scalar ones; the s1_* inner solves do not apply to it.
+     * Scope limits (refused naming both options, never ignored; the context stays usable): pc_kind 0 and 1 only (not 2, 3, 4);
+     * one slab / rank only. */
+    int32_t pc_ctr;          /* 0 (default: the launch sequence is unchanged), 1 */
     int32_t fs_additive;     /* pc_kind 2: 1 = PCFIELDSPLIT additive on (p,T) -- y_p = V(A_pp) x_p, y_T = V(A_TT) x_T, no coupling
                                 (pc_fieldsplit_diag, singlephase.py:371-375) -- instead of Schur FULL */
     /* Order of the composite's stages (pc_composite_pcs).  NOTE for ABI readers: the field stands HERE, between
@@ -345,6 +355,17 @@ int tp_ilu0_solve(tp_ctx *ctx, int32_t x, int32_t y);
  * "No").  y is read in all b fields (several slabs: its halo planes are exchanged first); only the npri primary planes of `out`
  * are written, owned cells only.  x, y and out must be three different vectors.  pc_kind 0, 1 or 3. */
 int tp_stage_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);
+/* The temperature stage of the composite (tp_options.pc_ctr).  All three fail with a message while pc_ctr is 0 or
+ * the preconditioner is not set up.
+ * tp_ctr_rhs: row 1 of the block residual in one kernel, out_1 = x_1 - sum_s sum_k J[s][1][k] y_k(neighbour s): only the b * slots
+ * Jacobian planes of row 1 are read, y in all b fields; field 1 of `out` is written (owned cells), its other planes are left
+ * untouched.  x, y and out must be three different vectors.
+ * tp_ctr_apply: y_1 = V(A_TT) x_1, every other field of y zero (CTRStage1PC.apply).  x and y must differ.
+ * tp_ctr_info: out = {pc_ctr in effect, levels of the A_TT hierarchy (0: not built), its set-ups since tp_create, T-stage
+ * applications launched since tp_create (one per tp_pc_apply / Krylov application, speculative ones included, and per tp_ctr_apply)}. */
+int tp_ctr_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);
+int tp_ctr_apply(tp_ctx *ctx, int32_t x, int32_t y);
+int tp_ctr_info(tp_ctx *ctx, int32_t out[4]);
 /* the stage-2 layout that was built from the options (read-only; sets the layout up if no factorisation has yet):
  * out = {B0, B1, B2, number of bjacobi blocks, number of tiles, block-local tile-diagonals, most tiles in one launch,
  * launches per sweep direction}.  One tile per block (the default): B = the tile, blocks = tiles, 1, tiles, 1. */
@@ -425,7 +446,8 @@ int tp_ew_history(tp_ctx *ctx, int32_t cap, double *rtol, double *fnorm, double 
  * step against 16 basis vectors (VecMDot + VecMAXPY + VecNorm; needs a Krylov basis from an earlier solve), 8 the same step
  * against 16 vectors of the fp32 basis (needs one from an earlier ksp_basis_single solve), 9 the stage-1 right-hand side of a later
  * S stage in one launch (tp_stage_rhs), 10 the pair of launches it replaces (block residual over all b rows and columns + the
- * decoupled right-hand side per primary field), 11 that block residual alone.  4 times the pc_order in force. */
+ * decoupled right-hand side per primary field), 11 that block residual alone, 12 the T stage's row right-hand side in one launch
+ * (tp_ctr_rhs; needs pc_ctr).  4 times the pc_order and pc_ctr in force. */
 int tp_time_kernel(tp_ctx *ctx, int32_t which, int32_t reps, double *ms_avg);
 int tp_amg_info(tp_ctx *ctx, int32_t which, int32_t *nlevels, double *op_complexity);
 /* level at which hierarchy `which` ends with relaxation only (amg_dom_tau), -1: full V-cycle; ratio0 = the

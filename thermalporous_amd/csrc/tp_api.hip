@@ -231,6 +231,7 @@ static void drop_hierarchies(tp_ctx *c) {
     delete c->amg_p; c->amg_p = nullptr;
     delete c->amg_T; c->amg_T = nullptr;
     delete c->bamg; c->bamg = nullptr;
+    delete c->amg_ctr; c->amg_ctr = nullptr;
 }
 
 }  // namespace tp
@@ -315,6 +316,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
+    pc_ctr_check_options(*opt, grid->nranks);
     ls_check_options(*opt);
     ew_check_options(*opt);
     amg_line_check_options(*opt, grid->nranks);
@@ -374,6 +376,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
+    pc_ctr_check_options(*opt, c->grid.nranks);
     ls_check_options(*opt);
     ew_check_options(*opt);
     amg_line_check_options(*opt, c->grid.nranks);
@@ -396,6 +399,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     c->opt = *opt;
     if (tile_changed) c->ilu.slots = 0;
     if (amg_changed) drop_hierarchies(c);
+    if (!opt->pc_ctr) { delete c->amg_ctr; c->amg_ctr = nullptr; }      // the T stage's hierarchy lives while its option is on
     if (schur_of(*opt) && c->Sm.n == 0) c->Sm.alloc((size_t)7 * c->g.ntot);
     c->pc_ready = false;
     c->graph_epoch++;            // any option may change the captured kernel sequence: drop the pc_apply graphs
@@ -846,6 +850,41 @@ int tp_stage_rhs(tp_ctx *c, int32_t x, int32_t y, int32_t out) {
     TP_API_END
 }
 
+// the composite's temperature stage (tp_options.pc_ctr)
+static void require_ctr(tp_ctx *c, const char *who) {
+    TP_REQUIRE(c, "null argument");
+    if (!c->opt.pc_ctr) throw Error(std::string(who) + ": pc_ctr is off (the temperature stage and its hierarchy exist with tp_options.pc_ctr = 1)");
+    if (!c->pc_ready || !c->amg_ctr) throw Error(std::string(who) + ": preconditioner not set up (the A_TT hierarchy of pc_ctr is that of tp_pc_setup)");
+}
+
+int tp_ctr_rhs(tp_ctx *c, int32_t x, int32_t y, int32_t out) {
+    TP_API_BEGIN
+    require_ctr(c, "tp_ctr_rhs");
+    TP_REQUIRE(x != y && x != out && y != out, "tp_ctr_rhs: x, y and out must differ");
+    row_rhs(c, vec_of(c, x).p, vec_of(c, y).p, vec_of(c, out).p + c->g.ntot);
+    TP_API_END
+}
+
+int tp_ctr_apply(tp_ctx *c, int32_t x, int32_t y) {
+    TP_API_BEGIN
+    require_ctr(c, "tp_ctr_apply");
+    TP_REQUIRE(x != y, "tp_ctr_apply: x and y must differ");
+    ctr_apply(c, vec_of(c, x).p, vec_of(c, y).p);
+    TP_API_END
+}
+
+int tp_ctr_info(tp_ctx *c, int32_t out[4]) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "bad arguments");
+    TP_REQUIRE(c->opt.pc_ctr, "tp_ctr_info: pc_ctr is off (the temperature stage exists with tp_options.pc_ctr = 1)");
+    TP_REQUIRE(c->pc_ready && c->amg_ctr, "tp_ctr_info: preconditioner not set up");
+    out[0] = c->opt.pc_ctr;
+    out[1] = (int32_t)c->amg_ctr->plan.lv.size();
+    out[2] = (int32_t)c->ctr_setups;
+    out[3] = (int32_t)c->ctr_applies;
+    TP_API_END
+}
+
 int tp_amg_setup(tp_ctx *c, int32_t which) {
     TP_API_BEGIN
     (void)which;
@@ -1029,6 +1068,7 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
     ensure_work(c);          // (w3 needs three planes even when b == 2: tp_solver.hip)
     if (which != 3) TP_REQUIRE(c->jac_ready, "Jacobian not assembled");
     if (which == 1 || which == 2 || which == 4 || which == 9 || which == 10) TP_REQUIRE(c->pc_ready, "preconditioner not set up");
+    if (which == 12) require_ctr(c, "tp_time_kernel 12");
     if (which == 9 || which == 10) TP_REQUIRE(c->opt.pc_kind == 0 || c->opt.pc_kind == 1 || c->opt.pc_kind == 3, "pc_kind 0, 1 or 3");
     auto run = [&]() {
         switch (which) {
@@ -1062,6 +1102,7 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
                 for (int q = 0; q < npri_of(c->opt); ++q) stage1_rhs(c, c->w1.p, q, c->w3.p + (long)q * c->g.ntot);
                 break;
             case 11: resid_block_cols(c, c->J.p, c->R.p, c->dx.p, c->b, c->w1.p); break;
+            case 12: row_rhs(c, c->R.p, c->dx.p, c->w3.p); break;       // (dx as in 9)
             default: throw Error("unknown kernel id");
         }
     };

@@ -359,6 +359,10 @@ struct tp_ctx {
     tp::DBuf<double> dcoef;       // decoupling coefficients d_q per cell (nprimary planes)
     tp::Stencil opA00, opA01, opA10;   // views used by stage 1
     tp::Amg *amg_p = nullptr, *amg_T = nullptr;
+    // tp_options.pc_ctr: the hierarchy of the composite's temperature stage, on the T-T planes of the undecoupled J (a view, as
+    // level 0 of the others); its set-ups and the T-stage applications launched since tp_create (tp_ctr_info)
+    tp::Amg *amg_ctr = nullptr;
+    long ctr_setups = 0, ctr_applies = 0;
     tp::BAmg *bamg = nullptr;          // pc_cptramg: system AMG on the (p,T) blocks (tp_amg_block.hip)
     tp::BStencil opPT;                 // pc_cptramg: the operator handed to bamg_setup (the slab's, or the gathered one)
     tp::InnerWork inner;               // s1_ksp != preonly: workspace of the inner Krylov solve (tp_inner.hip)
@@ -491,6 +495,7 @@ void selfp_build(tp_ctx *c);                                                    
 void selfp_post(tp_ctx *c, const double *b, const double *x, double *y);                  // y = x + w D^-1 (b - Sp x)
 void stage1_rhs(tp_ctx *c, const double *x, int q, double *out);                        // out = x_q - d_q x_s
 void stage_rhs(tp_ctx *c, const double *x, const double *y, double *out);                // out_q = [x - J y]_q - d_q [x - J y]_s, q < npri
+void row_rhs(tp_ctx *c, const double *x, const double *y, double *o1);                   // the plane o1 = [x - J y]_1, all b columns of y
 // ILU
 void ilu_setup(tp_ctx *c);
 void ilu_factor(tp_ctx *c);
@@ -542,6 +547,10 @@ void ensure_work(tp_ctx *c);          // scratch vectors w1..w4, dx of the preco
 void pc_setup(tp_ctx *c);
 void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary = true);
 void pc_apply(tp_ctx *c, const double *x, double *y);
+// the composite's temperature stage (tp_options.pc_ctr): what the option excludes (throws, naming both options), and the stage on
+// its own, y_1 = V(A_TT) x_1 with every other field of y zero
+void pc_ctr_check_options(const tp_options &o, int nranks);
+void ctr_apply(tp_ctx *c, const double *x, double *y);
 // rtol: the relative tolerance of THIS solve (tp_fgmres / tp_bcgs pass tp_options.ksp_rtol, newton() the same or, under ksp_ew, eta_k):
 // every reader of the tolerance -- both FGMRES loops, the speculation margin, the fp32-basis loop's true-residual test, the
 // BiCGStab latch on the device -- follows it; tp_options is never written

@@ -323,9 +323,10 @@ int vcycles_per_apply(const tp_ctx *c) {
     if (c->opt.pc_kind == 4) return 0;
     const int extra = c->opt.s1_ksp ? c->opt.s1_max_it - 1 : 0;      // per inner solve
     const int stages = c->opt.pc_order == 3 ? 2 : 1;                  // S stages of the order (pc_order 3 = SIS)
-    if (c->opt.fs_additive) return stages * (2 + extra);
-    if (schur_of(c->opt)) return stages * (3 + 2 * extra);            // K(A00) is applied twice
-    return stages * (1 + extra);
+    const int ctr = c->opt.pc_ctr ? 1 : 0;                            // the T stage: always one V-cycle, no inner solve
+    if (c->opt.fs_additive) return stages * (2 + extra) + ctr;
+    if (schur_of(c->opt)) return stages * (3 + 2 * extra) + ctr;      // K(A00) is applied twice
+    return stages * (1 + extra) + ctr;
 }
 
 void inner_ensure(tp_ctx *c) {

@@ -1244,6 +1244,47 @@ void stage_rhs(tp_ctx *c, const double *x, const double *y, double *out) {
     TP_HIP(hipGetLastError());
 }
 
+// ---- right-hand side of the composite's temperature stage (tp_options.pc_ctr) ------------------------------
+// out[c] = x1[c] - sum_s sum_k J[s][1][k][c] * y_k[c + off_s]: row 1 of the block residual x - J y, nothing else.  x1 and out are the
+// row's own planes (field 1 of the two vectors); y is read in all B columns.  Indexing, XCD mapping, plane order and the per-slot
+// batch of loads are those of k_stage_rhs / k_spmv_block: each of the B * NS Jacobian planes of the row is streamed exactly once,
+// coalesced, and only owned cells of the one output plane are written.
+template <int B, int NS>
+__global__ __launch_bounds__(256) void k_row_rhs(GridDev g, const double *__restrict__ J, const double *__restrict__ x1,
+                                                 const double *__restrict__ y, double *__restrict__ out) {
+    const long tid = xcd_tid();
+    if (tid >= g.nown) return;
+    const long c = g.np + tid, nt = g.ntot;
+    const long off[7] = {0, -1, 1, -(long)g.n0, (long)g.n0, -g.np, g.np};
+    double acc = 0.0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double yv[B];
+#pragma unroll
+        for (int k = 0; k < B; ++k) yv[k] = y[(long)k * nt + c + off[s]];
+#pragma unroll
+        for (int k = 0; k < B; ++k) acc += J[((long)(s * B + 1) * B + k) * nt + c] * yv[k];
+    }
+    out[c] = x1[c] - acc;
+}
+
+// the plane o1 = [x - J y]_1 (x, y: vectors of b fields; all b columns of y are read: its halo planes must be live); o1 lies in
+// neither x nor y, and nothing but its owned cells is written
+void row_rhs(tp_ctx *c, const double *x, const double *y, double *o1) {
+    const GridDev &g = c->g;
+    const dim3 gr = xcd_grid(g.nown), bl(256);
+    const bool d3 = g.gn2 > 1;
+    const double *x1 = x + g.ntot;
+    if (c->b == 3) {
+        if (d3) hipLaunchKernelGGL((k_row_rhs<3, 7>), gr, bl, 0, c->stream, g, c->J.p, x1, y, o1);
+        else    hipLaunchKernelGGL((k_row_rhs<3, 5>), gr, bl, 0, c->stream, g, c->J.p, x1, y, o1);
+    } else {
+        if (d3) hipLaunchKernelGGL((k_row_rhs<2, 7>), gr, bl, 0, c->stream, g, c->J.p, x1, y, o1);
+        else    hipLaunchKernelGGL((k_row_rhs<2, 5>), gr, bl, 0, c->stream, g, c->J.p, x1, y, o1);
+    }
+    TP_HIP(hipGetLastError());
+}
+
 // ---- scalar stencil: y = z + alpha * A x ----------------------------------------------------------
 __global__ __launch_bounds__(256) void k_spmv_scalar(GridDev g, Stencil A, const double *__restrict__ x,
                                                      double *__restrict__ y, double alpha,

@@ -76,7 +76,8 @@ static void refresh_pc_signature(tp_ctx *c) {
                              (uintptr_t)c->opt.amg_nu, (uintptr_t)c->opt.pc_kind, (uintptr_t)c->opt.pc_order, (uintptr_t)c->opt.decoup,
                              (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip, (uintptr_t)c->opt.amg_line_levels, (uintptr_t)c->opt.amg_gs_levels, (uintptr_t)c->opt.amg_gs_sweeps,
                              (uintptr_t)c->opt.s1_ksp, (uintptr_t)c->opt.s1_max_it, (uintptr_t)c->inner.V.p, (uintptr_t)c->inner.Z.p,
-                             (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole};
+                             (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole,
+                             (uintptr_t)c->amg_ctr, (uintptr_t)c->opt.pc_ctr};
     uintptr_t h = 1469598103934665603ull;
     for (uintptr_t v : sig) h = (h ^ v) * 1099511628211ull;
     if (h != c->pc_sig) { c->pc_sig = h; c->graph_epoch++; }
@@ -135,6 +136,9 @@ void pc_setup(tp_ctx *c) {
     ensure_work(c);
     amg_line_check_options(c->opt, c->grid.nranks);
     amg_gs_check_options(c->opt, c->grid.nranks);
+    pc_ctr_check_options(c->opt, c->grid.nranks);
+    TP_REQUIRE(!(c->opt.pc_ctr && c->dist), "pc_ctr on a context with a communicator (slabs / ranks): the temperature stage is "
+               "implemented for one GPU without one");
     if (c->opt.s1_ksp) inner_reset_stats(c);      // tp_inner_stats counts since the last set-up
     if (c->ilu.slots == 0) ilu_setup(c);          // (a stage-2 layout the options do not allow fails here, before the streams fork)
     if (c->opt.pc_kind == 4) {               // pc_bilu (twophase.py:758-762): bjacobi + ILU is the whole preconditioner
@@ -174,6 +178,24 @@ void pc_setup(tp_ctx *c) {
             amg_build(c, c->amg_T, gam, sg, gather_cells);
             TP_REQUIRE((c->amg_p->plan.dist_levels > 0) == (c->amg_T->plan.dist_levels > 0), "stage-1 hierarchies disagree on distribution");
         }
+    }
+    // pc_ctr: the hierarchy of the T stage, coarsened by the conduction strengths of amg_T and set up on the T-T planes of the
+    // UNDECOUPLED Jacobian: the stage takes its sub-matrix from the composite's operator, not from the decoupled copy
+    const bool ctr = c->opt.pc_ctr != 0;
+    Stencil Sc;
+    if (ctr) {
+        if (!c->amg_ctr) {
+            double sg[3];
+            const int n[3] = {gam.n0, gam.n1, gam.n2};
+            for (int a = 0; a < 3; ++a) {
+                const double hh = c->grid.h[a];
+                sg[a] = n[a] > 1 ? c->vol / (hh * hh) : 0.0;
+            }
+            amg_build(c, c->amg_ctr, gam, sg, gather_cells);
+        }
+        Sc.base = c->J.p + (long)(c->b + 1) * c->g.ntot;
+        Sc.slot_stride = (long)c->b * c->b * c->g.ntot;
+        ++c->ctr_setups;
     }
     require_replicated_for_inner(c, c->amg_p->plan);
     Stencil Sl;
@@ -236,17 +258,18 @@ void pc_setup(tp_ctx *c) {
         c->stream = c->aux[0];
         amg_setup(c, c->amg_p, c->opA00);
         TP_HIP(hipEventRecord(c->ev_join[0], c->aux[0]));
-        if (cptr) {
+        if (cptr || ctr) {
             TP_HIP(hipStreamWaitEvent(c->aux[1], c->ev_fork, 0));
             c->stream = c->aux[1];
             if (selfp) selfp_build(c);
-            amg_setup(c, c->amg_T, Sl);
+            if (cptr) amg_setup(c, c->amg_T, Sl);
+            if (ctr) amg_setup(c, c->amg_ctr, Sc);              // (behind amg_T on its stream: both are short chains)
             TP_HIP(hipEventRecord(c->ev_join[1], c->aux[1]));
         }
         c->stream = main;
         ilu_factor(c);
         TP_HIP(hipStreamWaitEvent(main, c->ev_join[0], 0));
-        if (cptr) TP_HIP(hipStreamWaitEvent(main, c->ev_join[1], 0));
+        if (cptr || ctr) TP_HIP(hipStreamWaitEvent(main, c->ev_join[1], 0));
         c->pc_ready = true;
     }
     // stage 2: numeric block-ILU(0) of every tile of this rank's slab
@@ -259,6 +282,7 @@ void pc_setup(tp_ctx *c) {
 void resolve_cycle_shapes(tp_ctx *c) {
     bool changed = amg_resolve_trunc(c, c->amg_p);
     changed = amg_resolve_trunc(c, c->amg_T) || changed;
+    if (c->opt.pc_ctr) changed = amg_resolve_trunc(c, c->amg_ctr) || changed;
     if (changed) c->graph_epoch++;
 }
 
@@ -399,8 +423,54 @@ static void pc_stage_I_full(tp_ctx *c, const double *x, double *y) {
     ilu_solve(c, c->w1.p, y, y, c->b);                      // y = y + M^-1 r, all fields of y read
 }
 
-// composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r  (pc_order 0 = SI; 1..3: the same two stages as IS, ISI, SIS)
+// ---- the composite's temperature stage (tp_options.pc_ctr) ------------------------------------------------
+void pc_ctr_check_options(const tp_options &o, int nranks) {
+    TP_REQUIRE(o.pc_ctr == 0 || o.pc_ctr == 1, "pc_ctr must be 0 or 1");
+    if (!o.pc_ctr) return;
+    TP_REQUIRE(o.pc_kind != 2, "pc_ctr with pc_kind 2 (pc_fieldsplit_cd): that preconditioner is no composite to append a stage to");
+    TP_REQUIRE(o.pc_kind != 3, "pc_ctr with pc_kind 3 (pc_cptramg): the temperature stage is implemented behind pc_cpr and pc_cptr");
+    TP_REQUIRE(o.pc_kind != 4, "pc_ctr with pc_kind 4 (pc_bilu): that preconditioner is no composite to append a stage to");
+    TP_REQUIRE(nranks <= 1, "pc_ctr with nranks > 1: the temperature stage is implemented for one slab");
+}
+
+// y_1 = V(A_TT) x_1, every other field of y zero: CTRStage1PC.apply
+void ctr_apply(tp_ctx *c, const double *x, double *y) {
+    const long nt = c->g.ntot;
+    resolve_cycle_shapes(c);
+    ++c->ctr_applies;
+    vec_zero(c, y, (long)c->b * nt);
+    amg_vcycle(c, c->amg_ctr, x + nt, y + nt);
+}
+
+// The T stage, last in every sequence (SIT, IST, ISIT, SIST): y_1 += V(A_TT) [x - J y]_1; every other field of y stays.
+// Invariants:
+//  - the row residual reads ALL b columns of y.  SI and ISI end with an I stage, which wrote every field of y; IS and SIS end
+//    with a later S stage, which added into the primary fields and left the secondary ones as the I stage before it wrote them.
+//    So all b columns are live in all four;
+//  - one slab only (pc_ctr_check_options, pc_setup): no halo exchange, and the halo planes of y that the kernel reads through
+//    its boundary cells meet zero Jacobian coefficients, as in every other residual of this file;
+//  - scratch: the right-hand side goes to the first plane of w3, the cycle's result e to the first plane of w1.  Both are dead at
+//    this point in all four sequences: w3 held the right-hand sides of an S stage whose stage1_run has returned (SI, SIS, IS) or
+//    that lies two stages back (ISI); w1 held the residual of an I stage whose ilu_solve has returned (SI, ISI) or the result of a
+//    later S stage that vec_axpy_owned has already added (IS, SIS).  w4 is not used.  None of them is x or y;
+//  - the V-cycle works in the hierarchy's own level vectors; the accumulation covers owned cells.
+static void pc_stage_T(tp_ctx *c, const double *x, double *y) {
+    const long nt = c->g.ntot;
+    row_rhs(c, x, y, c->w3.p);                              // one launch: only row 1 of the Jacobian
+    amg_vcycle(c, c->amg_ctr, c->w3.p, c->w1.p);
+    vec_axpy_owned(c, 1, 1.0, c->w1.p, y + nt);             // y_T += e
+}
+
+static void pc_apply_stages(tp_ctx *c, const double *x, double *y);
+
+// composite multiplicative: the stages of pc_order, then (pc_ctr) the temperature stage
 static void pc_apply_body(tp_ctx *c, const double *x, double *y) {
+    pc_apply_stages(c, x, y);
+    if (c->opt.pc_ctr) pc_stage_T(c, x, y);
+}
+
+// composite multiplicative: y = B1 x ; r = x - J y ; y += B2 r  (pc_order 0 = SI; 1..3: the same two stages as IS, ISI, SIS)
+static void pc_apply_stages(tp_ctx *c, const double *x, double *y) {
     if (c->opt.pc_kind == 4) { ilu_solve(c, x, y, nullptr, 0); return; }
     const int npri = npri_of(c->opt);
     if (c->opt.pc_order == 1 || c->opt.pc_order == 2) {      // IS, ISI
@@ -462,6 +532,7 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
     TP_REQUIRE(c->pc_ready, "pc_apply before pc_setup");
     static const bool use_graph = !(getenv("TP_GRAPH") && atoi(getenv("TP_GRAPH")) == 0);
     c->vcycles += vcycles_per_apply(c);
+    if (c->opt.pc_ctr) ++c->ctr_applies;
     ensure_work(c);                      // never allocate inside a stream capture
     resolve_cycle_shapes(c);             // (waits for the last set-up's dominance ratios: not inside a capture either)
     if (!use_graph) {

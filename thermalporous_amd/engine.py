@@ -47,7 +47,7 @@ class tp_options(C.Structure):
                 ("ilu_t1", C.c_int32), ("ilu_t2", C.c_int32), ("ilu_t0", C.c_int32),
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
                 ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
-                ("ilu_levels", C.c_int32), ("fs_additive", C.c_int32), ("pc_order", C.c_int32),
+                ("ilu_levels", C.c_int32), ("pc_ctr", C.c_int32), ("fs_additive", C.c_int32), ("pc_order", C.c_int32),
                 ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double),
                 ("ksp_ew", C.c_int32), ("ew_rtol0", C.c_double), ("ew_rtolmax", C.c_double), ("ew_gamma", C.c_double),
                 ("ew_alpha", C.c_double), ("ew_alpha2", C.c_double), ("ew_threshold", C.c_double), ("ilu_whole", C.c_int32),
@@ -78,7 +78,7 @@ API_SYMBOLS = (
     "tp_inner_stats", "tp_amg_tail_info", "tp_ilu_factor_bytes", "tp_amg_line_info", "tp_bcgs", "tp_ksp_info",
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
-    "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history",
+    "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -86,6 +86,9 @@ DEFAULT_OPTS = dict(
     pc_order="SI",          # order of the composite's stages, S = the CPR / CPTR / system-AMG stage, I = bjacobi + block-ILU: "SI" (the
                             # presets' order) | "IS" | "ISI" | "SIS" -- PCCOMPOSITE multiplicative, a block residual over all fields between
                             # two stages (pc_composite_pcs "bjacobi,fieldsplit", ...; check_pc_order_options).  Not pc fieldsplit_cd / bilu
+    pc_ctr=False,           # True: one more stage T behind the last stage of pc_order (SIT, IST, ISIT, SIST), y_T += V(A_TT) [x - J y]_T, one
+                            # V-cycle on the T-T block of the undecoupled Jacobian (the reference's cprctr composites, CTRStage1PC).  pc cpr
+                            # and cptr only, one slab (check_pc_ctr_options)
     ksp_rtol=1e-7, ksp_atol=1e-50, ksp_max_it=200, ksp_restart=200,
     ksp="fgmres",           # outer Krylov method: "fgmres" (restarted, ksp_restart) | "bcgs": right-preconditioned BiCGStab, seven vectors
                             # plus the shared scratch w2 whatever the iteration count, two preconditioner applications per iteration (tp_options.ksp_kind)
@@ -470,6 +473,23 @@ def check_pc_order_options(o):
                                   % (order,))
 
 
+def check_pc_ctr_options(o, nranks=1):
+    """pc_ctr (tp_options) against its values, the preconditioners that are no composite with a T stage behind it, and the slab
+    count: refused naming both, never ignored."""
+    v = o.get("pc_ctr", False)
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("pc_ctr = %r: False or True" % (v,))
+    if not v:
+        return
+    why = {"fieldsplit_cd": "(pc_kind 2): that preconditioner is no composite to append a stage to",
+           "cptramg": "(pc_kind 3): the temperature stage is implemented behind pc cpr and cptr",
+           "bilu": "(pc_kind 4): that preconditioner is no composite to append a stage to"}
+    if o.get("pc") in why:
+        raise NotImplementedError("pc_ctr with pc = %r %s" % (o["pc"], why[o["pc"]]))
+    if int(nranks) > 1:
+        raise NotImplementedError("pc_ctr with nranks = %d: the temperature stage is implemented for one slab" % int(nranks))
+
+
 def check_ksp_reorth_options(o):
     """ksp_reorth / ksp_reorth_eta (tp_options) against the range of eta and the configurations that have no fp64 basis."""
     eta = o.get("ksp_reorth_eta", 2.0**-0.5)
@@ -540,6 +560,7 @@ class HipEngine:
         check_ksp_basis_options(self.opts)
         check_ksp_reorth_options(self.opts)
         check_pc_order_options(self.opts)
+        check_pc_ctr_options(self.opts, nranks)
         check_linesearch_options(self.opts)
         check_ew_options(self.opts)
         self.nph = int(spec["nphase"])
@@ -595,9 +616,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        # (the line-search, refinement, stage-order and Eisenstat-Walker fields stand in the middle of the struct: they are set by
-        # name, everything else in declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "ksp_ew", "ew_"))]
+        # (the line-search, refinement, stage-order, temperature-stage and Eisenstat-Walker fields stand in the middle of the struct:
+        # they are set by name, everything else in declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "pc_ctr", "ksp_ew", "ew_"))]
         vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
@@ -611,7 +632,7 @@ class HipEngine:
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
         ew = {k: float(o.get(k, d)) for k, d in _EW_DEFAULTS.items()}
-        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
+        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], pc_ctr=int(bool(o.get("pc_ctr", False))), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
                           ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
                           ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
                           ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
@@ -630,6 +651,7 @@ class HipEngine:
         check_ksp_basis_options({**self.opts, **kw})
         check_ksp_reorth_options({**self.opts, **kw})
         check_pc_order_options({**self.opts, **kw})
+        check_pc_ctr_options({**self.opts, **kw}, self.nranks)
         check_linesearch_options({**self.opts, **kw})
         check_ew_options({**self.opts, **kw})
         self.opts.update(kw)
@@ -809,6 +831,22 @@ class HipEngine:
         """out_q = [x - J y]_q - d_q [x - J y]_s on the primary fields q (tp_stage_rhs): the right-hand side of a later S stage of
         the composite (pc_order), one kernel; the other fields of `out` are not written."""
         self._ck(self.lib.tp_stage_rhs(self.ctx, self.vec(x), self.vec(y), self.vec(out)))
+
+    def ctr_rhs(self, x, y, out):
+        """Field 1 of `out` = [x - J y]_1 (tp_ctr_rhs): the right-hand side of the composite's temperature stage (pc_ctr), one
+        kernel that reads only row 1 of the Jacobian; the other fields of `out` are not written."""
+        self._ck(self.lib.tp_ctr_rhs(self.ctx, self.vec(x), self.vec(y), self.vec(out)))
+
+    def ctr_apply(self, x, y):
+        """y_1 = V(A_TT) x_1, every other field of y zero (tp_ctr_apply): the temperature stage of pc_ctr on its own."""
+        self._ck(self.lib.tp_ctr_apply(self.ctx, self.vec(x), self.vec(y)))
+
+    def ctr_info(self):
+        """The temperature stage (tp_ctr_info): whether pc_ctr is in effect, the levels of its A_TT hierarchy, its set-ups and the
+        T-stage applications launched since the engine was created."""
+        out = (C.c_int32*4)()
+        self._ck(self.lib.tp_ctr_info(self.ctx, out))
+        return dict(enabled=bool(out[0]), levels=out[1], setups=out[2], applies=out[3])
 
     def ilu_factor(self):
         self._ck(self.lib.tp_ilu0_factor(self.ctx))

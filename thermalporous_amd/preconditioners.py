@@ -15,6 +15,7 @@ vectors of the engine; the arithmetic of every method is a HIP kernel sequence b
                                              no extra UFL assemblies, no SpGEMM)
     apply             -> tp_stage1_apply    r_p = x_p - D_ps D_ss^-1 x_s ; y_p = V-cycle(r_p) ; y_s = 0
     ConvDiffSchur*.apply -> tp_schur_apply  one V-cycle on S~
+    CTRStage1PC.apply    -> tp_ctr_apply    y_T = V-cycle(A_TT) x_T ; y_nonT = 0   (engine option pc_ctr)
 
 The production path does not go through Python per Krylov iteration (tp_newton_solve runs the whole
 Newton/FGMRES loop natively); these classes exist so that code written against the reference's PC
@@ -103,6 +104,28 @@ class CPTRStage1PC(CPRStage1PC):
         if pc.engine.opts["pc"] == "cptramg" or (appctx.get("vector") and pc.engine.opts["pc"] != "cptr"):
             self.kind = "cptramg"
         CPRStage1PC.initialize(self, pc)
+
+
+class CTRStage1PC(PCBase):
+    '''
+    Temperature-only stage of the cprctr composites: y_T = V-cycle(A_TT) x_T ; y_nonT = 0
+    '''
+
+    def initialize(self, pc):
+        eng = pc.engine
+        if not eng.opts.get("pc_ctr"):
+            eng.set_options(pc_ctr=True)               # builds the A_TT hierarchy with the next set-up
+        self.update(pc)
+
+    def update(self, pc):
+        # the T-T block is a zero-copy view of the Jacobian's planes: the set-up is the AMG set-up
+        pc.engine.pc_setup()
+
+    def apply(self, pc, x, y):
+        pc.engine.ctr_apply(x, y)
+
+    # should not be used
+    applyTranspose = apply
 
 
 class ConvDiffSchurTwoPhasesPC(PCBase):

@@ -18,6 +18,9 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
   pc_type composite, pc_composite_type multiplicative, pc_composite_pcs "python,bjacobi"
      also "bjacobi,X" | "bjacobi,X,bjacobi" | "X,bjacobi,X", X = python or fieldsplit (blanks and one trailing comma ignored): the
      engine key pc_order = "IS" | "ISI" | "SIS"; the k-th entry's keys carry sub_k_, a repeated entry must be configured identically
+     with the build key pc_ctr: True in the same dict, one more trailing "fieldsplit" entry whose pc_fieldsplit_0_fields is "1": the
+     temperature-only stage of the reference's cprctr composites (additive, fieldsplit_0 = one V-cycle, fieldsplit_1 = gmres /
+     ksp_max_it 0 / pc_type none on the remaining fields); without the key that entry is refused by name
      sub_0_pc_python_type  ...CPRStage1PC | ...CPTRStage1PC   sub_0_cpr_decoup  No|QI|TI
      sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur-FULL with ConvDiffSchurTwoPhasesPC
      sub_1_sub_pc_type ilu, sub_1_sub_pc_factor_levels 0, sub_1_pc_bjacobi_blocks
@@ -35,7 +38,7 @@ Defaults the reference inherits silently from Firedrake/PETSc are fixed here exp
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
 ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
 Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol, linesearch,
-ksp_reorth, ksp_reorth_eta, ksp_ew, ew_rtol0, ew_rtolmax, ew_gamma, ew_alpha, ew_alpha2, ew_threshold, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+ksp_reorth, ksp_reorth_eta, pc_order, pc_ctr, ksp_ew, ew_rtol0, ew_rtolmax, ew_gamma, ew_alpha, ew_alpha2, ew_threshold, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -53,6 +56,8 @@ _SCHUR_WHY = ("an iterative solver on the Schur split is not implemented: PETSc 
               "the (p,T) system solver of pc_cptramg) can be an inner iteration")
 _ADDITIVE_WHY = ("an iterative solver on the temperature block of the additive split is not implemented: only the pressure "
                  "solver K(A00) is wired to the inner iteration")
+_CTR_WHY = ("an iterative solver in the composite's temperature-only stage is not implemented: that stage (pc_ctr) is always one "
+            "V-cycle on A_TT; only the pressure solver K(A00) of an S stage is wired to the inner iteration")
 _CGS_REFINE = {"refine_never": "never", "refine_ifneeded": "ifneeded", "refine_always": "always"}
 _S1_MAXK = 32              # GMRES(k) without restart: k basis vectors of the stage-1 block are stored
 
@@ -70,7 +75,7 @@ def _take_vcycle(sp, prefix, used, schur=False):
             raise NotImplementedError("%s missing: the stage-1 solver must be one BoomerAMG V-cycle (v_cycle)" % k)
         if sp[k] != want:
             if schur and suf in ("ksp_type", "pc_hypre_boomeramg_max_iter"):
-                raise NotImplementedError("%s = %r: %s" % (k, sp[k], _ADDITIVE_WHY if schur == "additive" else _SCHUR_WHY))
+                raise NotImplementedError("%s = %r: %s" % (k, sp[k], {"additive": _ADDITIVE_WHY, "ctr": _CTR_WHY}.get(schur, _SCHUR_WHY)))
             raise NotImplementedError("%s = %r: only %r (one V-cycle per application)" % (k, sp[k], want))
         used.add(k)
     for k in sp:
@@ -167,13 +172,14 @@ def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
     from .engine import (check_amg_gs_options, check_amg_line_options, check_ew_options, check_ksp_basis_options,
-                         check_ksp_reorth_options, check_linesearch_options, check_pc_order_options)
+                         check_ksp_reorth_options, check_linesearch_options, check_pc_ctr_options, check_pc_order_options)
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_amg_gs_options(o, exc=NotImplementedError)
     check_ksp_basis_options(o)
     check_ksp_reorth_options(o)
     check_pc_order_options(o)
+    check_pc_ctr_options(o)
     check_linesearch_options(o)
     check_ew_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
@@ -287,7 +293,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
-                  "pc_order", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
+                  "pc_order", "pc_ctr", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
                   "ksp_ew", "ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
     for k in build_keys:
         if k in sp:
@@ -404,7 +410,13 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         return o
     # ---- composite multiplicative (stage 1, bjacobi/ILU(0)) -----------------------------------------------------
     _take(sp, used, "pc_composite_type", ("multiplicative",))
-    sp, pcs, order, given = _composite_stages(sp, used)
+    if not isinstance(o["pc_ctr"], bool):
+        raise ValueError("pc_ctr = %r: False or True" % (o["pc_ctr"],))
+    sp, pcs, order, given, has_t = _composite_stages(sp, used, ctr=o["pc_ctr"], two_phase=model_name == "Two-phase")
+    # (a trailing temperature-only entry needs pc_ctr: True beside it and was stripped; the key alone appends the stage to any dict)
+    if has_t and "pc_order" in solver_parameters and order != "SI" and o["pc_order"] != order:
+        raise NotImplementedError("pc_composite_pcs = %r ends its sequence %r with the temperature-only stage, but pc_order = %r "
+                                  "asks for another sequence, which that stage would not end" % (given, order + "T", o["pc_order"]))
     # the build key pc_order re-orders a dict written in the presets' order "S,I"; a dict that spells another order must agree
     if "pc_order" in solver_parameters and order != "SI" and o["pc_order"] != order:
         raise ValueError("the order of the composite's stages is configured twice and differently: pc_order = %r, "
@@ -426,7 +438,7 @@ _STAGE_OF = {"python": "S", "fieldsplit": "S", "bjacobi": "I"}
 _ORDERS = ("SI", "IS", "ISI", "SIS")
 
 
-def _composite_stages(sp, used):
+def _composite_stages(sp, used, ctr=False, two_phase=False):
     """pc_composite_pcs by PETSc's grammar: a comma-separated list of PC type names (blanks ignored, one trailing comma allowed)
     whose k-th entry is configured under the prefix sub_k_.  The hot path has two stages, S = the python / fieldsplit entry
     (CPR, CPTR, the system V-cycle) and I = bjacobi, in the orders S,I | I,S | I,S,I | S,I,S.  Returns the options with every
@@ -443,11 +455,28 @@ def _composite_stages(sp, used):
     prefixes = ["sub_%d_" % k for k in range(len(names))]
     entry = [{k[len(pre):]: v for k, v in sp.items() if k.startswith(pre)} for pre in prefixes]
     # (the reference's cprctr dicts: a third entry that is one V-cycle on field 1 alone, behind a stage on field 0)
-    for k, n in enumerate(names):
-        if n == "fieldsplit" and "".join(str(entry[k].get("pc_fieldsplit_0_fields", "")).split()) == "1":
-            raise NotImplementedError("pc_composite_pcs = %r: entry %d (sub_%d_) is a temperature-only stage, a V-cycle on field 1 "
-                                      "alone (sub_%d_pc_fieldsplit_0_fields = \"1\"): a third kind of stage is not implemented"
-                                      % (given, k, k, k))
+    t_at = [k for k, n in enumerate(names)
+            if n == "fieldsplit" and "".join(str(entry[k].get("pc_fieldsplit_0_fields", "")).split()) == "1"]
+    if t_at and not ctr:
+        k = t_at[0]
+        raise NotImplementedError("pc_composite_pcs = %r: entry %d (sub_%d_) is a temperature-only stage, a V-cycle on field 1 "
+                                  "alone (sub_%d_pc_fieldsplit_0_fields = \"1\"): a third kind of stage is not implemented "
+                                  "unless the build key pc_ctr: True stands in the same dict, which runs it as the last stage"
+                                  % (given, k, k, k))
+    if t_at:
+        # pc_ctr: ONE trailing T entry is validated key by key and stripped; the remaining entries map as without it
+        if len(t_at) > 1:
+            raise NotImplementedError("pc_composite_pcs = %r: entries %s are all temperature-only stages; pc_ctr runs one, as the "
+                                      "last stage" % (given, ", ".join("%d" % k for k in t_at)))
+        k = t_at[0]
+        if k != len(names) - 1:
+            raise NotImplementedError("pc_composite_pcs = %r: entry %d (sub_%d_) is a temperature-only stage in the middle of the "
+                                      "sequence; pc_ctr runs it as the last stage only" % (given, k, k))
+        _take_ctr_entry(sp, prefixes[k], used, two_phase)
+        sp = {q: v for q, v in sp.items() if not q.startswith(prefixes[k])}
+        names, prefixes, entry = names[:k], prefixes[:k], entry[:k]
+        kinds = kinds[:k]
+        s_names = sorted({n for n in names if _STAGE_OF.get(n) == "S"})
     if "?" in kinds or kinds not in _ORDERS or len(s_names) != 1:
         raise NotImplementedError("pc_composite_pcs = %r is not implemented on the hot path (supported, X = python or fieldsplit: "
                                   "'X,bjacobi', 'bjacobi,X', 'bjacobi,X,bjacobi', 'X,bjacobi,X')" % (given,))
@@ -477,7 +506,30 @@ def _composite_stages(sp, used):
                 break
         else:
             out[k] = v                                   # no entry has this prefix: left for _reject_unused
-    return out, s_names[0] + ",bjacobi", kinds, given
+    return out, s_names[0] + ",bjacobi", kinds, given, bool(t_at)
+
+
+def _take_ctr_entry(sp, prefix, used, two_phase):
+    """The composite's trailing temperature-only entry under ``prefix`` (the reference's cprctr dicts; engine key pc_ctr): an
+    additive fieldsplit whose first split is field 1 with exactly one V-cycle and whose second split, the remaining fields,
+    returns zero (gmres, max_it 0, pc none).  Every key is consumed or raises."""
+    _take(sp, used, prefix + "pc_fieldsplit_type", ("additive",))
+    _take(sp, used, prefix + "fieldsplit_1_ksp_type", ("gmres",))
+    _take(sp, used, prefix + "fieldsplit_1_pc_type", ("none",))
+    if prefix + "pc_fieldsplit_type" not in used or prefix + "fieldsplit_1_ksp_type" not in used \
+            or int(_take(sp, used, prefix + "fieldsplit_1_ksp_max_it", None, -1)) != 0 or prefix + "fieldsplit_1_pc_type" not in used:
+        raise NotImplementedError("%s: the temperature-only stage is pc_fieldsplit_type additive with fieldsplit_1 = gmres, "
+                                  "ksp_max_it 0, pc_type none (a second split that returns zero)" % prefix)
+    used.add(prefix + "pc_fieldsplit_0_fields")
+    rest = _take(sp, used, prefix + "pc_fieldsplit_1_fields")
+    want = "0,2" if two_phase else "0"
+    if rest is not None and "".join(str(rest).split()) != want:
+        raise NotImplementedError("%spc_fieldsplit_1_fields = %r: the remaining fields of the %s model are %r"
+                                  % (prefix, rest, "two-phase" if two_phase else "single-phase", want))
+    _take_vcycle(sp, prefix + "fieldsplit_0_", used, schur="ctr")
+    for k in sp:
+        if k.startswith(prefix) and k not in used:
+            raise KeyError("solver parameter %r is not consumed by the temperature-only stage (it would be silently ignored)" % k)
 
 
 _MISSING = object()
