@@ -97,6 +97,20 @@ typedef struct tp_options {
     int32_t amg_gather_cells;/* multi-GPU: AMG levels with more cells than this stay distributed over the slabs
                                 (halo exchange per sweep); smaller ones are gathered and replicated on every
                                 rank.  < 0: replicate the whole hierarchy.  Ignored on one GPU. */
+    /* Factorisation of the Schur split on (p,T) of pc_kind 1 and 2 (pc_fieldsplit_schur_fact_type, pc_fieldsplit_schur_scale;
+     * DESIGN.md 4.6h).  NOTE for ABI readers: the two fields stand HERE, between amg_gather_cells and amg_dom_tau (the tests of
+     * earlier options pin the order of the fields further down): schur_fact fills the four bytes of padding that preceded
+     * amg_dom_tau, every field from amg_dom_tau on moved by 8 and sizeof(tp_options) grew by 8; recompile callers.
+     * With r0, r1 the stage's right-hand sides, K0 = K(A00) (one V-cycle, or the s1_ksp inner solve) and KS = K(S) (the S~ cycle,
+     * the A11 cycle of schur_a11 1, the cycle + Jacobi sweep of schur_a11 2):
+     *   0 full   y0 = K0 r0 ; y1 = KS (r1 - A10 y0) ; y0 = K0 (r0 - A01 y1)      K0 twice, KS once
+     *   1 lower  y0 = K0 r0 ; y1 = KS (r1 - A10 y0)                              K0 once,  KS once
+     *   2 upper  y1 = KS r1 ; y0 = K0 (r0 - A01 y1)                              K0 once,  KS once
+     *   3 diag   y0 = K0 r0 ; y1 = schur_scale KS r1                             K0 once,  KS once
+     * Every S stage of pc_order uses the same factorisation.  Refused, naming both options, unless 0: pc_kind 0, 3, 4 (no Schur
+     * split) and fs_additive (PETSc's additive split is no Schur factorisation). */
+    int32_t schur_fact;      /* 0 full (default: the launch sequence is unchanged), 1 lower, 2 upper, 3 diag */
+    double  schur_scale;     /* schur_fact 3: the factor on KS r1 (PETSc's default -1); finite, and -1 (or 0, a zeroed field) otherwise */
     double  amg_dom_tau;     /* relaxation-only truncation: the first V(nu,nu) level whose operator has
                                 max_i sum_{j!=i}|a_ij| / |a_ii| <= amg_dom_tau ends the cycle with two damped-Jacobi
                                 sweeps (no coarse-grid correction: damped Jacobi already contracts by
@@ -366,6 +380,12 @@ int tp_stage_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);
 int tp_ctr_rhs(tp_ctx *ctx, int32_t x, int32_t y, int32_t out);
 int tp_ctr_apply(tp_ctx *ctx, int32_t x, int32_t y);
 int tp_ctr_info(tp_ctx *ctx, int32_t out[4]);
+/* The Schur split on (p,T) (tp_options.schur_fact): the factorisation and scale in force, and how often the
+ * pressure solver K(A00) and the Schur solver K(S) were applied since the last tp_pc_setup.  Counted on the host where a stage-1
+ * sequence is issued or replayed (tp_pc_apply and every Krylov application, speculative ones included; tp_stage1_apply): per
+ * Schur stage (2, 1) under full and (1, 1) under the other three.  pc_kind 0: (1, 0) per stage; fs_additive: (1, 1); pc_kind 3
+ * and 4 count nothing.  Any output pointer may be null. */
+int tp_schur_info(tp_ctx *ctx, int *fact, double *scale, long *k0_applies, long *ks_applies);
 /* the stage-2 layout that was built from the options (read-only; sets the layout up if no factorisation has yet):
  * out = {B0, B1, B2, number of bjacobi blocks, number of tiles, block-local tile-diagonals, most tiles in one launch,
  * launches per sweep direction}.  One tile per block (the default): B = the tile, blocks = tiles, 1, tiles, 1. */

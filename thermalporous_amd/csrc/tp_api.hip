@@ -316,6 +316,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
+    pc_schur_fact_check_options(*opt);
     pc_ctr_check_options(*opt, grid->nranks);
     ls_check_options(*opt);
     ew_check_options(*opt);
@@ -376,6 +377,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     basis_single_check_options(*opt);
     reorth_check_options(*opt);
     pc_order_check_options(*opt);
+    pc_schur_fact_check_options(*opt);
     pc_ctr_check_options(*opt, c->grid.nranks);
     ls_check_options(*opt);
     ew_check_options(*opt);
@@ -823,6 +825,7 @@ int tp_stage1_apply(tp_ctx *c, int32_t x, int32_t y) {
     TP_API_BEGIN
     TP_REQUIRE(c->pc_ready, "stage 1 not set up");
     TP_REQUIRE(x != y, "x and y must differ");
+    schur_count(c, 1);
     stage1_apply(c, vec_of(c, x).p, vec_of(c, y).p);
     TP_API_END
 }
@@ -882,6 +885,16 @@ int tp_ctr_info(tp_ctx *c, int32_t out[4]) {
     out[1] = (int32_t)c->amg_ctr->plan.lv.size();
     out[2] = (int32_t)c->ctr_setups;
     out[3] = (int32_t)c->ctr_applies;
+    TP_API_END
+}
+
+int tp_schur_info(tp_ctx *c, int *fact, double *scale, long *k0_applies, long *ks_applies) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "null argument");
+    if (fact) *fact = c->opt.schur_fact;
+    if (scale) *scale = c->opt.schur_fact == 3 ? c->opt.schur_scale : -1.0;
+    if (k0_applies) *k0_applies = c->schur_k0;
+    if (ks_applies) *ks_applies = c->schur_ks;
     TP_API_END
 }
 

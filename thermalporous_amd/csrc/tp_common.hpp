@@ -363,6 +363,8 @@ struct tp_ctx {
     // level 0 of the others); its set-ups and the T-stage applications launched since tp_create (tp_ctr_info)
     tp::Amg *amg_ctr = nullptr;
     long ctr_setups = 0, ctr_applies = 0;
+    // tp_schur_info: applications of K(A00) and of K(S) issued or replayed since the last pc_setup (host counters)
+    long schur_k0 = 0, schur_ks = 0;
     tp::BAmg *bamg = nullptr;          // pc_cptramg: system AMG on the (p,T) blocks (tp_amg_block.hip)
     tp::BStencil opPT;                 // pc_cptramg: the operator handed to bamg_setup (the slab's, or the gathered one)
     tp::InnerWork inner;               // s1_ksp != preonly: workspace of the inner Krylov solve (tp_inner.hip)
@@ -451,6 +453,7 @@ void vec_zero(tp_ctx *c, double *x, long n);
 void vec_copy(tp_ctx *c, const double *x, double *y, long n);
 void vec_axpy_owned(tp_ctx *c, int nf, double a, const double *x, double *y);            // y += a x
 void vec_scale_to(tp_ctx *c, int nf, double a, const double *x, double *y);             // y = a x (owned)
+void scale_plane(tp_ctx *c, const tp::GridDev &g, double a, double *x);                 // x *= a (owned cells of one plane of g)
 void multi_dot(tp_ctx *c, int nf, const double *V, long vstride, int k, const double *w, const double *w2,
                double *host_out);   // host_out[i] = <V_i, w>, i<k ; host_out[k] = <w2,w2> if w2
 void multi_axpy(tp_ctx *c, int nf, const double *V, long vstride, int k, const double *hcoef_host, double sign,
@@ -549,6 +552,10 @@ void stage1_apply(tp_ctx *c, const double *x, double *y, bool zero_secondary = t
 void pc_apply(tp_ctx *c, const double *x, double *y);
 // the composite's temperature stage (tp_options.pc_ctr): what the option excludes (throws, naming both options), and the stage on
 // its own, y_1 = V(A_TT) x_1 with every other field of y zero
+// the factorisation of the Schur split on (p,T) (tp_options.schur_fact, schur_scale): what it excludes (throws, naming both
+// options), and the host counters of tp_schur_info for `stages` stage-1 sequences issued or replayed
+void pc_schur_fact_check_options(const tp_options &o);
+void schur_count(tp_ctx *c, int stages);
 void pc_ctr_check_options(const tp_options &o, int nranks);
 void ctr_apply(tp_ctx *c, const double *x, double *y);
 // rtol: the relative tolerance of THIS solve (tp_fgmres / tp_bcgs pass tp_options.ksp_rtol, newton() the same or, under ksp_ew, eta_k):

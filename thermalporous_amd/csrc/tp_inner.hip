@@ -325,7 +325,8 @@ int vcycles_per_apply(const tp_ctx *c) {
     const int stages = c->opt.pc_order == 3 ? 2 : 1;                  // S stages of the order (pc_order 3 = SIS)
     const int ctr = c->opt.pc_ctr ? 1 : 0;                            // the T stage: always one V-cycle, no inner solve
     if (c->opt.fs_additive) return stages * (2 + extra) + ctr;
-    if (schur_of(c->opt)) return stages * (3 + 2 * extra) + ctr;      // K(A00) is applied twice
+    if (schur_of(c->opt) && c->opt.schur_fact) return stages * (2 + extra) + ctr;     // lower, upper, diag: K(A00) once
+    if (schur_of(c->opt)) return stages * (3 + 2 * extra) + ctr;      // full: K(A00) is applied twice
     return stages * (1 + extra) + ctr;
 }
 

@@ -62,6 +62,10 @@ void vec_scale_dev_norm(tp_ctx *c, int nf, const double *n2_dev, double *x) {
 void vec_scale_to(tp_ctx *c, int nf, double a, const double *x, double *y) {
     hipLaunchKernelGGL(k_axpy_owned<false>, grid_for(c->g.nown * nf), dim3(256), 0, c->stream, c->g, nf, a, x, y);
 }
+// x *= a over the owned cells of ONE plane of grid g (the slab's, or the gathered global one): the kernel of vec_scale_to, in place
+void scale_plane(tp_ctx *c, const GridDev &g, double a, double *x) {
+    hipLaunchKernelGGL(k_axpy_owned<false>, grid_for(g.nown), dim3(256), 0, c->stream, g, 1, a, x, x);
+}
 
 // ---- batched dot products (VecMDot + VecNorm of one FGMRES iteration in ONE pass over w) -----------
 // Each wave owns a chunk of owned entries (CHUNK per lane kept in registers), loops over the k basis

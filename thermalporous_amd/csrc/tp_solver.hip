@@ -70,6 +70,8 @@ static void face_strengths(tp_ctx *c, double st[3]) {
 
 // the captured pc_apply graphs bake in buffer addresses and options: invalidate them when any changes
 static void refresh_pc_signature(tp_ctx *c) {
+    uint64_t scale_bits = 0;                       // (the scale is a kernel argument of the recorded diag sequence)
+    if (c->opt.schur_fact == 3) memcpy(&scale_bits, &c->opt.schur_scale, sizeof scale_bits);
     const uintptr_t sig[] = {(uintptr_t)c->opA00.base, (uintptr_t)c->opA01.base, (uintptr_t)c->opA10.base,
                              (uintptr_t)c->Sm.p, (uintptr_t)c->ilu.fwd.p, (uintptr_t)c->ilu.fwd32.p, (uintptr_t)c->ilu.fwdp.p, (uintptr_t)c->amg_p, (uintptr_t)c->amg_T, (uintptr_t)c->bamg,
                              (uintptr_t)c->w1.p, (uintptr_t)c->w3.p, (uintptr_t)c->w4.p, (uintptr_t)c->dcoef.p, (uintptr_t)c->spbuf.p,
@@ -77,7 +79,8 @@ static void refresh_pc_signature(tp_ctx *c) {
                              (uintptr_t)c->opt.amg_single, (uintptr_t)c->opt.amg_gather_cells, (uintptr_t)c->opt.schur_a11, (uintptr_t)c->opt.fs_additive, (uintptr_t)c->opt.amg_full_levels, (uintptr_t)c->opt.amg_coarse_pre, (uintptr_t)c->opt.amg_coarse_post, (uintptr_t)c->opt.amg_tail_post, (uintptr_t)c->opt.amg_mid_skip, (uintptr_t)c->opt.amg_line_levels, (uintptr_t)c->opt.amg_gs_levels, (uintptr_t)c->opt.amg_gs_sweeps,
                              (uintptr_t)c->opt.s1_ksp, (uintptr_t)c->opt.s1_max_it, (uintptr_t)c->inner.V.p, (uintptr_t)c->inner.Z.p,
                              (uintptr_t)c->ilu.ntiles, (uintptr_t)c->ilu.nsteps, (uintptr_t)c->ilu.whole,
-                             (uintptr_t)c->amg_ctr, (uintptr_t)c->opt.pc_ctr};
+                             (uintptr_t)c->amg_ctr, (uintptr_t)c->opt.pc_ctr,
+                             (uintptr_t)c->opt.schur_fact, (uintptr_t)scale_bits};
     uintptr_t h = 1469598103934665603ull;
     for (uintptr_t v : sig) h = (h ^ v) * 1099511628211ull;
     if (h != c->pc_sig) { c->pc_sig = h; c->graph_epoch++; }
@@ -137,6 +140,8 @@ void pc_setup(tp_ctx *c) {
     amg_line_check_options(c->opt, c->grid.nranks);
     amg_gs_check_options(c->opt, c->grid.nranks);
     pc_ctr_check_options(c->opt, c->grid.nranks);
+    pc_schur_fact_check_options(c->opt);
+    c->schur_k0 = c->schur_ks = 0;                 // tp_schur_info counts since the last set-up
     TP_REQUIRE(!(c->opt.pc_ctr && c->dist), "pc_ctr on a context with a communicator (slabs / ranks): the temperature stage is "
                "implemented for one GPU without one");
     if (c->opt.s1_ksp) inner_reset_stats(c);      // tp_inner_stats counts since the last set-up
@@ -299,9 +304,34 @@ static Stage1Sys stage1_system(const tp_ctx *c, bool gathered) {
     return {c->gfull, {c->gA00.p, ng}, {c->gA01.p, ng}, {c->gA10.p, ng}, false};
 }
 
+// ---- the factorisation of the Schur split (tp_options.schur_fact, schur_scale) ---------------------------
+void pc_schur_fact_check_options(const tp_options &o) {
+    TP_REQUIRE(o.schur_fact >= 0 && o.schur_fact <= 3, "schur_fact must be 0 (full), 1 (lower), 2 (upper) or 3 (diag)");
+    TP_REQUIRE(std::isfinite(o.schur_scale), "schur_scale must be finite");
+    if (o.schur_fact != 3)      // (0: a zeroed field of a C caller)
+        TP_REQUIRE(o.schur_scale == -1.0 || o.schur_scale == 0.0, "schur_scale other than -1 with schur_fact other than 3 (diag): the "
+                   "scale belongs to the diag factorisation");
+    if (!o.schur_fact) return;
+    TP_REQUIRE(o.pc_kind != 0, "schur_fact other than 0 (full) with pc_kind 0 (pc_cpr): one V-cycle on the pressure block, no Schur split");
+    TP_REQUIRE(o.pc_kind != 3, "schur_fact other than 0 (full) with pc_kind 3 (pc_cptramg): one system V-cycle, no Schur split");
+    TP_REQUIRE(o.pc_kind != 4, "schur_fact other than 0 (full) with pc_kind 4 (pc_bilu): bjacobi + ILU alone, no Schur split");
+    TP_REQUIRE(!o.fs_additive, "schur_fact other than 0 (full) with fs_additive (pc_fieldsplit_diag): PETSc's additive split is no "
+               "Schur factorisation");
+}
+
+// tp_schur_info: `stages` stage-1 sequences are about to be issued or replayed
+void schur_count(tp_ctx *c, int stages) {
+    const tp_options &o = c->opt;
+    if (o.pc_kind == 3 || o.pc_kind == 4) return;
+    const bool split = npri_of(o) == 2;
+    c->schur_k0 += (long)stages * (split && !o.fs_additive && o.schur_fact == 0 ? 2 : 1);
+    c->schur_ks += split ? stages : 0;
+}
+
 // y = K r on system `s`; t and w are two work vectors of the system's grid.  npri == 1: y0 = K(A00) r0.  Else
-// PCFIELDSPLIT additive (pc_fieldsplit_diag, singlephase.py:371-375) or schur FULL on (p,T) (twophase.py:536-545):
-// K(A00), K(S~) = one V-cycle each (slab-distributed AMG levels: the V-cycles return owned cells, the couplings read halos)
+// PCFIELDSPLIT additive (pc_fieldsplit_diag, singlephase.py:371-375) or schur on (p,T) (twophase.py:536-545) in the
+// factorisation of schur_fact: K(A00), K(S~) = one V-cycle each (slab-distributed AMG levels: the V-cycles return owned cells,
+// the couplings read halos).  Nothing writes r0 or r1 (decoupling "No" on one GPU: they are the caller's x).
 static void stage1_sequence(tp_ctx *c, const Stage1Sys &s, const double *r0, const double *r1, double *y0, double *y1,
                             double *t, double *w) {
     // K(A00): one V-cycle of the pressure hierarchy, or (s1_ksp) an inner solve preconditioned by it
@@ -316,15 +346,37 @@ static void stage1_sequence(tp_ctx *c, const Stage1Sys &s, const double *r0, con
         return;
     }
     const long n = s.g.ntot;
-    K00(r0, w);                                                             // w = K(A00) r0
-    if (s.exchange) halo_exchange(c, s.g, w, 1, n);
-    spmv_scalar(c, s.g, s.A10, w, t, -1.0, r1);                             // t = r1 - A10 w
-    if (c->opt.schur_a11 == 2) {                                            // selfp (slab system only: pc_setup): V7 then one Jacobi sweep on the exact Sp
-        double *xv = c->spbuf.p + 9 * c->g.ntot;
-        amg_vcycle(c, c->amg_T, t, xv);
-        selfp_post(c, t, xv, y1);
-    } else {
-        amg_vcycle(c, c->amg_T, t, y1);                                     // y1 = K(S~) t
+    // K(S): one V-cycle on S~ / A11, or (selfp; slab system only: pc_setup) V7 then one Jacobi sweep on the exact Sp
+    const auto KS = [&](const double *b) {
+        if (c->opt.schur_a11 == 2) {
+            double *xv = c->spbuf.p + 9 * c->g.ntot;
+            amg_vcycle(c, c->amg_T, b, xv);
+            selfp_post(c, b, xv, y1);
+        } else {
+            amg_vcycle(c, c->amg_T, b, y1);                                 // y1 = K(S~) b
+        }
+    };
+    const int fact = c->opt.schur_fact;
+    if (fact == 3) {                       // diag: no coupling, no exchange; y1 scaled in place by an existing vector kernel
+        K00(r0, y0);
+        KS(r1);
+        scale_plane(c, s.g, c->opt.schur_scale, y1);
+        return;
+    }
+    if (fact == 1) {                       // lower: K(A00)'s result is y0 itself; the exchange in front of A10 is y0's
+        K00(r0, y0);
+        if (s.exchange) halo_exchange(c, s.g, y0, 1, n);
+        spmv_scalar(c, s.g, s.A10, y0, t, -1.0, r1);                        // t = r1 - A10 y0
+        KS(t);
+        return;
+    }
+    if (fact == 2) {                       // upper
+        KS(r1);
+    } else {                               // full (the launch sequence of every build before schur_fact)
+        K00(r0, w);                                                         // w = K(A00) r0
+        if (s.exchange) halo_exchange(c, s.g, w, 1, n);
+        spmv_scalar(c, s.g, s.A10, w, t, -1.0, r1);                         // t = r1 - A10 w
+        KS(t);
     }
     if (s.exchange) halo_exchange(c, s.g, y1, 1, n);
     spmv_scalar(c, s.g, s.A01, y1, t, -1.0, r0);                            // t = r0 - A01 y1
@@ -533,6 +585,7 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
     static const bool use_graph = !(getenv("TP_GRAPH") && atoi(getenv("TP_GRAPH")) == 0);
     c->vcycles += vcycles_per_apply(c);
     if (c->opt.pc_ctr) ++c->ctr_applies;
+    schur_count(c, c->opt.pc_order == 3 ? 2 : 1);
     ensure_work(c);                      // never allocate inside a stream capture
     resolve_cycle_shapes(c);             // (waits for the last set-up's dominance ratios: not inside a capture either)
     if (!use_graph) {

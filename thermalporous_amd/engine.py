@@ -46,7 +46,8 @@ class tp_options(C.Structure):
                 ("amg_omega", C.c_double), ("amg_nu", C.c_int32), ("amg_min_cells", C.c_int32),
                 ("ilu_t1", C.c_int32), ("ilu_t2", C.c_int32), ("ilu_t0", C.c_int32),
                 ("amg_full_levels", C.c_int32), ("amg_coarse_pre", C.c_int32), ("amg_coarse_post", C.c_int32),
-                ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32), ("amg_dom_tau", C.c_double),
+                ("amg_mid_skip", C.c_int32), ("amg_tail_post", C.c_int32), ("amg_single", C.c_int32), ("schur_a11", C.c_int32), ("amg_gather_cells", C.c_int32),
+                ("schur_fact", C.c_int32), ("schur_scale", C.c_double), ("amg_dom_tau", C.c_double),
                 ("ilu_levels", C.c_int32), ("pc_ctr", C.c_int32), ("fs_additive", C.c_int32), ("pc_order", C.c_int32),
                 ("ksp_reorth", C.c_int32), ("ksp_reorth_eta", C.c_double),
                 ("ksp_ew", C.c_int32), ("ew_rtol0", C.c_double), ("ew_rtolmax", C.c_double), ("ew_gamma", C.c_double),
@@ -79,6 +80,7 @@ API_SYMBOLS = (
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
     "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
+    "tp_schur_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -121,6 +123,11 @@ DEFAULT_OPTS = dict(
     schur_a11=False,
     fs_additive=False,      # pc_fieldsplit_type additive on (p,T): pc_fieldsplit_diag (singlephase.py:371-375)
     schur_selfp=False,      # pc_fieldsplit_schur_precondition selfp (pc_fieldsplit_selfp, singlephase.py:322-330)
+    schur_fact="full",      # factorisation of the Schur split on (p,T) (pc_fieldsplit_schur_fact_type): "full" (the presets': K(A00) twice,
+                            # K(S) once) | "lower" (y0 = K0 r0, y1 = KS (r1 - A10 y0)) | "upper" (y1 = KS r1, y0 = K0 (r0 - A01 y1)) | "diag"
+                            # (y0 = K0 r0, y1 = schur_scale KS r1): one K(A00) each.  pc cptr and fieldsplit_cd, not fs_additive
+                            # (check_schur_fact_options)
+    schur_scale=-1.0,       # "diag" only: the factor on K(S) r1 (pc_fieldsplit_schur_scale, PETSc's default -1); must stay -1 otherwise
     ilu_tile=None,          # None: see default_ilu_tile (3-D: whole axis-0 lines x a balanced t1 x t2; 2-D: ~24 x 32 cells)
     ilu_levels=0,           # sub_1_sub_pc_factor_levels: 0 (block-ILU(0)) or 1 (block-ILU(1), pc_cprilu1_gmres)
     bjacobi_blocks=None,    # -sub_1_pc_bjacobi_blocks N: N blocks over the whole grid; overrides ilu_tile.  One tile per block when
@@ -490,6 +497,34 @@ def check_pc_ctr_options(o, nranks=1):
         raise NotImplementedError("pc_ctr with nranks = %d: the temperature stage is implemented for one slab" % int(nranks))
 
 
+_SCHUR_FACT = {"full": 0, "lower": 1, "upper": 2, "diag": 3}
+
+
+def check_schur_fact_options(o):
+    """schur_fact / schur_scale (tp_options) against their values and the preconditioners that have no Schur factorisation on
+    (p,T) to choose: refused naming both, never ignored."""
+    fact = o.get("schur_fact", "full")
+    if not isinstance(fact, str) or fact not in _SCHUR_FACT:
+        raise ValueError("schur_fact = %r: 'full', 'lower', 'upper' or 'diag'" % (fact,))
+    scale = o.get("schur_scale", -1.0)
+    if not _is_number(scale) or not math.isfinite(float(scale)):
+        raise ValueError("schur_scale = %r: a finite number" % (scale,))
+    if fact != "diag" and float(scale) != -1.0:
+        raise ValueError("schur_scale = %r with schur_fact = %r: the scale belongs to schur_fact = 'diag' (it would be silently "
+                         "ignored)" % (scale, fact))
+    if fact == "full":
+        return
+    why = {"cpr": "(pc_kind 0): one V-cycle on the pressure block, no Schur split",
+           "cptramg": "(pc_kind 3): one system V-cycle on the (p,T) blocks, no Schur split",
+           "bilu": "(pc_kind 4): bjacobi + ILU alone, no Schur split"}
+    if o.get("pc") in why:
+        raise NotImplementedError("schur_fact = %r with pc = %r %s" % (fact, o["pc"], why[o["pc"]]))
+    if o.get("fs_additive"):
+        raise NotImplementedError("schur_fact = %r with fs_additive (pc_fieldsplit_type additive, pc_fieldsplit_diag): PETSc's "
+                                  "additive split is no Schur factorisation; schur_fact = 'diag' with schur_scale is the Schur one"
+                                  % (fact,))
+
+
 def check_ksp_reorth_options(o):
     """ksp_reorth / ksp_reorth_eta (tp_options) against the range of eta and the configurations that have no fp64 basis."""
     eta = o.get("ksp_reorth_eta", 2.0**-0.5)
@@ -561,6 +596,7 @@ class HipEngine:
         check_ksp_reorth_options(self.opts)
         check_pc_order_options(self.opts)
         check_pc_ctr_options(self.opts, nranks)
+        check_schur_fact_options(self.opts)
         check_linesearch_options(self.opts)
         check_ew_options(self.opts)
         self.nph = int(spec["nphase"])
@@ -616,9 +652,9 @@ class HipEngine:
     @staticmethod
     def _make_options(o):
         t = o["ilu_tile"]
-        # (the line-search, refinement, stage-order, temperature-stage and Eisenstat-Walker fields stand in the middle of the struct:
-        # they are set by name, everything else in declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "pc_ctr", "ksp_ew", "ew_"))]
+        # (the line-search, refinement, stage-order, temperature-stage, Schur-factorisation and Eisenstat-Walker fields stand in the
+        # middle of the struct: they are set by name, everything else in declaration order)
+        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "pc_ctr", "schur_fact", "schur_scale", "ksp_ew", "ew_"))]
         vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
                           o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
                           o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
@@ -632,7 +668,8 @@ class HipEngine:
                           _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
                           float(o.get("s1_atol", 0.0)))
         ew = {k: float(o.get(k, d)) for k, d in _EW_DEFAULTS.items()}
-        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], pc_ctr=int(bool(o.get("pc_ctr", False))), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
+        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], pc_ctr=int(bool(o.get("pc_ctr", False))),
+                          schur_fact=_SCHUR_FACT[o.get("schur_fact", "full")], schur_scale=float(o.get("schur_scale", -1.0)), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
                           ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
                           ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
                           ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
@@ -652,6 +689,7 @@ class HipEngine:
         check_ksp_reorth_options({**self.opts, **kw})
         check_pc_order_options({**self.opts, **kw})
         check_pc_ctr_options({**self.opts, **kw}, self.nranks)
+        check_schur_fact_options({**self.opts, **kw})
         check_linesearch_options({**self.opts, **kw})
         check_ew_options({**self.opts, **kw})
         self.opts.update(kw)
@@ -847,6 +885,13 @@ class HipEngine:
         out = (C.c_int32*4)()
         self._ck(self.lib.tp_ctr_info(self.ctx, out))
         return dict(enabled=bool(out[0]), levels=out[1], setups=out[2], applies=out[3])
+
+    def schur_info(self):
+        """The Schur split on (p,T) (tp_schur_info): the factorisation and scale in force and the applications of the pressure
+        solver K(A00) and of the Schur solver K(S) issued or replayed since the last pc_setup."""
+        fact, scale, k0, ks = C.c_int(), C.c_double(), C.c_long(), C.c_long()
+        self._ck(self.lib.tp_schur_info(self.ctx, C.byref(fact), C.byref(scale), C.byref(k0), C.byref(ks)))
+        return dict(fact={v: k for k, v in _SCHUR_FACT.items()}[fact.value], scale=scale.value, k0_applies=k0.value, ks_applies=ks.value)
 
     def ilu_factor(self):
         self._ck(self.lib.tp_ilu0_factor(self.ctx))

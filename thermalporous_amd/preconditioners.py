@@ -72,9 +72,10 @@ class CPRStage1PC(PCBase):
         if self.decoup.endswith("_temp") and (self.kind != "cpr" or pc.engine.b != 3):
             raise NotImplementedError("QI_temp/TI_temp: two-phase CPRStage1PC only (:367-368)")
         eng = pc.engine
-        # inner solve of the stage-1 block (engine options s1_ksp, s1_max_it, s1_rtol, s1_atol): passed through when the
-        # application context carries them
-        inner = {k: appctx[k] for k in ("s1_ksp", "s1_max_it", "s1_rtol", "s1_atol") if k in appctx and eng.opts.get(k) != appctx[k]}
+        # inner solve of the stage-1 block (engine options s1_ksp, s1_max_it, s1_rtol, s1_atol) and the factorisation of the Schur
+        # split (schur_fact, schur_scale; CPTRStage1PC): passed through when the application context carries them
+        inner = {k: appctx[k] for k in ("s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "schur_fact", "schur_scale")
+                 if k in appctx and eng.opts.get(k) != appctx[k]}
         if eng.opts["pc"] != self.kind or eng.opts["decoup"] != self.decoup or inner:
             eng.set_options(pc=self.kind, decoup=self.decoup, **inner)
         self.update(pc)
@@ -156,43 +157,64 @@ class ConvDiffSchurPC(ConvDiffSchurTwoPhasesPC):
 
 
 class FieldsplitSchurPC():
-    """PCFIELDSPLIT schur FULL on (p,T) with K(A00) = V-cycle and K(S) = the given Schur PC
-    (singlephase.py:309-319; the same three solves as pc_cptr's stage 1, twophase.py:536-545):
-        y0 = K(A00) x0 ;  y1 = K(S)(x1 - A10 y0) ;  y0 = K(A00)(x0 - A01 y1).
-    Assembled from the stage objects so tests can show that it reproduces tp_pc_apply."""
+    """PCFIELDSPLIT schur on (p,T) with K(A00) = V-cycle and K(S) = the given Schur PC (singlephase.py:309-319; the same solves
+    as pc_cptr's stage 1, twophase.py:536-545), in the factorisation the engine option schur_fact names:
+        full    y0 = K(A00) x0 ;  y1 = K(S)(x1 - A10 y0) ;  y0 = K(A00)(x0 - A01 y1)
+        lower   y0 = K(A00) x0 ;  y1 = K(S)(x1 - A10 y0)
+        upper   y1 = K(S) x1 ;    y0 = K(A00)(x0 - A01 y1)
+        diag    y0 = K(A00) x0 ;  y1 = schur_scale K(S) x1
+    schur_fact / schur_scale given here are passed through to the engine at set-up, as the stage-1 classes pass the inner-solve
+    options.  Assembled from the stage objects so tests can show that it reproduces tp_pc_apply."""
 
-    def __init__(self, schur_pc):
+    def __init__(self, schur_pc, schur_fact=None, schur_scale=None):
         self.schur = schur_pc
+        self.opts = {k: v for k, v in (("schur_fact", schur_fact), ("schur_scale", schur_scale)) if v is not None}
 
     def setUp(self, pc):
+        eng = pc.engine
+        new = {k: v for k, v in self.opts.items() if eng.opts.get(k) != v}
+        if new:
+            eng.set_options(**new)
         self.schur.setUp(pc)
 
     def apply(self, pc, x, y):
         eng = pc.engine
+        fact, scale = eng.opts.get("schur_fact", "full"), float(eng.opts.get("schur_scale", -1.0))
         xh = eng.vec_get(x)
-        eng.amg_vcycle(0, x, 0, "_fs_w", 0)
-        y0 = eng.vec_get("_fs_w")[0]
-        # couplings through MatMult on a vector with one live field (decoupling "No": A10, A01 are blocks of J)
-        z = np.zeros_like(xh)
-        z[0] = y0
-        eng.vec_set("_fs_w", z)
-        eng.spmv("_fs_w", "_fs_t")
-        t = xh.copy()
-        t[1] = xh[1] - eng.vec_get("_fs_t")[1]                     # x1 - A10 y0
-        eng.vec_set("_fs_t", t)
-        self.schur.apply(pc, "_fs_t", "_fs_w")                     # y1 = K(S~)(...)
-        y1 = eng.vec_get("_fs_w")[1]
-        z[:] = 0.0
-        z[1] = y1
-        eng.vec_set("_fs_w", z)
-        eng.spmv("_fs_w", "_fs_t")
-        t = xh.copy()
-        t[0] = xh[0] - eng.vec_get("_fs_t")[0]                     # x0 - A01 y1
-        eng.vec_set("_fs_t", t)
-        eng.amg_vcycle(0, "_fs_t", 0, "_fs_w", 0)
+
+        def k00(r0):
+            t = xh.copy()
+            t[0] = r0
+            eng.vec_set("_fs_t", t)
+            eng.amg_vcycle(0, "_fs_t", 0, "_fs_w", 0)
+            return eng.vec_get("_fs_w")[0].copy()
+
+        def ks(r1):
+            t = xh.copy()
+            t[1] = r1
+            eng.vec_set("_fs_t", t)
+            self.schur.apply(pc, "_fs_t", "_fs_w")                 # K(S~), temperature field
+            return eng.vec_get("_fs_w")[1].copy()
+
+        def coupling(row, col, v):
+            # through MatMult on a vector with one live field (decoupling "No": A10, A01 are blocks of J)
+            z = np.zeros_like(xh)
+            z[col] = v
+            eng.vec_set("_fs_w", z)
+            eng.spmv("_fs_w", "_fs_t")
+            return eng.vec_get("_fs_t")[row]
+
         out = np.zeros_like(xh)
-        out[0] = eng.vec_get("_fs_w")[0]
-        out[1] = y1
+        if fact == "upper":
+            out[1] = ks(xh[1])
+            out[0] = k00(xh[0] - coupling(0, 1, out[1]))           # x0 - A01 y1
+        elif fact == "diag":
+            out[0] = k00(xh[0])
+            out[1] = scale*ks(xh[1])
+        else:
+            y0 = k00(xh[0])
+            out[1] = ks(xh[1] - coupling(1, 0, y0))                # x1 - A10 y0
+            out[0] = y0 if fact == "lower" else k00(xh[0] - coupling(0, 1, out[1]))
         eng.vec_set(y, out)
 
 

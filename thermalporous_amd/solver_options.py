@@ -22,7 +22,11 @@ CONSUMED (and its value checked against what is implemented), purely cosmetic (m
      temperature-only stage of the reference's cprctr composites (additive, fieldsplit_0 = one V-cycle, fieldsplit_1 = gmres /
      ksp_max_it 0 / pc_type none on the remaining fields); without the key that entry is refused by name
      sub_0_pc_python_type  ...CPRStage1PC | ...CPTRStage1PC   sub_0_cpr_decoup  No|QI|TI
-     sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur-FULL with ConvDiffSchurTwoPhasesPC
+     sub_0_cpr_stage1*     boomeramg V-cycle / fieldsplit-schur with ConvDiffSchurTwoPhasesPC
+  pc_fieldsplit_schur_fact_type FULL | lower | upper | diag (any letter case, as PETSc) under the prefix of the Schur split on (p,T)
+     -- "", sub_0_fieldsplit_0_ or sub_0_cpr_stage1_ -> engine key schur_fact = "full" | "lower" | "upper" | "diag"; with diag,
+     pc_fieldsplit_schur_scale under the same prefix -> schur_scale (PETSc's default -1).  The scale with another fact type is a
+     ValueError (PETSc would ignore it), as is a fact type or scale given both as build key and as PETSc key with different values
      sub_1_sub_pc_type ilu, sub_1_sub_pc_factor_levels 0, sub_1_pc_bjacobi_blocks
   inner solve of the stage-1 PRESSURE solver K(A00) (pc_cptramg*: of the (p,T) system solver), under that solver's prefix
   (_take_inner): pc_hypre_boomeramg_max_iter k | ksp_type richardson, ksp_max_it k | ksp_type fgmres (gmres + ksp_pc_side
@@ -38,7 +42,7 @@ Defaults the reference inherits silently from Firedrake/PETSc are fixed here exp
 (SURVEY.md 8c): ksp_rtol 1e-7 (Firedrake), snes_rtol 1e-8, snes_atol 1e-50, snes_stol 1e-8,
 ksp_atol 1e-50; an inner fgmres without ksp_rtol/ksp_atol gets PETSc's own KSP defaults, 1e-5 and 1e-50.
 Build-specific tuning keys (not PETSc): amg_omega, amg_nu, amg_min_cells, ilu_tile, s1_ksp, s1_max_it, s1_rtol, s1_atol, linesearch,
-ksp_reorth, ksp_reorth_eta, pc_order, pc_ctr, ksp_ew, ew_rtol0, ew_rtolmax, ew_gamma, ew_alpha, ew_alpha2, ew_threshold, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
+ksp_reorth, ksp_reorth_eta, pc_order, pc_ctr, schur_fact, schur_scale, ksp_ew, ew_rtol0, ew_rtolmax, ew_gamma, ew_alpha, ew_alpha2, ew_threshold, ls_order, ls_alpha, ls_max_it, ls_maxstep, ls_minlambda, ls_max_change (per-field cap on the change per Newton iteration).  Two-phase string presets are layered on plain Newton-Krylov, not on the reference's
 experimental FAS nonlinear preconditioner (twophase.py:927; needs mesh hierarchies + MUMPS).
 """
 
@@ -89,6 +93,38 @@ def _set_inner(o, ksp, k, rtol=0.0, atol=0.0):
         raise ValueError("the inner stage-1 solve is configured twice and differently: build keys %r, PETSc keys %r"
                          % ({q: o[q] for q in new}, new))
     o.update(new)
+
+
+_SCHUR_FACTS = ("full", "lower", "upper", "diag")
+
+
+def _take_schur_fact(sp, used, prefix, o, given):
+    """``<prefix>pc_fieldsplit_schur_fact_type`` (FULL | lower | upper | diag in any letter case, as PETSc reads it) and
+    ``<prefix>pc_fieldsplit_schur_scale`` -> the engine keys schur_fact and schur_scale.  Returns whether the fact-type key is there
+    with one of the four values; the caller refuses the split otherwise.  ``given``: the dict as the caller got it, whose build
+    keys schur_fact / schur_scale must agree with the PETSc spelling."""
+    kf, ks = prefix + "pc_fieldsplit_schur_fact_type", prefix + "pc_fieldsplit_schur_scale"
+    fact = str(sp.get(kf, "")).lower()
+    if fact not in _SCHUR_FACTS:
+        return False
+    used.add(kf)
+    if "schur_fact" in given and o["schur_fact"] != fact:
+        raise ValueError("the Schur factorisation is configured twice and differently: schur_fact = %r, %s = %r"
+                         % (o["schur_fact"], kf, sp[kf]))
+    o["schur_fact"] = fact
+    if ks in sp:
+        scale = sp[ks]
+        used.add(ks)
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+            raise ValueError("%s = %r: a number" % (ks, scale))
+        if fact != "diag":
+            raise ValueError("%s = %r with %s = %r: the scale belongs to the diag factorisation (PETSc would silently ignore it)"
+                             % (ks, scale, kf, sp[kf]))
+        if "schur_scale" in given and float(o["schur_scale"]) != float(scale):
+            raise ValueError("the Schur factorisation is configured twice and differently: schur_scale = %r, %s = %r"
+                             % (o["schur_scale"], ks, scale))
+        o["schur_scale"] = float(scale)
+    return True
 
 
 def _take_inner(sp, prefix, used, o, ksp_default=None):
@@ -172,7 +208,7 @@ def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
     from .engine import (check_amg_gs_options, check_amg_line_options, check_ew_options, check_ksp_basis_options,
-                         check_ksp_reorth_options, check_linesearch_options, check_pc_ctr_options, check_pc_order_options)
+                         check_ksp_reorth_options, check_linesearch_options, check_pc_ctr_options, check_pc_order_options, check_schur_fact_options)
     _check_ilu_single(o)
     check_amg_line_options(o, exc=NotImplementedError)
     check_amg_gs_options(o, exc=NotImplementedError)
@@ -180,6 +216,7 @@ def _check_inner(o):
     check_ksp_reorth_options(o)
     check_pc_order_options(o)
     check_pc_ctr_options(o)
+    check_schur_fact_options(o)
     check_linesearch_options(o)
     check_ew_options(o)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
@@ -293,7 +330,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
                   "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
                   "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
-                  "pc_order", "pc_ctr", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
+                  "pc_order", "pc_ctr", "schur_fact", "schur_scale", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
                   "ksp_ew", "ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
     for k in build_keys:
         if k in sp:
@@ -369,7 +406,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         raise NotImplementedError("pc_type missing: only the composite CPR/CPTR preconditioners and pc_fieldsplit_cd/_a11 "
                                   "are on the hot path")
     if pc_type == "fieldsplit":
-        # pc_fieldsplit_cd (singlephase.py:309-319): Schur FULL on (p,T), V-cycle on A_pp, ConvDiffSchurPC on S;
+        # pc_fieldsplit_cd (singlephase.py:309-319): Schur FULL (or lower / upper / diag) on (p,T), V-cycle on A_pp, ConvDiffSchurPC on S;
         # pc_fieldsplit_a11 (:331-338): A_TT stands in for the Schur complement;
         # pc_fieldsplit_selfp (:322-330): Sp = A_TT - A_Tp diag(A_pp)^-1 A_pT
         if _take(sp, used, "pc_fieldsplit_type", ("schur", "additive")) == "additive":
@@ -382,11 +419,12 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
             _reject_unused(sp, used)
             _check_inner(o)
             return o
-        fact = str(_take(sp, used, "pc_fieldsplit_schur_fact_type", None, "")).upper()
+        fact = _take_schur_fact(sp, used, "", o, solver_parameters)
         pre = _take(sp, used, "pc_fieldsplit_schur_precondition", ("a11", "selfp"))
-        if "pc_fieldsplit_type" not in used or fact != "FULL":
-            raise NotImplementedError("fieldsplit preconditioners on the hot path: schur FULL with ConvDiffSchurPC "
-                                      "(pc_fieldsplit_cd), a11 (pc_fieldsplit_a11) or selfp (pc_fieldsplit_selfp)")
+        if "pc_fieldsplit_type" not in used or not fact:
+            raise NotImplementedError("fieldsplit preconditioners on the hot path: schur with pc_fieldsplit_schur_fact_type FULL, "
+                                      "lower, upper or diag and ConvDiffSchurPC (pc_fieldsplit_cd), a11 (pc_fieldsplit_a11) or "
+                                      "selfp (pc_fieldsplit_selfp)")
         _take_inner(sp, "fieldsplit_0_", used, o)
         if pre in ("a11", "selfp"):
             _take_vcycle(sp, "fieldsplit_1_", used, schur=True)
@@ -426,12 +464,13 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     if order != "SI":
         # the stages were renamed to the places they have in "S,I" (sub_0_ = S, sub_1_ = I): say so in whatever is raised below
         try:
-            return _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=not order.startswith("S"))
+            return _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=not order.startswith("S"),
+                                             given=solver_parameters)
         except (KeyError, NotImplementedError, ValueError) as e:
             msg = e.args[0] if e.args else ""
             raise type(e)("%s [pc_composite_pcs = %r: keys are named here by stage, sub_0_ = the %s entry's sub_%d_, sub_1_ = "
                           "the bjacobi entry's sub_%d_]" % (msg, given, pcs.split(",")[0], order.index("S"), order.index("I"))) from e
-    return _engine_options_composite(sp, used, o, pcs, model_name, vector)
+    return _engine_options_composite(sp, used, o, pcs, model_name, vector, given=solver_parameters)
 
 
 _STAGE_OF = {"python": "S", "fieldsplit": "S", "bjacobi": "I"}
@@ -535,8 +574,8 @@ def _take_ctr_entry(sp, prefix, used, two_phase):
 _MISSING = object()
 
 
-def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=False):
-    """The composite's two stages, S under sub_0_ and I under sub_1_ (engine_options)."""
+def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=False, given=()):
+    """The composite's two stages, S under sub_0_ and I under sub_1_ (engine_options); given: the dict as the caller wrote it."""
     if s_moved and "sub_0_cpr_decoup" in sp:
         # the model class reads sub_0_cpr_decoup, the S entry's key only when S comes first: elsewhere the entry's own key decides
         if o["decoup"] not in ("No", sp["sub_0_cpr_decoup"]):
@@ -582,12 +621,16 @@ def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=Fals
                 o["pc"] = "cpr"
         elif first == "fieldsplit":
             _take(sp, used, "sub_0_fieldsplit_0_pc_fieldsplit_type", ("schur",))
-            fact = str(_take(sp, used, "sub_0_fieldsplit_0_pc_fieldsplit_schur_fact_type", None, "")).upper()
+            fact = _take_schur_fact(sp, used, "sub_0_fieldsplit_0_", o, given)
             _reject_schur_krylov(sp, "sub_0_fieldsplit_0_fieldsplit_1_")
             _take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_ksp_type", ("preonly",))
             _take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_pc_type", ("python",))
             py = str(_take(sp, used, "sub_0_fieldsplit_0_fieldsplit_1_pc_python_type", None, ""))
-            if "sub_0_fieldsplit_0_pc_fieldsplit_type" not in used or fact != "FULL" or not py.endswith("ConvDiffSchurTwoPhasesPC"):
+            if not fact:
+                raise NotImplementedError("sub_0_fieldsplit_0_pc_fieldsplit_schur_fact_type = %r: the Schur split of the "
+                                          "fieldsplit,bjacobi composite is FULL, lower, upper or diag"
+                                          % (sp.get("sub_0_fieldsplit_0_pc_fieldsplit_schur_fact_type"),))
+            if "sub_0_fieldsplit_0_pc_fieldsplit_type" not in used or not py.endswith("ConvDiffSchurTwoPhasesPC"):
                 raise NotImplementedError("unsupported first split of the fieldsplit,bjacobi composite")
             if f0 not in ("0,1", "0, 1") or f1 not in (None, "2"):
                 raise NotImplementedError("pc_cptr_gmres splits fields (0,1 | 2)")
@@ -630,9 +673,10 @@ def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=Fals
         else:
             o["pc"] = "cptr"
             _take(sp, used, "sub_0_cpr_stage1_pc_fieldsplit_type", ("schur",))
-            fact = str(_take(sp, used, "sub_0_cpr_stage1_pc_fieldsplit_schur_fact_type", None, "")).upper()
-            if "sub_0_cpr_stage1_pc_fieldsplit_type" not in used or fact != "FULL":
-                raise NotImplementedError("CPTR stage 1: fieldsplit schur FULL only (twophase.py:536-538)")
+            fact = _take_schur_fact(sp, used, "sub_0_cpr_stage1_", o, given)
+            if "sub_0_cpr_stage1_pc_fieldsplit_type" not in used or not fact:
+                raise NotImplementedError("CPTR stage 1: fieldsplit schur with pc_fieldsplit_schur_fact_type FULL, lower, upper or "
+                                          "diag (twophase.py:536-538)")
             pre = _take(sp, used, "sub_0_cpr_stage1_pc_fieldsplit_schur_precondition", ("a11",))
             o["schur_a11"] = pre == "a11"                   # pc_cptr_a11 (twophase.py:598-616)
             _take_inner(sp, "sub_0_cpr_stage1_fieldsplit_0_", used, o)

@@ -277,9 +277,10 @@ class ThermalModel:
         self._log("Linear iterations: ", current_lits)
         if self.verbosity and self.engine_opts.get("s1_ksp", "preonly") != "preonly" and hasattr(self.engine, "inner_stats"):
             # inner stage-1 solves of the LAST linear solve of this step (the device counters restart at every PC set-up);
-            # pc_cptr / pc_fieldsplit_cd apply K(A00) twice per outer iteration
+            # pc_cptr / pc_fieldsplit_cd apply K(A00) twice per outer iteration under schur_fact "full", once under the others
             applies, its, unconv = self.engine.inner_stats()
-            per_outer = 2 if (self.engine_opts["pc"] in ("cptr", "fieldsplit_cd") and not self.engine_opts.get("fs_additive")) else 1
+            per_outer = 2 if (self.engine_opts["pc"] in ("cptr", "fieldsplit_cd") and not self.engine_opts.get("fs_additive")
+                              and self.engine_opts.get("schur_fact", "full") == "full") else 1
             self._log("Inner iterations per outer iteration: ", per_outer*its/max(applies, 1),
                       " (%d inner solves, %d above tolerance)" % (applies, unconv))
         self.total_nits += current_nits
