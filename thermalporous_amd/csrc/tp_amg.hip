@@ -321,8 +321,8 @@ struct LevelDevT {
 
 // omega / diag of an OWNED cell c without reading the stored plane: a kernel that streams the diagonal anyway recomputes in
 // registers what k_amg_weights stored -- the same correctly rounded division, the same rounding to R, so the same bits -- and
-// saves one plane in eleven of a Jacobi sweep.  (REG = false: the stored plane, TP_AMG_INVD_LOAD=1; kernels that read invd at
-// neighbours -- halo cells have a zero diagonal -- and the line, Gauss-Seidel and tail kernels always read the plane.)
+// saves one plane in eleven of a Jacobi sweep.  (REG = false: the stored plane, TP_AMG_INVD_LOAD=1; the line, Gauss-Seidel and
+// tail kernels always read the plane; pre2_cell, which needs it at neighbours too, has its own form of this.)
 template <class R, bool REG>
 __device__ __forceinline__ double invd_at(const LevelDevT<R> &L, long c) {
     if constexpr (REG) return (double)(R)(L.omega / (double)L.op.slot(0)[c]);
@@ -334,19 +334,31 @@ __device__ __forceinline__ void nb_offsets(const GridDev &g, long (&off)[7]) {
 }
 
 // two damped-Jacobi sweeps from a zero initial guess:  x1 = invd b ;  x2 = x1 + invd (b - A x1)
-template <class R>
+// (REG: omega / diag at the cell and its six neighbours from the diagonal plane the sweep streams anyway, as invd_at forms it; a
+// neighbour whose diagonal is zero -- a halo cell of a level that is not slab-distributed, where the stored plane holds the zero
+// it was allocated with -- gets 0.0, and either form multiplies it by the exact zero coefficient towards a boundary)
+template <class R, bool REG>
 __device__ __forceinline__ double pre2_cell(const LevelDevT<R> &L, const double *__restrict__ b, long tid) {
     const long c = L.g.np + tid;
     long off[7];
     nb_offsets(L.g, off);
-    double s = 0.0;
+    double s = 0.0, ic = 0.0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
         const long n = c + off[k];
-        s += L.op.slot(k)[c] * (L.invd[n] * b[n]);
+        double iv;
+        if constexpr (REG) {
+            const double d = (double)L.op.slot(0)[n];
+            const double q = (double)(R)(L.omega / d);
+            iv = d != 0.0 ? q : 0.0;
+        } else {
+            iv = (double)L.invd[n];
+        }
+        if (k == 0) ic = iv;
+        s += L.op.slot(k)[c] * (iv * b[n]);
     }
-    const double x1 = L.invd[c] * b[c];
-    return x1 + L.invd[c] * (b[c] - s);
+    const double x1 = ic * b[c];
+    return x1 + ic * (b[c] - s);
 }
 
 template <class R, bool REG = false>
@@ -564,12 +576,12 @@ __device__ __forceinline__ double prolong2_jacobi_cell(const LevelDevT<R> &L0, c
 }
 
 // ---- per-level kernels (big levels) -----------------------------------------------------------------
-template <class R>
+template <class R, bool REG>
 __global__ __launch_bounds__(256) void k_amg_pre(LevelDevT<R> L, const double *b, int two, double *out) {
     const long tid = xcd_tid();
     if (tid >= L.g.nown) return;
     const long c = L.g.np + tid;
-    out[c] = two ? pre2_cell(L, b, tid) : L.invd[c] * b[c];
+    out[c] = two ? pre2_cell<R, REG>(L, b, tid) : invd_at<R, REG>(L, c) * b[c];
 }
 template <class R, bool REG>
 __global__ __launch_bounds__(256) void k_amg_jacobi(LevelDevT<R> L, const double *b, const double *x, double *out) {
@@ -621,6 +633,126 @@ __global__ __launch_bounds__(256) void k_amg_restrict(LevelDevT<R> Lf, GridDev g
     const long tid = xcd_tid();
     if (tid >= gc.nown) return;
     rc[gc.np + tid] = restrict_cell(Lf, gc, r, tid);
+}
+// Residual + restriction of a top level in ONE launch that neither stores the residual (k_amg_resid -> k_amg_restrict: a
+// plane written and read back) nor recomputes it (k_amg_resid_restrict: three residuals per coarse cell, issue-bound up here).
+// Every thread owns K FINE cells of a tile: r = b - A x by resid_at, loads coalesced along axis 0 as in k_amg_resid; the
+// products wp r and wm r -- restrict_cell's vm of the C cell after it and vp of the C cell before it, the same two operands, so
+// the same bits -- go to LDS, and after one barrier the owners of the C cells add r + (hm ? vm : 0) + (hp ? vp : 0) in
+// restrict_cell's order.  Restriction couples cells along the coarsening axis a only, so a tile shares nothing with its
+// neighbours but the single F cell at each end along a, which both evaluate:
+//   a = 1, 2: a tile is W cells of a row x H cells along a (row: a line of n0 cells for a = 1, a whole plane for a = 2;
+//             W H <= K TP_BLOCK, H odd, slot s = j TP_BLOCK + thread is cell (s % W, s / W)), starts and ends on an F cell and
+//             writes its (H - 1) / 2 C cells per column: H residuals for H - 1 cells of the level;
+//   a = 0:    (FLAT) a tile is TP_BLOCK consecutive cells of the level, cut anywhere -- C/F parity comes from each cell's own i0,
+//             a line's last cell never pairs with the next line's first -- and writes the C cells among its inner TP_BLOCK - 2.
+// Cells outside the level (a tile's overhang) compute on clamped addresses and are never selected: no branch around a load.
+// Launched where the transfer does not cross a slab boundary (par_of = 0, no open ends: vcycle_impl keeps the two launches there).
+struct RrTile {
+    int W, H;               // tile: W cells along the row, H along the coarsening axis
+    int nr, nfa;            // row length, fine extent along the coarsening axis
+    unsigned ntw, nta;      // tiles per row, tiles along the coarsening axis
+    unsigned ntiles;
+    long sa, so;            // fine strides: along the coarsening axis, from row set to row set (a = 1: plane to plane)
+    long csa, cso;          // the same on the coarse grid
+};
+template <class R, bool FLAT, int K>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_resid_restrict_tile(LevelDevT<R> Lf, GridDev gc, RrTile T,
+                                                                      const double *__restrict__ b,
+                                                                      const double *__restrict__ x, double *__restrict__ rc) {
+    constexpr int NS = K * TP_BLOCK;                                // cells of a tile at most: K per thread
+    __shared__ double s_m[NS], s_p[NS];
+    const unsigned nb = gridDim.x, bi = blockIdx.x;
+    const unsigned tile = (bi & 7u) * (nb >> 3) + (bi >> 3);       // xcd_tid's block order: neighbouring tiles share an L2
+    if (tile >= T.ntiles) return;                                   // (whole workgroups of the grid's padding)
+    const int t = (int)threadIdx.x;
+    const GridDev &g = Lf.g;
+    double r[K];
+    long cc[K];             // the coarse cell a slot writes if its fine cell is a C cell
+    bool outc[K], hm[K], hp[K];
+    int lm[K], lp[K];       // LDS slots of the F neighbours
+    unsigned tw = 0, ta = 0, to = 0;
+    if constexpr (!FLAT) {
+        const unsigned rest = tile / T.ntw;
+        tw = tile - rest * T.ntw;
+        to = rest / T.nta;
+        ta = rest - to * T.nta;
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int s = j * TP_BLOCK + t;
+        long c, cw;         // the fine cell of this slot, clamped into the level; where it reads its weights
+        if constexpr (FLAT) {
+            const long raw = (long)tile * (TP_BLOCK - 2) - 1 + t;
+            const long tid = raw < 0 ? 0 : (raw < g.nown ? raw : g.nown - 1);
+            int i0, i1, i2;
+            cell_ijk(g, tid, i0, i1, i2);
+            c = g.np + tid;
+            cc[j] = gc.np + (long)(i0 >> 1) + (long)gc.n0 * i1 + gc.np * i2;
+            outc[j] = raw == tid && t >= 1 && t <= TP_BLOCK - 2 && !(i0 & 1);
+            hm[j] = i0 - 1 >= 0;
+            hp[j] = i0 + 1 < g.n0;
+            lm[j] = max(t - 1, 0);
+            lp[j] = min(t + 1, TP_BLOCK - 1);
+            cw = c;
+        } else {
+            const int h = (int)((unsigned)s / (unsigned)T.W), w = s - h * T.W;
+            const int q = (int)tw * T.W + w, fa = (int)ta * (T.H - 1) - 1 + h;
+            const int qc = min(q, T.nr - 1), fc = min(max(fa, 0), T.nfa - 1);
+            c = g.np + (long)qc + T.sa * fc + T.so * to;
+            cc[j] = gc.np + (long)qc + T.csa * (fc >> 1) + T.cso * to;
+            outc[j] = q == qc && fa == fc && h < T.H && (h & 1);    // (H - 1 is even: odd h <=> even fa <=> C cell)
+            hm[j] = fa - 1 >= 0;
+            hp[j] = fa + 1 < T.nfa;
+            lm[j] = s >= T.W ? s - T.W : s;
+            lp[j] = s + T.W < NS ? s + T.W : s;
+            // whole rows are C rows here and nobody reads a C cell's products: it loads the weights of the F cell next to it, a
+            // line the F row's own threads fetch anyway, so that half of the two weight planes never leaves HBM
+            cw = c + ((h & 1) ? (hp[j] ? T.sa : -T.sa) : 0);
+        }
+        r[j] = resid_at(Lf, b, x, c);
+        s_m[s] = (double)Lf.wp[cw] * r[j];
+        s_p[s] = (double)Lf.wm[cw] * r[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double vm = s_m[lm[j]], vp = s_p[lp[j]];
+        if (outc[j]) rc[cc[j]] = r[j] + (hm[j] ? vm : 0.0) + (hp[j] ? vp : 0.0);
+    }
+}
+// the tile of a level, RR_K cells per thread.  Rows: planes for a = 2 (W = 32), lines of n0 cells for a = 1 (W in [16, 36], the
+// one that wastes the fewest slots on the lines' ends and the tile's last row).  H: the tiles along a share its coarse cells
+// evenly, so that the last one does not hang over the level's end (C4, 5100-cell planes: 32 x 15 on 220 and 110 planes).
+constexpr int RR_K = 2;
+static RrTile rr_tile(const GridDev &gf, const GridDev &gc, int a) {
+    RrTile T = {};
+    if (a == 0) {
+        T.ntiles = (unsigned)((gf.nown + TP_BLOCK - 3) / (TP_BLOCK - 2));
+        return T;
+    }
+    const int NS = RR_K * TP_BLOCK;
+    T.nr = a == 1 ? gf.n0 : (int)gf.np;
+    T.nfa = a == 1 ? gf.n1 : gf.n2;
+    T.sa = a == 1 ? gf.n0 : gf.np;
+    T.so = a == 1 ? gf.np : 0;
+    T.csa = a == 1 ? gc.n0 : gc.np;
+    T.cso = a == 1 ? gc.np : 0;
+    T.W = 32;
+    if (a == 1) {
+        double best = 0.0;
+        for (int W = 16; W <= 36; ++W) {
+            const int H = (NS / W - 1) | 1;
+            const double e = (double)T.nr / ((double)((T.nr + W - 1) / W) * W) * (W * (H - 1));
+            if (e > best) { best = e; T.W = W; }
+        }
+    }
+    const long nca = (T.nfa + 1) / 2, per_max = (((NS / T.W - 1) | 1) - 1) / 2;
+    T.nta = (unsigned)((nca + per_max - 1) / per_max);
+    T.H = 2 * (int)((nca + T.nta - 1) / T.nta) + 1;
+    T.ntw = (unsigned)((T.nr + T.W - 1) / T.W);
+    T.ntiles = T.ntw * T.nta * (unsigned)(a == 1 ? gf.n2 : 1);
+    return T;
 }
 // x = P ec: the up-sweep of a pure transfer level
 template <class R>
@@ -798,7 +930,7 @@ __device__ __forceinline__ void tail_sweeps(const LevelDevT<R> *lv, int l0, int 
         }
         double *cur = L.x, *oth = L.x2;
         for (long i = t; i < L.g.nown; i += T)
-            cur[L.g.np + i] = L.pre >= 2 ? pre2_cell(L, b, i) : L.invd[L.g.np + i] * b[L.g.np + i];
+            cur[L.g.np + i] = L.pre >= 2 ? pre2_cell<R, false>(L, b, i) : L.invd[L.g.np + i] * b[L.g.np + i];
         __syncthreads();
         for (int k = 2; k < L.pre; ++k) {
             for (long i = t; i < L.g.nown; i += T) oth[L.g.np + i] = jacobi_cell(L, b, cur, i);
@@ -814,7 +946,7 @@ __device__ __forceinline__ void tail_sweeps(const LevelDevT<R> *lv, int l0, int 
         const double *b = (nlev - 1 == l0) ? b_top : Lc.b;
         double *e = (nlev - 1 == l0) ? e_top : Lc.e;
         if (trunc >= 0) {                 // relaxation-only level: x = x1 + invd (b - A x1), x1 = invd b
-            for (long i = t; i < Lc.g.nown; i += T) e[Lc.g.np + i] = pre2_cell(Lc, b, i);
+            for (long i = t; i < Lc.g.nown; i += T) e[Lc.g.np + i] = pre2_cell<R, false>(Lc, b, i);
             __syncthreads();
         } else {
         // 16 lanes per row: coalesced reads of the row, 4 independent products per lane, shuffle reduction
@@ -1395,6 +1527,8 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     static const bool pair_on = !(getenv("TP_AMG_PAIR") && atoi(getenv("TP_AMG_PAIR")) == 0);
     // the sweeps' centre-cell omega / diag: recomputed in registers (invd_at), or TP_AMG_INVD_LOAD=1: read from the stored plane
     static const bool invd_reg = !(getenv("TP_AMG_INVD_LOAD") && atoi(getenv("TP_AMG_INVD_LOAD")) != 0);
+    // residual + restriction of the top levels in one tiled launch; TP_AMG_RR_FUSE=0: k_amg_resid, then k_amg_restrict
+    static const bool rr_fuse = !(getenv("TP_AMG_RR_FUSE") && atoi(getenv("TP_AMG_RR_FUSE")) == 0);
 #define TP_AMG_REG_LAUNCH(KERNEL, ...)                                                                         \
     do {                                                                                                       \
         if (invd_reg) hipLaunchKernelGGL((KERNEL<R, true>), __VA_ARGS__);                                      \
@@ -1481,7 +1615,9 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
                 }
             } else {
             if (Ld.pre >= 2) hx(l, bl_);            // the fused double sweep reads invd*b of the neighbours
-            hipLaunchKernelGGL(k_amg_pre<R>, gr, bl, 0, c->stream, Ld, bl_, Ld.pre >= 2 ? 1 : 0, cur);
+            // (slab-distributed levels keep the stored plane: their halo diagonals are not exchanged)
+            if (invd_reg && l >= lg) hipLaunchKernelGGL((k_amg_pre<R, true>), gr, bl, 0, c->stream, Ld, bl_, Ld.pre >= 2 ? 1 : 0, cur);
+            else hipLaunchKernelGGL((k_amg_pre<R, false>), gr, bl, 0, c->stream, Ld, bl_, Ld.pre >= 2 ? 1 : 0, cur);
             for (int k = 2; k < Ld.pre; ++k) {
                 hx(l, cur);
                 TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)cur, oth);
@@ -1490,7 +1626,13 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             }
             xs[l] = cur;
             hx(l, cur);
-            if (slab_axis || L->g.nown >= amg->fuse_below) {
+            if (rr_fuse && !slab_axis && L->g.nown >= amg->fuse_below) {
+                // the residual goes to its coarse cells through LDS: one launch, no residual vector (k_amg_resid_restrict_tile)
+                const RrTile T = rr_tile(L->g, cv.g, L->axis);
+                const dim3 gt((T.ntiles + 7u) / 8u * 8u);
+                if (L->axis == 0) hipLaunchKernelGGL((k_amg_resid_restrict_tile<R, true, 1>), gt, dim3(TP_BLOCK), 0, c->stream, Ld, cv.g, T, bl_, (const double *)cur, bc);
+                else hipLaunchKernelGGL((k_amg_resid_restrict_tile<R, false, RR_K>), gt, dim3(TP_BLOCK), 0, c->stream, Ld, cv.g, T, bl_, (const double *)cur, bc);
+            } else if (slab_axis || L->g.nown >= amg->fuse_below) {
                 hipLaunchKernelGGL(k_amg_resid<R>, gr, bl, 0, c->stream, Ld, bl_, (const double *)cur, oth);
                 if (slab_axis) hx(l, oth);
                 hipLaunchKernelGGL(k_amg_restrict<R>, xcd_grid(cv.g.nown), bl, 0, c->stream, Ld, cv.g, (const double *)oth, bc);
@@ -1514,7 +1656,8 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             line_sweep(trunc, bt, L->x.p, et);
         } else {
         hx(trunc, bt);                              // the fused double sweep reads invd*b of the neighbours
-        hipLaunchKernelGGL(k_amg_pre<R>, xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, trunc), bt, 1, et);
+        if (invd_reg && trunc >= lg) hipLaunchKernelGGL((k_amg_pre<R, true>), xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, trunc), bt, 1, et);
+        else hipLaunchKernelGGL((k_amg_pre<R, false>), xcd_grid(L->g.nown), bl, 0, c->stream, dev_of<R>(amg, trunc), bt, 1, et);
         }
     } else {
         // the tail: every level from lt down to the coarsest (or the truncation level) and back, one launch
