@@ -1,5 +1,5 @@
 """Restarted FGMRES from x0 = 0 with both Krylov bases stored in fp32, in numpy: the reference of the GPU solver under
-tp_options.ksp_basis_single (fgmres_single in thermalporous_amd/csrc/tp_solver.hip), with the same stops and reason codes.
+tp_options.ksp_basis_single (fgmres in thermalporous_amd/csrc/tp_solver.hip, fp32 form), with the same stops and reason codes.
 
     tol = max(rtol ||b||, atol);  r = b;  beta = ||b||
     cycle:  stop = max(tol, theta beta);  V_0 = fl32(r / beta)

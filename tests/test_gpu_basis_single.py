@@ -181,6 +181,35 @@ def test_tight_tolerance_converges_on_the_true_residual():
     h.close()
 
 
+def test_discarded_speculation_leaves_no_trace():
+    """ksp_rtol 0.05 on the pc_cptramg_QI input (the pc_cptr input's convergence is too even for any tolerance to do this): the
+    reference converges in ONE iteration, its recurrence residual 0.0084 ||b|| a factor 2 and more under the threshold, and
+    confirms it on the true residual of its one cycle.  The pipelined loop has by then queued the speculative v_1,
+    z_1 = M^-1 v_1 and J z_1 (the predicted residual, ||b||, is above TP_SPEC_MARGIN x stop = 0.2 ||b||, by more than a factor 2
+    as well), through the staging vectors into slot 1 of both bases; that work is discarded.  This solve and the ordinary one
+    that follows on the same context are the reference's."""
+    rtol = 0.05
+    p = BY_NAME["c4_cptramg_QI"]
+    ref1, ref = reference(p, rtol=rtol), reference(p)
+    bn = ref["hist"][0]
+    assert (ref1["its"], ref1["reason"], ref1["cycles"]) == (1, 2, 1) and ref1["hist"][1] <= 0.5*rtol*bn and 2*4*rtol <= 1.0
+    h = gpu_engine(ref, p, opts=dict(ksp_rtol=rtol))
+    h.vec_set("b", ref["b"])
+    its, reason, rn = h.fgmres("b", "d")
+    x = h.vec_get("d")
+    tr = true_residual(ref, x)
+    info = h.ksp_basis_info()
+    print("discarded: its", its, "rnorm/||b|| %.4e" % (rn/bn), "ref %.4e" % (ref1["info"]["rnorm"]/bn), "x rel2 %.3e" % rel2(x, ref1["x"]))
+    assert (its, reason, info["cycles"], info["true_residuals"]) == (1, 2, 1, 1)
+    assert rel2(x, ref1["x"]) <= R.PARITY_TOL
+    assert abs(rn - tr) <= 1e-10*bn and rn <= rtol*bn
+    h.set_options(ksp_rtol=R.RTOL)
+    its, reason, rn = h.fgmres("b", "d")
+    assert reason == 2 and abs(its - ref["its"]) <= 1 and h.ksp_basis_info()["cycles"] == ref["cycles"]
+    assert rel2(h.vec_get("d"), ref["x"]) <= R.PARITY_TOL and rn <= R.RTOL*bn
+    h.close()
+
+
 def test_limits():
     p = BY_NAME["c4_cptr"]
     ref = reference(p)

@@ -412,7 +412,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
     wide = wide && allow_wide;
     const long nw = bc_nwaves(g, B, wide ? 2 : 1);
     const dim3 gw = xcd_grid(nw * 64, TP_BLOCK), bl(TP_BLOCK), one(1), wv(64);
-    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    const bool use_pin = tp_use_pin();
     double *pin = use_pin ? c->h_pin : nullptr;
     double hb[BH_N] = {0};
     // sums -> (all-reduced) state; every rank forms the same coefficients and latches from the same sums

@@ -460,10 +460,12 @@ void multi_axpy(tp_ctx *c, int nf, const double *V, long vstride, int k, const d
                 double *w);          // w += sign * sum_i h_i V_i
 double norm2(tp_ctx *c, int nf, const double *x);
 void multi_norm2sq(tp_ctx *c, int nf, int nvec, const double *const *x, double *host_out);   // host_out[i] = <x_i, x_i>
-// h = V^T w ; w -= V h ; host_out[0..k-1] = h, host_out[k] = ||w||^2  (one host sync)
+// TP_PIN (default 1; read once per process): the reductions' sums reach the host through the pinned, device-mapped buffer h_pin
+bool tp_use_pin();
+// h = V^T w ; w -= V h ; host_out[0..k-1] = h, host_out[k] = ||w||^2  (one host sync).  host_out = nullptr (only where
+// orthogonalize_can_split): enqueue only; orthogonalize_wait then hands the sums over, ||w||^2 stays at orthogonalize_norm_dev
 void orthogonalize(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w, double *host_out);
 bool orthogonalize_can_split(const tp_ctx *c, int k);
-void orthogonalize_enqueue(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w);
 const double *orthogonalize_norm_dev(const tp_ctx *c, int k);
 void orthogonalize_wait(tp_ctx *c, int k, double *host_out);
 // the same step with the refinement mode and eta given by the caller instead of tp_options (tp_vec_orth_step); *refined = the
@@ -481,7 +483,6 @@ void basis_scale_store_dev(tp_ctx *c, int nf, const double *n2_dev, double *x, f
 void multi_dot_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *w, double *host_out);
 void multi_axpy_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, const double *hcoef_host, double sign, double *w);
 void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w, double *host_out);
-void orthogonalize_enqueue_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w);
 // line search (tp_options.ls_kind = 1): host_out = {||dx||^2, max|dx_f| f < 3} over owned cells, all slabs (one host sync);
 // u = u0 - lambda dx on owned cells of all fields
 void ls_step_stats(tp_ctx *c, const double *dx, double *host_out);
@@ -559,7 +560,7 @@ void schur_count(tp_ctx *c, int stages);
 void pc_ctr_check_options(const tp_options &o, int nranks);
 void ctr_apply(tp_ctx *c, const double *x, double *y);
 // rtol: the relative tolerance of THIS solve (tp_fgmres / tp_bcgs pass tp_options.ksp_rtol, newton() the same or, under ksp_ew, eta_k):
-// every reader of the tolerance -- both FGMRES loops, the speculation margin, the fp32-basis loop's true-residual test, the
+// every reader of the tolerance -- the FGMRES loop in both basis representations, the speculation margin, the fp32 basis' true-residual test, the
 // BiCGStab latch on the device -- follows it; tp_options is never written
 int fgmres(tp_ctx *c, const double *b, double *x, int *its, double *rnorm, double rtol);
 // outer BiCGStab (tp_bcgs.hip): same contract as fgmres; reasons 2, -3, -5 (breakdown), -9

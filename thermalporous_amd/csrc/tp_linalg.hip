@@ -188,11 +188,15 @@ static long md_nwaves(const tp_ctx *c, int nf) {
     const long nall = c->g.nown * nf;
     return (nall + 64L * md_chunk() - 1) / (64L * md_chunk());
 }
+bool tp_use_pin() {
+    static const bool on = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    return on;
+}
 // second stage of a reduction + hand-over to the host: n sums of nw partials -> red_out (device) and host_out.  One GPU: the
 // kernel also writes to the pinned buffer and the host copies from there after the synchronisation; several GPUs: all-reduce,
 // then a device-to-host copy.
 static void reduce_to_host(tp_ctx *c, long nw, int n, double *host_out) {
-    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    const bool use_pin = tp_use_pin();
     double *pin = (use_pin && !c->dist && n <= tp_ctx::H_PIN) ? c->h_pin : nullptr;
     hipLaunchKernelGGL(k_reduce_partials, dim3(n), dim3(1024), 0, c->stream, c->gs_partial.p, nw, c->red_out.p, pin);
     TP_HIP(hipGetLastError());
@@ -860,7 +864,7 @@ static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *V
     else TP_MD_LAUNCH(k_multi_dot, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k, w,
                       (const double *)nullptr, c->gs_partial.p, nw);
     // one GPU: the sums also go straight to pinned host memory (no copy between the last kernel and the host's wake-up)
-    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    const bool use_pin = tp_use_pin();
     double *pin = (use_pin && !c->dist && k + 1 <= tp_ctx::H_PIN) ? c->h_pin : nullptr;
     hipLaunchKernelGGL(k_reduce_partials, dim3(k), dim3(1024), 0, c->stream, c->gs_partial.p, nw, c->red_out.p, pin);
     allreduce_sum(c, c->red_out.p, k);
@@ -875,7 +879,7 @@ static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *V
     allreduce_sum(c, c->red_out.p + k, 1);
     if (ro) reorth_pass(c, nf, V, vstride, k, w, nw, pin, ro, ro_eta, gs_rev);
     if (pin) {
-        if (!host_out) {                   // split form (orthogonalize_enqueue / orthogonalize_wait): the caller goes on enqueueing
+        if (!host_out) {                   // split form (orthogonalize_wait reads the sums): the caller goes on enqueueing
             TP_HIP(hipEventRecord(c->ev_h, c->stream));
             return;
         }
@@ -907,21 +911,12 @@ void orthogonalize_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, do
     orthogonalize_any(c, nf, nullptr, Vs, vstride, k, w, host_out);
 }
 
-// The same in two halves for the pipelined FGMRES loop: enqueue the kernels (and all-reduces) and record an event; later wait
+// The same in two halves for the pipelined FGMRES loop: host_out = nullptr enqueues the kernels (and all-reduces) and records an event; later wait
 // for that event only -- whatever was enqueued behind it (the next iteration's preconditioner application) keeps running -- and
 // read the k dots and ||w||^2 from the pinned buffer.  ||w||^2 also stays on the device at orthogonalize_norm_dev(c, k).
 // Several GPUs: every rank holds the same all-reduced sums, takes the same speculation decision and therefore issues the same
 // sequence of collectives.
-bool orthogonalize_can_split(const tp_ctx *c, int k) {
-    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
-    return use_pin && k + 1 <= tp_ctx::H_PIN;
-}
-void orthogonalize_enqueue(tp_ctx *c, int nf, const double *V, long vstride, int k, double *w) {
-    orthogonalize(c, nf, V, vstride, k, w, nullptr);
-}
-void orthogonalize_enqueue_s(tp_ctx *c, int nf, const float *Vs, long vstride, int k, double *w) {
-    orthogonalize_s(c, nf, Vs, vstride, k, w, nullptr);
-}
+bool orthogonalize_can_split(const tp_ctx *c, int k) { return tp_use_pin() && k + 1 <= tp_ctx::H_PIN; }
 const double *orthogonalize_norm_dev(const tp_ctx *c, int k) { return c->red_out.p + k; }
 void orthogonalize_wait(tp_ctx *c, int k, double *host_out) {
     TP_HIP(hipEventSynchronize(c->ev_h));
@@ -1035,7 +1030,7 @@ void ls_step_stats(tp_ctx *c, const double *dx, double *host_out) {
     const int nbx = (int)((g.nown + (long)TP_BLOCK * LS_PER - 1) / ((long)TP_BLOCK * LS_PER));
     if ((long)c->gs_partial.n < 2L * nf * nbx) c->gs_partial.alloc((size_t)2 * nf * nbx + 64);
     if ((long)c->red_out.n < 4) c->red_out.alloc(64);
-    static const bool use_pin = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    const bool use_pin = tp_use_pin();
     double *pin = (use_pin && !c->dist) ? c->h_pin : nullptr;
     hipLaunchKernelGGL(k_ls_step_stats, dim3(nbx, nf), dim3(TP_BLOCK), 0, c->stream, g, dx, c->gs_partial.p, nbx, nf);
     hipLaunchKernelGGL(k_ls_final, dim3(4), dim3(1024), 0, c->stream, (const double *)c->gs_partial.p, nbx, nf, c->red_out.p, pin);

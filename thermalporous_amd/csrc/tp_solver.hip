@@ -627,7 +627,7 @@ void pc_apply(tp_ctx *c, const double *x, double *y) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// FGMRES with the bases stored in fp32 (tp_options.ksp_basis_single; compressed-basis GMRES).
+// FGMRES's options.  The bases stored in fp32 (tp_options.ksp_basis_single; compressed-basis GMRES)
 void basis_single_check_options(const tp_options &o) {
     if (!o.ksp_basis_single) return;
     TP_REQUIRE(o.ksp_kind == 0, "ksp_basis_single with ksp_kind 1 (bcgs): BiCGStab has no basis to store in fp32");
@@ -677,48 +677,104 @@ static void hessenberg_solve(const std::vector<double> &H, const std::vector<dou
     }
 }
 
-// The loop of fgmres() below with three differences.  (1) Storage: Vs_j, Zs_j are floats; the fp64 vectors the preconditioner,
-// the SpMV and the orthogonalisation work on are the two staging vectors W and Zt.  z_j = M^-1 v_j is rounded into Zs_j and Zt
-// widened back BEFORE w = J Zt, so FGMRES stays exactly consistent with the stored Z; w is orthogonalised in W against the
-// widened Vs, then W <- widen(Vs_{j+1} = (float)(w/||w||)) in place, which is the next v.  (2) A cycle also ends when its
-// recurrence residual reaches theta * beta_cycle: below that the rounded basis has lost its orthogonality and the recurrence
-// no longer tracks the residual.  (3) Convergence is only ever declared on the recomputed r = b - J x at a cycle's end.
-static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
+// basis storage grows on demand (restart 200 x 2 vectors would be 10.8 GB on SPE10 3-D), to max(need, min(restart + 1,
+// max(32, 2 cap))) vectors; in the fp32 form the padding between two vectors arrives zeroed and is never written
+template <typename T>
+static void grow_basis(tp_ctx *c, DBuf<T> &V, DBuf<T> &Z, int &have, long stride, int need, int restart) {
+    if (have >= need) return;
+    const int cap = std::max(need, std::min(restart + 1, std::max(32, 2 * have)));
+    DBuf<T> nV, nZ;
+    nV.alloc((size_t)cap * stride);
+    nZ.alloc((size_t)cap * stride);
+    if (have > 0) {
+        TP_HIP(hipMemcpyAsync(nV.p, V.p, sizeof(T) * have * stride, hipMemcpyDeviceToDevice, c->stream));
+        TP_HIP(hipMemcpyAsync(nZ.p, Z.p, sizeof(T) * have * stride, hipMemcpyDeviceToDevice, c->stream));
+        TP_HIP(hipStreamSynchronize(c->stream));
+    }
+    std::swap(V.p, nV.p); std::swap(V.n, nV.n);
+    std::swap(Z.p, nZ.p); std::swap(Z.n, nZ.n);
+    have = cap;
+}
+
+// ------------------------------------------------------------------------------------------------
+// FGMRES(m) from x0 = 0 to the relative tolerance rtol (ksp_rtol, or the solve's eta under ksp_ew: tp_common.hpp).  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
+// (the other outer method, tp_options.ksp_kind = 1, is bcgs in tp_bcgs.hip)
+//
+// One restart loop serves both representations of the bases, chosen by tp_options.ksp_basis_single.  What
+// they differ in stands in the helpers at the head of the function and in the verdict at a cycle's end:
+//                   fp64 basis                               fp32 basis
+//   storage         V_j, Z_j doubles, nv apart (gs_cap)      Vs_j, Zs_j floats, basis_stride() apart (gs_cap_s); the fp64 vectors
+//                                                            the kernels work on are the staging vectors W and Zt (kstage)
+//   z_j, w          Z_j = M^-1 V_j ; V_{j+1} = J Z_j         Zt = M^-1 W ; Zs_j = (float) Zt, Zt widened back BEFORE W = J Zt, so
+//                                                            FGMRES stays exactly consistent with the stored Z
+//   v_{j+1}         V_{j+1} scaled in place                  Vs_{j+1} = (float)(W/||W||), W <- widen(Vs_{j+1}) in place
+//   orthogonalise   against V, with ksp_reorth               W against the widened Vs, one pass
+//   cycle ends at   tol                                      max(tol, theta beta_cycle), theta = ksp_single_floor: below that the
+//                                                            rounded basis has lost its orthogonality and the recurrence no
+//                                                            longer tracks the residual
+//   verdict         the recurrence residual; r = b - J x     always r = b - J x, recomputed at every cycle's end (counted in
+//                   is formed only to restart                ksp_cycles, ksp_true_res)
+int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
     const GridDev &g = c->g;
     const int B = c->b;
-    const long nv = (long)B * g.ntot, vs = basis_stride(c);
+    const bool single = c->opt.ksp_basis_single;
+    const long nv = (long)B * g.ntot, vs = single ? basis_stride(c) : nv;
     const int maxit = c->opt.ksp_max_it;
     const int restart = std::max(1, std::min(c->opt.ksp_restart, maxit));
-    const double theta = c->opt.ksp_single_floor;
     ensure_work(c);
-    c->ksp_cycles = c->ksp_true_res = 0;
-    if (c->kstage.n < (size_t)tp_ctx::KS_STAGE * nv) c->kstage.alloc((size_t)tp_ctx::KS_STAGE * nv);
-    double *W = c->kstage.p, *Zt = c->kstage.p + nv;
-    // growth on demand as in fgmres(); the padding between two vectors arrives zeroed and is never written
+    double *W = nullptr, *Zt = nullptr;
+    if (single) {
+        c->ksp_cycles = c->ksp_true_res = 0;
+        if (c->kstage.n < (size_t)tp_ctx::KS_STAGE * nv) c->kstage.alloc((size_t)tp_ctx::KS_STAGE * nv);
+        W = c->kstage.p;
+        Zt = c->kstage.p + nv;
+    }
+    // ---- the basis: everything the two representations differ in, up to the verdict at a cycle's end (the pointers are formed
+    // at the call: ensure_basis moves the storage) ----
     auto ensure_basis = [&](int need) {
-        if (c->gs_cap_s >= need) return;
-        const int cap = std::max(need, std::min(restart + 1, std::max(32, 2 * c->gs_cap_s)));
-        DBuf<float> nV, nZ;
-        nV.alloc((size_t)cap * vs);
-        nZ.alloc((size_t)cap * vs);
-        if (c->gs_cap_s > 0) {
-            TP_HIP(hipMemcpyAsync(nV.p, c->Vs.p, sizeof(float) * c->gs_cap_s * vs, hipMemcpyDeviceToDevice, c->stream));
-            TP_HIP(hipMemcpyAsync(nZ.p, c->Zs.p, sizeof(float) * c->gs_cap_s * vs, hipMemcpyDeviceToDevice, c->stream));
-            TP_HIP(hipStreamSynchronize(c->stream));
-        }
-        std::swap(c->Vs.p, nV.p); std::swap(c->Vs.n, nV.n);
-        std::swap(c->Zs.p, nZ.p); std::swap(c->Zs.n, nZ.n);
-        c->gs_cap_s = cap;
+        if (single) grow_basis(c, c->Vs, c->Zs, c->gs_cap_s, vs, need, restart);
+        else grow_basis(c, c->V, c->Z, c->gs_cap, nv, need, restart);
     };
+    auto w_of = [&](int j) { return single ? W : c->V.p + (long)(j + 1) * nv; };                 // where w = J z_j lives
+    auto apply_and_multiply = [&](int j) {                                                         // z_j = M^-1 v_j ; w = J z_j
+        double *v = single ? W : c->V.p + (long)j * nv, *z = single ? Zt : c->Z.p + (long)j * nv;
+        pc_apply(c, v, z);
+        if (single) basis_round_store(c, B, Zt, c->Zs.p + (long)j * vs);
+        spmv_block_halo(c, c->J.p, z, w_of(j));                  // (multi-GPU: exchange of z_j's halos overlapped)
+    };
+    auto orth = [&](int j, double *host_out) {                   // h = V^T w ; w -= V h ; ||w||^2 (host_out null: no host wait yet)
+        if (single) orthogonalize_s(c, B, c->Vs.p, vs, j + 1, W, host_out);
+        else orthogonalize(c, B, c->V.p, nv, j + 1, w_of(j), host_out);
+    };
+    auto set_v = [&](int j, double a, const double *src) {       // v_j = a src
+        if (single) basis_scale_store(c, B, a, src, W, c->Vs.p + (long)j * vs);
+        else vec_scale_to(c, B, a, src, c->V.p + (long)j * nv);
+    };
+    auto set_v_dev_norm = [&](int j) {                           // v_{j+1} = w/||w||, the norm still on the device
+        if (single) basis_scale_store_dev(c, B, orthogonalize_norm_dev(c, j + 1), W, c->Vs.p + (long)(j + 1) * vs);
+        else vec_scale_dev_norm(c, B, orthogonalize_norm_dev(c, j + 1), w_of(j));
+    };
+    auto add_Zy = [&](int k, const double *y, double *dst) {     // dst += Z y
+        if (single) multi_axpy_s(c, B, c->Zs.p, vs, k, y, 1.0, dst);
+        else multi_axpy(c, B, c->Z.p, nv, k, y, 1.0, dst);
+    };
+    int its = 0;
+    auto done = [&](int reason, double rnorm) { *its_out = its; *rnorm_out = rnorm; return reason; };
+
     vec_zero(c, x, nv);
     const double bnorm = norm2(c, B, bvec);
-    int its = 0;
-    if (bnorm == 0.0) { *its_out = 0; *rnorm_out = 0.0; return 2; }
-    if (!std::isfinite(bnorm)) { *its_out = 0; *rnorm_out = bnorm; return -9; }
+    if (bnorm == 0.0) return done(2, 0.0);
+    if (!std::isfinite(bnorm)) return done(-9, bnorm);
     const double tol = std::max(rtol * bnorm, c->opt.ksp_atol);
     double beta = bnorm;
     const double *rsrc = bvec;
     std::vector<double> H, cs, sn, gvec, hcol, yk;
+    // The loop is PIPELINED.  The host needs h (Givens rotations, convergence test) once per iteration; waiting for
+    // it with the stream empty leaves the GPU idle for a host wake-up plus a launch latency (~40 us of a 1.1 ms iteration).
+    // Instead v_{j+1} = w / ||w|| is formed from the norm on the device and z_{j+1} = M^-1 v_{j+1}, J z_{j+1} are enqueued
+    // BEFORE the host waits -- on an event behind the reductions, not on the stream.  Speculative: if iteration j turns out
+    // to be the last, that work is discarded (~0.9 ms), so it is only issued while the residual, extrapolated with the last
+    // reduction factor, stays 4x above the cycle's threshold.  Same arithmetic either way (bit-identical iterates).
     static const bool pipe_on = !(getenv("TP_FGMRES_PIPE") && atoi(getenv("TP_FGMRES_PIPE")) == 0);
     static const double spec_margin = getenv("TP_SPEC_MARGIN") ? atof(getenv("TP_SPEC_MARGIN")) : 4.0;
     while (true) {
@@ -727,52 +783,47 @@ static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out,
         cs.assign(m, 0.0); sn.assign(m, 0.0); gvec.assign(m + 1, 0.0);
         hcol.resize(m + 2);
         gvec[0] = beta;
-        const double stop = std::max(tol, theta * beta);                    // this cycle's stopping threshold
-        ++c->ksp_cycles;
+        // this cycle's stopping threshold (not folded into max(tol, 0 * beta): the fp64 form compares with tol whatever beta is)
+        const double stop = single ? std::max(tol, c->opt.ksp_single_floor * beta) : tol;
+        if (single) ++c->ksp_cycles;
         ensure_basis(2);
-        basis_scale_store(c, B, 1.0 / beta, rsrc, W, c->Vs.p);             // Vs_0 = (float)(r/beta), W = v_0
-        int k = 0;
-        bool nonfinite = false;
+        set_v(0, 1.0 / beta, rsrc);                                         // v0 = r/beta
+        int k = 0, reason = 0;
         double res = beta, res_prev = beta, rate = 1.0;
-        bool have_w = false;               // z_j, w = J z_j already enqueued by the previous iteration (pipelining: see fgmres())
+        bool have_w = false;               // z_j, w = J z_j already enqueued by the previous iteration
         for (int j = 0; j < m; ++j) {
             const bool pipe = pipe_on && !c->monitor && orthogonalize_can_split(c, j + 2);
             ensure_basis(j + (pipe ? 3 : 2));
-            if (!have_w) {
-                pc_apply(c, W, Zt);                                         // z_j = M^-1 v_j
-                basis_round_store(c, B, Zt, c->Zs.p + (long)j * vs);
-                spmv_block_halo(c, c->J.p, Zt, W);                          // w = J (stored z_j)
-            }
+            if (!have_w) apply_and_multiply(j);
             have_w = false;
             bool spec = false;
             if (pipe) {
-                orthogonalize_enqueue_s(c, B, c->Vs.p, vs, j + 1, W);
-                spec = j + 1 < m && its + 1 < maxit && res_prev * std::min(rate, 1.0) > spec_margin * stop;
+                orth(j, nullptr);
+                spec = j + 1 < m && its + 1 < maxit && res_prev * std::min(rate, 1.0) > spec_margin * stop;     // (predicted res_j)
                 if (spec) ++c->spec_issued; else ++c->spec_skipped;
                 if (spec) {
-                    basis_scale_store_dev(c, B, orthogonalize_norm_dev(c, j + 1), W, c->Vs.p + (long)(j + 1) * vs);
-                    pc_apply(c, W, Zt);
-                    basis_round_store(c, B, Zt, c->Zs.p + (long)(j + 1) * vs);
-                    spmv_block_halo(c, c->J.p, Zt, W);
+                    set_v_dev_norm(j);
+                    apply_and_multiply(j + 1);
                     have_w = true;
                 }
                 orthogonalize_wait(c, j + 1, hcol.data());
             } else {
-                orthogonalize_s(c, B, c->Vs.p, vs, j + 1, W, hcol.data());
+                orth(j, hcol.data());
             }
             const double hn = std::sqrt(hcol[j + 1]);
             res = givens_column(H, cs, sn, gvec, hcol.data(), hn, m, j);
             ++its;
             k = j + 1;
             if (c->monitor) {
-                // x_j = x + Zs y_j, r = b - J x_j, ||r_f|| per field (as in fgmres())
+                // ksp.buildResidual() per field (thermalmodel.py:44-74): x_j = x + Z y_j, r = b - J x_j, ||r_f||
                 std::vector<double> ym, fn(B, 0.0);
                 hessenberg_solve(H, gvec, m, k, ym);
-                double *xm = c->w4.p, *rm = c->w2.p;                        // free between pc_apply calls (this cycle's r is already in W)
+                double *xm = c->w4.p, *rm = c->w2.p;                        // free between pc_apply calls (this cycle's r is already in v0)
                 vec_copy(c, x, xm, nv);
-                multi_axpy_s(c, B, c->Zs.p, vs, k, ym.data(), 1.0, xm);
+                add_Zy(k, ym.data(), xm);
                 if (c->dist) halo_exchange(c, g, xm, B, g.ntot);
                 resid_block_cols(c, c->J.p, bvec, xm, B, rm);
+                // (each field plane as a 1-field vector)
                 for (int f = 0; f < B; ++f) { const double *one[1] = {rm + (long)f * g.ntot}; multi_norm2sq(c, 1, 1, one, &fn[f]); fn[f] = std::sqrt(fn[f]); }
                 c->monitor(its, res, fn.data(), B, c->monitor_user);
             }
@@ -781,172 +832,30 @@ static int fgmres_single(tp_ctx *c, const double *bvec, double *x, int *its_out,
             if (!std::isfinite(res) || res <= stop || hn == 0.0) {
                 if (have_w) ++c->spec_wasted;
                 if (have_w) c->vcycles -= vcycles_per_apply(c);   // (discarded application)
-                nonfinite = !std::isfinite(res);
+                reason = !std::isfinite(res) ? -9 : 2;                     // KSP_DIVERGED_NANORINF | the recurrence's end of the cycle (or happy breakdown)
                 break;
             }
-            if (!spec) basis_scale_store(c, B, 1.0 / hn, W, W, c->Vs.p + (long)(j + 1) * vs);       // Vs_{j+1} = (float)(w/||w||), W = v_{j+1}
+            if (!spec) set_v(j + 1, 1.0 / hn, w_of(j));                     // v_{j+1} = w/||w||
         }
         hessenberg_solve(H, gvec, m, k, yk);
-        multi_axpy_s(c, B, c->Zs.p, vs, k, yk.data(), 1.0, x);               // x += Zs y
-        if (nonfinite) { *its_out = its; *rnorm_out = res; return -9; }     // KSP_DIVERGED_NANORINF
-        // the true residual decides: r = b - J x
-        if (c->dist) halo_exchange(c, g, x, B, g.ntot);
-        resid_block_cols(c, c->J.p, bvec, x, B, c->w2.p);
-        beta = norm2(c, B, c->w2.p);
-        ++c->ksp_true_res;
-        rsrc = c->w2.p;
-        *its_out = its; *rnorm_out = beta;
-        if (!std::isfinite(beta)) return -9;
-        if (beta <= tol) return 2;
-        if (its >= maxit) return -3;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// FGMRES(m) from x0 = 0 to the relative tolerance rtol (ksp_rtol, or the solve's eta under ksp_ew: tp_common.hpp).  Returns KSP reason (2 = CONVERGED_RTOL, 3 = CONVERGED_ATOL, -3 = DIVERGED_ITS).
-// (the other outer method, tp_options.ksp_kind = 1, is bcgs in tp_bcgs.hip)
-// (tp_options.ksp_basis_single: the fp32-basis form above; with the option off the loop below is untouched)
-int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_out, double rtol) {
-    if (c->opt.ksp_basis_single) return fgmres_single(c, bvec, x, its_out, rnorm_out, rtol);
-    const GridDev &g = c->g;
-    const int B = c->b;
-    const long nv = (long)B * g.ntot;
-    const int maxit = c->opt.ksp_max_it;
-    const int restart = std::max(1, std::min(c->opt.ksp_restart, maxit));
-    ensure_work(c);
-    // basis storage grows on demand (restart 200 x 2 vectors would be 10.8 GB on SPE10 3-D)
-    auto ensure_basis = [&](int need) {
-        if (c->gs_cap >= need) return;
-        int cap = std::max(need, std::min(restart + 1, std::max(32, 2 * c->gs_cap)));
-        DBuf<double> nV, nZ;
-        nV.alloc((size_t)cap * nv);
-        nZ.alloc((size_t)cap * nv);
-        if (c->gs_cap > 0) {
-            TP_HIP(hipMemcpyAsync(nV.p, c->V.p, sizeof(double) * c->gs_cap * nv, hipMemcpyDeviceToDevice, c->stream));
-            TP_HIP(hipMemcpyAsync(nZ.p, c->Z.p, sizeof(double) * c->gs_cap * nv, hipMemcpyDeviceToDevice, c->stream));
-            TP_HIP(hipStreamSynchronize(c->stream));
+        add_Zy(k, yk.data(), x);                                            // x += Z y
+        if (reason == -9) return done(-9, res);
+        if (!single) {                     // the recurrence decides; its >= maxit is tested BEFORE a restart residual is formed
+            if (reason) return done(reason, res);
+            if (its >= maxit) return done(-3, res);
         }
-        std::swap(c->V.p, nV.p); std::swap(c->V.n, nV.n);
-        std::swap(c->Z.p, nZ.p); std::swap(c->Z.n, nZ.n);
-        c->gs_cap = cap;
-    };
-    vec_zero(c, x, nv);
-    const double bnorm = norm2(c, B, bvec);
-    int its = 0;
-    if (bnorm == 0.0) { *its_out = 0; *rnorm_out = 0.0; return 2; }
-    if (!std::isfinite(bnorm)) { *its_out = 0; *rnorm_out = bnorm; return -9; }
-    const double tol = std::max(rtol * bnorm, c->opt.ksp_atol);
-    double beta = bnorm;
-    const double *rsrc = bvec;
-    std::vector<double> H, cs, sn, gvec, hcol, yk;
-    while (true) {
-        const int m = std::min(restart, maxit - its);
-        H.assign((size_t)(m + 1) * m, 0.0);
-        cs.assign(m, 0.0); sn.assign(m, 0.0); gvec.assign(m + 1, 0.0);
-        hcol.resize(m + 2);
-        gvec[0] = beta;
-        ensure_basis(2);
-        vec_scale_to(c, B, 1.0 / beta, rsrc, c->V.p);                      // v0 = r/beta
-        int k = 0, reason = 0;
-        double res = beta;
-        // The loop is PIPELINED.  The host needs h (Givens rotations, convergence test) once per iteration; waiting for
-        // it with the stream empty leaves the GPU idle for a host wake-up plus a launch latency (~40 us of a 1.1 ms iteration).
-        // Instead v_{j+1} = w / ||w|| is formed from the norm on the device and z_{j+1} = M^-1 v_{j+1}, J z_{j+1} are enqueued
-        // BEFORE the host waits -- on an event behind the reductions, not on the stream.  Speculative: if iteration j turns out
-        // to be the last, that work is discarded (~0.9 ms), so it is only issued while the residual, extrapolated with the last
-        // reduction factor, stays 4x above the tolerance.  Same arithmetic either way (bit-identical iterates).
-        static const bool pipe_on = !(getenv("TP_FGMRES_PIPE") && atoi(getenv("TP_FGMRES_PIPE")) == 0);
-        static const double spec_margin = getenv("TP_SPEC_MARGIN") ? atof(getenv("TP_SPEC_MARGIN")) : 4.0;
-        bool have_w = false;               // z_j, w = J z_j already enqueued by the previous iteration
-        double res_prev = beta, rate = 1.0;
-        for (int j = 0; j < m; ++j) {
-            const bool pipe = pipe_on && !c->monitor && orthogonalize_can_split(c, j + 2);
-            ensure_basis(j + (pipe ? 3 : 2));
-            double *vj = c->V.p + (long)j * nv, *zj = c->Z.p + (long)j * nv, *w = c->V.p + (long)(j + 1) * nv;
-            if (!have_w) {
-                pc_apply(c, vj, zj);                                        // z_j = M^-1 v_j
-                spmv_block_halo(c, c->J.p, zj, w);                          // w = J z_j (multi-GPU: exchange of z_j's halos overlapped)
-            }
-            have_w = false;
-            bool spec = false;
-            if (pipe) {
-                orthogonalize_enqueue(c, B, c->V.p, nv, j + 1, w);          // h = V^T w ; w -= V h ; ||w||^2 (no host wait yet)
-                spec = j + 1 < m && its + 1 < maxit && res_prev * std::min(rate, 1.0) > spec_margin * tol;      // (predicted res_j)
-                if (spec) ++c->spec_issued; else ++c->spec_skipped;
-                if (spec) {
-                    vec_scale_dev_norm(c, B, orthogonalize_norm_dev(c, j + 1), w);          // v_{j+1} = w/||w||
-                    pc_apply(c, w, c->Z.p + (long)(j + 1) * nv);
-                    spmv_block_halo(c, c->J.p, c->Z.p + (long)(j + 1) * nv, c->V.p + (long)(j + 2) * nv);
-                    have_w = true;
-                }
-                orthogonalize_wait(c, j + 1, hcol.data());
-            } else {
-                orthogonalize(c, B, c->V.p, nv, j + 1, w, hcol.data());     // h = V^T w ; w -= V h ; ||w||^2
-            }
-            const double hn = std::sqrt(hcol[j + 1]);
-            for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = hcol[i];
-            H[(size_t)(j + 1) * m + j] = hn;
-            for (int i = 0; i < j; ++i) {                                   // previous Givens rotations
-                const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-                H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-                H[(size_t)i * m + j] = t;
-            }
-            const double d = std::hypot(H[(size_t)j * m + j], H[(size_t)(j + 1) * m + j]);
-            cs[j] = H[(size_t)j * m + j] / d;
-            sn[j] = H[(size_t)(j + 1) * m + j] / d;
-            H[(size_t)j * m + j] = d;
-            H[(size_t)(j + 1) * m + j] = 0.0;
-            gvec[j + 1] = -sn[j] * gvec[j];
-            gvec[j] = cs[j] * gvec[j];
-            ++its;
-            k = j + 1;
-            res = std::fabs(gvec[j + 1]);
-            if (c->monitor) {
-                // ksp.buildResidual() per field (thermalmodel.py:44-74): x_j = Z y_j, r = b - J x_j, ||r_f||
-                std::vector<double> ym(k, 0.0), fn(B, 0.0);
-                std::vector<double> gm(gvec.begin(), gvec.begin() + k);
-                for (int i = k - 1; i >= 0; --i) {
-                    double s = gm[i];
-                    for (int q = i + 1; q < k; ++q) s -= H[(size_t)i * m + q] * ym[q];
-                    ym[i] = s / H[(size_t)i * m + i];
-                }
-                double *xm = c->w4.p, *rm = c->w2.p;                        // free between pc_apply calls
-                vec_copy(c, x, xm, nv);
-                multi_axpy(c, B, c->Z.p, nv, k, ym.data(), 1.0, xm);
-                if (c->dist) halo_exchange(c, g, xm, B, g.ntot);
-                resid_block_cols(c, c->J.p, bvec, xm, B, rm);
-                std::vector<const double *> fp(B);
-                for (int f = 0; f < B; ++f) fp[f] = rm + (long)f * g.ntot;
-                // (each field plane as a 1-field vector)
-                for (int f = 0; f < B; ++f) { const double *one[1] = {fp[f]}; multi_norm2sq(c, 1, 1, one, &fn[f]); fn[f] = std::sqrt(fn[f]); }
-                c->monitor(its, res, fn.data(), B, c->monitor_user);
-            }
-            rate = res_prev > 0.0 ? res / res_prev : 1.0;
-            res_prev = res;
-            if (!std::isfinite(res) || res <= tol || hn == 0.0) {
-                if (have_w) ++c->spec_wasted;
-                if (have_w) c->vcycles -= vcycles_per_apply(c);   // (discarded application)
-                reason = !std::isfinite(res) ? -9 : 2;                     // KSP_DIVERGED_NANORINF | converged (or happy breakdown)
-                break;
-            }
-            if (!spec) vec_scale_to(c, B, 1.0 / hn, w, w);                  // v_{j+1} = w/||w||
-        }
-        // y = H^-1 g ; x += Z y
-        yk.assign(k, 0.0);
-        for (int i = k - 1; i >= 0; --i) {
-            double s = gvec[i];
-            for (int q = i + 1; q < k; ++q) s -= H[(size_t)i * m + q] * yk[q];
-            yk[i] = s / H[(size_t)i * m + i];
-        }
-        multi_axpy(c, B, c->Z.p, nv, k, yk.data(), 1.0, x);
-        if (reason) { *its_out = its; *rnorm_out = res; return reason; }
-        if (its >= maxit) { *its_out = its; *rnorm_out = res; return -3; }
-        // restart: r = b - J x
+        // r = b - J x: to restart from and, in the fp32 form, the only verdict
         if (c->dist) halo_exchange(c, g, x, B, g.ntot);
         resid_block_cols(c, c->J.p, bvec, x, B, c->w2.p);
         beta = norm2(c, B, c->w2.p);
         rsrc = c->w2.p;
-        if (beta <= tol) { *its_out = its; *rnorm_out = beta; return 2; }
+        // (fp64: no finiteness test here -- a non-finite beta surfaces as -9 one iteration later, with that iteration counted)
+        if (single) {
+            ++c->ksp_true_res;
+            if (!std::isfinite(beta)) return done(-9, beta);
+        }
+        if (beta <= tol) return done(2, beta);
+        if (single && its >= maxit) return done(-3, beta);
     }
 }
 
