@@ -90,8 +90,9 @@ def test_solver_parameters_spelling(name, two):
 
 def test_engine_constructor_and_set_options_call_the_check():
     import inspect
+    from thermalporous_amd.engine import check_options
     src = inspect.getsource(HipEngine.__init__) + inspect.getsource(HipEngine.set_options)
-    assert src.count("check_ksp_basis_options(") == 2
+    assert src.count("check_options(") == 2 and inspect.getsource(check_options).count("check_ksp_basis_options(o)") == 1
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------------

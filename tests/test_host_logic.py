@@ -1,6 +1,8 @@
 """Host-side mirror of the reference API: geometry, wells, problem description, solver options,
 the ThermalModel time loop (driven by the CPU oracle engine injected through the test hook) and
 the device-state cache protocol.  No GPU needed."""
+import re
+
 import numpy as np
 import pytest
 
@@ -18,7 +20,8 @@ from thermalporous_amd.wellheatercase import WellHeaterCase
 from thermalporous_amd.sourceterms import SourceTerms
 from thermalporous_amd.singlephase import SinglePhase
 from thermalporous_amd.twophase import TwoPhase
-from thermalporous_amd import problem, utils
+from thermalporous_amd import problem, solver_options, utils
+from thermalporous_amd.engine import BUILD_KEYS, DEFAULT_OPTS
 from thermalporous_amd.solver_options import engine_options
 
 
@@ -200,6 +203,11 @@ def test_solver_option_mapping_and_rejections():
          "sub_0_cpr_stage1": {"ksp_type": "preonly", "pc_type": "hypre", "pc_hypre_type": "boomeramg"},
          "sub_1_pc_bjacobi_blocks": 1, "sub_1_sub_pc_type": "ilu", "sub_1_sub_pc_factor_levels": 0, "mat_type": "aij"}
     assert engine_options(d, "Single phase")["pc"] == "cpr"
+    # the keys such a dict may carry straight through are engine options, and the module's documentation lists no other
+    assert set(BUILD_KEYS) <= set(DEFAULT_OPTS)
+    listed = solver_options.__doc__.split("Build-specific tuning keys (not PETSc):")[1].split(".  ")[0]
+    listed = [w.strip() for w in re.sub(r"\([^)]*\)", "", listed).split(",")]
+    assert len(listed) > 20 and set(listed) <= set(BUILD_KEYS)
 
 
 def test_fieldsplit_cd_oracle_time_loop():

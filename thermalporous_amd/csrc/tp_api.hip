@@ -295,6 +295,22 @@ static DBuf<double> &vec_of(tp_ctx *c, int id) {
     return *c->vecs[id];
 }
 
+// every option against its range and against the options it excludes (each check stands beside its feature); tp_create and
+// tp_set_options are the only places that store a tp_options, so whatever a context holds has passed this
+static void check_options(const tp_options &o, int nranks) {
+    inner_check_options(o);
+    bcgs_check_options(o);
+    basis_single_check_options(o);
+    reorth_check_options(o);
+    pc_order_check_options(o);
+    pc_schur_fact_check_options(o);
+    pc_ctr_check_options(o, nranks);
+    ls_check_options(o);
+    ew_check_options(o);
+    amg_line_check_options(o, nranks);
+    amg_gs_check_options(o, nranks);
+}
+
 extern "C" {
 
 const char *tp_last_error(void) { return tp::g_err.c_str(); }
@@ -311,17 +327,7 @@ int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, 
     TP_HIP(hipGetDeviceCount(&ndev));
     TP_REQUIRE(ndev > 0, "no HIP device: the thermalporous hot path has no CPU fallback");
     TP_REQUIRE(device >= 0 && device < ndev, "bad device ordinal");
-    inner_check_options(*opt);
-    bcgs_check_options(*opt);
-    basis_single_check_options(*opt);
-    reorth_check_options(*opt);
-    pc_order_check_options(*opt);
-    pc_schur_fact_check_options(*opt);
-    pc_ctr_check_options(*opt, grid->nranks);
-    ls_check_options(*opt);
-    ew_check_options(*opt);
-    amg_line_check_options(*opt, grid->nranks);
-    amg_gs_check_options(*opt, grid->nranks);
+    check_options(*opt, grid->nranks);
     TP_HIP(hipSetDevice(device));
     tp_ctx *c = new tp_ctx();
     c->grid = *grid; c->prm = *prm; c->opt = *opt; c->device = device;
@@ -372,17 +378,7 @@ int tp_set_options(tp_ctx *c, const tp_options *opt) {
     TP_REQUIRE(opt->ilu_levels == 0 || opt->ilu_levels == 1, "ilu_levels must be 0 or 1");
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_levels), "ilu_single (fp32 factor) is implemented for block-ILU(0): not with ilu_levels 1");
     TP_REQUIRE(!(opt->ilu_single && opt->ilu_whole), "ilu_single (fp32 factor) is implemented for one tile per block: not with ilu_whole");
-    inner_check_options(*opt);
-    bcgs_check_options(*opt);
-    basis_single_check_options(*opt);
-    reorth_check_options(*opt);
-    pc_order_check_options(*opt);
-    pc_schur_fact_check_options(*opt);
-    pc_ctr_check_options(*opt, c->grid.nranks);
-    ls_check_options(*opt);
-    ew_check_options(*opt);
-    amg_line_check_options(*opt, c->grid.nranks);
-    amg_gs_check_options(*opt, c->grid.nranks);
+    check_options(*opt, c->grid.nranks);
     const bool tile_changed = opt->ilu_t1 != c->opt.ilu_t1 || opt->ilu_t2 != c->opt.ilu_t2 || opt->ilu_t0 != c->opt.ilu_t0 ||
                               opt->ilu_levels != c->opt.ilu_levels || opt->ilu_whole != c->opt.ilu_whole ||
                               (opt->ilu_single != 0) != (c->opt.ilu_single != 0) ||

@@ -137,10 +137,6 @@ static void pc_setup_sysamg(tp_ctx *c) {
 void pc_setup(tp_ctx *c) {
     TP_REQUIRE(c->jac_ready, "pc_setup needs an assembled Jacobian");
     ensure_work(c);
-    amg_line_check_options(c->opt, c->grid.nranks);
-    amg_gs_check_options(c->opt, c->grid.nranks);
-    pc_ctr_check_options(c->opt, c->grid.nranks);
-    pc_schur_fact_check_options(c->opt);
     c->schur_k0 = c->schur_ks = 0;                 // tp_schur_info counts since the last set-up
     TP_REQUIRE(!(c->opt.pc_ctr && c->dist), "pc_ctr on a context with a communicator (slabs / ranks): the temperature stage is "
                "implemented for one GPU without one");

@@ -162,12 +162,21 @@ DEFAULT_OPTS = dict(
     ew_alpha2=(1.0 + math.sqrt(5.0))/2.0,   # version 1: the safeguard's exponent, in (1, 2]
     ew_threshold=0.1,       # the safeguard acts when its term exceeds this, in (0, 1)
 )
+# the keys a PETSc-style solver_parameters dict may carry straight through to the engine (solver_options.engine_options)
+BUILD_KEYS = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip",
+              "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
+              "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
+              "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
+              "pc_order", "pc_ctr", "schur_fact", "schur_scale", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep",
+              "ls_minlambda", "ls_max_change", "ksp_ew", "ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
 _LS = {"basic": 0, "bt": 1}
-_LS_DEFAULTS = dict(ls_order=3, ls_alpha=1e-4, ls_max_it=40, ls_maxstep=1e8, ls_minlambda=1e-12, ls_max_change=None)
+_LS_KEYS = ("ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change")
+_EW_KEYS = ("ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
 
 
-_EW_DEFAULTS = dict(ew_rtol0=0.3, ew_rtolmax=0.9, ew_gamma=1.0, ew_alpha=(1.0 + math.sqrt(5.0))/2.0,
-                    ew_alpha2=(1.0 + math.sqrt(5.0))/2.0, ew_threshold=0.1)
+def _opt(o, k):
+    """o[k], or the default of a key the dict does not carry."""
+    return o.get(k, DEFAULT_OPTS[k])
 
 
 def _is_number(v):
@@ -193,11 +202,11 @@ def ew_version(v):
 def check_ew_options(o):
     """ksp_ew and the ew_* keys (tp_options.ksp_ew ...): ranges (PETSc's) with the option on; off, every ew_* key must keep its
     default -- a value that would be ignored is refused."""
-    ver = ew_version(o.get("ksp_ew", False))
-    vals = {k: o.get(k, d) for k, d in _EW_DEFAULTS.items()}
+    ver = ew_version(_opt(o, "ksp_ew"))
+    vals = {k: _opt(o, k) for k in _EW_KEYS}
     if ver == 0:
-        for k, d in _EW_DEFAULTS.items():
-            if isinstance(vals[k], (bool, np.bool_)) or vals[k] != d:
+        for k in _EW_KEYS:
+            if isinstance(vals[k], (bool, np.bool_)) or vals[k] != DEFAULT_OPTS[k]:
                 raise ValueError("%s = %r with ksp_ew off: the key belongs to Eisenstat-Walker (it would be ignored)" % (k, vals[k]))
         return
     for k, v in vals.items():
@@ -213,15 +222,15 @@ def check_ew_options(o):
             raise ValueError("%s = %r: a number in (1, 2]" % (k, vals[k]))
     if not 0.0 < float(vals["ew_threshold"]) < 1.0:
         raise ValueError("ew_threshold = %r: a number in (0, 1)" % (vals["ew_threshold"],))
-    if float(o.get("ksp_rtol", 1e-7)) > float(vals["ew_rtolmax"]):
+    if float(_opt(o, "ksp_rtol")) > float(vals["ew_rtolmax"]):
         raise ValueError("ksp_rtol = %r exceeds ew_rtolmax = %r: ksp_rtol is the floor of the Eisenstat-Walker tolerance and "
-                         "would lie above its cap" % (o.get("ksp_rtol", 1e-7), vals["ew_rtolmax"]))
+                         "would lie above its cap" % (_opt(o, "ksp_rtol"), vals["ew_rtolmax"]))
 
 
 def check_linesearch_options(o):
     """linesearch and the ls_* keys (tp_options.ls_kind ...): ranges under "bt"; under "basic" every ls_* key must keep its
     default -- a value that would be ignored is refused."""
-    kind = o.get("linesearch", "basic")
+    kind = _opt(o, "linesearch")
     if kind not in _LS:
         raise NotImplementedError("linesearch = %r: 'basic' or 'bt'" % (kind,))
     mc = o.get("ls_max_change")
@@ -230,20 +239,20 @@ def check_linesearch_options(o):
         if len(mc) != 3 or not all(_is_number(v) and float(v) == float(v) for v in mc):
             raise ValueError("ls_max_change = %r: None or a (dp, dT, dS) triple of numbers (<= 0: no cap on that field)" % (o["ls_max_change"],))
     if kind == "basic":
-        for k, d in _LS_DEFAULTS.items():
-            v = o.get(k, d)
+        for k in _LS_KEYS:
+            v = _opt(o, k)
             if k == "ls_max_change":
                 if mc is not None and any(float(x) > 0 for x in mc):
                     raise ValueError("ls_max_change = %r with linesearch = 'basic': the key belongs to the bt search" % (v,))
-            elif v != d:
+            elif v != DEFAULT_OPTS[k]:
                 raise ValueError("%s = %r with linesearch = 'basic': the key belongs to the bt search" % (k, v))
         return
-    order, it = o.get("ls_order", 3), o.get("ls_max_it", 40)
+    order, it = _opt(o, "ls_order"), _opt(o, "ls_max_it")
     if isinstance(order, (bool, np.bool_)) or order not in (2, 3):
         raise ValueError("ls_order = %r: 2 (quadratic) or 3 (cubic)" % (order,))
     if not _is_number(it) or int(it) != it or it < 1:
         raise ValueError("ls_max_it = %r: a count >= 1" % (it,))
-    a, ms, ml = o.get("ls_alpha", 1e-4), o.get("ls_maxstep", 1e8), o.get("ls_minlambda", 1e-12)
+    a, ms, ml = _opt(o, "ls_alpha"), _opt(o, "ls_maxstep"), _opt(o, "ls_minlambda")
     if not _is_number(a) or not 0.0 < float(a) < 0.5:
         raise ValueError("ls_alpha = %r: a number in (0, 0.5)" % (a,))
     if not _is_number(ms) or not float(ms) > 0.0:
@@ -311,6 +320,23 @@ def blocks_for_count(n, nblocks):
     return tiles_for_blocks(n, nblocks, max_cols=None)
 
 
+def check_ilu_single_options(o, exc=EngineError, whole_is="", ext=None):
+    """ilu_single against the stage-2 variants that keep doubles: the fp32 factor stream exists for the default per-tile
+    block-ILU(0) only (tp_options.ilu_single), no silent doubles.  ext: the extents of a slab, with which the rule that depends on
+    the grid -- an ilu_block of several tiles, on resolved options -- is checked as well."""
+    if not o.get("ilu_single"):
+        return
+    if int(_opt(o, "ilu_levels")) != 0:
+        raise exc("ilu_single with ilu_levels = %r: the fp32 factor is implemented for block-ILU(0)" % (o["ilu_levels"],))
+    if o.get("ilu_whole"):
+        raise exc("ilu_single with ilu_whole%s: the fp32 factor is implemented for one tile per bjacobi block" % whole_is)
+    if ext is not None and o.get("ilu_block") is not None:
+        box = [min(o["ilu_block"][a], ext[a]) for a in range(3)]
+        if any(-(-box[a]//max(1, min(int(o["ilu_tile"][a]), box[a]))) > 1 for a in range(3)):
+            raise exc("ilu_single with an ilu_block of several tiles (block %r, tile %r): the fp32 factor is "
+                      "implemented for one tile per bjacobi block" % (tuple(box), tuple(o["ilu_tile"])))
+
+
 def resolve_ilu_options(opts, n, nranks=1):
     """Stage-2 layout options (ilu_tile, ilu_whole, ilu_block) of an engine on grid n = (n0, n1, n2) cut into `nranks` slabs,
     from the user's options (a copy is returned).  ``bjacobi_blocks = N``: N = nranks is one block per rank (ilu_whole); on one
@@ -345,19 +371,8 @@ def resolve_ilu_options(opts, n, nranks=1):
             o["ilu_tile"] = block_ilu_tile((min(blk[0], int(n[0])), min(blk[1], int(n[1])), min(blk[2], n2l)))
         else:
             o["ilu_tile"] = (whole_ilu_tile if o.get("ilu_whole") else default_ilu_tile)(n, nslabs=nranks)
-    if o.get("ilu_single"):
-        # the fp32 factor stream exists for the default per-tile block-ILU(0) only (tp_options.ilu_single): no silent doubles
-        if int(o.get("ilu_levels", 0)) != 0:
-            raise EngineError("ilu_single with ilu_levels = %r: the fp32 factor is implemented for block-ILU(0)" % (o["ilu_levels"],))
-        if o.get("ilu_whole"):
-            raise EngineError("ilu_single with ilu_whole (one block per rank, bjacobi_blocks = number of slabs): the fp32 factor "
-                              "is implemented for one tile per bjacobi block")
-        if blk is not None:
-            ext = (int(n[0]), int(n[1]), -(-int(n[2])//max(1, nranks)))
-            box = [min(blk[a], ext[a]) for a in range(3)]
-            if any(-(-box[a]//max(1, min(int(o["ilu_tile"][a]), box[a]))) > 1 for a in range(3)):
-                raise EngineError("ilu_single with an ilu_block of several tiles (block %r, tile %r): the fp32 factor is "
-                                  "implemented for one tile per bjacobi block" % (tuple(box), tuple(o["ilu_tile"])))
+    check_ilu_single_options(o, whole_is=" (one block per rank, bjacobi_blocks = number of slabs)",
+                             ext=(int(n[0]), int(n[1]), -(-int(n[2])//max(1, nranks))))
     return o
 
 
@@ -403,7 +418,7 @@ def tiles_for_blocks(n, nblocks, max_cols=64):
 
 def check_amg_line_options(o, nranks=1, exc=EngineError):
     """amg_line_levels (tp_options.amg_line_levels) against the options it excludes: refused naming both, never ignored."""
-    L = o.get("amg_line_levels", 0)
+    L = _opt(o, "amg_line_levels")
     if isinstance(L, bool) or int(L) != L or L < 0:
         raise ValueError("amg_line_levels = %r: an integer >= 0" % (L,))
     if L == 0:
@@ -424,7 +439,7 @@ def check_amg_line_options(o, nranks=1, exc=EngineError):
 def check_amg_gs_options(o, nranks=1, exc=EngineError):
     """amg_gs_levels / amg_gs_sweeps (tp_options) against their ranges and the options they exclude: refused naming both, never
     ignored."""
-    L, g = o.get("amg_gs_levels", 0), o.get("amg_gs_sweeps", 1)
+    L, g = _opt(o, "amg_gs_levels"), _opt(o, "amg_gs_sweeps")
     if isinstance(L, bool) or int(L) != L or L < 0:
         raise ValueError("amg_gs_levels = %r: an integer >= 0" % (L,))
     if isinstance(g, bool) or int(g) != g or not 1 <= g <= 4:
@@ -436,7 +451,7 @@ def check_amg_gs_options(o, nranks=1, exc=EngineError):
     if L > int(o["amg_full_levels"]):
         raise ValueError("amg_gs_levels = %d exceeds amg_full_levels = %d: Gauss-Seidel levels are V(g,g) levels, never "
                          "pure-transfer or paired ones" % (L, o["amg_full_levels"]))
-    if o.get("amg_line_levels", 0):
+    if _opt(o, "amg_line_levels"):
         raise exc("amg_gs_levels with amg_line_levels: one smoother per level, choose one")
     if o.get("amg_single"):
         raise exc("amg_gs_levels with amg_single: the red-black sweeps are implemented for fp64 operators")
@@ -450,12 +465,12 @@ def check_amg_gs_options(o, nranks=1, exc=EngineError):
 
 def check_ksp_basis_options(o):
     """ksp_basis_single / ksp_single_floor (tp_options) against the range of theta and the method that has no basis."""
-    th = o.get("ksp_single_floor", 1e-7)
+    th = _opt(o, "ksp_single_floor")
     # (checked whether or not ksp_basis_single is on: a value that could never be used is a mistake in the options either way;
     # the library itself, which C callers may hand a zeroed field, checks it only with the option on)
     if isinstance(th, (bool, np.bool_)) or not isinstance(th, (int, float, np.integer, np.floating)) or not 2.0**-24 < float(th) < 1.0:
         raise ValueError("ksp_single_floor = %r: a number in (2^-24, 1)" % (th,))
-    if o.get("ksp_basis_single") and o.get("ksp", "fgmres") == "bcgs":
+    if o.get("ksp_basis_single") and _opt(o, "ksp") == "bcgs":
         raise NotImplementedError("ksp_basis_single with ksp = 'bcgs' (ksp_type fbcgs): BiCGStab keeps no Krylov basis to store "
                                   "in fp32; ksp_basis_single is an option of the restarted FGMRES")
 
@@ -467,7 +482,7 @@ _PC_ORDER = {"SI": 0, "IS": 1, "ISI": 2, "SIS": 3}
 def check_pc_order_options(o):
     """pc_order (tp_options) against its values and the preconditioners that have only one of the two stages: refused naming
     both, never ignored."""
-    order = o.get("pc_order", "SI")
+    order = _opt(o, "pc_order")
     if not isinstance(order, str) or order not in _PC_ORDER:
         raise ValueError("pc_order = %r: 'SI', 'IS', 'ISI' or 'SIS'" % (order,))
     if order == "SI":
@@ -483,7 +498,7 @@ def check_pc_order_options(o):
 def check_pc_ctr_options(o, nranks=1):
     """pc_ctr (tp_options) against its values, the preconditioners that are no composite with a T stage behind it, and the slab
     count: refused naming both, never ignored."""
-    v = o.get("pc_ctr", False)
+    v = _opt(o, "pc_ctr")
     if not isinstance(v, (bool, np.bool_)):
         raise ValueError("pc_ctr = %r: False or True" % (v,))
     if not v:
@@ -503,13 +518,13 @@ _SCHUR_FACT = {"full": 0, "lower": 1, "upper": 2, "diag": 3}
 def check_schur_fact_options(o):
     """schur_fact / schur_scale (tp_options) against their values and the preconditioners that have no Schur factorisation on
     (p,T) to choose: refused naming both, never ignored."""
-    fact = o.get("schur_fact", "full")
+    fact = _opt(o, "schur_fact")
     if not isinstance(fact, str) or fact not in _SCHUR_FACT:
         raise ValueError("schur_fact = %r: 'full', 'lower', 'upper' or 'diag'" % (fact,))
-    scale = o.get("schur_scale", -1.0)
+    scale = _opt(o, "schur_scale")
     if not _is_number(scale) or not math.isfinite(float(scale)):
         raise ValueError("schur_scale = %r: a finite number" % (scale,))
-    if fact != "diag" and float(scale) != -1.0:
+    if fact != "diag" and float(scale) != DEFAULT_OPTS["schur_scale"]:
         raise ValueError("schur_scale = %r with schur_fact = %r: the scale belongs to schur_fact = 'diag' (it would be silently "
                          "ignored)" % (scale, fact))
     if fact == "full":
@@ -527,21 +542,35 @@ def check_schur_fact_options(o):
 
 def check_ksp_reorth_options(o):
     """ksp_reorth / ksp_reorth_eta (tp_options) against the range of eta and the configurations that have no fp64 basis."""
-    eta = o.get("ksp_reorth_eta", 2.0**-0.5)
+    eta = _opt(o, "ksp_reorth_eta")
     # (checked whether or not the refinement is on, as ksp_single_floor is)
     if not _is_number(eta) or not 0.0 < float(eta) < 1.0:
         raise ValueError("ksp_reorth_eta = %r: a number in (0, 1)" % (eta,))
-    mode = o.get("ksp_reorth", "never")
+    mode = _opt(o, "ksp_reorth")
     if mode not in _REORTH:
         raise ValueError("ksp_reorth = %r: 'never', 'ifneeded' or 'always'" % (mode,))
     if mode == "never":
         return
-    if o.get("ksp", "fgmres") == "bcgs":
+    if _opt(o, "ksp") == "bcgs":
         raise NotImplementedError("ksp_reorth = %r with ksp = 'bcgs' (ksp_type fbcgs): BiCGStab keeps no Krylov basis to "
                                   "orthogonalise against; ksp_reorth is an option of the restarted FGMRES" % (mode,))
     if o.get("ksp_basis_single"):
         raise NotImplementedError("ksp_reorth = %r with ksp_basis_single: a basis rounded to fp32 cannot be orthonormal below "
                                   "2^-24, so a second Gram-Schmidt pass buys nothing; ksp_reorth needs the fp64 bases" % (mode,))
+
+
+def check_options(o, nranks=1, exc=EngineError):
+    """Every check of an option against its range and against the options it excludes, in one fixed order (exc: what the AMG
+    smoother checks raise for a combination that is not implemented)."""
+    check_amg_line_options(o, nranks, exc)
+    check_amg_gs_options(o, nranks, exc)
+    check_ksp_basis_options(o)
+    check_ksp_reorth_options(o)
+    check_pc_order_options(o)
+    check_pc_ctr_options(o, nranks)
+    check_schur_fact_options(o)
+    check_linesearch_options(o)
+    check_ew_options(o)
 
 
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
@@ -590,15 +619,7 @@ class HipEngine:
         self.opts = dict(DEFAULT_OPTS)
         self.opts.update(opts or {})
         self.opts = resolve_ilu_options(self.opts, spec["n"], nranks)
-        check_amg_line_options(self.opts, nranks)
-        check_amg_gs_options(self.opts, nranks)
-        check_ksp_basis_options(self.opts)
-        check_ksp_reorth_options(self.opts)
-        check_pc_order_options(self.opts)
-        check_pc_ctr_options(self.opts, nranks)
-        check_schur_fact_options(self.opts)
-        check_linesearch_options(self.opts)
-        check_ew_options(self.opts)
+        check_options(self.opts, nranks)
         self.nph = int(spec["nphase"])
         self.b = self.nph + 1
         n0, n1, gn2 = (int(v) for v in spec["n"])
@@ -651,47 +672,42 @@ class HipEngine:
 
     @staticmethod
     def _make_options(o):
+        """The options as the library's struct: every field by name, a key the dict does not carry at its default."""
+        # (but amg_dom_tau: a dict without the key packs 0, no truncation, not the engine's default of 0.25)
+        o = {**DEFAULT_OPTS, "amg_dom_tau": 0.0, **o}
         t = o["ilu_tile"]
-        # (the line-search, refinement, stage-order, temperature-stage, Schur-factorisation and Eisenstat-Walker fields stand in the
-        # middle of the struct: they are set by name, everything else in declaration order)
-        rest = [f[0] for f in tp_options._fields_ if not f[0].startswith(("ls_", "ksp_reorth", "pc_order", "pc_ctr", "schur_fact", "schur_scale", "ksp_ew", "ew_"))]
-        vals = (_PC[o["pc"]], _DECOUP[o["decoup"]], o["ksp_rtol"], o["ksp_atol"], o["ksp_max_it"],
-                          o["ksp_restart"], o["snes_rtol"], o["snes_atol"], o["snes_stol"], o["snes_max_it"],
-                          o["amg_omega"], o["amg_nu"], o["amg_min_cells"], int(min(t[1], 64)), int(min(t[2], 64)),
-                          0 if t[0] >= (1 << 30) else int(t[0]), int(o["amg_full_levels"]), int(o["amg_coarse_pre"]),
-                          int(o["amg_coarse_post"]), int(bool(o["amg_mid_skip"])), int(o["amg_tail_post"]), int(bool(o["amg_single"])), 2 if o.get("schur_selfp") else int(bool(o["schur_a11"])),
-                          int(o["amg_gather_cells"]), float(o.get("amg_dom_tau", 0.0)), int(o.get("ilu_levels", 0)), int(bool(o.get("fs_additive", False))),
-                          int(bool(o.get("ilu_whole", False))), int(o.get("amg_gs_levels", 0)), int(o.get("amg_gs_sweeps", 1)),
-                          (C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o.get("ilu_block") or (0, 0, 0))]),
-                          int(bool(o.get("ilu_single", False))), int(o.get("amg_line_levels", 0)),
-                          int(bool(o.get("ksp_basis_single", False))), float(o.get("ksp_single_floor", 1e-7)), HipEngine._ksp_kind(o),
-                          _S1_KSP[o.get("s1_ksp", "preonly")], int(o.get("s1_max_it", 1)), float(o.get("s1_rtol", 0.0)),
-                          float(o.get("s1_atol", 0.0)))
-        ew = {k: float(o.get(k, d)) for k, d in _EW_DEFAULTS.items()}
-        return tp_options(**dict(zip(rest, vals)), ksp_ew=ew_version(o.get("ksp_ew", False)), **ew, pc_order=_PC_ORDER[o.get("pc_order", "SI")], pc_ctr=int(bool(o.get("pc_ctr", False))),
-                          schur_fact=_SCHUR_FACT[o.get("schur_fact", "full")], schur_scale=float(o.get("schur_scale", -1.0)), ksp_reorth=_REORTH[o.get("ksp_reorth", "never")],
-                          ksp_reorth_eta=float(o.get("ksp_reorth_eta", 2.0**-0.5)), ls_kind=_LS[o.get("linesearch", "basic")], ls_order=int(o.get("ls_order", 3)),
-                          ls_max_it=int(o.get("ls_max_it", 40)), ls_alpha=float(o.get("ls_alpha", 1e-4)),
-                          ls_maxstep=float(o.get("ls_maxstep", 1e8)), ls_minlambda=float(o.get("ls_minlambda", 1e-12)),
-                          ls_max_change=(C.c_double*3)(*[float(v) for v in (o.get("ls_max_change") or (0.0, 0.0, 0.0))]))
+        return tp_options(
+            pc_kind=_PC[o["pc"]], decoup=_DECOUP[o["decoup"]], ksp_rtol=o["ksp_rtol"], ksp_atol=o["ksp_atol"],
+            ksp_max_it=o["ksp_max_it"], ksp_restart=o["ksp_restart"], snes_rtol=o["snes_rtol"], snes_atol=o["snes_atol"],
+            snes_stol=o["snes_stol"], snes_max_it=o["snes_max_it"], amg_omega=o["amg_omega"], amg_nu=o["amg_nu"],
+            amg_min_cells=o["amg_min_cells"], ilu_t1=int(min(t[1], 64)), ilu_t2=int(min(t[2], 64)),
+            ilu_t0=0 if t[0] >= (1 << 30) else int(t[0]), amg_full_levels=int(o["amg_full_levels"]),
+            amg_coarse_pre=int(o["amg_coarse_pre"]), amg_coarse_post=int(o["amg_coarse_post"]),
+            amg_mid_skip=int(bool(o["amg_mid_skip"])), amg_tail_post=int(o["amg_tail_post"]), amg_single=int(bool(o["amg_single"])),
+            schur_a11=2 if o["schur_selfp"] else int(bool(o["schur_a11"])), amg_gather_cells=int(o["amg_gather_cells"]),
+            schur_fact=_SCHUR_FACT[o["schur_fact"]], schur_scale=float(o["schur_scale"]), amg_dom_tau=float(o["amg_dom_tau"]),
+            ilu_levels=int(o["ilu_levels"]), pc_ctr=int(bool(o["pc_ctr"])), fs_additive=int(bool(o["fs_additive"])),
+            pc_order=_PC_ORDER[o["pc_order"]], ksp_reorth=_REORTH[o["ksp_reorth"]], ksp_reorth_eta=float(o["ksp_reorth_eta"]),
+            ksp_ew=ew_version(o["ksp_ew"]), **{k: float(o[k]) for k in _EW_KEYS}, ilu_whole=int(bool(o["ilu_whole"])),
+            amg_gs_levels=int(o["amg_gs_levels"]), amg_gs_sweeps=int(o["amg_gs_sweeps"]),
+            ilu_block=(C.c_int32*3)(*[int(min(int(v), 1 << 30)) for v in (o["ilu_block"] or (0, 0, 0))]),
+            ilu_single=int(bool(o["ilu_single"])), ls_kind=_LS[o["linesearch"]], ls_order=int(o["ls_order"]),
+            ls_max_it=int(o["ls_max_it"]), ls_alpha=float(o["ls_alpha"]), ls_maxstep=float(o["ls_maxstep"]),
+            ls_minlambda=float(o["ls_minlambda"]),
+            ls_max_change=(C.c_double*3)(*[float(v) for v in (o["ls_max_change"] or (0.0, 0.0, 0.0))]),
+            amg_line_levels=int(o["amg_line_levels"]), ksp_basis_single=int(bool(o["ksp_basis_single"])),
+            ksp_single_floor=float(o["ksp_single_floor"]), ksp_kind=HipEngine._ksp_kind(o), s1_ksp=_S1_KSP[o["s1_ksp"]],
+            s1_max_it=int(o["s1_max_it"]), s1_rtol=float(o["s1_rtol"]), s1_atol=float(o["s1_atol"]))
 
     @staticmethod
     def _ksp_kind(o):
-        k = o.get("ksp", "fgmres")
+        k = _opt(o, "ksp")
         if k not in _KSP:
             raise ValueError("ksp = %r: 'fgmres' or 'bcgs'" % (k,))
         return _KSP[k]
 
     def set_options(self, **kw):
-        check_amg_line_options({**self.opts, **kw}, self.nranks)
-        check_amg_gs_options({**self.opts, **kw}, self.nranks)
-        check_ksp_basis_options({**self.opts, **kw})
-        check_ksp_reorth_options({**self.opts, **kw})
-        check_pc_order_options({**self.opts, **kw})
-        check_pc_ctr_options({**self.opts, **kw}, self.nranks)
-        check_schur_fact_options({**self.opts, **kw})
-        check_linesearch_options({**self.opts, **kw})
-        check_ew_options({**self.opts, **kw})
+        check_options({**self.opts, **kw}, self.nranks)
         self.opts.update(kw)
         self._opt = self._make_options(self.opts)
         self._ck(self.lib.tp_set_options(self.ctx, C.byref(self._opt)))

@@ -66,6 +66,41 @@ _CGS_REFINE = {"refine_never": "never", "refine_ifneeded": "ifneeded", "refine_a
 _S1_MAXK = 32              # GMRES(k) without restart: k basis vectors of the stage-1 block are stored
 
 
+_STAGE_OF = {"python": "S", "fieldsplit": "S", "bjacobi": "I"}
+_ORDERS = ("SI", "IS", "ISI", "SIS")
+_MISSING = object()
+
+
+def _take(sp, used, key, allowed=None, default=None):
+    """Consume `key`; `allowed` = the values the hot path implements."""
+    if key not in sp:
+        return default
+    v = sp[key]
+    if allowed is not None and v not in allowed:
+        raise NotImplementedError("%s = %r is not implemented on the hot path (supported: %s)"
+                                  % (key, v, ", ".join(repr(a) for a in allowed)))
+    used.add(key)
+    return v
+
+
+def _set_checked(o, key, value, given, what, said, norm=lambda v: v):
+    """o[key] = value, read from the PETSc spelling.  ``given``: the dict as the caller wrote it, whose build key ``key`` must agree
+    (compared through ``norm``); what, said: what the message calls the option, and the two spellings side by side."""
+    if key in given and norm(o[key]) != norm(value):
+        raise ValueError("%s is configured twice and differently: %s" % (what, said))
+    o[key] = value
+
+
+def _take_zero_split(sp, used, prefix):
+    """``<prefix>pc_fieldsplit_type additive`` whose second split returns zero: ``<prefix>fieldsplit_1_`` = gmres, ksp_max_it 0,
+    pc_type none.  Consumes the four keys; whether all of them are there with these values."""
+    _take(sp, used, prefix + "pc_fieldsplit_type", ("additive",))
+    _take(sp, used, prefix + "fieldsplit_1_ksp_type", ("gmres",))
+    _take(sp, used, prefix + "fieldsplit_1_pc_type", ("none",))
+    return (prefix + "pc_fieldsplit_type" in used and prefix + "fieldsplit_1_ksp_type" in used
+            and int(_take(sp, used, prefix + "fieldsplit_1_ksp_max_it", None, -1)) == 0 and prefix + "fieldsplit_1_pc_type" in used)
+
+
 def _take_vcycle(sp, prefix, used, schur=False):
     """``<prefix>`` must configure exactly the reference's one-V-cycle solver (v_cycle dicts, singlephase.py:303-307,
     twophase.py:478-482); hypre tuning keys are not honoured and therefore rejected.  schur: the prefix is (inside) the
@@ -108,10 +143,7 @@ def _take_schur_fact(sp, used, prefix, o, given):
     if fact not in _SCHUR_FACTS:
         return False
     used.add(kf)
-    if "schur_fact" in given and o["schur_fact"] != fact:
-        raise ValueError("the Schur factorisation is configured twice and differently: schur_fact = %r, %s = %r"
-                         % (o["schur_fact"], kf, sp[kf]))
-    o["schur_fact"] = fact
+    _set_checked(o, "schur_fact", fact, given, "the Schur factorisation", "schur_fact = %r, %s = %r" % (o["schur_fact"], kf, sp[kf]))
     if ks in sp:
         scale = sp[ks]
         used.add(ks)
@@ -120,10 +152,8 @@ def _take_schur_fact(sp, used, prefix, o, given):
         if fact != "diag":
             raise ValueError("%s = %r with %s = %r: the scale belongs to the diag factorisation (PETSc would silently ignore it)"
                              % (ks, scale, kf, sp[kf]))
-        if "schur_scale" in given and float(o["schur_scale"]) != float(scale):
-            raise ValueError("the Schur factorisation is configured twice and differently: schur_scale = %r, %s = %r"
-                             % (o["schur_scale"], ks, scale))
-        o["schur_scale"] = float(scale)
+        _set_checked(o, "schur_scale", float(scale), given, "the Schur factorisation",
+                     "schur_scale = %r, %s = %r" % (o["schur_scale"], ks, scale), norm=float)
     return True
 
 
@@ -192,33 +222,12 @@ def _take_inner(sp, prefix, used, o, ksp_default=None):
     _set_inner(o, "fgmres", k, rtol, atol)
 
 
-def _check_ilu_single(o):
-    """ilu_single stores the factor of the default per-tile block-ILU(0) in fp32; the other stage-2 variants keep doubles and
-    are refused with it (blocks of several tiles depend on the grid: thermalporous_amd.engine.resolve_ilu_options)."""
-    if not o.get("ilu_single"):
-        return
-    if int(o.get("ilu_levels", 0)) != 0:
-        raise NotImplementedError("ilu_single with ilu_levels = %r: the fp32 factor is implemented for block-ILU(0)"
-                                  % (o["ilu_levels"],))
-    if o.get("ilu_whole"):
-        raise NotImplementedError("ilu_single with ilu_whole: the fp32 factor is implemented for one tile per bjacobi block")
-
-
 def _check_inner(o):
     """Validate s1_* however they were given (build keys or PETSc spelling), ilu_single against the stage-2 layout and
     amg_line_levels against what it excludes (the slab count is the engine's to check)."""
-    from .engine import (check_amg_gs_options, check_amg_line_options, check_ew_options, check_ksp_basis_options,
-                         check_ksp_reorth_options, check_linesearch_options, check_pc_ctr_options, check_pc_order_options, check_schur_fact_options)
-    _check_ilu_single(o)
-    check_amg_line_options(o, exc=NotImplementedError)
-    check_amg_gs_options(o, exc=NotImplementedError)
-    check_ksp_basis_options(o)
-    check_ksp_reorth_options(o)
-    check_pc_order_options(o)
-    check_pc_ctr_options(o)
-    check_schur_fact_options(o)
-    check_linesearch_options(o)
-    check_ew_options(o)
+    from .engine import check_ilu_single_options, check_options
+    check_ilu_single_options(o, NotImplementedError)      # (blocks of several tiles depend on the grid: resolve_ilu_options)
+    check_options(o, exc=NotImplementedError)
     ksp, k = o["s1_ksp"], o["s1_max_it"]
     if ksp not in ("preonly", "richardson", "fgmres"):
         raise NotImplementedError("s1_ksp = %r: preonly, richardson or fgmres" % (ksp,))
@@ -232,18 +241,6 @@ def _check_inner(o):
         raise NotImplementedError("s1_max_it = %d: the inner GMRES keeps its whole basis (no restart), at most %d" % (k, _S1_MAXK))
     if o["s1_rtol"] < 0 or o["s1_atol"] < 0:
         raise ValueError("s1_rtol / s1_atol must be >= 0")
-
-
-def _take(sp, used, key, allowed=None, default=None):
-    """Consume `key`; `allowed` = the values the hot path implements."""
-    if key not in sp:
-        return default
-    v = sp[key]
-    if allowed is not None and v not in allowed:
-        raise NotImplementedError("%s = %r is not implemented on the hot path (supported: %s)"
-                                  % (key, v, ", ".join(repr(a) for a in allowed)))
-    used.add(key)
-    return v
 
 
 _EW_KEYS = (("snes_ksp_ew_rtol0", "ew_rtol0"), ("snes_ksp_ew_rtolmax", "ew_rtolmax"), ("snes_ksp_ew_gamma", "ew_gamma"),
@@ -278,16 +275,12 @@ def _take_ew(sp, used, o, given):
         if ver == 3:
             raise NotImplementedError("snes_ksp_ew_version 3 is not implemented: it needs the line search's predicted and actual "
                                       "reduction; versions 1 and 2 are")
-    if "ksp_ew" in given and ew_version(o["ksp_ew"]) != ver:
-        raise ValueError("Eisenstat-Walker is configured twice and differently: ksp_ew = %r, but snes_ksp_ew = %r%s says %s"
-                         % (o["ksp_ew"], sp["snes_ksp_ew"], " with snes_ksp_ew_version %r" % sp["snes_ksp_ew_version"]
-                            if "snes_ksp_ew_version" in sp else "", "version %d" % ver if ver else "off"))
-    o["ksp_ew"] = ver
+    _set_checked(o, "ksp_ew", ver, given, "Eisenstat-Walker", "ksp_ew = %r, but snes_ksp_ew = %r%s says %s"
+                 % (o["ksp_ew"], sp["snes_ksp_ew"], " with snes_ksp_ew_version %r" % sp["snes_ksp_ew_version"]
+                    if "snes_ksp_ew_version" in sp else "", "version %d" % ver if ver else "off"), norm=ew_version)
     for k_src, k_dst in _EW_KEYS:
         if k_src in sp:
-            if k_dst in given and o[k_dst] != sp[k_src]:
-                raise ValueError("Eisenstat-Walker is configured twice and differently: %s = %r, %s = %r" % (k_dst, o[k_dst], k_src, sp[k_src]))
-            o[k_dst] = sp[k_src]
+            _set_checked(o, k_dst, sp[k_src], given, "Eisenstat-Walker", "%s = %r, %s = %r" % (k_dst, o[k_dst], k_src, sp[k_src]))
             used.add(k_src)
 
 
@@ -303,9 +296,6 @@ def _reject_unused(sp, used):
             continue
         raise KeyError("solver parameter %r is not consumed by the hot path (it would be silently ignored)" % k)
 
-_V_CYCLE = {"ksp_type": "preonly", "pc_type": "hypre", "pc_hypre_type": "boomeramg",
-            "pc_hypre_boomeramg_max_iter": 1}
-
 
 def _flatten(d, prefix=""):
     """PETSc semantics: a nested dict is a prefix (``"sub_0_cpr_stage1": v_cycle``)."""
@@ -319,7 +309,7 @@ def _flatten(d, prefix=""):
 
 
 def engine_options(solver_parameters, model_name, decoup="No", vector=False):
-    from .engine import DEFAULT_OPTS
+    from .engine import BUILD_KEYS, DEFAULT_OPTS
     sp = _flatten(dict(solver_parameters))
     o = dict(DEFAULT_OPTS)
     o["decoup"] = decoup
@@ -327,12 +317,7 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     o["schur_selfp"] = False
     o["fs_additive"] = False
     used = set()
-    build_keys = ("amg_omega", "amg_nu", "amg_min_cells", "amg_full_levels", "amg_coarse_pre", "amg_coarse_post", "amg_mid_skip", "amg_tail_post", "amg_single", "ilu_single", "amg_line_levels", "amg_gs_levels", "amg_gs_sweeps",
-                  "amg_gather_cells", "amg_dom_tau", "ilu_tile", "ilu_levels", "ilu_whole", "ilu_block",
-                  "s1_ksp", "s1_max_it", "s1_rtol", "s1_atol", "ksp_basis_single", "ksp_single_floor", "ksp_reorth", "ksp_reorth_eta",
-                  "pc_order", "pc_ctr", "schur_fact", "schur_scale", "linesearch", "ls_order", "ls_alpha", "ls_max_it", "ls_maxstep", "ls_minlambda", "ls_max_change",
-                  "ksp_ew", "ew_rtol0", "ew_rtolmax", "ew_gamma", "ew_alpha", "ew_alpha2", "ew_threshold")
-    for k in build_keys:
+    for k in BUILD_KEYS:
         if k in sp:
             o[k] = sp.pop(k)
     # ---- Newton / Krylov (singlephase.py:289-301, twophase.py:416-433) --------------------------------------
@@ -344,10 +329,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     ls_keys = (("snes_linesearch_order", "ls_order"), ("snes_linesearch_alpha", "ls_alpha"), ("snes_linesearch_max_it", "ls_max_it"),
                ("snes_linesearch_maxstep", "ls_maxstep"), ("snes_linesearch_minlambda", "ls_minlambda"))
     if ls is not None:
-        if "linesearch" in solver_parameters and o["linesearch"] != ls:
-            raise ValueError("the line search is configured twice and differently: linesearch = %r, snes_linesearch_type = %r"
-                             % (o["linesearch"], ls))
-        o["linesearch"] = ls
+        _set_checked(o, "linesearch", ls, solver_parameters, "the line search",
+                     "linesearch = %r, snes_linesearch_type = %r" % (o["linesearch"], ls))
     for k_src, k_dst in ls_keys:
         if k_src in sp:
             if o["linesearch"] != "bt":
@@ -372,10 +355,8 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
     # Gram-Schmidt refinement of the outer GMRES (PETSc: KSPGMRESSetCGSRefinementType)
     ref = _take(sp, used, "ksp_gmres_cgs_refinement_type", tuple(_CGS_REFINE))
     if ref is not None:
-        if "ksp_reorth" in solver_parameters and o["ksp_reorth"] != _CGS_REFINE[ref]:
-            raise ValueError("the Gram-Schmidt refinement is configured twice and differently: ksp_reorth = %r, "
-                             "ksp_gmres_cgs_refinement_type = %r" % (o["ksp_reorth"], ref))
-        o["ksp_reorth"] = _CGS_REFINE[ref]
+        _set_checked(o, "ksp_reorth", _CGS_REFINE[ref], solver_parameters, "the Gram-Schmidt refinement",
+                     "ksp_reorth = %r, ksp_gmres_cgs_refinement_type = %r" % (o["ksp_reorth"], ref))
     for k_src, k_dst in (("ksp_rtol", "ksp_rtol"), ("ksp_atol", "ksp_atol"), ("ksp_max_it", "ksp_max_it"),
                          ("ksp_gmres_restart", "ksp_restart"), ("snes_max_it", "snes_max_it"),
                          ("snes_rtol", "snes_rtol"), ("snes_atol", "snes_atol"), ("snes_stol", "snes_stol")):
@@ -456,11 +437,9 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
         raise NotImplementedError("pc_composite_pcs = %r ends its sequence %r with the temperature-only stage, but pc_order = %r "
                                   "asks for another sequence, which that stage would not end" % (given, order + "T", o["pc_order"]))
     # the build key pc_order re-orders a dict written in the presets' order "S,I"; a dict that spells another order must agree
-    if "pc_order" in solver_parameters and order != "SI" and o["pc_order"] != order:
-        raise ValueError("the order of the composite's stages is configured twice and differently: pc_order = %r, "
-                         "pc_composite_pcs = %r" % (o["pc_order"], given))
-    if "pc_order" not in solver_parameters:
-        o["pc_order"] = order
+    if order != "SI" or "pc_order" not in solver_parameters:
+        _set_checked(o, "pc_order", order, solver_parameters, "the order of the composite's stages",
+                     "pc_order = %r, pc_composite_pcs = %r" % (o["pc_order"], given))
     if order != "SI":
         # the stages were renamed to the places they have in "S,I" (sub_0_ = S, sub_1_ = I): say so in whatever is raised below
         try:
@@ -471,10 +450,6 @@ def engine_options(solver_parameters, model_name, decoup="No", vector=False):
             raise type(e)("%s [pc_composite_pcs = %r: keys are named here by stage, sub_0_ = the %s entry's sub_%d_, sub_1_ = "
                           "the bjacobi entry's sub_%d_]" % (msg, given, pcs.split(",")[0], order.index("S"), order.index("I"))) from e
     return _engine_options_composite(sp, used, o, pcs, model_name, vector, given=solver_parameters)
-
-
-_STAGE_OF = {"python": "S", "fieldsplit": "S", "bjacobi": "I"}
-_ORDERS = ("SI", "IS", "ISI", "SIS")
 
 
 def _composite_stages(sp, used, ctr=False, two_phase=False):
@@ -552,11 +527,7 @@ def _take_ctr_entry(sp, prefix, used, two_phase):
     """The composite's trailing temperature-only entry under ``prefix`` (the reference's cprctr dicts; engine key pc_ctr): an
     additive fieldsplit whose first split is field 1 with exactly one V-cycle and whose second split, the remaining fields,
     returns zero (gmres, max_it 0, pc none).  Every key is consumed or raises."""
-    _take(sp, used, prefix + "pc_fieldsplit_type", ("additive",))
-    _take(sp, used, prefix + "fieldsplit_1_ksp_type", ("gmres",))
-    _take(sp, used, prefix + "fieldsplit_1_pc_type", ("none",))
-    if prefix + "pc_fieldsplit_type" not in used or prefix + "fieldsplit_1_ksp_type" not in used \
-            or int(_take(sp, used, prefix + "fieldsplit_1_ksp_max_it", None, -1)) != 0 or prefix + "fieldsplit_1_pc_type" not in used:
+    if not _take_zero_split(sp, used, prefix):
         raise NotImplementedError("%s: the temperature-only stage is pc_fieldsplit_type additive with fieldsplit_1 = gmres, "
                                   "ksp_max_it 0, pc_type none (a second split that returns zero)" % prefix)
     used.add(prefix + "pc_fieldsplit_0_fields")
@@ -569,9 +540,6 @@ def _take_ctr_entry(sp, prefix, used, two_phase):
     for k in sp:
         if k.startswith(prefix) and k not in used:
             raise KeyError("solver parameter %r is not consumed by the temperature-only stage (it would be silently ignored)" % k)
-
-
-_MISSING = object()
 
 
 def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=False, given=()):
@@ -597,12 +565,7 @@ def _engine_options_composite(sp, used, o, pcs, model_name, vector, s_moved=Fals
         # twophase.py:619-634,670-699): additive fieldsplit whose second split is "gmres, max_it 0, pc none" -- i.e.
         # returns zero, exactly the y_nonp = 0 of CPRStage1PC/CPTRStage1PC.apply -- with decoupling "No".
         # pc_cpr_gmres == pc_cpr and pc_cptr_gmres == pc_cptr (the two-phase default, twophase.py:930) as algebra.
-        _take(sp, used, "sub_0_pc_fieldsplit_type", ("additive",))
-        _take(sp, used, "sub_0_fieldsplit_1_ksp_type", ("gmres",))
-        _take(sp, used, "sub_0_fieldsplit_1_pc_type", ("none",))
-        if "sub_0_pc_fieldsplit_type" not in used or "sub_0_fieldsplit_1_ksp_type" not in used \
-                or int(_take(sp, used, "sub_0_fieldsplit_1_ksp_max_it", None, -1)) != 0 \
-                or "sub_0_fieldsplit_1_pc_type" not in used:
+        if not _take_zero_split(sp, used, "sub_0_"):
             raise NotImplementedError("fieldsplit,bjacobi composite: only the *_gmres emulations of pc_cpr / pc_cptr")
         if o["decoup"] != "No":
             raise NotImplementedError("the fieldsplit emulations have no decoupling stage")
