@@ -1,0 +1,35 @@
+"""Heat loss into cap and base rock: a homogeneous 3-D two-phase box with two heaters whose top and bottom are thermal
+boundaries held at the initial temperature (conduction only; the four lateral sides stay closed).  The time loop's log then
+carries the energy flux through each set side.  Usage:
+    python test3D_heaters_thermal_walls.py cptr 0.1 1.0 [Nx Ny Nz]      # pcname maxdt[days] end[days]"""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from thermalporous_amd.physicalparameters import PhysicalParameters as Params
+from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo as GeoModel
+from thermalporous_amd.heatercase import HeaterCase as TestCase
+from thermalporous_amd.twophase import TwoPhase as ThermalModel
+
+params = Params()
+params.S_o = 0.9
+params.T_inj = 373.15
+
+pcname = sys.argv[1] if len(sys.argv) > 1 else "cptr"
+maxdt = float(sys.argv[2]) if len(sys.argv) > 2 else 0.1
+end = float(sys.argv[3]) if len(sys.argv) > 3 else 1.0
+Nx, Ny, Nz = (int(v) for v in sys.argv[4:7]) if len(sys.argv) > 6 else (20, 20, 10)
+
+geo = GeoModel(Nx, Ny, Nz, params, Length=Nx*6.096, Length_y=Ny*6.096, Length_z=Nz*0.6096)
+geo.set_boundary("z-", "thermal", T=params.T_prod)      # base rock
+geo.set_boundary("z+", "thermal", T=params.T_prod)      # cap rock
+case = TestCase(params, geo, well_case="default")
+
+suffix = os.path.splitext(__file__)[0]
+model = ThermalModel(geo, case, params, end=end, maxdt=maxdt, save=False, small_dt_start=False,
+                     solver_parameters="pc_" + pcname, filename=suffix + "_" + pcname + "_results.txt")
+model.solve()
+loss = model.rates().get("boundary_energy", {})
+print("total Newton its %d, total Krylov its %d, last dt %.4g days, failed solves %d"
+      % (model.total_nits, model.total_lits, model.last_dt/86400.0, model.failed_solves))
+print("energy leaving through the walls at the last assembly:", loss)

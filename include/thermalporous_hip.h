@@ -291,6 +291,20 @@ int tp_set_field(tp_ctx *ctx, const char *name, const double *host, int64_t n);
 int tp_finalize_fields(tp_ctx *ctx);
 int tp_set_sources(tp_ctx *ctx, int32_t n, const tp_source *entries);   /* wells/heaters: wellcase.py:78-108,171-266,
                                                                            heatercase.py:63-77, sourceterms.py:77-84,155-269 */
+/* Dirichlet sides of the box (every side is closed to flow and heat until one is set).  side = 2*a + d in
+ * internal axes: a the axis, d = 0 its low-index side, d = 1 its high-index side.  kind: 0 none (removes the side; values may be
+ * NULL), 1 open (flow and conduction to the ghost state), 2 thermal (conduction only: the ghost pressure cannot change any output
+ * bit).  values: the ghost state (p_b, T_b[, S_b]) per boundary face, field-major, b * nfaces doubles; a face is numbered over
+ * the other two internal axes, the lower axis fastest, so nfaces is n1*n2, n0*n2 or n0*n1.  The face is an interior face to a ghost
+ * cell half a cell away that has the cell's own porosity and static conductivity: same upwinding, gravity and harmonic
+ * conduction; only R, the diagonal block of J and the diagonal of S~ gain terms.  Callable any time after tp_finalize_fields; a
+ * later call replaces the side, so the values may change between time steps.  Checked: the side and kind ranges, nfaces against
+ * the grid, finite values, S_b in [0, 1].  One slab only: with nranks > 1 the call fails, naming the boundary and nranks.
+ * tp_boundary_flux: out[side*b + r] = the sum over the faces of `side` of what they added to equation r of R at the last
+ * assembly (tp_residual, tp_jacobian, or the last one of tp_newton_solve): the residual's sign, positive leaves the domain, and
+ * the equation's own scaling; summed on the host in face order; 0 for a side that is not set.  6*b doubles. */
+int tp_set_boundary(tp_ctx *ctx, int32_t side, int32_t kind, const double *values, int64_t nfaces);
+int tp_boundary_flux(tp_ctx *ctx, double *out);
 
 /* state u, old state u_ (thermalmodel.py:93-94,296), time step (thermalmodel.py:13). */
 int tp_set_state(tp_ctx *ctx, const double *u_host);      /* b*ntot doubles */
@@ -467,7 +481,8 @@ int tp_ew_history(tp_ctx *ctx, int32_t cap, double *rtol, double *fnorm, double 
  * against 16 vectors of the fp32 basis (needs one from an earlier ksp_basis_single solve), 9 the stage-1 right-hand side of a later
  * S stage in one launch (tp_stage_rhs), 10 the pair of launches it replaces (block residual over all b rows and columns + the
  * decoupled right-hand side per primary field), 11 that block residual alone, 12 the T stage's row right-hand side in one launch
- * (tp_ctr_rhs; needs pc_ctr).  4 times the pc_order and pc_ctr in force. */
+ * (tp_ctr_rhs; needs pc_ctr), 13 the boundary-face kernel alone (needs a side from tp_set_boundary; it adds to R, J and S~, so
+ * assemble again before using them; 3 includes it when a side is set).  4 times the pc_order and pc_ctr in force. */
 int tp_time_kernel(tp_ctx *ctx, int32_t which, int32_t reps, double *ms_avg);
 int tp_amg_info(tp_ctx *ctx, int32_t which, int32_t *nlevels, double *op_complexity);
 /* level at which hierarchy `which` ends with relaxation only (amg_dom_tau), -1: full V-cycle; ratio0 = the

@@ -1,0 +1,269 @@
+"""Dirichlet sides (open and thermal boundary faces) on the host: the definition of the boundary face (tests/bc_ref.py) against the
+unchanged oracle on a box padded by a ghost layer, against complex-step differentiation and against an analytic conduction
+profile; the mapping of ``geo.set_boundary`` into ``spec["boundary"]``; what is refused; the two new symbols of the C ABI."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases
+from bc_ref import (BcProblem, assert_both_directions, hydrostatic_boundary, hydrostatic_column, make_boundary, side_shape,
+                    side_slice)
+from oracle.tpfa import Problem
+from thermalporous_amd.problem import build_spec
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "thermalporous_hip.h")
+
+
+# ---- padded-box equivalence -----------------------------------------------------------------------------------------------
+def _padded(spec, P, u, side, B):
+    """The box with one more layer of cells on `side` that hold the ghost state, K_a and the static kT of the layer scaled by
+    1e15 (the harmonic mean then sees the owned cell alone, at twice the weight: half the distance); returns the unchanged
+    oracle's residual on the owned rows."""
+    a, d = divmod(side, 2)
+    sl = side_slice(side)
+    shp = side_shape(P.n, side)
+
+    def pad(arr, val):
+        arr = np.broadcast_to(np.asarray(arr, dtype=float), P.shape)
+        g = np.expand_dims(np.broadcast_to(val, shp), 2 - a)
+        return np.concatenate([arr, g] if d else [g, arr], axis=2 - a)
+    s2 = dict(spec)
+    n = list(spec["n"])
+    n[a] += 1
+    s2["n"] = tuple(n)
+    s2["phi"] = pad(spec["phi"], P.phi[sl])
+    s2["K"] = [pad(P.K[k], P.K[k][sl]*(1e15 if k == a else 1.0)) for k in range(3)]
+    s2["kT"] = pad(P.kT_static, P.kT_static[sl]*1e15)
+    fields = [pad(u[0], B["p"]), pad(u[1], B["T"])] + ([pad(u[2], B["S"])] if P.nph == 2 else [])
+    u2 = np.array(fields)
+    P2 = Problem(s2)
+    P2.set_old(u2)
+    P2.set_dt(864.0)
+    cut = [slice(None)]*4
+    cut[3 - a] = slice(0, -1) if d else slice(1, None)
+    return P2.residual(u2)[tuple(cut)]
+
+
+@pytest.mark.parametrize("side", [0, 1, 2, 3])
+@pytest.mark.parametrize("nphase", [1, 2])
+def test_boundary_face_equals_a_padded_box(nphase, side):
+    """2-D 7x5, every side: BcProblem.residual against the unchanged Problem on the padded box, owned rows within 1e-12 of each
+    field's largest entry; and the boundary moves the residual by more than 1e-4 of it."""
+    spec, *_ = cases.c3_spe10_2d(Nx=7, Ny=5, nphase=nphase)
+    spec["sources"] = None
+    if nphase == 2:                      # the two-phase ghost conductivity follows S_b; with zero conductivities there is none
+        for k in ("ko", "kw", "kr"):
+            spec["prm"][k] = 0.0
+    u = cases.perturbed_state(spec, seed=3)
+    B = make_boundary(spec, u, {side: "open"}, seed=1)
+    P = BcProblem(spec, B)
+    P.set_old(u)
+    P.set_dt(864.0)
+    Rb = P.residual(u)
+    assert_both_directions(P)
+    R2 = _padded(spec, P, u, side, B[side])
+    R0 = Problem.residual(P, u)
+    for q in range(P.b):
+        scale = np.abs(R2[q]).max()
+        err, moved = np.abs(Rb[q] - R2[q]).max()/scale, np.abs(Rb[q] - R0[q]).max()/scale
+        print("nphase %d side %d field %d: error %.2e, boundary effect %.2e" % (nphase, side, q, err, moved))
+        assert err < 1e-12
+        assert moved > 1e-4
+
+
+# ---- Jacobian -------------------------------------------------------------------------------------------------------------
+def _jac_case(which):
+    if which == "3d_2ph":
+        spec, u0, *_ = cases.c4_spe10_3d(Nx=5, Ny=4, Nz=3, nphase=2)
+        kinds = {0: "open", 1: "thermal", 2: "open", 3: "open", 4: "thermal", 5: "open"}     # axis 0 is z: gravity on side 0
+    else:
+        spec, u0, *_ = cases.c3_spe10_2d(Nx=6, Ny=5, nphase=1)
+        kinds = {0: "open", 1: "thermal", 2: "thermal", 3: "open"}
+    return spec, u0, kinds
+
+
+@pytest.mark.parametrize("which", ["3d_2ph", "2d_1ph"])
+def test_boundary_jacobian_equals_complex_step(which):
+    spec, u0, kinds = _jac_case(which)
+    u = cases.perturbed_state(spec, seed=4)
+    P = BcProblem(spec, make_boundary(spec, u, kinds, seed=2))
+    assert which != "3d_2ph" or P.gaxis == 0
+    P.set_old(u0)
+    P.set_dt(2000.0)
+    J, Sm = P.jacobian(u, want_schur=True)
+    Jc = P.jacobian_complex_step(u)             # (inherited: it differentiates the overridden residual)
+    assert np.abs(J - Jc).max() <= 1e-13*np.abs(Jc).max()
+    J0 = Problem.jacobian(P, u)
+    assert np.abs(J[0] - J0[0]).max() > 1e-3*np.abs(J0[0]).max() and np.array_equal(J[1:], J0[1:])
+    # S~ gains the conduction and the upwinded advection of the boundary faces on its diagonal only
+    S0 = Problem.jacobian(P, u, want_schur=True)[1]
+    assert np.array_equal(Sm[1:], S0[1:]) and np.abs(Sm[0] - S0[0]).max() > 1e-3*np.abs(S0[0]).max()
+
+
+# ---- analytic conduction profile ------------------------------------------------------------------------------------------
+def _line(p_b):
+    spec, *_ = cases.c1_homogeneous(N=8, nphase=1)
+    spec = dict(spec)
+    spec["n"], spec["sources"] = (8, 1, 1), None
+    for k in ("phi", "kT"):
+        spec[k] = np.ascontiguousarray(np.asarray(spec[k])[:1, :1, :])
+    spec["K"] = [np.ascontiguousarray(np.asarray(K)[:1, :1, :]) for K in spec["K"]]
+    TL, TR = 300.0, 380.0
+    T = TL + (np.arange(8) + 0.5)*(TR - TL)/8
+    u = np.array([np.full((1, 1, 8), 41.369), T.reshape(1, 1, 8)])
+    one = np.ones((1, 1))
+    B = {0: {"kind": "thermal", "p": p_b[0]*one, "T": TL*one, "S": None},
+         1: {"kind": "thermal", "p": p_b[1]*one, "T": TR*one, "S": None}}
+    P = BcProblem(spec, B)
+    P.set_old(u)
+    P.set_dt(864.0)
+    return P, u, (TR - TL)/8
+
+
+def test_linear_profile_between_two_thermal_ends_is_stationary():
+    """8 cells, uniform p and kT, old state = state, both ends thermal at T_L and T_R: the linear profile through the two wall
+    temperatures has zero residual (the half-cell faces carry exactly the interior flux), below 1e-12 of one face term."""
+    P, u, dT = _line((41.369, 41.369))
+    R = P.residual(u)
+    face = float(np.max(P.kT_static))*P.G[0]*dT
+    assert face > 0.0
+    assert np.abs(R).max() < 1e-12*face
+    # without the two ends the end cells are out of balance by one face term
+    assert np.abs(Problem.residual(P, u)[1]).max() > 0.5*face
+    # thermal: no flow through the face, so the ghost pressure cannot change a bit of anything
+    P2, _, _ = _line((10.0, 90.0))
+    assert P2.residual(u).tobytes() == R.tobytes()
+    for a, b in zip(P.jacobian(u, want_schur=True), P2.jacobian(u, want_schur=True)):
+        assert a.tobytes() == b.tobytes()
+    assert P2.last_flux.tobytes() == P.last_flux.tobytes()
+
+
+def test_open_end_at_the_hydrostatic_pressure_carries_no_flow():
+    """The half-cell gravity head (gam_b = g h_a/4 times the two densities) against something that does not contain it: the
+    ghost pressure half a cell below the bottom cell / above the top cell on the hydrostat dp/dz = -rho g, integrated finely.
+    The flux through both open ends must vanish to 1e-6 of the flux the gravity head alone drives (ghost pressure = cell
+    pressure); a factor other than 1/4 leaves a flux of the order of that scale."""
+    spec, u, pb = hydrostatic_column()
+    fl = {}
+    for name, B in (("hydrostatic", hydrostatic_boundary(spec, u, pb)),
+                    ("equal_p", hydrostatic_boundary(spec, u, {0: u[0, 0, 0, 0], 1: u[0, 0, 0, -1]}))):
+        P = BcProblem(spec, B)
+        P.set_old(u)
+        P.set_dt(864.0)
+        P.residual(u)
+        fl[name] = P.last_flux.copy()
+    assert pb[0] > u[0, 0, 0, 0] and pb[1] < u[0, 0, 0, -1]                     # heavier below, lighter above
+    for side in (0, 1):
+        print("side %d: mass flux %.3e at the hydrostatic ghost, %.3e at equal pressures" % (side, fl["hydrostatic"][side, 0], fl["equal_p"][side, 0]))
+        assert abs(fl["equal_p"][side, 0]) > 0.0
+        assert abs(fl["hydrostatic"][side, 0]) < 1e-6*abs(fl["equal_p"][side, 0])
+        assert abs(fl["hydrostatic"][side, 1]) < 1e-6*abs(fl["equal_p"][side, 1])
+    assert fl["equal_p"][0, 0] > 0.0 and fl["equal_p"][1, 0] < 0.0               # without support the column drains downwards
+
+
+# ---- build_spec mapping ---------------------------------------------------------------------------------------------------
+def _geo(dim, Nx, Ny, Nz=1):
+    from thermalporous_amd.physicalparameters import PhysicalParameters
+    from thermalporous_amd.homogeneousgeo import HomogeneousGeo
+    from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo
+    p = PhysicalParameters()
+    p.S_o = 0.9
+    g = HomogeneousGeo(Nx, Ny, p, 20., 30.) if dim == 2 else HomogeneousBoxGeo(Nx, Ny, Nz, p)
+    return p, g
+
+
+@pytest.mark.parametrize("dim,N", [(2, (4, 3, 1)), (3, (3, 5, 2)), (3, (5, 3, 2))], ids=["2d", "3d_Ny_ge_Nx", "3d_Ny_lt_Nx"])
+def test_build_spec_maps_each_physical_side(dim, N):
+    """Each physical side lands on the right internal side with the right transposition: the ghost arrays encode their own
+    physical face index, and a cell field that encodes the physical cell index tells which cell each internal face belongs to."""
+    p, g = _geo(dim, *N)
+    names = ["x-", "x+", "y-", "y+"] + (["z-", "z+"] if dim == 3 else [])
+    from thermalporous_amd.boundary import SIDES
+    for nm in names:
+        pa = SIDES[nm][0]
+        shape = tuple(N[k] for k in range(3) if k != pa)
+        code = (1000.0*(names.index(nm) + 1) + np.arange(shape[0]*shape[1])).reshape(shape)     # [j1, j2] -> id
+        g.set_boundary(nm, "open", p=code if dim == 3 else code.reshape(-1), T=code + 0.25, S=0.5)
+    spec = build_spec(g, None, p, 2)
+    axes = spec["axes"]
+    assert axes == ((0, 1, 2) if dim == 2 else ((2, 0, 1) if N[1] >= N[0] else (2, 1, 0)))
+    assert sorted(spec["boundary"]) == list(range(2*dim))
+    ix, iy, iz = np.meshgrid(np.arange(N[0]), np.arange(N[1]), np.arange(N[2]), indexing="ij")
+    from thermalporous_amd.problem import to_internal
+    cell = [to_internal(v, g, axes) for v in (ix, iy, iz)]                 # physical coordinates of every internal cell
+    for nm in names:
+        pa, d = SIDES[nm]
+        sid = 2*axes.index(pa) + d
+        e = spec["boundary"][sid]
+        assert e["kind"] == "open" and e["p"].shape == side_shape(spec["n"], sid)
+        co = [c[side_slice(sid)] for c in cell]                            # physical (ix, iy, iz) of the side's cells
+        assert np.all(co[pa] == (N[pa] - 1 if d else 0))
+        o1, o2 = [k for k in range(3) if k != pa]
+        expect = 1000.0*(names.index(nm) + 1) + co[o1]*N[o2] + co[o2]
+        assert np.array_equal(e["p"], expect) and np.array_equal(e["T"], expect + 0.25)
+        assert np.array_equal(e["S"], np.full(expect.shape, 0.5))
+    # single-phase: no S; thermal: p is p_ref whatever was given, S defaults to S_o in the two-phase model
+    g.set_boundary("x-", "thermal", p=7.0, T=300.0)
+    sid = 2*axes.index(0)
+    assert build_spec(g, None, p, 1)["boundary"][sid]["S"] is None
+    e = build_spec(g, None, p, 2)["boundary"][sid]
+    assert np.all(e["p"] == p.p_ref) and np.all(e["S"] == p.S_o) and e["kind"] == "thermal"
+    for nm in names:
+        g.set_boundary(nm, "none")
+    assert "boundary" not in build_spec(g, None, p, 2)
+
+
+def test_spec_is_unchanged_without_a_boundary():
+    spec, *_ = cases.c4_spe10_3d(Nx=4, Ny=5, Nz=3, nphase=2)
+    assert "boundary" not in spec
+
+
+# ---- what is refused ------------------------------------------------------------------------------------------------------
+def test_rejections():
+    p, g2 = _geo(2, 4, 3)
+    _, g3 = _geo(3, 3, 5, 2)
+    with pytest.raises(ValueError, match="unknown side 'w-'"):
+        g3.set_boundary("w-", "open", T=300.0)
+    with pytest.raises(ValueError, match="2-D grid has no z sides"):
+        g2.set_boundary("z+", "thermal", T=300.0)
+    with pytest.raises(ValueError, match=r"T on side 'x-' has shape \(5, 3\)"):
+        g3.set_boundary("x-", "thermal", T=np.zeros((5, 3)))
+    with pytest.raises(ValueError, match="p on side 'y\\+' holds a non-finite value"):
+        g3.set_boundary("y+", "open", p=np.inf, T=300.0, S=0.5)
+    with pytest.raises(ValueError, match="T on side 'y\\+' holds a non-finite value"):
+        g3.set_boundary("y+", "open", T=np.full((3, 2), np.nan), S=0.5)
+    with pytest.raises(ValueError, match=r"S on side 'x\+' lies outside \[0, 1\]"):
+        g3.set_boundary("x+", "open", T=300.0, S=1.5)
+    with pytest.raises(ValueError, match="boundary kind 'closed'"):
+        g3.set_boundary("x+", "closed", T=300.0)
+    with pytest.raises(ValueError, match="ghost temperature T is required"):
+        g3.set_boundary("x+", "open", p=40.0, S=0.5)
+    assert not getattr(g3, "boundaries", {})                         # nothing of the refused calls was kept
+    g3.set_boundary("x+", "open", T=300.0)
+    build_spec(g3, None, p, 1)                                        # single-phase: no S to miss
+    with pytest.raises(ValueError, match="S is required for a two-phase open boundary"):
+        build_spec(g3, None, p, 2)
+
+
+# ---- slabs and symbols ----------------------------------------------------------------------------------------------------
+def test_boundary_on_several_slabs_is_refused_on_the_host():
+    """Before the library is loaded and any context exists: no GPU needed."""
+    from thermalporous_amd.engine import HipEngine
+    spec, u0, *_ = cases.c4_spe10_3d(Nx=4, Ny=6, Nz=3, nphase=2)
+    spec["boundary"] = make_boundary(spec, u0, {1: "thermal"})
+    with pytest.raises(NotImplementedError, match=r"boundary \(sides \[1\]\) with nranks = 2"):
+        HipEngine(spec, dict(pc="cptr"), rank=0, nranks=2)
+
+
+def test_the_two_calls_are_declared_and_exported():
+    from thermalporous_amd import engine
+    hdr = open(HEADER).read()
+    assert re.search(r"\bint tp_set_boundary\(tp_ctx \*ctx, int32_t side, int32_t kind, const double \*values, int64_t nfaces\);", hdr)
+    assert re.search(r"\bint tp_boundary_flux\(tp_ctx \*ctx, double \*out\);", hdr)
+    assert {"tp_set_boundary", "tp_boundary_flux"} <= set(engine.API_SYMBOLS)
+    lib = engine.load_library()
+    assert lib.tp_set_boundary and lib.tp_boundary_flux
+    assert hasattr(engine.HipEngine, "set_boundary") and hasattr(engine.HipEngine, "boundary_flux")

@@ -5,10 +5,11 @@ numpy arrays of shape (Nx, Ny, Nz), index k increasing upwards (z up; gravity ac
 """
 import numpy as np
 
+from .boundary import BoundaryMixin
 from .mesh import StructuredMesh
 
 
-class BoxGeo():
+class BoxGeo(BoundaryMixin):
     def __init__(self, Nx, Ny, Nz, params, Length=365.76, Length_y=365.76, Length_z=1.8288, mg=False):
         self.Nx = int(Nx)
         self.Ny = int(Ny)

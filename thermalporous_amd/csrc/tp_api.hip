@@ -480,6 +480,7 @@ int tp_set_field(tp_ctx *c, const char *name, const double *host, int64_t n) {
 int tp_finalize_fields(tp_ctx *c) {
     TP_API_BEGIN
     compute_trans(c);
+    bc_trans(c);                 // (the half-cell transmissibilities of the Dirichlet sides follow K; nothing when no side is set)
     TP_HIP(hipStreamSynchronize(c->stream));
     c->fields_ready = true;
     drop_hierarchies(c);
@@ -509,6 +510,19 @@ int tp_set_sources(tp_ctx *c, int32_t n, const tp_source *entries) {
     c->rates.alloc((size_t)3 * std::max(1, n));
     if (n) copy_sync(c, c->src.p, v.data(), sizeof(tp_source) * n, hipMemcpyHostToDevice);
     copy_sync(c, c->src_start.p, start.data(), sizeof(int) * start.size(), hipMemcpyHostToDevice);
+    TP_API_END
+}
+
+int tp_set_boundary(tp_ctx *c, int32_t side, int32_t kind, const double *values, int64_t nfaces) {
+    TP_API_BEGIN
+    bc_set(c, side, kind, values, (long)nfaces);
+    TP_API_END
+}
+
+int tp_boundary_flux(tp_ctx *c, double *out) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out, "null argument");
+    bc_flux(c, out);
     TP_API_END
 }
 
@@ -1112,6 +1126,10 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
                 break;
             case 11: resid_block_cols(c, c->J.p, c->R.p, c->dx.p, c->b, c->w1.p); break;
             case 12: row_rhs(c, c->R.p, c->dx.p, c->w3.p); break;       // (dx as in 9)
+            case 13:        // k_assemble_bc alone: it ADDS to R, J and S~, which are no assembly afterwards (re-assemble)
+                TP_REQUIRE(c->bc.ncells > 0, "no boundary set (tp_set_boundary)");
+                assemble_bc(c, true, schur_of(c->opt));
+                break;
             default: throw Error("unknown kernel id");
         }
     };

@@ -17,6 +17,8 @@
 #include "tp_common.hpp"
 #include "tp_closures.hpp"
 #include <cstdlib>
+#include <cmath>
+#include <algorithm>
 
 namespace tp {
 
@@ -417,6 +419,111 @@ __global__ __launch_bounds__(256) void k_assemble_lds(AsmArgs a) {
     if (SCHUR) a.Sm[c] = sd;
 }
 
+// ---- Dirichlet sides (tp_set_boundary) ---------------------------------------------------------------------
+// A boundary face is an interior face whose other cell is a ghost state half a cell away: face_flux, unchanged, between the
+// cell and Props evaluated at (p_b, T_b, S_b) with the cell's own phi and static kT.  Orientation as inside: the lower index
+// is '+', so on a high side (d = 1) the cell is P and the ghost M, on a low side the ghost is P and the cell M.  Half-cell
+// distance: T^K = 2 K_a(c)|E|/h_a^2 (open) or 0 (thermal: conduction only), Ga = 2|e_a|/h_a, gam = g h_a/4 on the gravity axis.
+// There is no ghost unknown: only R, the diagonal block of J and the diagonal of S~ gain terms.
+//
+// One thread per boundary cell, for ALL the set sides that cell lies on (an edge or corner cell has one writer, no atomics),
+// launched behind the cell kernel on the same stream: read-modify-write of R, slot 0 of J and Sm[c].  The cell list is sorted,
+// so consecutive lanes hold consecutive cells wherever the surface has them: whole planes on the sides of axis 2, runs of n0
+// on the sides of axis 1.  On the sides of axis 0 consecutive lanes are n0 cells apart and every access by cell index costs a
+// memory transaction per lane; the per-face arrays (ghost values, T^K, flux scratch) stay contiguous there too, because the
+// face number follows the same order as the sorted cells.
+struct BcArgs {
+    AsmArgs a;
+    const int *cells;
+    int ncells;
+    int kind[6];
+    const double *val[6], *tk[6];
+    double *flux[6];
+    long nf[6];
+};
+
+__device__ __forceinline__ long bc_face(const GridDev &g, int ax, int i0, int i1, int i2) {
+    return ax == 0 ? (long)i1 + (long)g.n1 * i2 : (ax == 1 ? (long)i0 + (long)g.n0 * i2 : (long)i0 + (long)g.n0 * i1);
+}
+
+template <int NPH, bool JAC, bool SCHUR>
+__global__ __launch_bounds__(256) void k_assemble_bc(BcArgs s) {
+    constexpr int B = NPH + 1;
+    const int t = blockIdx.x * TP_BLOCK + threadIdx.x;
+    if (t >= s.ncells) return;
+    const AsmArgs &a = s.a;
+    const GridDev &g = a.g;
+    const DevPrm &q = a.q;
+    const long tid = s.cells[t];
+    const long c = g.np + tid;
+    const int i2 = (int)(tid / g.np);
+    const int rem = (int)(tid - (long)i2 * g.np);
+    const int i1 = rem / g.n0;
+    const int i0 = rem - i1 * g.n0;
+    const long nt = g.ntot;
+    const double phi = a.phi[c], kTs = a.kTs[c];
+    const Props<NPH> me = eval_props<NPH>(a.u[c], a.u[nt + c], NPH == 2 ? a.u[2 * nt + c] : 0.0, phi, kTs, q);
+    double R[B], Jd[B][B], sd = 0.0;
+#pragma unroll
+    for (int r = 0; r < B; ++r) {
+        R[r] = 0.0;
+#pragma unroll
+        for (int k = 0; k < B; ++k) Jd[r][k] = 0.0;
+    }
+#pragma unroll 1
+    for (int side = 0; side < 6; ++side) {
+        const int ax = side >> 1, dir = side & 1;
+        const int ia = ax == 0 ? i0 : (ax == 1 ? i1 : i2);          // (selects, not indexed local arrays: nothing to demote to scratch)
+        const int na = ax == 0 ? g.n0 : (ax == 1 ? g.n1 : g.n2);
+        if (s.kind[side] == 0 || ia != (dir ? na - 1 : 0)) continue;
+        const long nf = s.nf[side];
+        const long f_ = bc_face(g, ax, i0, i1, i2);
+        const double *v = s.val[side];
+        const Props<NPH> gh = eval_props<NPH>(v[f_], v[nf + f_], NPH == 2 ? v[2 * nf + f_] : 0.0, phi, kTs, q);
+        const double TK = s.tk[side][f_];
+        const double gam = 0.5 * a.gam[ax], Ga = 2.0 * a.Ga[ax];
+        double f[B], dP[B][B], dM[B][B], sP = 0.0, sM = 0.0;
+        if (dir) face_flux<NPH, SCHUR>(me, gh, TK, gam, Ga, q, f, dP, dM, sP, sM);
+        else     face_flux<NPH, SCHUR>(gh, me, TK, gam, Ga, q, f, dP, dM, sP, sM);
+        const double sg = dir ? 1.0 : -1.0;
+#pragma unroll
+        for (int r = 0; r < B; ++r) {
+            const double fr = sg * f[r];
+            R[r] += fr;
+            s.flux[side][(long)r * nf + f_] = fr;
+            if (JAC) {
+#pragma unroll
+                for (int k = 0; k < B; ++k) Jd[r][k] += dir ? dP[r][k] : -dM[r][k];
+            }
+        }
+        if (SCHUR) sd += dir ? sP : -sM;
+    }
+#pragma unroll
+    for (int r = 0; r < B; ++r) a.R[(long)r * nt + c] += R[r];
+    if (JAC) {
+#pragma unroll
+        for (int r = 0; r < B; ++r)
+#pragma unroll
+            for (int k = 0; k < B; ++k) a.J[((long)r * B + k) * nt + c] += Jd[r][k];
+    }
+    if (SCHUR) a.Sm[c] += sd;
+}
+
+// half-cell transmissibility of every face of one side: one thread per face
+__global__ void k_bc_trans(GridDev g, const double *K, int side, int open, double geom, long nf, double *tk) {
+    const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nf) return;
+    const int ax = side >> 1, dir = side & 1;
+    const int na = ax == 0 ? g.n1 : g.n0;                 // extent of the faster of the two other axes
+    const int lo = (int)(f % na), hi = (int)(f / na);
+    int i0, i1, i2;
+    if (ax == 0)      { i0 = dir ? g.n0 - 1 : 0; i1 = lo; i2 = hi; }
+    else if (ax == 1) { i0 = lo; i1 = dir ? g.n1 - 1 : 0; i2 = hi; }
+    else              { i0 = lo; i1 = hi; i2 = dir ? g.n2 - 1 : 0; }
+    const long c = g.np + (long)i0 + (long)g.n0 * i1 + g.np * i2;
+    tk[f] = open ? 2.0 * K[c] * geom : 0.0;
+}
+
 // ---- accumulation of the old state (once per time step) -------------------------------------------
 template <int NPH>
 __global__ void k_accum_old(GridDev g, DevPrm q, const double *u, const double *phi_, double *acc) {
@@ -587,12 +694,9 @@ void accum_old(tp_ctx *c) {
     TP_HIP(hipGetLastError());
 }
 
-void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
-    TP_REQUIRE(c->fields_ready, "fields not finalised (tp_finalize_fields)");
-    TP_REQUIRE(c->have_old && c->dt > 0.0, "old state / dt not set");
-    const GridDev &g = c->g;
+static AsmArgs asm_args(tp_ctx *c) {
     AsmArgs a;
-    a.g = g; a.q = c->dprm;
+    a.g = c->g; a.q = c->dprm;
     a.u = c->u.p; a.phi = c->phi.p; a.kTs = c->kTs.p;
     for (int ax = 0; ax < 3; ++ax) {
         a.TK[ax] = c->TK[ax].p;
@@ -603,6 +707,145 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
     a.acc_old = c->acc_old.p;
     a.Vdt = c->vol / c->dt;
     a.R = c->R.p; a.J = c->J.p; a.Sm = c->Sm.p;
+    return a;
+}
+
+// ---- Dirichlet sides: host side ------------------------------------------------------------------------------------------
+static long bc_side_faces(const GridDev &g, int side) {
+    const int ax = side >> 1;
+    return ax == 0 ? (long)g.n1 * g.n2 : (ax == 1 ? (long)g.n0 * g.n2 : (long)g.n0 * g.n1);
+}
+
+static void bc_trans_side(tp_ctx *c, int side) {
+    BcSide &s = c->bc.side[side];
+    if (s.kind == 0) return;
+    const int ax = side >> 1;
+    const double h = c->grid.h[ax];
+    hipLaunchKernelGGL(k_bc_trans, grid_for(s.nf), dim3(256), 0, c->stream, c->g, c->K[ax].p, side, s.kind == 1 ? 1 : 0,
+                       c->vol / (h * h), s.nf, s.tk.p);
+    TP_HIP(hipGetLastError());
+}
+
+void bc_trans(tp_ctx *c) {
+    for (int side = 0; side < 6; ++side) bc_trans_side(c, side);
+}
+
+// the sorted list of the cells that lie on a set side
+static void bc_rebuild_cells(tp_ctx *c) {
+    const GridDev &g = c->g;
+    std::vector<int> cells;
+    for (int side = 0; side < 6; ++side) {
+        if (c->bc.side[side].kind == 0) continue;
+        const int ax = side >> 1, dir = side & 1;
+        const int ext[3] = {g.n0, g.n1, g.n2};
+        int lo[3] = {0, 0, 0}, hi[3] = {g.n0, g.n1, g.n2};
+        lo[ax] = dir ? ext[ax] - 1 : 0;
+        hi[ax] = lo[ax] + 1;
+        for (int i2 = lo[2]; i2 < hi[2]; ++i2)
+            for (int i1 = lo[1]; i1 < hi[1]; ++i1)
+                for (int i0 = lo[0]; i0 < hi[0]; ++i0) cells.push_back((int)(i0 + (long)g.n0 * i1 + g.np * i2));
+    }
+    std::sort(cells.begin(), cells.end());
+    cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
+    c->bc.ncells = (int)cells.size();
+    c->bc.cells.free();
+    if (!cells.empty()) {
+        c->bc.cells.alloc(cells.size());
+        copy_sync(c, c->bc.cells.p, cells.data(), sizeof(int) * cells.size(), hipMemcpyHostToDevice);
+    }
+}
+
+void bc_set(tp_ctx *c, int side, int kind, const double *values, long nfaces) {
+    TP_REQUIRE(c, "null argument");
+    if (c->grid.nranks > 1 || c->dist)
+        throw Error("tp_set_boundary: a boundary with nranks = " + std::to_string(c->grid.nranks) +
+                    " is not implemented: Dirichlet sides exist on one slab");
+    TP_REQUIRE(c->fields_ready, "tp_set_boundary: fields not finalised (tp_finalize_fields)");
+    if (side < 0 || side > 5) throw Error("tp_set_boundary: side = " + std::to_string(side) + ": 2*axis + d in 0..5");
+    if (kind < 0 || kind > 2) throw Error("tp_set_boundary: kind = " + std::to_string(kind) + ": 0 (none), 1 (open) or 2 (thermal)");
+    TP_HIP(hipStreamSynchronize(c->stream));       // nothing in flight reads what is replaced
+    BcSide &s = c->bc.side[side];
+    if (kind == 0) {
+        const bool was = s.kind != 0;
+        s.kind = 0; s.nf = 0;
+        s.val.free(); s.tk.free(); s.flux.free();
+        if (was) bc_rebuild_cells(c);
+        return;
+    }
+    const long nf = bc_side_faces(c->g, side);
+    if (nfaces != nf)
+        throw Error("tp_set_boundary: nfaces = " + std::to_string(nfaces) + " but side " + std::to_string(side) + " of this grid has " +
+                    std::to_string(nf) + " faces");
+    TP_REQUIRE(values, "tp_set_boundary: null values");
+    const long nv = (long)c->b * nf;
+    for (long i = 0; i < nv; ++i)
+        if (!std::isfinite(values[i])) throw Error("tp_set_boundary: non-finite ghost value at entry " + std::to_string(i));
+    if (c->nph == 2)
+        for (long i = 2 * nf; i < nv; ++i)
+            if (values[i] < 0.0 || values[i] > 1.0)
+                throw Error("tp_set_boundary: ghost saturation S_b outside [0, 1] at face " + std::to_string(i - 2 * nf));
+    const bool was = s.kind != 0;
+    if (!was) { s.val.alloc(nv); s.tk.alloc(nf); s.flux.alloc(nv); }
+    else TP_HIP(hipMemsetAsync(s.flux.p, 0, sizeof(double) * nv, c->stream));   // (no assembly has seen these values yet)
+    s.kind = kind; s.nf = nf;
+    copy_sync(c, s.val.p, values, sizeof(double) * nv, hipMemcpyHostToDevice);
+    bc_trans_side(c, side);
+    TP_HIP(hipStreamSynchronize(c->stream));
+    if (!was) bc_rebuild_cells(c);
+}
+
+void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur) {
+    if (c->bc.ncells == 0) return;
+    TP_REQUIRE(c->fields_ready, "fields not finalised (tp_finalize_fields)");
+    TP_REQUIRE(c->have_old && c->dt > 0.0, "old state / dt not set");
+    BcArgs s;
+    s.a = asm_args(c);
+    s.cells = c->bc.cells.p;
+    s.ncells = c->bc.ncells;
+    for (int i = 0; i < 6; ++i) {
+        const BcSide &b = c->bc.side[i];
+        s.kind[i] = b.kind; s.val[i] = b.val.p; s.tk[i] = b.tk.p; s.flux[i] = b.flux.p; s.nf[i] = b.nf;
+    }
+    if (want_schur) TP_REQUIRE(c->Sm.p, "S~ storage not allocated");
+    const dim3 gr = grid_for(s.ncells), bl(256);
+#define LAUNCH_BC(NPH, JAC, SCH) hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH>), gr, bl, 0, c->stream, s)
+    if (c->nph == 2) {
+        if (!want_jac) LAUNCH_BC(2, false, false);
+        else if (want_schur) LAUNCH_BC(2, true, true);
+        else LAUNCH_BC(2, true, false);
+    } else {
+        if (!want_jac) LAUNCH_BC(1, false, false);
+        else if (want_schur) LAUNCH_BC(1, true, true);
+        else LAUNCH_BC(1, true, false);
+    }
+#undef LAUNCH_BC
+    TP_HIP(hipGetLastError());
+}
+
+// out[side*b + r]: what the faces of `side` added to equation r of R at the last assembly, summed in face order on the host
+void bc_flux(tp_ctx *c, double *out) {
+    const int b = c->b;
+    for (int i = 0; i < 6 * b; ++i) out[i] = 0.0;
+    TP_HIP(hipStreamSynchronize(c->stream));
+    std::vector<double> h;
+    for (int side = 0; side < 6; ++side) {
+        const BcSide &s = c->bc.side[side];
+        if (s.kind == 0) continue;
+        h.resize((size_t)b * s.nf);
+        copy_sync(c, h.data(), s.flux.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost);
+        for (int r = 0; r < b; ++r) {
+            double acc = 0.0;
+            for (long f = 0; f < s.nf; ++f) acc += h[(size_t)r * s.nf + f];
+            out[side * b + r] = acc;
+        }
+    }
+}
+
+void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
+    TP_REQUIRE(c->fields_ready, "fields not finalised (tp_finalize_fields)");
+    TP_REQUIRE(c->have_old && c->dt > 0.0, "old state / dt not set");
+    const GridDev &g = c->g;
+    const AsmArgs a = asm_args(c);
     if (want_schur) TP_REQUIRE(c->Sm.p, "S~ storage not allocated");
     const dim3 gr = xcd_grid(g.nown), bl(256);
     static const bool lds_tiled = getenv("TP_ASM_LDS") && atoi(getenv("TP_ASM_LDS")) == 1;
@@ -626,6 +869,7 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
         else LAUNCH(1, true, false);
     }
 #undef LAUNCH
+    if (c->bc.ncells > 0) assemble_bc(c, want_jac, want_jac && want_schur);
     if (c->nsrc_groups > 0) {
         double *J = want_jac ? c->J.p : nullptr;
         double *Sm = (want_jac && want_schur) ? c->Sm.p : nullptr;

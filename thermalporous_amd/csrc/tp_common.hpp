@@ -300,6 +300,22 @@ struct FBatch {
     int n = 0;
 };
 
+// Dirichlet sides of the box (tp_set_boundary; k_assemble_bc in tp_assembly.hip).  side = 2*axis + d in internal axes, d = 0 the
+// low-index side; a face of a side is numbered over the other two internal axes, the lower axis fastest.  Every array is
+// surface-sized.  With no side set (ncells == 0) nothing of this is allocated, launched or read.
+struct BcSide {
+    int kind = 0;              // 0 none, 1 open (flow and conduction), 2 thermal (conduction only)
+    long nf = 0;               // faces of the side
+    DBuf<double> val;          // ghost state, b fields of nf
+    DBuf<double> tk;           // T^K of the half cell: 2 K_a(c) |E| / h_a^2 (open), 0 (thermal)
+    DBuf<double> flux;         // what each face added to R at the last assembly, b fields of nf (tp_boundary_flux)
+};
+struct Bc {
+    BcSide side[6];
+    DBuf<int> cells;           // owned indices (c - np) of the cells that touch a set side, ascending: one thread each
+    int ncells = 0;
+};
+
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
@@ -353,6 +369,7 @@ struct tp_ctx {
     tp::DBuf<int> src_start;      // groups of entries sharing a cell
     int nsrc = 0, nsrc_groups = 0;
     tp::DBuf<double> rates;       // 3*nsrc
+    tp::Bc bc;                    // Dirichlet sides (tp_set_boundary)
     // linear algebra
     std::vector<tp::DBuf<double> *> vecs;
     tp::DBuf<double> At;          // decoupled primary block (QI/TI); planes as in J with b' = nprimary
@@ -448,6 +465,13 @@ void compute_trans(tp_ctx *c);
 void accum_old(tp_ctx *c);
 void assemble(tp_ctx *c, bool want_jac, bool want_schur);
 void well_rates(tp_ctx *c);
+// Dirichlet sides: bc_set checks and stores one side (kind 0 removes it), bc_trans refills the half-cell transmissibilities of
+// the set sides from K (tp_finalize_fields), assemble_bc adds the boundary faces to R, slot 0 of J and the diagonal of S~
+// (assemble calls it behind the cell kernel when a side is set), bc_flux sums each side's last contributions on the host
+void bc_set(tp_ctx *c, int side, int kind, const double *values, long nfaces);
+void bc_trans(tp_ctx *c);
+void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur);
+void bc_flux(tp_ctx *c, double *out);
 // vectors / reductions (vectors are b field planes of ntot; reductions run over owned cells only)
 void vec_zero(tp_ctx *c, double *x, long n);
 void vec_copy(tp_ctx *c, const double *x, double *y, long n);

@@ -14,6 +14,8 @@ import os
 
 import numpy as np
 
+from .boundary import KINDS, pack_values
+
 _LIB = None
 _LIBPATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libthermalporous_hip.so")
 
@@ -80,7 +82,7 @@ API_SYMBOLS = (
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
     "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
-    "tp_schur_info",
+    "tp_schur_info", "tp_set_boundary", "tp_boundary_flux",
 )
 
 DEFAULT_OPTS = dict(
@@ -573,6 +575,13 @@ def check_options(o, nranks=1, exc=EngineError):
     check_ew_options(o)
 
 
+def check_boundary_slabs(boundary, nranks=1):
+    """Dirichlet sides (spec["boundary"], HipEngine.set_boundary) against the slab count: refused naming both."""
+    if boundary and int(nranks) > 1:
+        raise NotImplementedError("a boundary (sides %s) with nranks = %d: Dirichlet sides are implemented for one slab"
+                                  % (sorted(boundary), int(nranks)))
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -614,6 +623,7 @@ class HipEngine:
     """Same interface as oracle.engine.OracleEngine; all arithmetic on the GPU."""
 
     def __init__(self, spec, opts=None, rank=0, nranks=1, device=None, comm_bootstrap=None, local_group=None):
+        check_boundary_slabs(spec.get("boundary"), nranks)       # (host-side: before the library and any context)
         self.lib = load_library()
         self.spec = spec
         self.opts = dict(DEFAULT_OPTS)
@@ -656,6 +666,9 @@ class HipEngine:
             self._ck(self.lib.tp_set_field(self.ctx, name.encode(), _dptr(a), C.c_int64(a.size)))
         self._ck(self.lib.tp_finalize_fields(self.ctx))
         self._set_sources(spec.get("sources"))
+        self.boundary = {}                     # side id -> the entry in force (spec["boundary"] layout)
+        for side, e in sorted((spec.get("boundary") or {}).items()):
+            self.set_boundary(side, e["kind"], p=e["p"], T=e["T"], S=e.get("S"))
         self.last = {}
         self._vec_ids = {}
         self._fbatch_ids = {}
@@ -744,6 +757,57 @@ class HipEngine:
         self._ck(self.lib.tp_set_sources(self.ctx, len(mine), arr))
         # the library sorts entries by cell (stable): reproduce the permutation for rate read-back
         self._src_order = np.argsort(cells[mine], kind="stable")
+
+    # ---- Dirichlet sides (boundary.py; include/thermalporous_hip.h: tp_set_boundary) -------------------
+    def _side_shape(self, side):
+        a = int(side)//2
+        lo, hi = [k for k in range(3) if k != a]
+        return (self.n[hi], self.n[lo])
+
+    def set_boundary(self, side, kind, p=None, T=None, S=None):
+        """Set, replace or (kind "none") remove the Dirichlet state of internal side 2*a + d, any time between two solves.
+        kind: "open" | "thermal" | "none"; p, T, S: the ghost state in internal layout, scalars or arrays of shape (n_hi, n_lo)
+        over the other two internal axes (the entries of spec["boundary"]).  T is required; p defaults to p_ref and is
+        replaced by it for "thermal" (no flow: it cannot matter); S (two-phase) is required for "open" and defaults to S_o
+        for "thermal"."""
+        check_boundary_slabs({side: kind}, self.nranks)
+        if isinstance(side, (bool, np.bool_)) or int(side) != side or not 0 <= int(side) <= 5:
+            raise ValueError("boundary side %r: the internal side id 2*a + d in 0..5" % (side,))
+        side = int(side)
+        if kind not in KINDS:
+            raise ValueError("boundary kind %r: 'open', 'thermal' or 'none'" % (kind,))
+        if kind == "none":
+            self._ck(self.lib.tp_set_boundary(self.ctx, side, 0, None, C.c_int64(0)))
+            self.boundary.pop(side, None)
+            return
+        if T is None:
+            raise ValueError("boundary side %d, kind %r: the ghost temperature T is required" % (side, kind))
+        shape, prm = self._side_shape(side), self.spec["prm"]
+        if self.nph == 2 and S is None:
+            if kind == "open":
+                raise ValueError("boundary side %d: S is required for a two-phase open boundary" % side)
+            S = prm["S_o"]
+        if p is None or kind == "thermal":
+            p = prm["p_ref"]
+        e = {"kind": kind}
+        for name, v in (("p", p), ("T", T)) + ((("S", S),) if self.nph == 2 else ()):
+            a = np.asarray(v, dtype=float)
+            if a.ndim and a.size != shape[0]*shape[1]:
+                raise ValueError("%s on boundary side %d has %d entries: a scalar or %d faces (shape %r)"
+                                 % (name, side, a.size, shape[0]*shape[1], shape))
+            e[name] = np.broadcast_to(a, shape).copy() if a.ndim == 0 else a.reshape(shape).copy()
+        e.setdefault("S", None)
+        vals = pack_values(e, self.nph)
+        self._ck(self.lib.tp_set_boundary(self.ctx, side, KINDS[kind], _dptr(vals), C.c_int64(shape[0]*shape[1])))
+        self.boundary[side] = e
+
+    def boundary_flux(self):
+        """(6, b): per internal side and equation, the sum of what the side's faces added to the residual at the last assembly
+        (tp_boundary_flux): the residual's sign -- positive leaves the domain -- and the equation's own scaling; zero rows
+        for the sides that are not set."""
+        out = np.zeros((6, self.b))
+        self._ck(self.lib.tp_boundary_flux(self.ctx, _dptr(out)))
+        return out
 
     # ---- engine interface ---------------------------------------------------------------------------
     def set_state(self, u):

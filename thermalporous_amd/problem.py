@@ -13,6 +13,7 @@ the C-ABI consumes through tp_create / tp_set_field / tp_set_params / tp_set_sou
 """
 import numpy as np
 
+from .boundary import boundary_spec
 from .wellcase import peaceman_WI
 
 PROD, INJ, HEATER = 0, 1, 2
@@ -114,6 +115,9 @@ def build_spec(geo, case, params, nphase, axes=None):
         "WI": np.array([peaceman_WI(kx[c], ky[c]) if e[1] != HEATER else 0.0 for e, c in zip(ent, cells)], dtype=float),
         "const": np.array([1 if e[5] else 0 for e in ent], dtype=np.int32),
     }
+    bnd = boundary_spec(geo, params, nphase, axes)      # Dirichlet sides (boundary.py); no key when none is set
+    if bnd:
+        spec["boundary"] = bnd
     return spec
 
 

@@ -8,10 +8,11 @@ multigrid experiments outside the hot path and are rejected.
 """
 import numpy as np
 
+from .boundary import BoundaryMixin
 from .mesh import StructuredMesh
 
 
-class RectangleGeo():
+class RectangleGeo(BoundaryMixin):
     def __init__(self, Nx, Ny, params, Length=365.76, Length_y=365.76, mg={}):
         self.Nx = int(Nx)
         self.Ny = int(Ny)

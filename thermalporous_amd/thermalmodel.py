@@ -19,6 +19,7 @@ from datetime import datetime
 import numpy as np
 
 from . import exceptions
+from .boundary import SIDES, check_boundary, side_name, to_internal_side
 from .function import Constant, Function
 from .problem import build_spec, field_major_to_internal, internal_to_field_major, _flat
 from .solver_options import engine_options
@@ -162,8 +163,9 @@ class ThermalModel:
     def rates(self):
         """Total injection / production (/ water / oil) rates = sum over entries of delta_i|E_i| * rate_i."""
         r = self.engine.well_rates()
+        bnd = self._boundary_energy()
         if not r:
-            return {}
+            return bnd
         src = self.spec["sources"]
         idx = getattr(self.engine, "src_index", np.arange(len(src["cell"])))
         kind, wt = src["kind"][idx], src["wt"][idx]
@@ -171,7 +173,32 @@ class ThermalModel:
         if "water_rate" in r:
             out["water"] = float(np.sum((wt*r["water_rate"])[kind == 0]))
             out["oil"] = float(np.sum((wt*r["oil_rate"])[kind == 0]))
+        out.update(bnd)
         return out
+
+    # ---- Dirichlet sides (boundary.py) ---------------------------------------------------------------
+    def _boundary_energy(self):
+        """{"boundary_energy": {side name: energy leaving through it at the last assembly}} when a side is set, else {}."""
+        sides = getattr(self.engine, "boundary", None)
+        if not sides or not hasattr(self.engine, "boundary_flux"):
+            return {}
+        flux = self.engine.boundary_flux()
+        return {"boundary_energy": {side_name(s, self.spec["axes"]): float(flux[s, 1]) for s in sorted(sides)}}
+
+    def set_boundary(self, side, kind, p=None, T=None, S=None):
+        """``geo.set_boundary`` on the running model: replaces the state of physical side `side` ("x-" ... "z+") in the engine,
+        so the values of a side may change between two time steps."""
+        geo = self.geo
+        e = check_boundary(side, kind, p, T, S, (geo.Nx, geo.Ny, geo.Nz), geo.dim)
+        pa, d = SIDES[side]
+        sid = 2*tuple(self.spec["axes"]).index(pa) + d
+        if e is None:
+            self.engine.set_boundary(sid, "none")
+            self.spec.get("boundary", {}).pop(sid, None)
+            return
+        sid, entry = to_internal_side(side, e, (geo.Nx, geo.Ny, geo.Nz), self.spec["axes"], self.nfields - 1, self.params)
+        self.engine.set_boundary(sid, entry["kind"], p=entry["p"], T=entry["T"], S=entry["S"])
+        self.spec.setdefault("boundary", {})[sid] = entry
 
     # ---- the time loop -------------------------------------------------------------------------------
     def start(self):
@@ -265,6 +292,8 @@ class ThermalModel:
             self._log("Total oil production rate is ", r["oil"])
         if "prod" in r:
             self._log("Total production rate is ", r["prod"])
+        for side, q in r.get("boundary_energy", {}).items():
+            self._log("Energy flux through side ", side, " is ", q)
 
         u_.assign(u)
         current_dt = float(self.dt.values()[0])
