@@ -305,6 +305,20 @@ int tp_set_sources(tp_ctx *ctx, int32_t n, const tp_source *entries);   /* wells
  * the equation's own scaling; summed on the host in face order; 0 for a side that is not set.  6*b doubles. */
 int tp_set_boundary(tp_ctx *ctx, int32_t side, int32_t kind, const double *values, int64_t nfaces);
 int tp_boundary_flux(tp_ctx *ctx, double *out);
+/* Graded tensor-product grid: one width per cell index along each internal axis instead of tp_grid.h.  h0, h1,
+ * h2: host arrays of n0, n1, n2 doubles, whose lengths must be the grid's extents (a 2-D grid passes h2 = {1}); all three
+ * pointers NULL: back to the uniform grid of tp_grid.h.  Cell volume |E_c| = h0[i0] h1[i1] h2[i2]; a face along a between the
+ * cells P (lower index) and M has area |e| = |E_P|/h_a[i_P], half distances d = h_a/2 and c = d/|e| on each side:
+ * T^K = K_P K_M/(c_P K_M + c_M K_P), gam = g (d_P + d_M)/2 on the gravity axis, conduction H = k_P k_M/(c_P k_M + c_M k_P); a
+ * boundary face (tp_set_boundary) has both half distances h_a/4 of its cell.  Equal widths reproduce the uniform formulas up to
+ * rounding; with no spacing set every result is bit for bit that of the uniform code.  Checked: the lengths, finite positive
+ * widths.  The call marks the fields as not finalised: tp_finalize_fields recomputes the interior and boundary transmissibilities
+ * (and drops the AMG hierarchies, whose conduction strengths become the mean of |e|/(d_P + d_M) over an axis's interior faces).
+ * tp_grid.h stays the mean widths and is read by nothing once spacing is set.  One slab only: the call fails on a context with a
+ * communicator or an in-process slab group (or nranks > 1), and tp_comm_init / tp_comm_init_local fail on a context with spacing.
+ * tp_spacing_info: *graded = 1 if spacing is set, and per internal axis the smallest and largest width (tp_grid.h when uniform). */
+int tp_set_spacing(tp_ctx *ctx, const double *h0, int64_t n0, const double *h1, int64_t n1, const double *h2, int64_t n2);
+int tp_spacing_info(tp_ctx *ctx, int32_t *graded, double *hmin, double *hmax);
 
 /* state u, old state u_ (thermalmodel.py:93-94,296), time step (thermalmodel.py:13). */
 int tp_set_state(tp_ctx *ctx, const double *u_host);      /* b*ntot doubles */

@@ -1,0 +1,393 @@
+"""Graded tensor-product grids without a GPU: the numpy reference against the oracle (tests/graded_ref.py), ``geo.set_spacing`` and
+its validation, cell picking and well weights on a graded geo, ``spec["hs"]``, the RectilinearGrid output, the checkpoint's
+widths, the grading helper, and the engines' refusals that need no device."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases
+from bc_ref import BcProblem, make_boundary
+from graded_ref import (GradedBcProblem, GradedProblem, equal_widths, field_change, graded_oracle, hydrostatic_graded_column, random_widths,
+                        spec_lengths)
+from oracle.tpfa import Problem
+from thermalporous_amd import utils
+from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo
+from thermalporous_amd.homogeneousgeo import HomogeneousGeo
+from thermalporous_amd.physicalparameters import PhysicalParameters
+from thermalporous_amd.problem import build_spec
+from thermalporous_amd.spacing import geometric_widths
+from thermalporous_amd.wellcase import WellCase
+
+TOL = 1e-11            # (tests/test_gpu_assembly_edges.py's entry tolerance; that module needs no GPU to import but is a GPU suite)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+CASES = [
+    ("2ph_2d_7x5", cases.c3_spe10_2d, dict(Nx=7, Ny=5, nphase=2)),
+    ("1ph_3d_6x5x4", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=1)),
+    ("2ph_3d_6x5x4", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=2)),
+]
+
+
+def _all(P, u, dt=8640.0):
+    P.set_old(u)
+    P.set_dt(dt)
+    J, Sm = P.jacobian(u, want_schur=True)
+    return P.residual(u), J, Sm
+
+
+def _close(a, b, tag):
+    scale = np.abs(b).max()
+    assert np.abs(a - b).max() <= TOL*scale, (tag, np.abs(a - b).max(), scale)
+
+
+# ---- the reference against itself --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pid,builder,kw", CASES, ids=[c[0] for c in CASES])
+def test_equal_widths_reproduce_the_oracle(pid, builder, kw):
+    spec, *_ = builder(**kw)
+    u = cases.perturbed_state(spec, seed=3)
+    R0, J0, S0 = _all(Problem(spec), u)
+    R1, J1, S1 = _all(GradedProblem(spec, equal_widths(spec)), u)
+    for f in range(R0.shape[0]):
+        _close(R1[f], R0[f], ("residual", f))
+        for c in range(R0.shape[0]):
+            _close(J1[:, f, c], J0[:, f, c], ("J", f, c))
+    _close(S1, S0, "S~")
+
+
+@pytest.mark.parametrize("pid,builder,kw", CASES, ids=[c[0] for c in CASES])
+def test_random_widths_change_every_field_and_the_analytic_jacobian_is_exact(pid, builder, kw):
+    spec, *_ = builder(**kw)
+    u = cases.perturbed_state(spec, seed=3)
+    R0, J0, S0 = _all(Problem(spec), u)
+    G = GradedProblem(spec, random_widths(spec["n"], spec_lengths(spec), 7))
+    R1, J1, S1 = _all(G, u)
+    change = field_change(R1, R0, spec)
+    print(pid, "change of the residual fields:", change)
+    assert min(change) > 0.01
+    Jc = G.jacobian_complex_step(u)
+    for r in range(G.b):
+        for c in range(G.b):
+            _close(J1[:, r, c], Jc[:, r, c], ("J", r, c))
+    assert np.abs(S1[1:] - S0[1:]).max() > 0.01*np.abs(S0[1:]).max()      # (the off-diagonals: the faces alone)
+    # a closed box conserves: with no sources the residual sums to nothing
+    P = GradedProblem(dict(spec, sources=None), G.hs)
+    P.set_old(u)
+    P.set_dt(8640.0)
+    R = P.residual(u)
+    for f in range(P.b):
+        assert abs(R[f].sum()) < 1e-12*np.abs(R[f]).sum()
+
+
+def test_graded_sides_reduce_to_the_uniform_sides_and_differentiate_exactly():
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
+    u = cases.perturbed_state(spec, seed=3)
+    spec["boundary"] = make_boundary(spec, u, {s: "open" for s in range(6)}, seed=4)
+    R0, J0, S0 = _all(BcProblem(spec), u)
+    R1, J1, S1 = _all(GradedBcProblem(spec, hs=equal_widths(spec)), u)
+    _close(R1, R0, "R")
+    _close(J1, J0, "J")
+    _close(S1, S0, "S~")
+    G = GradedBcProblem(spec, hs=random_widths(spec["n"], spec_lengths(spec), 9))
+    R2, J2, _ = _all(G, u)
+    assert np.abs(G.last_flux - BcProblem(spec).last_flux).max() > 0.0
+    Jc = G.jacobian_complex_step(u)
+    for r in range(3):
+        for c in range(3):
+            _close(J2[:, r, c], Jc[:, r, c], ("J", r, c))
+
+
+def test_the_reference_alone_meets_the_hydrostatic_bound():
+    spec, u, scale = hydrostatic_graded_column()
+    res = []
+    for P in (GradedProblem(spec), Problem(spec)):
+        P.set_old(u)
+        P.set_dt(864.0)
+        R = P.residual(u)[0].reshape(-1)
+        res.append(np.cumsum(R)[:-1]/scale)
+    print("graded:", res[0], "uniform formula:", res[1])
+    assert np.abs(res[0]).max() < 1e-8 and np.abs(res[1]).max() > 0.05
+
+
+def test_strengths_follow_the_library_rule():
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
+    P, G = Problem(spec), GradedProblem(spec, equal_widths(spec))
+    assert np.allclose(G.G, P.G, rtol=1e-13)
+    hs = random_widths(spec["n"], spec_lengths(spec), 7)
+    G = GradedProblem(spec, hs)
+    for a in range(3):
+        lo = [slice(None)]*3
+        lo[2 - a] = slice(None, -1)
+        hi = [slice(None)]*3
+        hi[2 - a] = slice(1, None)
+        brute = np.mean(G.Aa[a][tuple(lo)]/(0.5*(G.ha[a][tuple(lo)] + G.ha[a][tuple(hi)])))
+        assert abs(G.G[a] - brute) < 1e-12*brute
+
+
+# ---- set_spacing ---------------------------------------------------------------------------------------------------------------
+def _box(Nx=6, Ny=5, Nz=4):
+    p = PhysicalParameters()
+    return HomogeneousBoxGeo(Nx, Ny, Nz, p, Length=12.0, Length_y=10.0, Length_z=4.0), p
+
+
+def test_set_spacing_validation():
+    g, p = _box()
+    with pytest.raises(ValueError, match="5 widths but the grid has 6"):
+        g.set_spacing(x=np.full(5, 2.4))
+    with pytest.raises(ValueError, match="positive"):
+        g.set_spacing(y=[2.0, 2.0, 0.0, 3.0, 3.0])
+    with pytest.raises(ValueError, match="positive"):
+        g.set_spacing(y=[2.0, 2.0, float("nan"), 3.0, 3.0])
+    with pytest.raises(ValueError, match="sum to"):
+        g.set_spacing(z=[1.0, 1.0, 1.0, 1.0 + 1e-9])
+    assert not g.graded
+    g.set_spacing(z=[0.5, 1.5, 1.5, 0.5])
+    assert g.graded and (g.Dx, g.Dy, g.Dz) == (2.0, 2.0, 1.0)                    # the mean widths stay
+    hx, hy, hz = g.cell_widths()
+    assert np.all(hx == 2.0) and np.all(hy == 2.0) and list(hz) == [0.5, 1.5, 1.5, 0.5]
+    assert g.cell_volumes().shape == (6, 5, 4) and abs(g.cell_volumes().sum() - 480.0) < 1e-12
+    g.set_spacing()
+    assert not g.graded
+    g.set_spacing(z=[0.5, 1.5, 1.5, 0.5])
+    WellCase(p, g, prod_points=[[3.0, 5.0, 0.3]], inj_points=[[9.0, 5.0, 3.7]])
+    with pytest.raises(RuntimeError, match="after a case"):
+        g.set_spacing(z=[1.0, 1.0, 1.0, 1.0])
+    g2, p2 = _box()
+    build_spec(g2, None, p2, 1)
+    with pytest.raises(RuntimeError, match="after a case"):
+        g2.set_spacing(x=np.full(6, 2.0))
+    r = HomogeneousGeo(4, 4, p, 8.0, 8.0)
+    with pytest.raises(ValueError, match="no z axis"):
+        r.set_spacing(z=[1.0])
+
+
+def test_cell_centres_and_picking():
+    g, p = _box()
+    g.set_spacing(x=[0.5, 0.5, 1.0, 2.0, 4.0, 4.0], z=[0.2, 1.8, 1.8, 0.2])
+    X, Y, Z = g.cell_centres()
+    assert np.allclose(X[:, 0, 0], [0.25, 0.75, 1.5, 3.0, 6.0, 10.0]) and np.allclose(Z[0, 0], [0.1, 1.1, 2.9, 3.9])
+    assert np.allclose(Y[0, :, 0], [1, 3, 5, 7, 9])
+    # a point inside a thin cell picks that cell, though with mean widths floor(w/D) names another
+    c = utils.GetNodeClosestToCoordinate(g, [0.7, 5.0, 3.95])
+    assert c == utils.cell_index(g, 1, 2, 3)
+    assert int(np.floor(0.7/g.Dx)) == 0 and int(np.floor(3.95/g.Dz)) == 3
+    c = utils.GetNodeClosestToCoordinate(g, [11.9, 0.1, 0.15])
+    assert c == utils.cell_index(g, 5, 0, 0)
+    # equidistant from two centres (x = 0.5 between 0.25 and 0.75; y = 4 between 3 and 5): the lower flat index wins
+    assert utils.GetNodeClosestToCoordinate(g, [0.5, 4.0, 0.1]) == utils.cell_index(g, 0, 1, 0)
+    # the brute-force scan over all centres agrees everywhere on a set of random points
+    rng = np.random.default_rng(0)
+    cc = np.stack([a.transpose(2, 1, 0).reshape(-1) for a in (X, Y, Z)], axis=1)
+    for w in rng.uniform([0, 0, 0], [12.0, 10.0, 4.0], (200, 3)):
+        assert utils.GetNodeClosestToCoordinate(g, list(w)) == int(np.argmin(np.sqrt(((cc - w)**2).sum(axis=1))))
+
+
+def test_well_weights_sum_to_one_on_a_graded_geo():
+    g, p = _box(Nx=12, Ny=10, Nz=8)
+    g.set_spacing(x=geometric_widths(12, 12.0, 1.4, "low"), y=geometric_widths(10, 10.0, 1.3, "both"),
+                  z=geometric_widths(8, 4.0, 1.5, "high"))
+    vol = utils.cell_volume(g)
+    assert vol.shape == (960,) and abs(vol.sum() - 480.0) < 1e-10
+    d = utils.well_delta(g, [0.3, 5.0, 3.9])
+    assert len(d.cells) == 1 and abs(d.weights.sum() - 1.0) < 1e-15 and d.values[0] == 1.0/vol[d.cells[0]]
+    for w, radius, height in (([0.4, 5.0, 3.8], 0.6, 0.5), ([9.0, 2.0, 1.0], 2.5, 1.0), ([5.0, 5.0, 2.0], 3.0, 1.5)):
+        d = utils.well_circle(g, w, radius, height=height)
+        assert len(d.cells) >= (1 if radius < 1.0 else 4) and np.all(np.diff(d.cells) > 0)
+        assert abs(d.weights.sum() - 1.0) < 1e-14 and np.all(d.weights > 0.0)
+        # exactly the cells whose centre lies inside, found without the window
+        X, Y, Z = (a.transpose(2, 1, 0).reshape(-1) for a in g.cell_centres())
+        inside = ((X - w[0])**2 + (Y - w[1])**2 < radius**2) & (np.abs(Z - w[2]) < height)
+        if not inside.any():           # no centre inside the bump: the nearest cell alone, as on a uniform grid
+            assert list(d.cells) == [utils.GetNodeClosestToCoordinate(g, w)] and radius < 1.0
+            continue
+        assert list(d.cells) == list(np.nonzero(inside)[0])
+        vals = np.exp(-1.0/(radius**2 - ((X - w[0])**2 + (Y - w[1])**2)[inside]))
+        assert np.allclose(d.weights, vals*vol[inside]/np.sum(vals*vol[inside]), rtol=1e-13)
+    # 2-D
+    r = HomogeneousGeo(9, 6, p, 9.0, 6.0)
+    r.set_spacing(x=geometric_widths(9, 9.0, 1.5, "both"))
+    d = utils.well_circle(r, [4.4, 3.1], 1.6)
+    assert len(d.cells) > 1 and abs(d.weights.sum() - 1.0) < 1e-14
+    # the source cases follow the same rule
+    from thermalporous_amd.sourceterms import SourceTerms
+    s = SourceTerms(p, g, prod_points=[[0.4, 5.0, 3.8]], inj_points=[[9.0, 2.0, 1.0]], heater_points=[[6.0, 9.7, 0.2]])
+    for dl in (s.deltas_prod, s.deltas_inj, s.deltas_heaters):
+        assert abs(dl.weights.sum() - 1.0) < 1e-14
+
+
+# ---- build_spec ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("Nx,Ny,axes", [(5, 6, (2, 0, 1)), (6, 5, (2, 1, 0))], ids=["Ny>=Nx", "Ny<Nx"])
+def test_build_spec_puts_hs_in_internal_order(Nx, Ny, axes):
+    p = PhysicalParameters()
+    g = HomogeneousBoxGeo(Nx, Ny, 4, p, Length=float(Nx), Length_y=float(2*Ny), Length_z=4.0)
+    assert "hs" not in build_spec(HomogeneousBoxGeo(Nx, Ny, 4, p, Length=float(Nx), Length_y=float(2*Ny), Length_z=4.0), None, p, 2)
+    w = {"x": geometric_widths(Nx, float(Nx), 1.2), "z": geometric_widths(4, 4.0, 2.0, "high")}
+    g.set_spacing(**w)
+    spec = build_spec(g, None, p, 2)
+    assert spec["axes"] == axes and spec["h"] == tuple((1.0, 2.0, 1.0)[a] for a in axes)
+    phys = (w["x"], np.full(Ny, 2.0), w["z"])
+    assert len(spec["hs"]) == 3
+    for k, a in enumerate(axes):
+        assert np.array_equal(spec["hs"][k], phys[a]) and spec["hs"][k].size == spec["n"][k]
+    r = HomogeneousGeo(4, 3, p, 8.0, 6.0)
+    r.set_spacing(y=[1.0, 2.0, 3.0])
+    spec = build_spec(r, None, p, 1)
+    assert [list(v) for v in spec["hs"]] == [[2.0]*4, [1.0, 2.0, 3.0], [1.0]] and spec["n"] == (4, 3, 1)
+
+
+# ---- output and checkpoint ------------------------------------------------------------------------------------------------------
+def test_vtr_round_trip(tmp_path):
+    from thermalporous_amd.output import File, read_vti, read_vtr
+    g, p = _box()
+    vals = np.arange(120, dtype=float)*0.5
+    f = File(str(tmp_path / "pressure.pvd"))
+    f.write("pressure", vals, g, time=0.0)
+    assert os.path.exists(tmp_path / "pressure_0.vti") and np.array_equal(read_vti(str(tmp_path / "pressure_0.vti"))[1], vals)
+    g.set_spacing(x=[0.5, 0.5, 1.0, 2.0, 4.0, 4.0], z=[0.2, 1.8, 1.8, 0.2])
+    f = File(str(tmp_path / "temperature.pvd"))
+    f.write("temperature", vals, g, time=0.5)
+    f.write("temperature", vals + 1.0, g, time=1.0)
+    name, got, (x, y, z) = read_vtr(str(tmp_path / "temperature_1.vtr"))
+    assert name == "temperature" and np.array_equal(got, vals + 1.0)
+    ex, ey, ez = g.cell_edges()
+    assert np.array_equal(x, ex) and np.array_equal(y, ey) and np.array_equal(z, ez)
+    assert list(x) == [0.0, 0.5, 1.0, 2.0, 4.0, 8.0, 12.0] and z[-1] == 4.0 and len(y) == 6
+    pvd = open(tmp_path / "temperature.pvd").read()
+    assert 'file="temperature_0.vtr"' in pvd and 'file="temperature_1.vtr"' in pvd and ".vti" not in pvd
+    r = HomogeneousGeo(4, 3, p, 8.0, 6.0)
+    r.set_spacing(y=[1.0, 2.0, 3.0])
+    File(str(tmp_path / "s.pvd")).write("s", np.arange(12.0), r)
+    _, got, (x, y, z) = read_vtr(str(tmp_path / "s_0.vtr"))
+    assert list(y) == [0.0, 1.0, 3.0, 6.0] and list(z) == [0.0, 1.0] and np.array_equal(got, np.arange(12.0))
+
+
+def _factory(spec, opts):
+    return graded_oracle(spec, opts) if "hs" in spec else __import__("oracle.engine").engine.OracleEngine(spec, opts)
+
+
+_factory.supports_spacing = True
+
+
+def _model(tmp, z, checkpointing):
+    from thermalporous_amd.twophase import TwoPhase
+    p = PhysicalParameters()
+    p.rate, p.S_o, p.T_inj = 2e-4, 0.9, 373.15
+    g = HomogeneousBoxGeo(4, 5, 4, p, Length=8.0, Length_y=10.0, Length_z=4.0)
+    if z is not None:
+        g.set_spacing(z=z)
+    c = WellCase(p, g, prod_points=[[2.0, 5.0, 0.3]], inj_points=[[6.0, 5.0, 3.7]])
+    return TwoPhase(g, c, p, end=0.002, maxdt=0.001, small_dt_start=False, solver_parameters="pc_cptr", filename=None,
+                    verbosity=False, checkpointing=checkpointing, _engine_factory=_factory)
+
+
+def test_checkpoint_stores_the_widths_and_refuses_other_ones(tmp_path):
+    name = str(tmp_path / "chk")
+    z = [0.5, 1.5, 1.5, 0.5]
+    m = _model(tmp_path, z, {"save": True, "savename": name})
+    m.start()
+    m.finish()
+    chk = np.load(name + ".npz")
+    assert list(chk["widths_z"]) == z and list(chk["widths_x"]) == [2.0]*4 and list(chk["widths_y"]) == [2.0]*5
+    m = _model(tmp_path, z, {"load": True, "loadname": name})
+    m.start()                                                     # the same widths: accepted
+    for other in ([0.4, 1.6, 1.5, 0.5], None):
+        m = _model(tmp_path, other, {"load": True, "loadname": name})
+        with pytest.raises(ValueError, match="other cell widths along z"):
+            m.start()
+    # a checkpoint from before graded grids holds no widths: a uniform grid
+    u = np.load(name + ".npz")["solution"]
+    np.savez(name + "_old.npz", solution=u, t=0.0, dt=1.0)
+    _model(tmp_path, None, {"load": True, "loadname": name + "_old"}).start()
+    with pytest.raises(ValueError, match="holds no cell widths"):
+        _model(tmp_path, z, {"load": True, "loadname": name + "_old"}).start()
+
+
+def test_oil_in_place_uses_the_cells_own_volumes(tmp_path):
+    z = [0.5, 1.5, 1.5, 0.5]
+    m = _model(tmp_path, z, {})
+    m.start()
+    u = m.u._read()
+    vol = utils.cell_volume(m.geo)
+    want = float(np.sum(_phi_flat(m)*u[2]*m.params.oil_rho(u[0], u[1])*vol))
+    assert abs(m.oil_mass() - want) <= 1e-14*want
+    # uniform S, p, T and phi: the graded box holds the oil of the uniform box of the same size
+    m0 = _model(tmp_path, None, {})
+    m0.start()
+    assert abs(m.oil_mass() - m0.oil_mass()) < 1e-12*m0.oil_mass()
+    # oil in the thin bottom layer only: a quarter of what mean volumes would count
+    S = np.zeros((4, 5, 4))
+    S[0] = 0.9                                   # [k, j, i]: the state is x fastest
+    u2 = np.array(u)
+    u2[2] = S.reshape(-1)
+    m.u.assign(u2)
+    m0.u.assign(u2)
+    assert abs(m.oil_mass() - 0.5*m0.oil_mass()) < 1e-12*m0.oil_mass()
+
+
+def _phi_flat(m):
+    from thermalporous_amd.problem import _flat
+    return _flat(m.geo.phi, m.geo)
+
+
+# ---- engines ----------------------------------------------------------------------------------------------------------------------
+def test_other_engines_refuse_a_graded_spec():
+    from oracle.engine import OracleEngine
+    from thermalporous_amd.twophase import TwoPhase
+    p = PhysicalParameters()
+    p.S_o = 0.9
+    g = HomogeneousBoxGeo(4, 5, 4, p, Length=8.0, Length_y=10.0, Length_z=4.0)
+    g.set_spacing(z=[0.5, 1.5, 1.5, 0.5])
+    c = WellCase(p, g, prod_points=[[2.0, 5.0, 0.3]], inj_points=[[6.0, 5.0, 3.7]])
+    with pytest.raises(NotImplementedError, match="graded grid.*OracleEngine"):
+        TwoPhase(g, c, p, filename=None, verbosity=False, _engine_factory=OracleEngine)
+
+
+def test_hip_engine_refuses_slabs_before_any_context(monkeypatch):
+    from thermalporous_amd import engine as E
+    spec, *_ = cases.c4_spe10_3d(Nx=4, Ny=5, Nz=6, nphase=1)
+    spec["hs"] = random_widths(spec["n"], spec_lengths(spec), 5)
+
+    def no_library(*a, **k):
+        raise AssertionError("the library was loaded before the refusal")
+    monkeypatch.setattr(E, "load_library", no_library)
+    with pytest.raises(NotImplementedError, match=r"graded grid.*nranks = 2"):
+        E.HipEngine(spec, dict(pc="fieldsplit_cd"), rank=0, nranks=2)
+    with pytest.raises(NotImplementedError, match=r"slab group"):
+        E.HipEngine(spec, dict(pc="fieldsplit_cd"), rank=0, nranks=2, local_group=object())
+    with pytest.raises(NotImplementedError, match=r"communicator"):
+        E.HipEngine(spec, dict(pc="fieldsplit_cd"), comm_bootstrap=lambda make: b"")
+    with pytest.raises(ValueError, match="widths but the grid has"):
+        E.check_spacing((spec["hs"][0][:-1], spec["hs"][1], spec["hs"][2]), spec["n"])
+    with pytest.raises(ValueError, match="positive"):
+        E.check_spacing((spec["hs"][0]*0.0, spec["hs"][1], spec["hs"][2]), spec["n"])
+
+
+def test_exports_are_declared():
+    from thermalporous_amd import engine
+    hdr = open(os.path.join(ROOT, "include", "thermalporous_hip.h")).read()
+    assert re.search(r"\bint tp_set_spacing\(tp_ctx \*ctx, const double \*h0, int64_t n0, const double \*h1, int64_t n1, "
+                     r"const double \*h2, int64_t n2\);", hdr)
+    assert re.search(r"\bint tp_spacing_info\(tp_ctx \*ctx, int32_t \*graded, double \*hmin, double \*hmax\);", hdr)
+    assert {"tp_set_spacing", "tp_spacing_info"} <= set(engine.API_SYMBOLS)
+
+
+# ---- the helper ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,length,ratio", [(10, 1.8288, 1.3), (7, 365.76, 2.0), (85, 51.816, 1.05), (1, 3.0, 1.7), (6, 4.0, 1.0)])
+def test_geometric_widths(N, length, ratio):
+    for refine in ("low", "high", "both"):
+        w = geometric_widths(N, length, ratio, refine=refine)
+        assert w.shape == (N,) and np.all(w > 0.0) and float(np.sum(w)) == length
+        q = w[1:]/w[:-1]
+        if refine == "low":
+            assert np.allclose(q, ratio, rtol=1e-12)
+        elif refine == "high":
+            assert np.allclose(q, 1.0/ratio, rtol=1e-12)
+        else:
+            h = (N - 1)//2
+            assert np.allclose(q[:h], ratio, rtol=1e-12) and np.allclose(q[N - 1 - h:], 1.0/ratio, rtol=1e-12)
+            assert np.allclose(w, w[::-1], rtol=1e-12)
+    with pytest.raises(ValueError, match="ratio"):
+        geometric_widths(4, 1.0, 0.5)
+    with pytest.raises(ValueError, match="refine"):
+        geometric_widths(4, 1.0, 1.5, refine="middle")

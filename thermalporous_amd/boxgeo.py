@@ -3,13 +3,12 @@
 Reference: ``ExtrudedMesh(RectangleMesh(Nx,Ny,...), Nz, Dz)`` + DQ0 (:42-43,:86).  Fields are
 numpy arrays of shape (Nx, Ny, Nz), index k increasing upwards (z up; gravity acts along -z).
 """
-import numpy as np
-
 from .boundary import BoundaryMixin
 from .mesh import StructuredMesh
+from .spacing import SpacingMixin
 
 
-class BoxGeo(BoundaryMixin):
+class BoxGeo(BoundaryMixin, SpacingMixin):
     def __init__(self, Nx, Ny, Nz, params, Length=365.76, Length_y=365.76, Length_z=1.8288, mg=False):
         self.Nx = int(Nx)
         self.Ny = int(Ny)
@@ -45,8 +44,4 @@ class BoxGeo(BoundaryMixin):
     def init_function_space(self):
         self.V = self.mesh.dq0()
 
-    def cell_centres(self):
-        x = (np.arange(self.Nx) + 0.5)*self.Dx
-        y = (np.arange(self.Ny) + 0.5)*self.Dy
-        z = (np.arange(self.Nz) + 0.5)*self.Dz
-        return np.meshgrid(x, y, z, indexing="ij")
+    # cell_centres(), cell_widths(), cell_volumes(), cell_edges() and set_spacing(): spacing.SpacingMixin

@@ -417,6 +417,7 @@ int tp_comm_init(tp_ctx *c, const void *id128) {
     TP_API_BEGIN
     TP_REQUIRE(c && id128, "null argument");
     TP_REQUIRE(c->grid.nranks >= 1, "bad nranks");     // a 1-rank communicator is legal (exercises the RCCL calls on one GPU)
+    TP_REQUIRE(!c->graded, "tp_comm_init: this context has spacing (tp_set_spacing): graded grids exist on one slab without a communicator");
     TP_HIP(hipSetDevice(c->device));
     ncclUniqueId id;
     std::memcpy(&id, id128, sizeof(id));
@@ -451,6 +452,7 @@ int tp_comm_init_local(tp_ctx *c, void *group) {
     TP_API_BEGIN
     TP_REQUIRE(c && group, "null argument");
     LocalGroup *G = (LocalGroup *)group;
+    TP_REQUIRE(!c->graded, "tp_comm_init_local: this context has spacing (tp_set_spacing): graded grids exist on one slab without a slab group");
     TP_REQUIRE(c->grid.nranks == G->n, "group size differs from the context's nranks");
     int lo, hi;
     slab_of(c, c->grid.rank, lo, hi);
@@ -523,6 +525,25 @@ int tp_boundary_flux(tp_ctx *c, double *out) {
     TP_API_BEGIN
     TP_REQUIRE(c && out, "null argument");
     bc_flux(c, out);
+    TP_API_END
+}
+
+int tp_set_spacing(tp_ctx *c, const double *h0, int64_t n0, const double *h1, int64_t n1, const double *h2, int64_t n2) {
+    TP_API_BEGIN
+    spacing_set(c, h0, (long)n0, h1, (long)n1, h2, (long)n2);
+    TP_API_END
+}
+
+int tp_spacing_info(tp_ctx *c, int32_t *graded, double *hmin, double *hmax) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && graded && hmin && hmax, "null argument");
+    *graded = c->graded ? 1 : 0;
+    for (int a = 0; a < 3; ++a) {
+        hmin[a] = hmax[a] = c->grid.h[a];
+        if (!c->graded) continue;
+        hmin[a] = *std::min_element(c->hs_host[a].begin(), c->hs_host[a].end());
+        hmax[a] = *std::max_element(c->hs_host[a].begin(), c->hs_host[a].end());
+    }
     TP_API_END
 }
 

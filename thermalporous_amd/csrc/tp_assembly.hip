@@ -77,10 +77,13 @@ __device__ __forceinline__ Props<NPH> eval_props(double p, double T, double S, d
 
 // Flux through one face from the '+' cell P to the '-' cell M and its derivatives w.r.t. both
 // states.  gam = g*Delta_h/2 on the gravity axis, else 0; Ga = |e|/Delta_h.
-template <int NPH, bool SCHUR>
+// GRADED (tp_set_spacing): the two cells have widths of their own, so the harmonic mean of kT weighs each side by
+// its half distance over the face area: Ga carries c_P = d_P/|e| and cM carries c_M = d_M/|e|; gam = g (d_P + d_M)/2 and TK come
+// from the caller as before.  The false branch is the uniform code.
+template <int NPH, bool SCHUR, bool GRADED = false>
 __device__ __forceinline__ void face_flux(const Props<NPH> &P, const Props<NPH> &M, double TK, double gam,
                                           double Ga, const DevPrm &q, double *f, double (*dP)[NPH + 1],
-                                          double (*dM)[NPH + 1], double &sP, double &sM) {
+                                          double (*dM)[NPH + 1], double &sP, double &sM, double cM = 0.0) {
     constexpr int B = NPH + 1;
 #pragma unroll
     for (int r = 0; r < B; ++r) {
@@ -121,6 +124,24 @@ __device__ __forceinline__ void face_flux(const Props<NPH> &P, const Props<NPH> 
     } else {
         phase(q.c_v_o, 1.0, false, P.ro, P.ro_p, P.ro_T, M.ro, M.ro_p, M.ro_T, P.Lo, M.Lo);
     }
+    if (GRADED) {
+        // conduction through two half cells in series: H = k_P k_M / D, D = c_P k_M + c_M k_P
+        const double cP = Ga;
+        const double D = cP * M.kT + cM * P.kT;
+        const double H = D > 0.0 ? P.kT * M.kT / D : 0.0;
+        const double dT = P.T - M.T;
+        f[1] += H * dT;
+        dP[1][1] += H;
+        dM[1][1] -= H;
+        if (SCHUR) { sP += H; sM -= H; }
+        if (NPH == 2) {
+            const double dHP = D > 0.0 ? cP * M.kT * M.kT / (D * D) : 0.0;
+            const double dHM = D > 0.0 ? cM * P.kT * P.kT / (D * D) : 0.0;
+            dP[1][2] += dT * dHP * P.kT_S;
+            dM[1][2] += dT * dHM * M.kT_S;
+        }
+        return;
+    }
     // conduction with harmonic kT (singlephase.py:103,125)
     const double s2 = P.kT + M.kT;
     const double Hk = s2 > 0.0 ? 2.0 * P.kT * M.kT / s2 : 0.0;
@@ -147,9 +168,44 @@ struct AsmArgs {
     double *R, *J, *Sm;
 };
 
-template <int NPH, bool JAC, bool SCHUR>
-__global__ __launch_bounds__(256) void k_assemble(AsmArgs a) {
+// Per-axis cell widths (tp_set_spacing): what the graded instantiations take on top of AsmArgs, whose Vdt, gam and Ga they do not
+// read.  hs[a][i]: width of the cells of index i along internal axis a (a few KB: hs[0] is indexed by the lane, hs[1] and hs[2]
+// are nearly wave-uniform; all of it stays in cache beside the 616 B per cell of the assembly).
+struct Spacing {
+    const double *hs[3];
+    double inv_dt;       // 1/dt: the accumulation takes |E_c|/dt per cell
+    double g4;           // g/4: gam_f = g (h_P + h_M)/4 on the gravity axis
+    int gaxis;
+};
+struct AsmArgsG {
+    AsmArgs a;
+    Spacing sp;
+};
+template <bool GRADED> struct AsmSel { using type = AsmArgs; };
+template <> struct AsmSel<true> { using type = AsmArgsG; };
+__device__ __forceinline__ const AsmArgs &asm_base(const AsmArgs &a) { return a; }
+__device__ __forceinline__ const AsmArgs &asm_base(const AsmArgsG &a) { return a.a; }
+
+// Geometry of one graded cell: its widths, its volume and 1/|e_a| of its faces.  The area of a face along a is the product of the
+// other two widths, so both cells of a face form the same c_P, c_M and gam from the same numbers: the face's flux has the same
+// bits in both rows.
+struct CellGeom {
+    double h[3], V, invA[3];
+};
+__device__ __forceinline__ CellGeom cell_geom(const Spacing &sp, int i0, int i1, int i2) {
+    CellGeom m;
+    m.h[0] = sp.hs[0][i0]; m.h[1] = sp.hs[1][i1]; m.h[2] = sp.hs[2][i2];
+    m.V = m.h[0] * m.h[1] * m.h[2];
+    m.invA[0] = 1.0 / (m.h[1] * m.h[2]);
+    m.invA[1] = 1.0 / (m.h[0] * m.h[2]);
+    m.invA[2] = 1.0 / (m.h[0] * m.h[1]);
+    return m;
+}
+
+template <int NPH, bool JAC, bool SCHUR, bool GRADED = false>
+__global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type aa) {
     constexpr int B = NPH + 1;
+    const AsmArgs &a = asm_base(aa);
     const long tid = xcd_tid();
     const GridDev &g = a.g;
     if (tid >= g.nown) return;
@@ -166,6 +222,12 @@ __global__ __launch_bounds__(256) void k_assemble(AsmArgs a) {
 
     double R[B], Jd[B][B];
     double sd = 0.0;
+    // graded: |E_c|/dt of this cell takes the place of the box's one number in the thread's copy of the arguments
+    CellGeom cg;
+    if constexpr (GRADED) {
+        cg = cell_geom(aa.sp, i0, i1, g.off2 + i2);
+        aa.a.Vdt = cg.V * aa.sp.inv_dt;
+    }
     // ---- accumulation (singlephase.py:120,123 ; twophase.py:162-176) -----------------------------
     {
         const double phi = a.phi[c];
@@ -218,8 +280,19 @@ __global__ __launch_bounds__(256) void k_assemble(AsmArgs a) {
                 const long nb = dir ? c + stride[ax] : c - stride[ax];
                 const Props<NPH> ot =
                     eval_props<NPH>(up_[nb], uT_[nb], NPH == 2 ? uS_[nb] : 0.0, a.phi[nb], a.kTs[nb], q);
+                // graded: gam and the half distances over the area, c_me and c_nb, of this face
+                double gam = 0.0, c_me = 0.0, c_nb = 0.0;
+                if constexpr (GRADED) {
+                    const double hn = aa.sp.hs[ax][dir ? idx[ax] + 1 : idx[ax] - 1];
+                    gam = ax == aa.sp.gaxis ? aa.sp.g4 * (dir ? cg.h[ax] + hn : hn + cg.h[ax]) : 0.0;
+                    c_me = 0.5 * cg.h[ax] * cg.invA[ax];
+                    c_nb = 0.5 * hn * cg.invA[ax];
+                }
                 if (dir) {
-                    face_flux<NPH, SCHUR>(me, ot, a.TK[ax][c], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
+                    if constexpr (GRADED)
+                        face_flux<NPH, SCHUR, true>(me, ot, a.TK[ax][c], gam, c_me, q, f, dP, dM, sP, sM, c_nb);
+                    else
+                        face_flux<NPH, SCHUR>(me, ot, a.TK[ax][c], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
 #pragma unroll
                     for (int r = 0; r < B; ++r) {
                         R[r] += f[r];
@@ -228,7 +301,10 @@ __global__ __launch_bounds__(256) void k_assemble(AsmArgs a) {
                     }
                     if (SCHUR) sd += sP;
                 } else {
-                    face_flux<NPH, SCHUR>(ot, me, a.TK[ax][nb], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
+                    if constexpr (GRADED)
+                        face_flux<NPH, SCHUR, true>(ot, me, a.TK[ax][nb], gam, c_nb, q, f, dP, dM, sP, sM, c_me);
+                    else
+                        face_flux<NPH, SCHUR>(ot, me, a.TK[ax][nb], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
 #pragma unroll
                     for (int r = 0; r < B; ++r) {
                         R[r] -= f[r];
@@ -446,9 +522,21 @@ __device__ __forceinline__ long bc_face(const GridDev &g, int ax, int i0, int i1
     return ax == 0 ? (long)i1 + (long)g.n1 * i2 : (ax == 1 ? (long)i0 + (long)g.n0 * i2 : (long)i0 + (long)g.n0 * i1);
 }
 
-template <int NPH, bool JAC, bool SCHUR>
-__global__ __launch_bounds__(256) void k_assemble_bc(BcArgs s) {
+// graded (tp_set_spacing): the same face with both half distances h_a(c)/4, h_a(c) the boundary cell's own width along the side's
+// axis: c_P = c_M = h/(4|e|), gam = g h/4; T^K = 2 K|e|/h comes from k_bc_trans_g
+struct BcArgsG {
+    BcArgs s;
+    Spacing sp;
+};
+template <bool GRADED> struct BcSel { using type = BcArgs; };
+template <> struct BcSel<true> { using type = BcArgsG; };
+__device__ __forceinline__ const BcArgs &bc_base(const BcArgs &s) { return s; }
+__device__ __forceinline__ const BcArgs &bc_base(const BcArgsG &s) { return s.s; }
+
+template <int NPH, bool JAC, bool SCHUR, bool GRADED = false>
+__global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED>::type ss) {
     constexpr int B = NPH + 1;
+    const BcArgs &s = bc_base(ss);
     const int t = blockIdx.x * TP_BLOCK + threadIdx.x;
     if (t >= s.ncells) return;
     const AsmArgs &a = s.a;
@@ -481,10 +569,21 @@ __global__ __launch_bounds__(256) void k_assemble_bc(BcArgs s) {
         const double *v = s.val[side];
         const Props<NPH> gh = eval_props<NPH>(v[f_], v[nf + f_], NPH == 2 ? v[2 * nf + f_] : 0.0, phi, kTs, q);
         const double TK = s.tk[side][f_];
-        const double gam = 0.5 * a.gam[ax], Ga = 2.0 * a.Ga[ax];
+        double gam, Ga;
+        if constexpr (GRADED) {
+            const Spacing &sp = ss.sp;
+            const double h0 = sp.hs[0][i0], h1 = sp.hs[1][i1], h2 = sp.hs[2][i2];
+            const double h = ax == 0 ? h0 : (ax == 1 ? h1 : h2);
+            const double A = ax == 0 ? h1 * h2 : (ax == 1 ? h0 * h2 : h0 * h1);
+            gam = ax == sp.gaxis ? sp.g4 * h : 0.0;
+            Ga = 0.25 * h / A;                                 // (c_P = c_M: the ghost lies as far from the face as the centre)
+        } else {
+            gam = 0.5 * a.gam[ax];
+            Ga = 2.0 * a.Ga[ax];
+        }
         double f[B], dP[B][B], dM[B][B], sP = 0.0, sM = 0.0;
-        if (dir) face_flux<NPH, SCHUR>(me, gh, TK, gam, Ga, q, f, dP, dM, sP, sM);
-        else     face_flux<NPH, SCHUR>(gh, me, TK, gam, Ga, q, f, dP, dM, sP, sM);
+        if (dir) face_flux<NPH, SCHUR, GRADED>(me, gh, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
+        else     face_flux<NPH, SCHUR, GRADED>(gh, me, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
         const double sg = dir ? 1.0 : -1.0;
 #pragma unroll
         for (int r = 0; r < B; ++r) {
@@ -522,6 +621,25 @@ __global__ void k_bc_trans(GridDev g, const double *K, int side, int open, doubl
     else              { i0 = lo; i1 = hi; i2 = dir ? g.n2 - 1 : 0; }
     const long c = g.np + (long)i0 + (long)g.n0 * i1 + g.np * i2;
     tk[f] = open ? 2.0 * K[c] * geom : 0.0;
+}
+
+// graded: T^K = K/(2c) with c = h_a(c)/(4|e|), i.e. 2 K |e| / h_a(c) with the cell's own width and face area
+__global__ void k_bc_trans_g(GridDev g, const double *K, int side, int open, const double *hs0, const double *hs1,
+                             const double *hs2, long nf, double *tk) {
+    const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nf) return;
+    const int ax = side >> 1, dir = side & 1;
+    const int na = ax == 0 ? g.n1 : g.n0;
+    const int lo = (int)(f % na), hi = (int)(f / na);
+    int i0, i1, i2;
+    if (ax == 0)      { i0 = dir ? g.n0 - 1 : 0; i1 = lo; i2 = hi; }
+    else if (ax == 1) { i0 = lo; i1 = dir ? g.n1 - 1 : 0; i2 = hi; }
+    else              { i0 = lo; i1 = hi; i2 = dir ? g.n2 - 1 : 0; }
+    const long c = g.np + (long)i0 + (long)g.n0 * i1 + g.np * i2;
+    const double h0 = hs0[i0], h1 = hs1[i1], h2 = hs2[i2];
+    const double h = ax == 0 ? h0 : (ax == 1 ? h1 : h2);
+    const double A = ax == 0 ? h1 * h2 : (ax == 1 ? h0 * h2 : h0 * h1);
+    tk[f] = open ? 2.0 * K[c] * A / h : 0.0;
 }
 
 // ---- accumulation of the old state (once per time step) -------------------------------------------
@@ -567,6 +685,31 @@ __global__ void k_trans(GridDev g, const double *K, int ax, double geom, double 
         const double kp = K[c], km = K[c + stride];
         const double s = kp + km;
         t = s > 0.0 ? 2.0 * kp * km / s * geom : 0.0;
+    }
+    TK[c] = t;
+}
+
+// graded (tp_set_spacing): T^K = K_P K_M / (c_P K_M + c_M K_P), c = (h_a/2)/|e|, |e| the product of the other two widths; 0 where
+// the denominator is not positive.  One GPU: idx along axis 2 is the plane itself and the halo plane of TK[2] stays zero.
+__global__ void k_trans_g(GridDev g, const double *K, int ax, const double *hs0, const double *hs1, const double *hs2, double *TK) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= g.nown) return;
+    const long c = g.np + tid;
+    const int i2 = (int)(tid / g.np);
+    const int rem = (int)(tid - (long)i2 * g.np);
+    const int i1 = rem / g.n0, i0 = rem - i1 * g.n0;
+    const long stride = ax == 0 ? 1 : (ax == 1 ? g.n0 : g.np);
+    const int idx = ax == 0 ? i0 : (ax == 1 ? i1 : i2);
+    const int ext = ax == 0 ? g.n0 : (ax == 1 ? g.n1 : g.n2);
+    double t = 0.0;
+    if (idx < ext - 1) {
+        const double h0 = hs0[i0], h1 = hs1[i1], h2 = hs2[i2];
+        const double *hs = ax == 0 ? hs0 : (ax == 1 ? hs1 : hs2);
+        const double A = ax == 0 ? h1 * h2 : (ax == 1 ? h0 * h2 : h0 * h1);
+        const double cp = 0.5 * hs[idx] / A, cm = 0.5 * hs[idx + 1] / A;
+        const double kp = K[c], km = K[c + stride];
+        const double d = cp * km + cm * kp;
+        t = d > 0.0 ? kp * km / d : 0.0;
     }
     TK[c] = t;
 }
@@ -672,6 +815,15 @@ __global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *
 
 void compute_trans(tp_ctx *c) {
     const GridDev &g = c->g;
+    if (c->graded) {
+        for (int ax = 0; ax < 3; ++ax)
+            hipLaunchKernelGGL(k_trans_g, grid_for(g.nown), dim3(256), 0, c->stream, g, c->K[ax].p, ax, c->hs[0].p, c->hs[1].p,
+                               c->hs[2].p, c->TK[ax].p);
+        // (one slab, off2 == 0: the uniform halo kernel writes the zeros of a box without a slab below)
+        hipLaunchKernelGGL(k_trans_halo, grid_for(g.np), dim3(256), 0, c->stream, g, c->K[2].p, 0.0, c->TK[2].p);
+        TP_HIP(hipGetLastError());
+        return;
+    }
     for (int ax = 0; ax < 3; ++ax) {
         const double h = c->grid.h[ax];
         const double geom = c->vol / (h * h);
@@ -710,6 +862,71 @@ static AsmArgs asm_args(tp_ctx *c) {
     return a;
 }
 
+static Spacing spacing_args(tp_ctx *c) {
+    Spacing sp;
+    for (int ax = 0; ax < 3; ++ax) sp.hs[ax] = c->hs[ax].p;
+    sp.inv_dt = 1.0 / c->dt;
+    sp.g4 = 0.25 * c->prm.g;
+    sp.gaxis = c->grid.gaxis;
+    return sp;
+}
+
+// ---- graded grid: host side (tp_set_spacing) ---------------------------------------------------------------------------------
+void spacing_set(tp_ctx *c, const double *h0, long n0, const double *h1, long n1, const double *h2, long n2) {
+    TP_REQUIRE(c, "null argument");
+    if (c->grid.nranks > 1 || c->dist || c->comm || c->lgroup)
+        throw Error("tp_set_spacing: spacing on a context with a communicator or a slab group (nranks = " +
+                    std::to_string(c->grid.nranks) + ") is not implemented: graded grids exist on one slab");
+    const double *h[3] = {h0, h1, h2};
+    const long n[3] = {n0, n1, n2};
+    const int ext[3] = {c->g.n0, c->g.n1, c->g.n2};
+    const bool clear = !h0 && !h1 && !h2;
+    if (!clear) {
+        for (int a = 0; a < 3; ++a) {
+            if (!h[a]) throw Error("tp_set_spacing: null widths for axis " + std::to_string(a) + ": three arrays, or three nulls for a uniform grid");
+            if (n[a] != ext[a])
+                throw Error("tp_set_spacing: " + std::to_string(n[a]) + " widths for axis " + std::to_string(a) + " but the grid has " +
+                            std::to_string(ext[a]) + " cells along it");
+            for (long i = 0; i < n[a]; ++i)
+                if (!std::isfinite(h[a][i]) || !(h[a][i] > 0.0))
+                    throw Error("tp_set_spacing: width " + std::to_string(i) + " of axis " + std::to_string(a) + " is not a positive finite number");
+        }
+    }
+    TP_HIP(hipStreamSynchronize(c->stream));       // nothing in flight reads what is replaced
+    for (int a = 0; a < 3; ++a) {
+        if (clear) { c->hs_host[a].clear(); c->hs[a].free(); continue; }
+        c->hs_host[a].assign(h[a], h[a] + n[a]);
+        c->hs[a].alloc(n[a]);
+        copy_sync(c, c->hs[a].p, h[a], sizeof(double) * n[a], hipMemcpyHostToDevice);
+    }
+    c->graded = !clear;
+    c->fields_ready = false;                       // T^K of the interior and of the sides follow the widths: tp_finalize_fields
+}
+
+void conduction_strengths(const tp_ctx *c, const GridDev &gam, double sg[3]) {
+    const int n[3] = {gam.n0, gam.n1, gam.n2};
+    for (int a = 0; a < 3; ++a) {
+        if (!c->graded) {
+            const double hh = c->grid.h[a];
+            sg[a] = n[a] > 1 ? c->vol / (hh * hh) : 0.0;
+            continue;
+        }
+        sg[a] = 0.0;
+        if (n[a] <= 1) continue;
+        double area = 1.0;                         // mean face area: the product of the other two axes' mean widths
+        for (int o = 0; o < 3; ++o) {
+            if (o == a) continue;
+            double sum = 0.0;
+            for (double w : c->hs_host[o]) sum += w;
+            area *= sum / (double)c->hs_host[o].size();
+        }
+        const std::vector<double> &w = c->hs_host[a];
+        double inv = 0.0;                          // mean of 1/(d_P + d_M) over the interior faces
+        for (size_t i = 0; i + 1 < w.size(); ++i) inv += 1.0 / (0.5 * (w[i] + w[i + 1]));
+        sg[a] = area * inv / (double)(w.size() - 1);
+    }
+}
+
 // ---- Dirichlet sides: host side ------------------------------------------------------------------------------------------
 static long bc_side_faces(const GridDev &g, int side) {
     const int ax = side >> 1;
@@ -721,8 +938,12 @@ static void bc_trans_side(tp_ctx *c, int side) {
     if (s.kind == 0) return;
     const int ax = side >> 1;
     const double h = c->grid.h[ax];
-    hipLaunchKernelGGL(k_bc_trans, grid_for(s.nf), dim3(256), 0, c->stream, c->g, c->K[ax].p, side, s.kind == 1 ? 1 : 0,
-                       c->vol / (h * h), s.nf, s.tk.p);
+    if (c->graded)
+        hipLaunchKernelGGL(k_bc_trans_g, grid_for(s.nf), dim3(256), 0, c->stream, c->g, c->K[ax].p, side, s.kind == 1 ? 1 : 0,
+                           c->hs[0].p, c->hs[1].p, c->hs[2].p, s.nf, s.tk.p);
+    else
+        hipLaunchKernelGGL(k_bc_trans, grid_for(s.nf), dim3(256), 0, c->stream, c->g, c->K[ax].p, side, s.kind == 1 ? 1 : 0,
+                           c->vol / (h * h), s.nf, s.tk.p);
     TP_HIP(hipGetLastError());
 }
 
@@ -808,7 +1029,13 @@ void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur) {
     }
     if (want_schur) TP_REQUIRE(c->Sm.p, "S~ storage not allocated");
     const dim3 gr = grid_for(s.ncells), bl(256);
-#define LAUNCH_BC(NPH, JAC, SCH) hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH>), gr, bl, 0, c->stream, s)
+    BcArgsG sg;
+    if (c->graded) { sg.s = s; sg.sp = spacing_args(c); }
+#define LAUNCH_BC(NPH, JAC, SCH)                                                                                         \
+    do {                                                                                                                 \
+        if (c->graded) hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH, true>), gr, bl, 0, c->stream, sg);                \
+        else hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH>), gr, bl, 0, c->stream, s);                                 \
+    } while (0)
     if (c->nph == 2) {
         if (!want_jac) LAUNCH_BC(2, false, false);
         else if (want_schur) LAUNCH_BC(2, true, true);
@@ -850,9 +1077,13 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
     const dim3 gr = xcd_grid(g.nown), bl(256);
     static const bool lds_tiled = getenv("TP_ASM_LDS") && atoi(getenv("TP_ASM_LDS")) == 1;
     const dim3 grl((g.n0 + ATX - 1) / ATX, (g.n1 + ATY - 1) / ATY, (g.n2 + ATZ - 1) / ATZ);
+    // a context with spacing always launches the plain graded kernel (the LDS-tiled variant has no graded twin)
+    AsmArgsG ag;
+    if (c->graded) { ag.a = a; ag.sp = spacing_args(c); }
 #define LAUNCH(NPH, JAC, SCH)                                                                                            \
     do {                                                                                                                 \
-        if (lds_tiled) {                                                                                                 \
+        if (c->graded) hipLaunchKernelGGL((k_assemble<NPH, JAC, SCH, true>), gr, bl, 0, c->stream, ag);                   \
+        else if (lds_tiled) {                                                                                            \
             const size_t bytes = (size_t)PropsLds<NPH>::NV * ANS * sizeof(double);                                        \
             TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_lds<NPH, JAC, SCH>),                    \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));                         \

@@ -370,6 +370,11 @@ struct tp_ctx {
     int nsrc = 0, nsrc_groups = 0;
     tp::DBuf<double> rates;       // 3*nsrc
     tp::Bc bc;                    // Dirichlet sides (tp_set_boundary)
+    // graded tensor-product grid (tp_set_spacing): widths of the cells along each internal axis, on the host and
+    // on the device.  graded == false: nothing of this is allocated or read and grid.h / vol describe every cell.
+    bool graded = false;
+    std::vector<double> hs_host[3];
+    tp::DBuf<double> hs[3];
     // linear algebra
     std::vector<tp::DBuf<double> *> vecs;
     tp::DBuf<double> At;          // decoupled primary block (QI/TI); planes as in J with b' = nprimary
@@ -472,6 +477,11 @@ void bc_set(tp_ctx *c, int side, int kind, const double *values, long nfaces);
 void bc_trans(tp_ctx *c);
 void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur);
 void bc_flux(tp_ctx *c, double *out);
+// graded grid (tp_set_spacing): spacing_set checks and stores the widths (all null: back to uniform) and marks the fields as not
+// finalised; conduction_strengths gives the per-axis coarsening strengths of amg_T and the pc_ctr hierarchy on grid `gam`: |E|/h_a^2,
+// or with spacing the mean of |e|/(d_P + d_M) over the axis's interior faces
+void spacing_set(tp_ctx *c, const double *h0, long n0, const double *h1, long n1, const double *h2, long n2);
+void conduction_strengths(const tp_ctx *c, const GridDev &gam, double sg[3]);
 // vectors / reductions (vectors are b field planes of ntot; reductions run over owned cells only)
 void vec_zero(tp_ctx *c, double *x, long n);
 void vec_copy(tp_ctx *c, const double *x, double *y, long n);

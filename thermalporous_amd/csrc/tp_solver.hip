@@ -171,11 +171,7 @@ void pc_setup(tp_ctx *c) {
         amg_build(c, c->amg_p, gam, st, gather_cells);
         if (cptr) {
             double sg[3];
-            const int n[3] = {gam.n0, gam.n1, gam.n2};
-            for (int a = 0; a < 3; ++a) {
-                const double hh = c->grid.h[a];
-                sg[a] = n[a] > 1 ? c->vol / (hh * hh) : 0.0;
-            }
+            conduction_strengths(c, gam, sg);
             amg_build(c, c->amg_T, gam, sg, gather_cells);
             TP_REQUIRE((c->amg_p->plan.dist_levels > 0) == (c->amg_T->plan.dist_levels > 0), "stage-1 hierarchies disagree on distribution");
         }
@@ -187,11 +183,7 @@ void pc_setup(tp_ctx *c) {
     if (ctr) {
         if (!c->amg_ctr) {
             double sg[3];
-            const int n[3] = {gam.n0, gam.n1, gam.n2};
-            for (int a = 0; a < 3; ++a) {
-                const double hh = c->grid.h[a];
-                sg[a] = n[a] > 1 ? c->vol / (hh * hh) : 0.0;
-            }
+            conduction_strengths(c, gam, sg);
             amg_build(c, c->amg_ctr, gam, sg, gather_cells);
         }
         Sc.base = c->J.p + (long)(c->b + 1) * c->g.ntot;

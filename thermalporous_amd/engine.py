@@ -82,7 +82,7 @@ API_SYMBOLS = (
     "tp_ksp_basis_info", "tp_fvec_create_batch", "tp_fvec_store", "tp_fvec_get", "tp_fvec_dot_batch", "tp_fvec_axpy_batch",
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
     "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
-    "tp_schur_info", "tp_set_boundary", "tp_boundary_flux",
+    "tp_schur_info", "tp_set_boundary", "tp_boundary_flux", "tp_set_spacing", "tp_spacing_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -582,6 +582,31 @@ def check_boundary_slabs(boundary, nranks=1):
                                   % (sorted(boundary), int(nranks)))
 
 
+def check_spacing_slabs(hs, nranks=1, local_group=None, comm_bootstrap=None):
+    """Graded widths (spec["hs"]) against slabs: refused, naming both, before any context exists."""
+    if hs is None:
+        return
+    if int(nranks) > 1 or local_group is not None or comm_bootstrap is not None:
+        raise NotImplementedError("a graded grid (spec[\"hs\"], geo.set_spacing) with nranks = %d%s: per-axis cell widths are "
+                                  "implemented for one slab without a communicator"
+                                  % (int(nranks), " and a slab group" if local_group is not None else ""))
+
+
+def check_spacing(hs, n):
+    """spec["hs"] against the grid n = (n0, n1, n2): three arrays of positive finite widths in internal axis order."""
+    if len(hs) != 3:
+        raise ValueError("spec[\"hs\"] holds %d arrays: one per internal axis, three" % len(hs))
+    out = []
+    for a in range(3):
+        w = np.ascontiguousarray(hs[a], dtype=float).reshape(-1)
+        if w.size != int(n[a]):
+            raise ValueError("spec[\"hs\"][%d] has %d widths but the grid has %d cells along internal axis %d" % (a, w.size, n[a], a))
+        if not np.isfinite(w).all() or (w <= 0.0).any():
+            raise ValueError("spec[\"hs\"][%d]: the widths must be positive and finite" % a)
+        out.append(w)
+    return tuple(out)
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -624,6 +649,7 @@ class HipEngine:
 
     def __init__(self, spec, opts=None, rank=0, nranks=1, device=None, comm_bootstrap=None, local_group=None):
         check_boundary_slabs(spec.get("boundary"), nranks)       # (host-side: before the library and any context)
+        check_spacing_slabs(spec.get("hs"), nranks, local_group, comm_bootstrap)
         self.lib = load_library()
         self.spec = spec
         self.opts = dict(DEFAULT_OPTS)
@@ -659,6 +685,11 @@ class HipEngine:
                 raise EngineError("multi-slab engine needs comm_bootstrap(make_id) -> 128-byte id")
             ident = comm_bootstrap(self._unique_id)
             self._ck(self.lib.tp_comm_init(self.ctx, C.c_char_p(bytes(ident))))
+        # graded grid (spacing.py; include/thermalporous_hip.h: tp_set_spacing): the widths go in before the fields are
+        # finalised, so that the transmissibilities are formed once, from them
+        self.spacing = None                    # the widths per internal axis in force, or None on a uniform grid
+        if spec.get("hs") is not None:
+            self.set_spacing(spec["hs"], finalize=False)
         # fields (slab + halo planes; halo of a physical boundary replicates the boundary plane)
         for name, arr in (("phi", spec["phi"]), ("kT", spec["kT"]), ("K0", spec["K"][0]), ("K1", spec["K"][1]),
                           ("K2", spec["K"][2])):
@@ -757,6 +788,30 @@ class HipEngine:
         self._ck(self.lib.tp_set_sources(self.ctx, len(mine), arr))
         # the library sorts entries by cell (stable): reproduce the permutation for rate read-back
         self._src_order = np.argsort(cells[mine], kind="stable")
+
+    # ---- graded grid (spacing.py; include/thermalporous_hip.h: tp_set_spacing) --------------------------
+    def set_spacing(self, hs, finalize=True):
+        """Cell widths per internal axis (three arrays of n0, n1, n2 positive numbers), or None for the uniform grid of
+        spec["h"].  The library recomputes the interior and boundary transmissibilities at tp_finalize_fields, which this
+        call issues unless `finalize` is False."""
+        check_spacing_slabs(hs, self.nranks)
+        if hs is None:
+            self._ck(self.lib.tp_set_spacing(self.ctx, None, C.c_int64(0), None, C.c_int64(0), None, C.c_int64(0)))
+            self.spacing = None
+        else:
+            w = check_spacing(hs, self.gn)
+            self._ck(self.lib.tp_set_spacing(self.ctx, _dptr(w[0]), C.c_int64(w[0].size), _dptr(w[1]), C.c_int64(w[1].size),
+                                             _dptr(w[2]), C.c_int64(w[2].size)))
+            self.spacing = w
+        if finalize:
+            self._ck(self.lib.tp_finalize_fields(self.ctx))
+
+    def spacing_info(self):
+        """tp_spacing_info: dict(graded, hmin, hmax) with the smallest and largest width per internal axis."""
+        graded = C.c_int32(0)
+        lo, hi = np.zeros(3), np.zeros(3)
+        self._ck(self.lib.tp_spacing_info(self.ctx, C.byref(graded), _dptr(lo), _dptr(hi)))
+        return dict(graded=bool(graded.value), hmin=tuple(lo), hmax=tuple(hi))
 
     # ---- Dirichlet sides (boundary.py; include/thermalporous_hip.h: tp_set_boundary) -------------------
     def _side_shape(self, side):

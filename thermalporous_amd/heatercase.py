@@ -1,5 +1,6 @@
 """Heaters: energy source U*(T_inj - T)*delta (mirror of /root/reference/thermalporous/heatercase.py:6-118)."""
 from . import utils
+from .spacing import lock_spacing
 
 
 class HeaterCase():
@@ -13,6 +14,7 @@ class HeaterCase():
         self.V = geo.V
         self.mesh = geo.mesh
         self.geo = geo
+        lock_spacing(geo)             # the heaters below pick their cells on the grid as it is now
         self.params = params
         L, Ly = self.Length, self.Length_y
         pts = None

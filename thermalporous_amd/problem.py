@@ -9,11 +9,13 @@ the C-ABI consumes through tp_create / tp_set_field / tp_set_params / tp_set_sou
   longer of x,y (smallest slab cross-section), a1 = the other.  2-D: (x, y, -).
 * fields transposed to internal order, shape (n2, n1, n0);
 * wells/heaters flattened to per-cell source entries with their Peaceman index
-  (wellcase.py:182-191 of the reference: hard-coded Dx=Dy=h=5, rw=0.1; Kx,Ky at the cell).
+  (wellcase.py:182-191 of the reference: hard-coded Dx=Dy=h=5, rw=0.1; Kx,Ky at the cell);
+* ``hs``: the cell widths per internal axis of a graded grid (``geo.set_spacing``), absent on a uniform one.
 """
 import numpy as np
 
 from .boundary import boundary_spec
+from .spacing import lock_spacing
 from .wellcase import peaceman_WI
 
 PROD, INJ, HEATER = 0, 1, 2
@@ -86,6 +88,7 @@ def build_spec(geo, case, params, nphase, axes=None):
         raise NotImplementedError("gravity2D is orientation-dependent in the reference "
                                   "(singlephase.py:105-109) and used by no configuration")
     axes = tuple(axes) if axes is not None else choose_axes(geo)
+    lock_spacing(geo)                     # a model is being built on the grid as it is now
     N = (geo.Nx, geo.Ny, geo.Nz)
     D = (geo.Dx, geo.Dy, geo.Dz if geo.dim == 3 else 1.0)
     Kphys = [geo.K_x, geo.K_y, getattr(geo, "K_z", 0.0)]
@@ -115,6 +118,11 @@ def build_spec(geo, case, params, nphase, axes=None):
         "WI": np.array([peaceman_WI(kx[c], ky[c]) if e[1] != HEATER else 0.0 for e, c in zip(ent, cells)], dtype=float),
         "const": np.array([1 if e[5] else 0 for e in ent], dtype=np.int32),
     }
+    if getattr(geo, "graded", False):
+        # graded grid (spacing.py): the widths per internal axis; "h" above stays the mean widths, which nothing reads as a
+        # cell's size once "hs" is present
+        w = geo.cell_widths()
+        spec["hs"] = tuple(np.ascontiguousarray(w[a], dtype=float) for a in axes)
     bnd = boundary_spec(geo, params, nphase, axes)      # Dirichlet sides (boundary.py); no key when none is set
     if bnd:
         spec["boundary"] = bnd

@@ -6,13 +6,12 @@ numpy arrays of shape (Nx, Ny) (or scalars for the homogeneous models) indexed [
 like the ``slice_*.npy`` files (SPE10model.py:36-40).  Mesh hierarchies (:36-61) are geometric
 multigrid experiments outside the hot path and are rejected.
 """
-import numpy as np
-
 from .boundary import BoundaryMixin
 from .mesh import StructuredMesh
+from .spacing import SpacingMixin
 
 
-class RectangleGeo(BoundaryMixin):
+class RectangleGeo(BoundaryMixin, SpacingMixin):
     def __init__(self, Nx, Ny, params, Length=365.76, Length_y=365.76, mg={}):
         self.Nx = int(Nx)
         self.Ny = int(Ny)
@@ -45,7 +44,4 @@ class RectangleGeo(BoundaryMixin):
     def init_function_space(self):
         self.V = self.mesh.dq0()
 
-    def cell_centres(self):
-        x = (np.arange(self.Nx) + 0.5)*self.Dx
-        y = (np.arange(self.Ny) + 0.5)*self.Dy
-        return np.meshgrid(x, y, indexing="ij")
+    # cell_centres(), cell_widths(), cell_volumes(), cell_edges() and set_spacing(): spacing.SpacingMixin

@@ -6,6 +6,7 @@ In 3-D the bump height is 0.1 here (:116), not 1.0."""
 import numpy as np
 
 from . import utils
+from .spacing import lock_spacing
 from .wellcase import WellCase
 
 
@@ -21,6 +22,7 @@ class SourceTerms():
         self.V = geo.V
         self.mesh = geo.mesh
         self.geo = geo
+        lock_spacing(geo)             # the deltas below pick their cells on the grid as it is now
         self.params = params
         if not hasattr(self.params, "prod_rate"):
             self.params.prod_rate = self.params.rate
@@ -39,12 +41,12 @@ class SourceTerms():
         self.deltas_heaters = deltas(heater_points)
 
     def _merge(self, ds, accumulate):
-        vol = utils.cell_volume(self.geo)
         acc = {}
         for d in ds:
             for c, v in zip(d.cells, d.values):
                 acc[int(c)] = (acc.get(int(c), 0.0) + v) if accumulate else v
         cells = sorted(acc)
+        vol = utils.cell_volume(self.geo, cells)      # (one number, or with spacing the volume of each of `cells`)
         return utils.Delta(cells, [acc[c] for c in cells], vol)
 
     def make_circles(self, ws):                      # (:88-96): deltas accumulate

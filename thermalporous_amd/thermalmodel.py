@@ -23,6 +23,7 @@ from .boundary import SIDES, check_boundary, side_name, to_internal_side
 from .function import Constant, Function
 from .problem import build_spec, field_major_to_internal, internal_to_field_major, _flat
 from .solver_options import engine_options
+from .utils import cell_volume
 
 DAY = 24.0*3600.0
 
@@ -104,6 +105,10 @@ class ThermalModel:
         if factory is None:
             from .engine import HipEngine
             factory = HipEngine      # no fallback: raises if the HIP library or the GPU is missing
+        elif "hs" in self.spec and not getattr(factory, "supports_spacing", False):
+            raise NotImplementedError("a graded grid (geo.set_spacing, spec[\"hs\"]) with the engine %r: per-axis cell widths "
+                                      "are implemented by HipEngine; this engine would read the mean widths spec[\"h\"] as "
+                                      "every cell's size" % (getattr(factory, "__name__", factory),))
         if self.comm.size > 1:
             # one process per GPU: this rank's slab of internal axis 2, RCCL bootstrapped through torch.distributed
             from . import parallel
@@ -157,6 +162,8 @@ class ThermalModel:
     def oil_mass(self):
         u = self.u._read()
         phi = _flat(self.geo.phi, self.geo)
+        if getattr(self.geo, "graded", False):       # every cell's own volume (flat, x fastest, as the state)
+            return float(np.sum(phi*u[2]*self.params.oil_rho(u[0], u[1])*cell_volume(self.geo)))
         vol = self.geo.Dx*self.geo.Dy*(self.geo.Dz if self.geo.dim == 3 else 1.0)
         return float(np.sum(phi*u[2]*self.params.oil_rho(u[0], u[1]))*vol)
 
@@ -200,6 +207,23 @@ class ThermalModel:
         self.engine.set_boundary(sid, entry["kind"], p=entry["p"], T=entry["T"], S=entry["S"])
         self.spec.setdefault("boundary", {})[sid] = entry
 
+    def _check_checkpoint_widths(self, chk):
+        """A checkpoint holds the cell widths of the grid it was written on (a file from before graded grids holds none: a
+        uniform grid); restarting onto a geo with other widths is an error, not an interpolation."""
+        if not hasattr(self.geo, "cell_widths"):
+            return
+        for name, w in zip(("widths_x", "widths_y", "widths_z"), self.geo.cell_widths()):
+            if name in chk.files:
+                old = np.asarray(chk[name], dtype=float)
+            elif getattr(self.geo, "graded", False):
+                raise ValueError("checkpoint %s holds no cell widths (a uniform grid) but the geo has spacing set"
+                                 % self.checkpointing["loadname"])
+            else:
+                continue
+            if old.shape != w.shape or not np.allclose(old, w, rtol=1e-12, atol=0.0):
+                raise ValueError("checkpoint %s was written on a grid with other cell widths along %s: a restart needs the "
+                                 "same spacing (geo.set_spacing)" % (self.checkpointing["loadname"], name[-1]))
+
     # ---- the time loop -------------------------------------------------------------------------------
     def start(self):
         """Initial condition, dt ramp and counters (thermalmodel.py:84-149)."""
@@ -212,6 +236,7 @@ class ThermalModel:
         if self.checkpointing["load"] is True:     # .npz instead of DumbCheckpoint (:87-91)
             self.resultprint("Using as initial solution checkpoint " + self.checkpointing["loadname"])
             chk = np.load(self.checkpointing["loadname"] + ".npz")
+            self._check_checkpoint_widths(chk)
             u.assign(chk["solution"])
             u_.assign(chk["solution"])
         else:
@@ -353,7 +378,9 @@ class ThermalModel:
         t = self.t
         nits_vec, lits_vec, dt_vec, timings = self.nits_vec, self.lits_vec, self.dt_vec, self.timings
         if self.checkpointing["save"] is True:
-            np.savez(self.checkpointing["savename"] + ".npz", solution=u._read(), t=t, dt=self.dt.values()[0])
+            hx, hy, hz = (self.geo.cell_widths() if hasattr(self.geo, "cell_widths") else (np.zeros(0),)*3)
+            np.savez(self.checkpointing["savename"] + ".npz", solution=u._read(), t=t, dt=self.dt.values()[0],
+                     widths_x=hx, widths_y=hy, widths_z=hz)
             self.resultprint("Saving checkpoint solution in " + self.checkpointing["savename"])
         dt_counter = len(dt_vec)
         if self.comm.rank == 0 and self.verbosity:

@@ -10,10 +10,12 @@ per-time-step rate diagnostics (thermalmodel.py:232-294).
 import numpy as np
 
 from . import utils
+from .spacing import lock_spacing
 
 
 def peaceman_WI(Kx, Ky):
-    """2*pi*h*Ke/ln(ro/rw) with the hard-coded Dx=Dy=h=5, rw=0.1 of wellcase.py:182-191."""
+    """2*pi*h*Ke/ln(ro/rw) with the hard-coded Dx=Dy=h=5, rw=0.1 of wellcase.py:182-191.  The reference's constants hold on
+    every grid, a graded one (geo.set_spacing) included: the Peaceman radius is not taken from the true size of the well's cell."""
     h, rw, Dx, Dy = 5.0, 0.1, 5.0, 5.0
     ro = 0.28*((Ky/Kx)**0.5*Dx**2 + (Kx/Ky)**0.5*Dy**2)**0.5/((Ky/Kx)**0.25 + (Kx/Ky)**0.25)
     Ke = (Kx*Ky)**0.5
@@ -31,6 +33,7 @@ class WellCase():
         self.V = geo.V
         self.mesh = geo.mesh
         self.geo = geo
+        lock_spacing(geo)             # the wells below pick their cells on the grid as it is now
         self.params = params
         self.wellfunc = 'circle'
         self.constant_rate = bool(constant_rate)
