@@ -319,6 +319,36 @@ int tp_boundary_flux(tp_ctx *ctx, double *out);
  * tp_spacing_info: *graded = 1 if spacing is set, and per internal axis the smallest and largest width (tp_grid.h when uniform). */
 int tp_set_spacing(tp_ctx *ctx, const double *h0, int64_t n0, const double *h1, int64_t n1, const double *h2, int64_t n2);
 int tp_spacing_info(tp_ctx *ctx, int32_t *graded, double *hmin, double *hmax);
+/* Saturation functions of the two-phase model (off by default: kr_o = S_o, kr_w = 1 - S_o and one pressure for
+ * both phases, physicalparameters.py:92-98, the only form the reference executes; its Brooks-Corey members :100-152 are dead code).
+ * With D = 1 - Sr_o - Sr_w, Se_o = (S_o - Sr_o)/D, Se_w = (1 - S_o - Sr_w)/D:
+ *   relperm 1 (Corey):    kr_o = kro_max Se_o^n_o for 0 < Se_o < 1, 0 at and below 0, kro_max at and above 1; kr_w alike on Se_w
+ *                         with krw_max, n_w; the derivatives are exactly 0 at and beyond either end (Brooks-Corey is Corey with
+ *                         n_o = n_w = (2 + 3 lmbda)/lmbda: the caller translates, engine.pack_satfn);
+ *   capillary 1 (linear): p_c = p_ct (1 - min(max(Se_w, 0), 1));
+ *   capillary 2 (Brooks-Corey): p_c = p_ct s^(-1/lmbda), s = min(max(Se_w, pc_se_min), 1);
+ * p_c = p_o - p_w with p_o = p the unknown (twophase.py:104-106).  p_w = p - p_c(S_o) is where water's density is evaluated in the
+ * accumulation (new and old), the water mobility and water's gravity head, and the water driving force is p_w+ - p_w- -
+ * gam (rho_w+ + rho_w-); oil, kT, the weights and the tie rules do not change; a Dirichlet ghost state goes through the same
+ * closures.  Wells keep drawdown and densities at p; a producer's total mobility and phase split use kr_a(S_o)/mu_a.  The 7-point
+ * block structure of J and S~ is unchanged.  NULL, or relperm 0 with capillary 0: back to the default, whose results are bit for
+ * bit those of a context that never heard of this call.  Checked, each failure naming the key: relperm in 0..1, capillary in
+ * 0..2, every number finite, Sr_o >= 0, Sr_w >= 0, Sr_o + Sr_w < 1, n_o >= 1, n_w >= 1, kro_max > 0, krw_max > 0, lmbda > 0,
+ * p_ct >= 0, 0 < pc_se_min <= 1; a non-default setting on a single-phase context fails (no saturation).  Callable any time
+ * between two solves, on every slab's context alike (the setting is pointwise); the accumulation of the old state is recomputed.
+ * tp_saturation_info: the setting in force (the defaults below when none) and *active = 1 unless it is the default. */
+typedef struct tp_satfn {
+    int32_t relperm;         /* 0 linear (default), 1 Corey                                    */
+    int32_t capillary;       /* 0 none (default), 1 linear, 2 Brooks-Corey                     */
+    double  Sr_o, Sr_w;      /* residual oil, connate water (0, 0)                             */
+    double  n_o, n_w;        /* Corey exponents (2, 2)                                         */
+    double  kro_max, krw_max; /* end points (1, 1)                                             */
+    double  lmbda;           /* Brooks-Corey pore-size index of p_c (2)                        */
+    double  p_ct;            /* capillary entry pressure, MPa (0)                              */
+    double  pc_se_min;       /* floor of Se_w in the Brooks-Corey p_c (0.05)                   */
+} tp_satfn;
+int tp_set_saturation_functions(tp_ctx *ctx, const tp_satfn *sat);
+int tp_saturation_info(tp_ctx *ctx, tp_satfn *out, int32_t *active);
 
 /* state u, old state u_ (thermalmodel.py:93-94,296), time step (thermalmodel.py:13). */
 int tp_set_state(tp_ctx *ctx, const double *u_host);      /* b*ntot doubles */

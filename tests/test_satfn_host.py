@@ -1,0 +1,286 @@
+"""Saturation functions without a GPU: known values and end behaviour of the host curves
+(PhysicalParameters) and of the numpy reference (tests/satfn_ref.py), the reference against the existing oracle in the
+degenerate Corey case -- whose analytic Jacobian thereby checks the complex-step one --, spec handling, the host refusals, and
+the capillary-gravity column."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases
+from oracle.tpfa import Problem
+from satfn_ref import (DEGENERATE, M1, M2, M3, SatfnProblem, capillary_gravity_column, column_face_fluxes, curves)
+from test_gpu_assembly_edges import TOL, assert_entries
+from thermalporous_amd.physicalparameters import SATFN_DEFAULT, PhysicalParameters, check_satfn, satfn_is_default
+from thermalporous_amd.problem import build_spec
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REL = 1e-15
+
+
+def _params(**kw):
+    p = PhysicalParameters()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _rel(a, b):
+    return abs(a - b) <= REL*abs(b)
+
+
+def _both(sat, S):
+    """(kr_o, kr_w, p_c) of the host class and of the reference, which must agree to rounding."""
+    p = _params(**sat)
+    host = (p.rel_perm_o(S), p.rel_perm_w(S), p.capillary_pressure(S))
+    ref = curves(sat, np.asarray(S, dtype=float))
+    for a, b in zip(host, ref):
+        assert np.abs(np.asarray(a) - np.asarray(b)).max() <= 4e-16*max(1.0, np.abs(np.asarray(b)).max())
+    return host
+
+
+# ---- known values ------------------------------------------------------------------------------------------------------------
+def test_known_values():
+    Sr_o, Sr_w = 0.2, 0.15
+    D = 1.0 - Sr_o - Sr_w
+    S_half_o = Sr_o + 0.5*D                 # Se_o = Se_w = 0.5
+    base = dict(Sr_o=Sr_o, Sr_w=Sr_w)
+    kro, krw, _ = _both(dict(base, relperm="corey", n_o=2.0, n_w=2.0, kro_max=0.9, krw_max=0.4), S_half_o)
+    assert _rel(kro, 0.25*0.9) and _rel(krw, 0.25*0.4)
+    kro, krw, _ = _both(dict(base, relperm="brooks_corey", lmbda=2.0), S_half_o)
+    assert _rel(kro, 0.0625) and _rel(krw, 0.0625)
+    _, _, pc = _both(dict(base, capillary="linear", p_ct=0.05), S_half_o)
+    assert _rel(pc, 0.025)
+    bc = dict(base, capillary="brooks_corey", p_ct=0.01, lmbda=2.0, pc_se_min=0.05)
+    _, _, pc = _both(bc, S_half_o)
+    assert _rel(pc, np.sqrt(2.0)*0.01)
+    S_at = lambda se_w: 1.0 - Sr_w - se_w*D
+    _, _, pc_floor = _both(bc, S_at(0.05))
+    _, _, pc_below = _both(bc, S_at(0.025))
+    assert pc_below == pc_floor and _rel(pc_floor, 0.01*0.05**-0.5)
+
+
+def _slope(sat, S, which):
+    return float(curves(sat, np.array([S + 1e-30j]))[which][0].imag/1e-30)
+
+
+@pytest.mark.parametrize("name", ["M1", "M2", "M3"])
+def test_every_curve_is_flat_at_and_beyond_its_ends(name):
+    sat = {"M1": M1, "M2": M2, "M3": M3}[name]
+    Sr_o, Sr_w = sat["Sr_o"], sat["Sr_w"]
+    D = 1.0 - Sr_o - Sr_w
+    for S in (Sr_o, Sr_o - 0.05, 0.0):                          # oil at and below its residual
+        assert curves(sat, np.array([S]))[0][0] == 0.0 and _slope(sat, S, 0) == 0.0
+        if S < Sr_o:                                             # (water beyond its upper end: at the end point, flat)
+            assert curves(sat, np.array([S]))[1][0] == sat.get("krw_max", 1.0) and _slope(sat, S, 1) == 0.0
+    for S in (1.0 - Sr_w, 1.0 - Sr_w + 0.05, 1.0):              # water at and below connate
+        assert curves(sat, np.array([S]))[1][0] == 0.0 and _slope(sat, S, 1) == 0.0
+        if S > 1.0 - Sr_w:
+            assert curves(sat, np.array([S]))[0][0] == sat.get("kro_max", 1.0) and _slope(sat, S, 0) == 0.0
+    assert _slope(sat, Sr_o + 0.3*D, 0) > 0.0 and _slope(sat, Sr_o + 0.3*D, 1) < 0.0
+    if sat.get("capillary") == "linear":
+        for S in (Sr_o - 0.05, 0.0, 1.0 - Sr_w, 1.0):
+            assert _slope(sat, S, 2) == 0.0
+        assert curves(sat, np.array([Sr_o - 0.05]))[2][0] == 0.0 and curves(sat, np.array([1.0 - Sr_w]))[2][0] == sat["p_ct"]
+        assert _rel(_slope(sat, Sr_o + 0.3*D, 2), sat["p_ct"]/D)
+    if sat.get("capillary") == "brooks_corey":
+        S_floor = 1.0 - Sr_w - sat["pc_se_min"]*D
+        for S in (Sr_o - 0.05, 0.0, S_floor + 1e-3, 1.0):
+            assert _slope(sat, S, 2) == 0.0
+        assert curves(sat, np.array([Sr_o - 0.05]))[2][0] == sat["p_ct"]
+        se = 0.4
+        want = sat["p_ct"]*se**(-1.0/sat["lmbda"] - 1.0)/(sat["lmbda"]*D)
+        assert abs(_slope(sat, 1.0 - Sr_w - se*D, 2) - want) <= 1e-14*want
+
+
+def test_the_host_curves_default_to_the_linear_ones():
+    p = PhysicalParameters()
+    S = np.linspace(-0.1, 1.1, 13)
+    assert np.array_equal(p.rel_perm_o(S), S) and np.array_equal(p.rel_perm_w(S), 1.0 - S)
+    assert np.array_equal(p.capillary_pressure(S), np.zeros_like(S))
+    assert satfn_is_default(p.satfn_dict()) and p.satfn_dict() == SATFN_DEFAULT
+
+
+# ---- the reference against the existing oracle -------------------------------------------------------------------------------
+TIE = [
+    ("2ph_2d_7x5", cases.c3_spe10_2d, dict(Nx=7, Ny=5, nphase=2)),
+    ("2ph_3d_6x5x4", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=2)),
+]
+
+
+def _all(P, u, dt=8640.0):
+    P.set_old(u)
+    P.set_dt(dt)
+    J, Sm = P.jacobian(u, want_schur=True)
+    return P.residual(u), J, Sm
+
+
+@pytest.mark.parametrize("pid,builder,kw", TIE, ids=[c[0] for c in TIE])
+def test_degenerate_corey_reproduces_the_oracle(pid, builder, kw):
+    spec, *_ = builder(**kw)
+    u = cases.perturbed_state(spec, seed=3)
+    Ro, Jo, So = _all(Problem(spec), u)
+    R, J, Sm = _all(SatfnProblem(spec, satfn=DEGENERATE), u)
+    assert_entries(R, J, Sm, Ro, Jo, So, pid)
+
+
+def test_the_models_change_every_residual_field():
+    from graded_ref import field_change
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
+    u = cases.perturbed_state(spec, seed=3)
+    Ro, _, _ = _all(Problem(spec), u)
+    for sat in (M1, M2, M3):
+        P = SatfnProblem(spec, satfn=sat)
+        P.set_old(u)
+        P.set_dt(8640.0)
+        assert min(field_change(P.residual(u), Ro, spec)) > 0.01
+    # a closed box conserves under M2
+    P = SatfnProblem(dict(spec, sources=None), satfn=M2)
+    P.set_old(u)
+    P.set_dt(8640.0)
+    R = P.residual(u)
+    for f in range(3):
+        assert abs(R[f].sum()) < 1e-12*np.abs(R[f]).sum()
+
+
+# ---- spec handling -----------------------------------------------------------------------------------------------------------
+def _box(params, nphase=2):
+    from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo
+    geo = HomogeneousBoxGeo(4, 3, 2, params, Length=20.0, Length_y=15.0, Length_z=4.0)
+    return build_spec(geo, None, params, nphase)
+
+
+def test_spec_carries_satfn_only_when_set():
+    p = PhysicalParameters()
+    assert len(p.as_dict()) == 17 and "relperm" not in p.as_dict()
+    assert "satfn" not in _box(p) and "satfn" not in _box(p, nphase=1)
+    p.Sr_o = 0.3                                       # numbers alone do not switch the model on
+    assert "satfn" not in _box(p)
+    q = _params(**M2)
+    spec = _box(q)
+    assert spec["satfn"] == q.satfn_dict() == check_satfn(M2)
+    assert spec["satfn"]["relperm"] == "brooks_corey" and spec["satfn"]["capillary"] == "linear" and spec["satfn"]["p_ct"] == 0.05
+    assert len(q.as_dict()) == 17 and spec["prm"] == q.as_dict()
+    # the reference reads the same dict
+    P = SatfnProblem(dict(spec, sources=None))
+    assert {k: P.sat[k] for k in spec["satfn"]} == spec["satfn"]
+    r = _params(capillary="linear", p_ct=0.02)         # capillary pressure alone, linear curves
+    assert _box(r)["satfn"]["relperm"] == "linear"
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------
+def test_single_phase_refuses_saturation_functions():
+    with pytest.raises(NotImplementedError, match="single-phase"):
+        _box(_params(**M1), nphase=1)
+    with pytest.raises(NotImplementedError, match="capillary = 'linear'"):
+        _box(_params(capillary="linear", p_ct=0.01), nphase=1)
+
+
+BAD = [
+    ("relperm", dict(relperm="stone")), ("capillary", dict(capillary="leverett")),
+    ("Sr_o", dict(Sr_o=-0.1)), ("Sr_w", dict(Sr_w=-0.1)), ("Sr_o \\+ Sr_w", dict(Sr_o=0.6, Sr_w=0.4)),
+    ("n_o", dict(n_o=0.5)), ("n_w", dict(n_w=0.99)), ("kro_max", dict(kro_max=0.0)), ("krw_max", dict(krw_max=-1.0)),
+    ("lmbda", dict(lmbda=0.0)), ("lmbda", dict(lmbda=-2.0)), ("p_ct", dict(p_ct=-0.01)),
+    ("pc_se_min", dict(pc_se_min=0.0)), ("pc_se_min", dict(pc_se_min=1.5)),
+    ("n_o", dict(n_o=float("nan"))), ("p_ct", dict(p_ct=float("inf"))), ("Sr_w", dict(Sr_w="0.1")),
+    ("unknown key", dict(Sr_g=0.1)),
+]
+
+
+@pytest.mark.parametrize("key,bad", BAD, ids=["%s_%d" % (re.sub(r"\W+", "_", b[0]), i) for i, b in enumerate(BAD)])
+def test_out_of_range_parameters_are_refused_by_name(key, bad):
+    with pytest.raises(ValueError, match=key):
+        check_satfn({**M3, **bad})
+    if "Sr_g" in bad:
+        return
+    p = _params(**{**M3, **bad})
+    with pytest.raises(ValueError, match=key):
+        _box(p)
+    with pytest.raises(ValueError, match=key):
+        p.rel_perm_o(0.5)
+
+
+def test_exports_are_declared():
+    from thermalporous_amd import engine
+    hdr = open(os.path.join(ROOT, "include", "thermalporous_hip.h")).read()
+    assert re.search(r"\bint tp_set_saturation_functions\(tp_ctx \*ctx, const tp_satfn \*sat\);", hdr)
+    assert re.search(r"\bint tp_saturation_info\(tp_ctx \*ctx, tp_satfn \*out, int32_t \*active\);", hdr)
+    assert {"tp_set_saturation_functions", "tp_saturation_info"} <= set(engine.API_SYMBOLS)
+    assert hasattr(engine.HipEngine, "set_saturation_functions") and hasattr(engine.HipEngine, "saturation_info")
+    # the ctypes struct follows the header's
+    body = re.search(r"typedef struct tp_satfn \{(.*?)\} tp_satfn;", hdr, flags=re.S).group(1)
+    names = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert names == [f[0] for f in engine.tp_satfn._fields_]
+
+
+def _wells(p):
+    from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo
+    from thermalporous_amd.wellcase import WellCase
+    p.rate, p.S_o, p.T_inj = 2e-4, 0.9, 373.15
+    geo = HomogeneousBoxGeo(4, 5, 4, p, Length=8.0, Length_y=10.0, Length_z=4.0)
+    return geo, WellCase(p, geo, prod_points=[[2.0, 5.0, 0.3]], inj_points=[[6.0, 5.0, 3.7]])
+
+
+def test_other_engines_refuse_a_satfn_spec():
+    """A model whose engine factory does not declare saturation functions would run the linear curves: refused by name."""
+    from oracle.engine import OracleEngine
+    from thermalporous_amd.twophase import TwoPhase
+    p = _params(**M1)
+    geo, case = _wells(p)
+    with pytest.raises(NotImplementedError, match="saturation functions.*OracleEngine"):
+        TwoPhase(geo, case, p, filename=None, verbosity=False, _engine_factory=OracleEngine)
+
+
+def test_single_phase_model_refuses():
+    from oracle.engine import OracleEngine
+    from thermalporous_amd.singlephase import SinglePhase
+    p = _params(**M2)
+    geo, case = _wells(p)
+    with pytest.raises(NotImplementedError, match="single-phase"):
+        SinglePhase(geo, case, p, filename=None, verbosity=False, _engine_factory=OracleEngine)
+
+
+def test_the_time_loop_runs_the_model_on_the_reference():
+    """TwoPhase.solve() through the numpy reference as its engine: the model reaches the engine through spec["satfn"], the run
+    ends without a failed solve and S_o stays in [0, 1]."""
+    from satfn_ref import satfn_oracle
+    from thermalporous_amd.twophase import TwoPhase
+    factory = lambda spec, opts: satfn_oracle(spec, opts)
+    factory.supports_satfn = True
+    p = _params(**M1)
+    geo, case = _wells(p)
+    m = TwoPhase(geo, case, p, end=0.002, maxdt=0.001, small_dt_start=False, solver_parameters="pc_cptr", filename=None,
+                 verbosity=False, _engine_factory=factory)
+    assert m.spec["satfn"]["relperm"] == "corey" and isinstance(m.engine.prob, SatfnProblem)
+    m.solve()
+    S = m.u._read()[2]
+    assert S.min() >= 0.0 and S.max() <= 1.0 and S.min() < 0.9
+
+
+# ---- the capillary-gravity column --------------------------------------------------------------------------------------------
+def test_capillary_gravity_column_is_an_equilibrium_of_the_reference():
+    spec, u, scale = capillary_gravity_column()
+    sat = spec["satfn"]
+    assert tuple(spec["n"]) == (8, 1, 1) and spec["h"][0] == 2.5 and spec["prm"]["API"] == 40.0
+    assert sat["capillary"] == "linear" and sat["p_ct"] == 0.05 and sat["Sr_o"] == 0.2 and sat["Sr_w"] == 0.15
+    D = 1.0 - sat["Sr_o"] - sat["Sr_w"]
+    S = u[2].reshape(-1)
+    Se_w = ((1.0 - sat["Sr_w"]) - S)/D
+    print("S_o up the column:", S, "Se_w:", Se_w)
+    assert abs(Se_w[0] - 0.9) < 1e-15 and np.all((Se_w > 0.0) & (Se_w < 1.0))
+    assert np.all(np.diff(S) > 0.0) and S[-1] - S[0] > 0.2
+    P = SatfnProblem(spec)
+    P.set_old(u)
+    P.set_dt(1e10)
+    R = P.residual(u)
+    F = column_face_fluxes(P, R)
+    print("face fluxes / (T^K L rho g dz): water", F[0]/scale[0], "oil", F[1]/scale[1])
+    assert np.all(np.abs(F) < 1e-8*scale) and np.all(scale > 0.0)
+    assert np.abs(R[1]).max() == 0.0 or np.abs(R[1]).max() < 1e-8*np.abs(u[1]).max()*scale.max()*spec["prm"]["c_v_w"]
+    # without the capillary pressure the same state is no equilibrium
+    Q = SatfnProblem(spec, satfn=dict(sat, capillary=None))
+    Q.set_old(u)
+    Q.set_dt(1e10)
+    F0 = column_face_fluxes(Q, Q.residual(u))
+    assert np.abs(F0[0]/scale[0]).max() > 0.05

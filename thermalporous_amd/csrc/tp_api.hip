@@ -547,6 +547,20 @@ int tp_spacing_info(tp_ctx *c, int32_t *graded, double *hmin, double *hmax) {
     TP_API_END
 }
 
+int tp_set_saturation_functions(tp_ctx *c, const tp_satfn *sat) {
+    TP_API_BEGIN
+    satfn_set(c, sat);
+    TP_API_END
+}
+
+int tp_saturation_info(tp_ctx *c, tp_satfn *out, int32_t *active) {
+    TP_API_BEGIN
+    TP_REQUIRE(c && out && active, "null argument");
+    *out = c->satfn ? c->sat_host : satfn_defaults();
+    *active = c->satfn ? 1 : 0;
+    TP_API_END
+}
+
 int tp_set_state(tp_ctx *c, const double *u_host) {
     TP_API_BEGIN
     TP_REQUIRE(c && u_host, "null argument");

@@ -13,7 +13,8 @@
 // from HBM once), forms the six face fluxes with their derivatives w.r.t. both sides, and writes
 // its residual entries, its diagonal block and its six off-diagonal blocks -- every Jacobian
 // plane is written exactly once, fully coalesced, no atomics.  HBM-bound: ~616 B per cell
-// (SURVEY.md 8d); the 3 exp + 1 pow per closure evaluation stay under the memory time.
+// (SURVEY.md 8d); the 3 exp + 1 pow per closure evaluation stay under the memory time.  The SATFN instantiations
+// (tp_set_saturation_functions) add up to three pow per evaluation: measured in DESIGN.md 4.1.3.
 #include "tp_common.hpp"
 #include "tp_closures.hpp"
 #include <cstdlib>
@@ -33,11 +34,14 @@ struct Props {
     double Lw[4];
     double kT, kT_S;
     double mo, mw;
+    double pc, pc_S, rw_S;        // SATFN only: p_c(S), its slope, and d rho_w / dS = -rw_p pc_S of rho_w(p - p_c(S), T)
 };
 
-template <int NPH>
+// SATFN (tp_set_saturation_functions): kr_o, kr_w and p_c of `sat` instead of S, 1 - S and 0; water's density
+// and its mobility at p_w = p - p_c(S).  The kr slopes and rw_S go into Lo[3] and Lw[3].  The false branch is the code as it was.
+template <int NPH, bool SATFN = false>
 __device__ __forceinline__ Props<NPH> eval_props(double p, double T, double S, double phi, double kTs,
-                                                 const DevPrm &q) {
+                                                 const DevPrm &q, const DevSat *sat = nullptr) {
     Props<NPH> r;
     r.p = p; r.T = T; r.S = S;
     oil_rho_factors(p, T, q, r.rf1, r.rf2);
@@ -45,7 +49,27 @@ __device__ __forceinline__ Props<NPH> eval_props(double p, double T, double S, d
     double mo, mo_T;
     oil_mu(T, q, mo, mo_T);
     r.mo = mo;
-    if (NPH == 2) {
+    if constexpr (SATFN) {
+        static_assert(NPH == 2, "saturation functions need a saturation");
+        const Dual1 Sd{S, 1.0};
+        const Dual1 kro = kr_o_t(Sd, *sat), krw = kr_w_t(Sd, *sat), pc = pc_t(Sd, *sat);
+        r.pc = pc.v; r.pc_S = pc.d;
+        water_rho(p - pc.v, T, r.rw, r.rw_p, r.rw_T);
+        r.rw_S = -r.rw_p * pc.d;
+        double mw, mw_T;
+        water_mu(T, mw, mw_T);
+        r.mw = mw;
+        r.Lw[0] = krw.v * r.rw / mw;
+        r.Lw[1] = krw.v * r.rw_p / mw;
+        r.Lw[2] = krw.v * (r.rw_T / mw - r.rw * mw_T / (mw * mw));
+        r.Lw[3] = krw.d * r.rw / mw + krw.v * r.rw_S / mw;
+        r.Lo[0] = kro.v * r.ro / mo;
+        r.Lo[1] = kro.v * r.ro_p / mo;
+        r.Lo[2] = kro.v * (r.ro_T / mo - r.ro * mo_T / (mo * mo));
+        r.Lo[3] = kro.d * r.ro / mo;
+        r.kT = phi * (S * q.ko + (1.0 - S) * q.kw) + (1.0 - phi) * q.kr;
+        r.kT_S = phi * (q.ko - q.kw);
+    } else if (NPH == 2) {
         water_rho(p, T, r.rw, r.rw_p, r.rw_T);
         double mw, mw_T;
         water_mu(T, mw, mw_T);
@@ -80,7 +104,9 @@ __device__ __forceinline__ Props<NPH> eval_props(double p, double T, double S, d
 // GRADED (tp_set_spacing): the two cells have widths of their own, so the harmonic mean of kT weighs each side by
 // its half distance over the face area: Ga carries c_P = d_P/|e| and cM carries c_M = d_M/|e|; gam = g (d_P + d_M)/2 and TK come
 // from the caller as before.  The false branch is the uniform code.
-template <int NPH, bool SCHUR, bool GRADED = false>
+// SATFN (tp_set_saturation_functions): water is driven by p_w = p - p_c(S) of either side, and its Phi depends on
+// both saturations through p_c and through rho_w(p_w, T): dPhi/dS+ = -pc_S+ - gam rw_S+, dPhi/dS- = +pc_S- - gam rw_S-.
+template <int NPH, bool SCHUR, bool GRADED = false, bool SATFN = false>
 __device__ __forceinline__ void face_flux(const Props<NPH> &P, const Props<NPH> &M, double TK, double gam,
                                           double Ga, const DevPrm &q, double *f, double (*dP)[NPH + 1],
                                           double (*dM)[NPH + 1], double &sP, double &sM, double cM = 0.0) {
@@ -94,13 +120,20 @@ __device__ __forceinline__ void face_flux(const Props<NPH> &P, const Props<NPH> 
     sP = 0.0; sM = 0.0;
     auto phase = [&](double ce, double c0, bool to2, double rP, double rP_p, double rP_T, double rM,
                      double rM_p, double rM_T, const double *LP, const double *LM) {
-        const double Phi = P.p - M.p - gam * (rP + rM);
+        double Phi, dsP = 0.0, dsM = 0.0;               // dsP, dsM: dPhi/dS of either side
+        if constexpr (SATFN) {
+            if (!to2) {                                 // (two phases: water is the phase that has no row of its own)
+                Phi = (P.p - P.pc) - (M.p - M.pc) - gam * (rP + rM);
+                dsP = -P.pc_S - gam * P.rw_S;
+                dsM = M.pc_S - gam * M.rw_S;
+            } else Phi = P.p - M.p - gam * (rP + rM);
+        } else Phi = P.p - M.p - gam * (rP + rM);
         const bool up = Phi > 0.0;                      // gt(flow, 0): strict, ties -> '-' side
         const double L = up ? LP[0] : LM[0];
         const double Tu = up ? P.T : M.T;
         const double F = TK * L * Phi;
-        const double dPhiP[3] = {1.0 - gam * rP_p, -gam * rP_T, 0.0};
-        const double dPhiM[3] = {-1.0 - gam * rM_p, -gam * rM_T, 0.0};
+        const double dPhiP[3] = {1.0 - gam * rP_p, -gam * rP_T, dsP};
+        const double dPhiM[3] = {-1.0 - gam * rM_p, -gam * rM_T, dsM};
         f[0] += q.w0 * c0 * F;
         f[1] += ce * Tu * F;
         if (to2) f[B - 1] += q.w2 * F;
@@ -181,10 +214,22 @@ struct AsmArgsG {
     AsmArgs a;
     Spacing sp;
 };
-template <bool GRADED> struct AsmSel { using type = AsmArgs; };
-template <> struct AsmSel<true> { using type = AsmArgsG; };
+// Saturation functions (tp_set_saturation_functions): what the SATFN instantiations take beside the arguments of their twin
+template <class A> struct WithSat {
+    A a;
+    DevSat sat;
+};
+template <bool GRADED, bool SATFN = false> struct AsmSel { using type = AsmArgs; };
+template <> struct AsmSel<true, false> { using type = AsmArgsG; };
+template <> struct AsmSel<false, true> { using type = WithSat<AsmArgs>; };
+template <> struct AsmSel<true, true> { using type = WithSat<AsmArgsG>; };
 __device__ __forceinline__ const AsmArgs &asm_base(const AsmArgs &a) { return a; }
 __device__ __forceinline__ const AsmArgs &asm_base(const AsmArgsG &a) { return a.a; }
+// the twin's arguments inside a SATFN instantiation's (themselves otherwise), and the curves (none otherwise)
+template <class A> __device__ __forceinline__ A &sat_inner(A &a) { return a; }
+template <class A> __device__ __forceinline__ A &sat_inner(WithSat<A> &w) { return w.a; }
+template <class A> __device__ __forceinline__ const DevSat *sat_of(const A &) { return nullptr; }
+template <class A> __device__ __forceinline__ const DevSat *sat_of(const WithSat<A> &w) { return &w.sat; }
 
 // Geometry of one graded cell: its widths, its volume and 1/|e_a| of its faces.  The area of a face along a is the product of the
 // other two widths, so both cells of a face form the same c_P, c_M and gam from the same numbers: the face's flux has the same
@@ -202,9 +247,11 @@ __device__ __forceinline__ CellGeom cell_geom(const Spacing &sp, int i0, int i1,
     return m;
 }
 
-template <int NPH, bool JAC, bool SCHUR, bool GRADED = false>
-__global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type aa) {
+template <int NPH, bool JAC, bool SCHUR, bool GRADED = false, bool SATFN = false>
+__global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED, SATFN>::type aa_) {
     constexpr int B = NPH + 1;
+    auto &aa = sat_inner(aa_);
+    const DevSat *sat = sat_of(aa_);
     const AsmArgs &a = asm_base(aa);
     const long tid = xcd_tid();
     const GridDev &g = a.g;
@@ -218,7 +265,7 @@ __global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type 
     const DevPrm &q = a.q;
 
     const double *up_ = a.u, *uT_ = a.u + nt, *uS_ = a.u + 2 * nt;
-    const Props<NPH> me = eval_props<NPH>(up_[c], uT_[c], NPH == 2 ? uS_[c] : 0.0, a.phi[c], a.kTs[c], q);
+    const Props<NPH> me = eval_props<NPH, SATFN>(up_[c], uT_[c], NPH == 2 ? uS_[c] : 0.0, a.phi[c], a.kTs[c], q, sat);
 
     double R[B], Jd[B][B];
     double sd = 0.0;
@@ -235,7 +282,8 @@ __global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type 
         if (NPH == 2) {
             const double S = me.S, T = me.T;
             const double Mw = phi * me.rw * (1.0 - S), Mo = phi * me.ro * S;
-            const double dMw[3] = {phi * me.rw_p * (1.0 - S), phi * me.rw_T * (1.0 - S), -phi * me.rw};
+            double dMw[3] = {phi * me.rw_p * (1.0 - S), phi * me.rw_T * (1.0 - S), -phi * me.rw};
+            if constexpr (SATFN) dMw[2] += phi * me.rw_S * (1.0 - S);      // rho_w(p - p_c(S), T) follows S
             const double dMo[3] = {phi * me.ro_p * S, phi * me.ro_T * S, phi * me.ro};
             const double e0 = q.c_v_w * Mw + q.c_v_o * Mo;
             R[0] = q.w0 * (e0 - a.acc_old[c]) * a.Vdt;
@@ -279,7 +327,7 @@ __global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type 
             if (exists) {
                 const long nb = dir ? c + stride[ax] : c - stride[ax];
                 const Props<NPH> ot =
-                    eval_props<NPH>(up_[nb], uT_[nb], NPH == 2 ? uS_[nb] : 0.0, a.phi[nb], a.kTs[nb], q);
+                    eval_props<NPH, SATFN>(up_[nb], uT_[nb], NPH == 2 ? uS_[nb] : 0.0, a.phi[nb], a.kTs[nb], q, sat);
                 // graded: gam and the half distances over the area, c_me and c_nb, of this face
                 double gam = 0.0, c_me = 0.0, c_nb = 0.0;
                 if constexpr (GRADED) {
@@ -290,9 +338,9 @@ __global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type 
                 }
                 if (dir) {
                     if constexpr (GRADED)
-                        face_flux<NPH, SCHUR, true>(me, ot, a.TK[ax][c], gam, c_me, q, f, dP, dM, sP, sM, c_nb);
+                        face_flux<NPH, SCHUR, true, SATFN>(me, ot, a.TK[ax][c], gam, c_me, q, f, dP, dM, sP, sM, c_nb);
                     else
-                        face_flux<NPH, SCHUR>(me, ot, a.TK[ax][c], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
+                        face_flux<NPH, SCHUR, false, SATFN>(me, ot, a.TK[ax][c], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
 #pragma unroll
                     for (int r = 0; r < B; ++r) {
                         R[r] += f[r];
@@ -302,9 +350,9 @@ __global__ __launch_bounds__(256) void k_assemble(typename AsmSel<GRADED>::type 
                     if (SCHUR) sd += sP;
                 } else {
                     if constexpr (GRADED)
-                        face_flux<NPH, SCHUR, true>(ot, me, a.TK[ax][nb], gam, c_nb, q, f, dP, dM, sP, sM, c_me);
+                        face_flux<NPH, SCHUR, true, SATFN>(ot, me, a.TK[ax][nb], gam, c_nb, q, f, dP, dM, sP, sM, c_me);
                     else
-                        face_flux<NPH, SCHUR>(ot, me, a.TK[ax][nb], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
+                        face_flux<NPH, SCHUR, false, SATFN>(ot, me, a.TK[ax][nb], a.gam[ax], a.Ga[ax], q, f, dP, dM, sP, sM);
 #pragma unroll
                     for (int r = 0; r < B; ++r) {
                         R[r] -= f[r];
@@ -528,14 +576,19 @@ struct BcArgsG {
     BcArgs s;
     Spacing sp;
 };
-template <bool GRADED> struct BcSel { using type = BcArgs; };
-template <> struct BcSel<true> { using type = BcArgsG; };
+template <bool GRADED, bool SATFN = false> struct BcSel { using type = BcArgs; };
+template <> struct BcSel<true, false> { using type = BcArgsG; };
+template <> struct BcSel<false, true> { using type = WithSat<BcArgs>; };
+template <> struct BcSel<true, true> { using type = WithSat<BcArgsG>; };
 __device__ __forceinline__ const BcArgs &bc_base(const BcArgs &s) { return s; }
 __device__ __forceinline__ const BcArgs &bc_base(const BcArgsG &s) { return s.s; }
 
-template <int NPH, bool JAC, bool SCHUR, bool GRADED = false>
-__global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED>::type ss) {
+// SATFN: the cell and the ghost state (p_b, T_b, S_b) go through the same curves
+template <int NPH, bool JAC, bool SCHUR, bool GRADED = false, bool SATFN = false>
+__global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED, SATFN>::type ss_) {
     constexpr int B = NPH + 1;
+    auto &ss = sat_inner(ss_);
+    const DevSat *sat = sat_of(ss_);
     const BcArgs &s = bc_base(ss);
     const int t = blockIdx.x * TP_BLOCK + threadIdx.x;
     if (t >= s.ncells) return;
@@ -550,7 +603,7 @@ __global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED>::typ
     const int i0 = rem - i1 * g.n0;
     const long nt = g.ntot;
     const double phi = a.phi[c], kTs = a.kTs[c];
-    const Props<NPH> me = eval_props<NPH>(a.u[c], a.u[nt + c], NPH == 2 ? a.u[2 * nt + c] : 0.0, phi, kTs, q);
+    const Props<NPH> me = eval_props<NPH, SATFN>(a.u[c], a.u[nt + c], NPH == 2 ? a.u[2 * nt + c] : 0.0, phi, kTs, q, sat);
     double R[B], Jd[B][B], sd = 0.0;
 #pragma unroll
     for (int r = 0; r < B; ++r) {
@@ -567,7 +620,7 @@ __global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED>::typ
         const long nf = s.nf[side];
         const long f_ = bc_face(g, ax, i0, i1, i2);
         const double *v = s.val[side];
-        const Props<NPH> gh = eval_props<NPH>(v[f_], v[nf + f_], NPH == 2 ? v[2 * nf + f_] : 0.0, phi, kTs, q);
+        const Props<NPH> gh = eval_props<NPH, SATFN>(v[f_], v[nf + f_], NPH == 2 ? v[2 * nf + f_] : 0.0, phi, kTs, q, sat);
         const double TK = s.tk[side][f_];
         double gam, Ga;
         if constexpr (GRADED) {
@@ -582,8 +635,8 @@ __global__ __launch_bounds__(256) void k_assemble_bc(typename BcSel<GRADED>::typ
             Ga = 2.0 * a.Ga[ax];
         }
         double f[B], dP[B][B], dM[B][B], sP = 0.0, sM = 0.0;
-        if (dir) face_flux<NPH, SCHUR, GRADED>(me, gh, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
-        else     face_flux<NPH, SCHUR, GRADED>(gh, me, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
+        if (dir) face_flux<NPH, SCHUR, GRADED, SATFN>(me, gh, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
+        else     face_flux<NPH, SCHUR, GRADED, SATFN>(gh, me, TK, gam, Ga, q, f, dP, dM, sP, sM, Ga);
         const double sg = dir ? 1.0 : -1.0;
 #pragma unroll
         for (int r = 0; r < B; ++r) {
@@ -643,8 +696,10 @@ __global__ void k_bc_trans_g(GridDev g, const double *K, int side, int open, con
 }
 
 // ---- accumulation of the old state (once per time step) -------------------------------------------
-template <int NPH>
-__global__ void k_accum_old(GridDev g, DevPrm q, const double *u, const double *phi_, double *acc) {
+// SATFN: water's density at p_old - p_c(S_old), as the accumulation of the new state takes it
+template <int NPH, bool SATFN>
+__device__ __forceinline__ void accum_old_cell(const GridDev &g, const DevPrm &q, const double *u, const double *phi_, double *acc,
+                                               const DevSat *sat) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= g.nown) return;
     const long c = g.np + tid, nt = g.ntot;
@@ -656,7 +711,8 @@ __global__ void k_accum_old(GridDev g, DevPrm q, const double *u, const double *
     if (NPH == 2) {
         const double S = u[2 * nt + c];
         double rw, rw_p, rw_T;
-        water_rho(p, T, rw, rw_p, rw_T);
+        if constexpr (SATFN) water_rho(p - pc_t(Dual1{S, 1.0}, *sat).v, T, rw, rw_p, rw_T);
+        else water_rho(p, T, rw, rw_p, rw_T);
         const double Mw = phi * rw * (1.0 - S), Mo = phi * ro * S;
         const double e0 = q.c_v_w * Mw + q.c_v_o * Mo;
         acc[c] = e0;
@@ -667,6 +723,13 @@ __global__ void k_accum_old(GridDev g, DevPrm q, const double *u, const double *
         acc[c] = Mo;
         acc[nt + c] = q.c_v_o * Mo * T + rock * T;
     }
+}
+template <int NPH>
+__global__ void k_accum_old(GridDev g, DevPrm q, const double *u, const double *phi_, double *acc) {
+    accum_old_cell<NPH, false>(g, q, u, phi_, acc, nullptr);
+}
+__global__ void k_accum_old_sat(GridDev g, DevPrm q, const double *u, const double *phi_, double *acc, DevSat sat) {
+    accum_old_cell<2, true>(g, q, u, phi_, acc, &sat);
 }
 
 // ---- face transmissibilities T^K_f = H(K)|e|/Delta_h (singlephase.py:98-103) -----------------------
@@ -730,9 +793,11 @@ __global__ void k_trans_halo(GridDev g, const double *K, double geom, double *TK
 // ---- wells / heaters: tiny kernel, one thread per group of entries sharing a cell ------------------
 // Rate laws: wellcase.py:171-266; contributions to F: singlephase.py:151-165, twophase.py:212-235;
 // to S~: preconditioners.py:102-108,269-276.  Derivatives by forward-mode duals (3 partials).
-template <int NPH>
+// SATFN (tp_set_saturation_functions): the producers' total mobility and phase split use kr_a(S_o)/mu_a of the curves; drawdown
+// and densities stay at p, injectors inject water only and do not change.
+template <int NPH, bool SATFN = false>
 __device__ void source_eval(const tp_source &e, const DevPrm &q, Dual3 p, Dual3 T, Dual3 S, Dual3 *out,
-                            double *rates, double &schur_diag) {
+                            double *rates, double &schur_diag, const DevSat *sat = nullptr) {
     constexpr int B = NPH + 1;
     for (int r = 0; r < B; ++r) out[r] = Dual3(0.0);
     rates[0] = rates[1] = rates[2] = 0.0;
@@ -769,10 +834,13 @@ __device__ void source_eval(const tp_source &e, const DevPrm &q, Dual3 p, Dual3 
         const Dual3 mw = water_mu_t(T);
         const Dual3 rw = water_rho_t(p, T);
         if (e.kind == 0) {
-            const Dual3 lam_t = S / mo + (Dual3(1.0) - S) / mw;
+            Dual3 lam_o, lam_w;
+            if constexpr (SATFN) { lam_o = kr_o_t(S, *sat) / mo; lam_w = kr_w_t(S, *sat) / mw; }
+            else { lam_o = S / mo; lam_w = (Dual3(1.0) - S) / mw; }
+            const Dual3 lam_t = lam_o + lam_w;
             const Dual3 rate = cap(dd * lam_t * e.WI);
-            const Dual3 qw = (Dual3(1.0) - S) / mw / lam_t * rate;
-            const Dual3 qo = S / mo / lam_t * rate;
+            const Dual3 qw = lam_w / lam_t * rate;
+            const Dual3 qo = lam_o / lam_t * rate;
             rates[0] = rate.v; rates[1] = qw.v; rates[2] = qo.v;
             out[0] = (rw * qw * q.c_v_w + ro * qo * q.c_v_o) * (q.w0 * e.wt);
             out[2] = ro * qo * (q.w2 * e.wt);
@@ -788,9 +856,10 @@ __device__ void source_eval(const tp_source &e, const DevPrm &q, Dual3 p, Dual3 
     }
 }
 
-template <int NPH>
-__global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *start, int ngroups,
-                          const double *u, double *R, double *J, double *Sm, double *rates, int nsrc) {
+template <int NPH, bool SATFN>
+__device__ __forceinline__ void sources_group(const GridDev &g, const DevPrm &q, const tp_source *src, const int *start, int ngroups,
+                                              const double *u, double *R, double *J, double *Sm, double *rates, int nsrc,
+                                              const DevSat *sat) {
     constexpr int B = NPH + 1;
     const int gi = blockIdx.x * blockDim.x + threadIdx.x;
     if (gi >= ngroups) return;
@@ -800,7 +869,7 @@ __global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *
     for (int k = start[gi]; k < start[gi + 1]; ++k) {
         Dual3 out[B];
         double rt[3], sd;
-        source_eval<NPH>(src[k], q, p, T, S, out, rt, sd);
+        source_eval<NPH, SATFN>(src[k], q, p, T, S, out, rt, sd, sat);
         if (rates) { rates[k] = rt[0]; rates[nsrc + k] = rt[1]; rates[2 * nsrc + k] = rt[2]; }
         if (R)
             for (int r = 0; r < B; ++r) R[(long)r * nt + c] -= out[r].v;
@@ -809,6 +878,15 @@ __global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *
                 for (int k2 = 0; k2 < B; ++k2) J[((long)r * B + k2) * nt + c] -= out[r].d[k2];
         if (Sm) Sm[c] -= sd;
     }
+}
+template <int NPH>
+__global__ void k_sources(GridDev g, DevPrm q, const tp_source *src, const int *start, int ngroups,
+                          const double *u, double *R, double *J, double *Sm, double *rates, int nsrc) {
+    sources_group<NPH, false>(g, q, src, start, ngroups, u, R, J, Sm, rates, nsrc, nullptr);
+}
+__global__ void k_sources_sat(GridDev g, DevPrm q, const tp_source *src, const int *start, int ngroups,
+                              const double *u, double *R, double *J, double *Sm, double *rates, int nsrc, DevSat sat) {
+    sources_group<2, true>(g, q, src, start, ngroups, u, R, J, Sm, rates, nsrc, &sat);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -837,7 +915,10 @@ void compute_trans(tp_ctx *c) {
 
 void accum_old(tp_ctx *c) {
     const GridDev &g = c->g;
-    if (c->nph == 2)
+    if (c->satfn)
+        hipLaunchKernelGGL(k_accum_old_sat, grid_for(g.nown), dim3(256), 0, c->stream, g, c->dprm, c->u_old.p, c->phi.p,
+                           c->acc_old.p, c->dsat);
+    else if (c->nph == 2)
         hipLaunchKernelGGL(k_accum_old<2>, grid_for(g.nown), dim3(256), 0, c->stream, g, c->dprm, c->u_old.p,
                            c->phi.p, c->acc_old.p);
     else
@@ -869,6 +950,64 @@ static Spacing spacing_args(tp_ctx *c) {
     sp.g4 = 0.25 * c->prm.g;
     sp.gaxis = c->grid.gaxis;
     return sp;
+}
+
+// ---- saturation functions: host side (tp_set_saturation_functions) -----------------------------------------------------------
+tp_satfn satfn_defaults() {
+    tp_satfn d;
+    d.relperm = 0; d.capillary = 0;
+    d.Sr_o = 0.0; d.Sr_w = 0.0; d.n_o = 2.0; d.n_w = 2.0; d.kro_max = 1.0; d.krw_max = 1.0;
+    d.lmbda = 2.0; d.p_ct = 0.0; d.pc_se_min = 0.05;
+    return d;
+}
+
+void satfn_set(tp_ctx *c, const tp_satfn *sat) {
+    TP_REQUIRE(c, "null argument");
+    const char *fn = "tp_set_saturation_functions: ";
+    bool on = false;
+    if (sat) {
+        const tp_satfn &t = *sat;
+        if (t.relperm < 0 || t.relperm > 1) throw Error(std::string(fn) + "relperm = " + std::to_string(t.relperm) + ": 0 (linear) or 1 (Corey)");
+        if (t.capillary < 0 || t.capillary > 2)
+            throw Error(std::string(fn) + "capillary = " + std::to_string(t.capillary) + ": 0 (none), 1 (linear) or 2 (Brooks-Corey)");
+        const struct { const char *key; double v; } num[] = {{"Sr_o", t.Sr_o}, {"Sr_w", t.Sr_w}, {"n_o", t.n_o}, {"n_w", t.n_w},
+            {"kro_max", t.kro_max}, {"krw_max", t.krw_max}, {"lmbda", t.lmbda}, {"p_ct", t.p_ct}, {"pc_se_min", t.pc_se_min}};
+        for (const auto &e : num)
+            if (!std::isfinite(e.v)) throw Error(std::string(fn) + e.key + " is not a finite number");
+        auto bad = [&](const char *key, double v, const char *want) {
+            throw Error(std::string(fn) + key + " = " + std::to_string(v) + ": " + want);
+        };
+        if (t.Sr_o < 0.0) bad("Sr_o", t.Sr_o, "the residual oil saturation, >= 0");
+        if (t.Sr_w < 0.0) bad("Sr_w", t.Sr_w, "the connate water saturation, >= 0");
+        if (!(t.Sr_o + t.Sr_w < 1.0)) bad("Sr_o + Sr_w", t.Sr_o + t.Sr_w, "the residual saturations must leave a mobile range, < 1");
+        if (t.n_o < 1.0) bad("n_o", t.n_o, "a Corey exponent, >= 1");
+        if (t.n_w < 1.0) bad("n_w", t.n_w, "a Corey exponent, >= 1");
+        if (!(t.kro_max > 0.0)) bad("kro_max", t.kro_max, "an end-point relative permeability, > 0");
+        if (!(t.krw_max > 0.0)) bad("krw_max", t.krw_max, "an end-point relative permeability, > 0");
+        if (!(t.lmbda > 0.0)) bad("lmbda", t.lmbda, "the Brooks-Corey pore-size index, > 0");
+        if (t.p_ct < 0.0) bad("p_ct", t.p_ct, "the capillary entry pressure in MPa, >= 0");
+        if (!(t.pc_se_min > 0.0 && t.pc_se_min <= 1.0)) bad("pc_se_min", t.pc_se_min, "the floor of Se_w in the Brooks-Corey p_c, in (0, 1]");
+        on = t.relperm != 0 || t.capillary != 0;
+        if (on && c->nph != 2)
+            throw Error(std::string(fn) + "relperm = " + std::to_string(t.relperm) + ", capillary = " + std::to_string(t.capillary) +
+                        " on a single-phase context: saturation functions need a saturation, which only nphase = 2 has");
+    }
+    TP_HIP(hipStreamSynchronize(c->stream));       // nothing in flight reads what is replaced
+    c->satfn = on;
+    c->sat_host = on ? *sat : satfn_defaults();
+    if (on) {
+        const tp_satfn &t = *sat;
+        DevSat &d = c->dsat;
+        d.Sr_o = t.Sr_o; d.So_max = 1.0 - t.Sr_w; d.D = 1.0 - t.Sr_o - t.Sr_w; d.invD = 1.0 / d.D;
+        d.n_o = t.n_o; d.n_w = t.n_w; d.kro_max = t.kro_max; d.krw_max = t.krw_max;
+        d.p_ct = t.p_ct; d.inv_lmbda = 1.0 / t.lmbda; d.pc_se_min = t.pc_se_min;
+        d.pc_max = t.p_ct * std::pow(t.pc_se_min, -1.0 / t.lmbda);
+        d.kr_kind = t.relperm; d.pc_kind = t.capillary;
+    }
+    // the old state's accumulation holds water's density at the old setting's p_w: recomputed here, before any assembly
+    if (c->have_old) accum_old(c);
+    c->jac_ready = false;
+    c->pc_ready = false;
 }
 
 // ---- graded grid: host side (tp_set_spacing) ---------------------------------------------------------------------------------
@@ -1036,7 +1175,17 @@ void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur) {
         if (c->graded) hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH, true>), gr, bl, 0, c->stream, sg);                \
         else hipLaunchKernelGGL((k_assemble_bc<NPH, JAC, SCH>), gr, bl, 0, c->stream, s);                                 \
     } while (0)
-    if (c->nph == 2) {
+#define LAUNCH_BC_SAT(JAC, SCH)                                                                                          \
+    do {                                                                                                                 \
+        if (c->graded) hipLaunchKernelGGL((k_assemble_bc<2, JAC, SCH, true, true>), gr, bl, 0, c->stream,                 \
+                                          WithSat<BcArgsG>{sg, c->dsat});                                                \
+        else hipLaunchKernelGGL((k_assemble_bc<2, JAC, SCH, false, true>), gr, bl, 0, c->stream, WithSat<BcArgs>{s, c->dsat}); \
+    } while (0)
+    if (c->satfn) {
+        if (!want_jac) LAUNCH_BC_SAT(false, false);
+        else if (want_schur) LAUNCH_BC_SAT(true, true);
+        else LAUNCH_BC_SAT(true, false);
+    } else if (c->nph == 2) {
         if (!want_jac) LAUNCH_BC(2, false, false);
         else if (want_schur) LAUNCH_BC(2, true, true);
         else LAUNCH_BC(2, true, false);
@@ -1046,6 +1195,7 @@ void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur) {
         else LAUNCH_BC(1, true, false);
     }
 #undef LAUNCH_BC
+#undef LAUNCH_BC_SAT
     TP_HIP(hipGetLastError());
 }
 
@@ -1090,7 +1240,18 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
             hipLaunchKernelGGL((k_assemble_lds<NPH, JAC, SCH>), grl, bl, bytes, c->stream, a);                            \
         } else hipLaunchKernelGGL((k_assemble<NPH, JAC, SCH>), gr, bl, 0, c->stream, a);                                 \
     } while (0)
-    if (c->nph == 2) {
+    // a context with saturation functions launches the plain kernel too (the LDS image holds no p_c)
+#define LAUNCH_SAT(JAC, SCH)                                                                                             \
+    do {                                                                                                                 \
+        if (c->graded) hipLaunchKernelGGL((k_assemble<2, JAC, SCH, true, true>), gr, bl, 0, c->stream,                    \
+                                          WithSat<AsmArgsG>{ag, c->dsat});                                               \
+        else hipLaunchKernelGGL((k_assemble<2, JAC, SCH, false, true>), gr, bl, 0, c->stream, WithSat<AsmArgs>{a, c->dsat}); \
+    } while (0)
+    if (c->satfn) {
+        if (!want_jac) LAUNCH_SAT(false, false);
+        else if (want_schur) LAUNCH_SAT(true, true);
+        else LAUNCH_SAT(true, false);
+    } else if (c->nph == 2) {
         if (!want_jac) LAUNCH(2, false, false);
         else if (want_schur) LAUNCH(2, true, true);
         else LAUNCH(2, true, false);
@@ -1100,12 +1261,16 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
         else LAUNCH(1, true, false);
     }
 #undef LAUNCH
+#undef LAUNCH_SAT
     if (c->bc.ncells > 0) assemble_bc(c, want_jac, want_jac && want_schur);
     if (c->nsrc_groups > 0) {
         double *J = want_jac ? c->J.p : nullptr;
         double *Sm = (want_jac && want_schur) ? c->Sm.p : nullptr;
         const dim3 g2 = grid_for(c->nsrc_groups, 64);
-        if (c->nph == 2)
+        if (c->satfn)
+            hipLaunchKernelGGL(k_sources_sat, g2, dim3(64), 0, c->stream, g, c->dprm, c->src.p, c->src_start.p,
+                               c->nsrc_groups, c->u.p, c->R.p, J, Sm, (double *)nullptr, c->nsrc, c->dsat);
+        else if (c->nph == 2)
             hipLaunchKernelGGL(k_sources<2>, g2, dim3(64), 0, c->stream, g, c->dprm, c->src.p, c->src_start.p,
                                c->nsrc_groups, c->u.p, c->R.p, J, Sm, (double *)nullptr, c->nsrc);
         else
@@ -1119,7 +1284,11 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
 void well_rates(tp_ctx *c) {
     if (c->nsrc_groups == 0) return;
     const dim3 g2 = grid_for(c->nsrc_groups, 64);
-    if (c->nph == 2)
+    if (c->satfn)
+        hipLaunchKernelGGL(k_sources_sat, g2, dim3(64), 0, c->stream, c->g, c->dprm, c->src.p, c->src_start.p,
+                           c->nsrc_groups, c->u.p, (double *)nullptr, (double *)nullptr, (double *)nullptr,
+                           c->rates.p, c->nsrc, c->dsat);
+    else if (c->nph == 2)
         hipLaunchKernelGGL(k_sources<2>, g2, dim3(64), 0, c->stream, c->g, c->dprm, c->src.p, c->src_start.p,
                            c->nsrc_groups, c->u.p, (double *)nullptr, (double *)nullptr, (double *)nullptr,
                            c->rates.p, c->nsrc);

@@ -112,4 +112,60 @@ __device__ inline Dual3 water_mu_t(const Dual3 &T) {
     return o;
 }
 
+// ---- saturation functions (tp_set_saturation_functions) ---------------------------------------------------------
+// kr_o, kr_w and p_c of S_o, written once over the number type: Dual1 (value and d/dS) in the cell kernels, whose derivatives
+// w.r.t. p and T are carried by hand, Dual3 in the well kernel.  Every clamp decides on the value and gives a constant (slope
+// exactly 0) at and beyond either end: the strict gt of the reference's rel_perm_*_B_C and the tie rule of the upwinding.
+struct Dual1 {
+    double v, d;
+};
+__device__ __forceinline__ Dual1 sat_const(const Dual1 &, double c) { return Dual1{c, 0.0}; }
+__device__ __forceinline__ Dual3 sat_const(const Dual3 &, double c) { return Dual3(c); }
+// the number with value v and the derivative dv times that of x: f(x), f'(x) by the chain rule
+__device__ __forceinline__ Dual1 sat_chain(const Dual1 &x, double v, double dv) { return Dual1{v, dv * x.d}; }
+__device__ __forceinline__ Dual3 sat_chain(const Dual3 &x, double v, double dv) {
+    Dual3 r; r.v = v;
+    for (int k = 0; k < 3; ++k) r.d[k] = dv * x.d[k];
+    return r;
+}
+// x^n and n x^(n-1) from one pow; the exponents 1 and 2 (the linear and the common Corey curve) take none.  n is uniform over
+// the grid, so no wave diverges here.
+template <class N> __device__ __forceinline__ N sat_pow(const N &x, double n) {
+    if (n == 1.0) return x;
+    if (n == 2.0) return sat_chain(x, x.v * x.v, 2.0 * x.v);
+    const double pw = pow(x.v, n - 1.0);
+    return sat_chain(x, pw * x.v, n * pw);
+}
+// effective saturations: the value by a true division (correctly rounded, so the ends lie where the definition puts them)
+template <class N> __device__ __forceinline__ N sat_se_o(const N &S, const DevSat &s) { return sat_chain(S, (S.v - s.Sr_o) / s.D, s.invD); }
+template <class N> __device__ __forceinline__ N sat_se_w(const N &S, const DevSat &s) { return sat_chain(S, (s.So_max - S.v) / s.D, -s.invD); }
+
+template <class N> __device__ __forceinline__ N sat_corey(const N &Se, double n, double kmax) {
+    if (!(Se.v > 0.0)) return sat_const(Se, 0.0);
+    if (!(Se.v < 1.0)) return sat_const(Se, kmax);
+    const N pw = sat_pow(Se, n);
+    return sat_chain(pw, kmax * pw.v, kmax);
+}
+template <class N> __device__ __forceinline__ N kr_o_t(const N &S, const DevSat &s) {
+    if (s.kr_kind == 0) return S;                                    // (:92-94)
+    return sat_corey(sat_se_o(S, s), s.n_o, s.kro_max);              // (:124-129, with the clamp at Se > 1)
+}
+template <class N> __device__ __forceinline__ N kr_w_t(const N &S, const DevSat &s) {
+    if (s.kr_kind == 0) return sat_chain(S, 1.0 - S.v, -1.0);        // (:96-98)
+    return sat_corey(sat_se_w(S, s), s.n_w, s.krw_max);              // (:131-138)
+}
+// p_c = p_o - p_w >= 0: linear (:147-152) or Brooks-Corey with Se_w floored at pc_se_min (:140-145)
+template <class N> __device__ __forceinline__ N pc_t(const N &S, const DevSat &s) {
+    if (s.pc_kind == 0) return sat_const(S, 0.0);
+    const N Se = sat_se_w(S, s);
+    if (!(Se.v < 1.0)) return sat_const(S, s.pc_kind == 1 ? 0.0 : s.p_ct);
+    if (s.pc_kind == 1) {
+        if (!(Se.v > 0.0)) return sat_const(S, s.p_ct);
+        return sat_chain(Se, s.p_ct * (1.0 - Se.v), -s.p_ct);
+    }
+    if (!(Se.v > s.pc_se_min)) return sat_const(S, s.pc_max);
+    const N pw = sat_pow(Se, -s.inv_lmbda);
+    return sat_chain(pw, s.p_ct * pw.v, s.p_ct);
+}
+
 }  // namespace tp

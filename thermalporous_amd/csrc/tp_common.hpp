@@ -111,6 +111,16 @@ struct DevPrm {
     double w0, w2;                          // equation weights (twophase.py:142-147)
 };
 
+// Saturation functions (tp_set_saturation_functions) as the kernels read them: Corey's curves on
+// Se_o = (S - Sr_o)/D and Se_w = (So_max - S)/D, So_max = 1 - Sr_w (this order, so that S = 1 - Sr_w is the end exactly, as
+// S = Sr_o is), and the capillary pressure.  Only the SATFN instantiations take one; DevPrm does not change.
+struct DevSat {
+    double Sr_o, So_max, D, invD;           // residual oil, 1 - Sr_w, D = 1 - Sr_o - Sr_w and 1/D
+    double n_o, n_w, kro_max, krw_max;      // Corey exponents and end points (Brooks-Corey: translated by the caller)
+    double p_ct, inv_lmbda, pc_se_min, pc_max;   // entry pressure, 1/lmbda, floor of Se_w, and p_c at that floor
+    int kr_kind, pc_kind;                   // tp_satfn.relperm, tp_satfn.capillary
+};
+
 template <class T>
 struct DBuf {
     T *p = nullptr;
@@ -375,6 +385,11 @@ struct tp_ctx {
     bool graded = false;
     std::vector<double> hs_host[3];
     tp::DBuf<double> hs[3];
+    // saturation functions (tp_set_saturation_functions).  satfn == false: the kernels launched are the
+    // instantiations without them, with the arguments they have always had
+    bool satfn = false;
+    tp_satfn sat_host;
+    tp::DevSat dsat;
     // linear algebra
     std::vector<tp::DBuf<double> *> vecs;
     tp::DBuf<double> At;          // decoupled primary block (QI/TI); planes as in J with b' = nprimary
@@ -480,6 +495,10 @@ void bc_flux(tp_ctx *c, double *out);
 // graded grid (tp_set_spacing): spacing_set checks and stores the widths (all null: back to uniform) and marks the fields as not
 // finalised; conduction_strengths gives the per-axis coarsening strengths of amg_T and the pc_ctr hierarchy on grid `gam`: |E|/h_a^2,
 // or with spacing the mean of |e|/(d_P + d_M) over the axis's interior faces
+// saturation functions (tp_set_saturation_functions): checks every range, stores the setting (null, or linear without p_c: the
+// default) and recomputes the old state's accumulation; satfn_defaults: the values tp_saturation_info reports when none is set
+void satfn_set(tp_ctx *c, const tp_satfn *sat);
+tp_satfn satfn_defaults();
 void spacing_set(tp_ctx *c, const double *h0, long n0, const double *h1, long n1, const double *h2, long n2);
 void conduction_strengths(const tp_ctx *c, const GridDev &gam, double sg[3]);
 // vectors / reductions (vectors are b field planes of ntot; reductions run over owned cells only)

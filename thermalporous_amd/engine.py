@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from .boundary import KINDS, pack_values
+from .physicalparameters import SATFN_NUMBERS, check_satfn, satfn_is_default
 
 _LIB = None
 _LIBPATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libthermalporous_hip.so")
@@ -68,6 +69,12 @@ class tp_solve_info(C.Structure):
                 ("fnorm0", C.c_double), ("fnorm", C.c_double), ("vcycles", C.c_int32)]
 
 
+class tp_satfn(C.Structure):
+    _fields_ = [("relperm", C.c_int32), ("capillary", C.c_int32), ("Sr_o", C.c_double), ("Sr_w", C.c_double),
+                ("n_o", C.c_double), ("n_w", C.c_double), ("kro_max", C.c_double), ("krw_max", C.c_double),
+                ("lmbda", C.c_double), ("p_ct", C.c_double), ("pc_se_min", C.c_double)]
+
+
 # every symbol include/thermalporous_hip.h declares (tests check that the library exports them all)
 API_SYMBOLS = (
     "tp_last_error", "tp_version", "tp_create", "tp_destroy", "tp_set_options", "tp_comm_unique_id", "tp_comm_init",
@@ -83,6 +90,7 @@ API_SYMBOLS = (
     "tp_ls_info", "tp_ls_history", "tp_ls_step_stats", "tp_ls_trial", "tp_amg_gs_info", "tp_vec_orth_step", "tp_ksp_reorth_info",
     "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
     "tp_schur_info", "tp_set_boundary", "tp_boundary_flux", "tp_set_spacing", "tp_spacing_info",
+    "tp_set_saturation_functions", "tp_saturation_info",
 )
 
 DEFAULT_OPTS = dict(
@@ -607,6 +615,21 @@ def check_spacing(hs, n):
     return tuple(out)
 
 
+_CAPILLARY = {None: 0, "linear": 1, "brooks_corey": 2}
+
+
+def pack_satfn(sat):
+    """A saturation-function setting (physicalparameters.check_satfn's dict) as the library's struct.  The library knows the
+    linear curves (relperm 0) and Corey's (1): "brooks_corey" goes in as Corey with n_o = n_w = (2 + 3 lmbda)/lmbda."""
+    d = check_satfn(sat)
+    n_o, n_w = d["n_o"], d["n_w"]
+    if d["relperm"] == "brooks_corey":
+        n_o = n_w = (2.0 + 3.0*d["lmbda"])/d["lmbda"]
+    return tp_satfn(relperm=0 if d["relperm"] == "linear" else 1, capillary=_CAPILLARY[d["capillary"]], Sr_o=d["Sr_o"],
+                    Sr_w=d["Sr_w"], n_o=n_o, n_w=n_w, kro_max=d["kro_max"], krw_max=d["krw_max"], lmbda=d["lmbda"],
+                    p_ct=d["p_ct"], pc_se_min=d["pc_se_min"])
+
+
 _PC = {"cpr": 0, "cptr": 1, "fieldsplit_cd": 2, "cptramg": 3, "bilu": 4}
 _DECOUP = {"No": 0, "QI": 1, "TI": 2, "QI_temp": 3, "TI_temp": 4}
 _S1_KSP = {"preonly": 0, "richardson": 1, "fgmres": 2}
@@ -646,6 +669,7 @@ def slab_range(gn2, rank, nranks):
 
 class HipEngine:
     """Same interface as oracle.engine.OracleEngine; all arithmetic on the GPU."""
+    supports_satfn = True          # spec["satfn"] is honoured (thermalmodel.init_solver refuses engines that do not say so)
 
     def __init__(self, spec, opts=None, rank=0, nranks=1, device=None, comm_bootstrap=None, local_group=None):
         check_boundary_slabs(spec.get("boundary"), nranks)       # (host-side: before the library and any context)
@@ -696,6 +720,11 @@ class HipEngine:
             a = self._with_halo(np.asarray(arr, dtype=float))
             self._ck(self.lib.tp_set_field(self.ctx, name.encode(), _dptr(a), C.c_int64(a.size)))
         self._ck(self.lib.tp_finalize_fields(self.ctx))
+        # saturation functions (physicalparameters.py; include/thermalporous_hip.h: tp_set_saturation_functions): pointwise in
+        # the closures, so every slab's context takes the same setting
+        self.satfn = None                      # the setting in force (check_satfn's dict), or None for the linear / no-p_c default
+        if spec.get("satfn") is not None:
+            self.set_saturation_functions(spec["satfn"])
         self._set_sources(spec.get("sources"))
         self.boundary = {}                     # side id -> the entry in force (spec["boundary"] layout)
         for side, e in sorted((spec.get("boundary") or {}).items()):
@@ -812,6 +841,33 @@ class HipEngine:
         lo, hi = np.zeros(3), np.zeros(3)
         self._ck(self.lib.tp_spacing_info(self.ctx, C.byref(graded), _dptr(lo), _dptr(hi)))
         return dict(graded=bool(graded.value), hmin=tuple(lo), hmax=tuple(hi))
+
+    # ---- saturation functions (physicalparameters.py; include/thermalporous_hip.h: tp_set_saturation_functions) ----
+    def set_saturation_functions(self, sat):
+        """Relative permeabilities and capillary pressure of the two-phase model: a dict with the keys of
+        PhysicalParameters.satfn_dict() (missing keys at their defaults), or None for the linear curves without capillary
+        pressure.  Any time between two solves; the library recomputes the old state's accumulation."""
+        if sat is None:
+            self._ck(self.lib.tp_set_saturation_functions(self.ctx, None))
+            self.satfn = None
+            return
+        d = check_satfn(sat)
+        if self.nph != 2 and not satfn_is_default(d):
+            raise NotImplementedError("relperm = %r, capillary = %r on a single-phase engine: saturation functions need a "
+                                      "saturation, which only the two-phase model has" % (d["relperm"], d["capillary"]))
+        st = pack_satfn(d)
+        self._ck(self.lib.tp_set_saturation_functions(self.ctx, C.byref(st)))
+        self.satfn = None if satfn_is_default(d) else d
+
+    def saturation_info(self):
+        """tp_saturation_info: dict(active, relperm ("linear" | "corey"), capillary, and the numbers as the library holds them:
+        a "brooks_corey" relperm reads back as "corey" with its exponents)."""
+        st, active = tp_satfn(), C.c_int32(0)
+        self._ck(self.lib.tp_saturation_info(self.ctx, C.byref(st), C.byref(active)))
+        out = {k: float(getattr(st, k)) for k in SATFN_NUMBERS}
+        out.update(active=bool(active.value), relperm=("linear", "corey")[st.relperm],
+                   capillary={v: k for k, v in _CAPILLARY.items()}[st.capillary])
+        return out
 
     # ---- Dirichlet sides (boundary.py; include/thermalporous_hip.h: tp_set_boundary) -------------------
     def _side_shape(self, side):

@@ -4,9 +4,24 @@ Mirrors /root/reference/thermalporous/physicalparameters.py:3-98 attribute for a
 (same names, same SI/MPa/mm^2 scaling), so driver scripts that mutate ``params.rate`` etc.
 keep working.  The closure methods here are numpy restatements used on the host only for
 diagnostics (oil in place, well rates); the device evaluates its own copy inside the HIP
-assembly kernels (csrc/tp_closures.hpp).  Brooks-Corey / capillary-pressure members of the
-reference (:100-152) are dead code behind ``if False:`` (twophase.py:103,277) and are not
-carried over.
+assembly kernels (csrc/tp_closures.hpp).
+
+Saturation functions.  The reference's Brooks-Corey / capillary-pressure members
+(:100-152: ``Sr_o``, ``Sr_w``, ``lmbda``, ``p_ct``, ``rel_perm_*_B_C``, ``capillary_pressure_*``) sit
+behind ``if False:`` (twophase.py:103,277) and never run there; here they are a model option, off by
+default: ``relperm`` = "linear" (``kr_o = S_o``, ``kr_w = 1 - S_o``: the reference's executed curves) |
+"corey" | "brooks_corey", ``capillary`` = None | "linear" | "brooks_corey", with the attributes below.
+With D = 1 - Sr_o - Sr_w, Se_o = (S_o - Sr_o)/D, Se_w = (1 - S_o - Sr_w)/D (formed as ((1 - Sr_w) - S_o)/D, so that the
+state S_o = 1 - Sr_w is the end of the curve exactly, as S_o = Sr_o is) and c(x) = min(max(x, 0), 1):
+
+    corey          kr_o = kro_max c(Se_o)^n_o,  kr_w = krw_max c(Se_w)^n_w
+    brooks_corey   corey with n_o = n_w = (2 + 3 lmbda)/lmbda (the reference's rel_perm_*_B_C, which however
+                   has no clamp at Se > 1: there it grows past the end point, here it stays at it)
+    p_c linear        p_ct (1 - c(Se_w))
+    p_c brooks_corey  p_ct s^(-1/lmbda),  s = min(max(Se_w, pc_se_min), 1)
+
+p_c = p_o - p_w >= 0 with p_o = p the unknown (twophase.py:104-106).  ``rel_perm_o`` / ``rel_perm_w`` follow
+``relperm``; ``satfn_dict()`` is what ``build_spec`` passes on as ``spec["satfn"]`` when the setting is not the default.
 """
 import numpy as np
 
@@ -59,14 +74,111 @@ class PhysicalParameters():
         Tf = 1.8*(T - 272.15) + 32
         return 1E-3*Aw/(-1 + Bw*Tf + Cw*Tf**2)
 
-    def rel_perm_o(self, S_o):                                 # (:92-94)
-        return S_o
+    # saturation functions (module docstring): the defaults are the reference's executed model
+    relperm = "linear"     # "linear" | "corey" | "brooks_corey"
+    Sr_o = 0.0             # residual oil saturation                 (:100-103)
+    Sr_w = 0.0             # connate water saturation
+    n_o = 2.0              # Corey exponents, >= 1
+    n_w = 2.0
+    kro_max = 1.0          # end-point relative permeabilities, > 0
+    krw_max = 1.0
+    lmbda = 2.0            # Brooks-Corey pore-size index, > 0
+    capillary = None       # None | "linear" | "brooks_corey"
+    p_ct = 0.0             # capillary entry pressure, MPa, >= 0
+    pc_se_min = 0.05       # floor of Se_w in the Brooks-Corey p_c, in (0, 1]: a model parameter
 
-    def rel_perm_w(self, S_o):                                 # (:96-98)
-        return 1.0 - S_o
+    def effective_saturation_o(self, S_o):                     # (:100-103)
+        return (S_o - self.Sr_o)/(1.0 - self.Sr_o - self.Sr_w)
+
+    def effective_saturation_w(self, S_o):                     # (:105-109)
+        return ((1.0 - self.Sr_w) - S_o)/(1.0 - self.Sr_o - self.Sr_w)     # (this order: S_o = 1 - Sr_w gives exactly 0)
+
+    def _corey_exponents(self):
+        if self.relperm == "brooks_corey":
+            n = (2.0 + 3.0*self.lmbda)/self.lmbda              # (:129,137)
+            return n, n
+        return float(self.n_o), float(self.n_w)
+
+    def rel_perm_o(self, S_o):                                 # (:92-94, :124-129)
+        check_satfn(self.satfn_dict())
+        if self.relperm == "linear":
+            return S_o
+        return self.kro_max*np.clip(self.effective_saturation_o(S_o), 0.0, 1.0)**self._corey_exponents()[0]
+
+    def rel_perm_w(self, S_o):                                 # (:96-98, :131-138)
+        check_satfn(self.satfn_dict())
+        if self.relperm == "linear":
+            return 1.0 - S_o
+        return self.krw_max*np.clip(self.effective_saturation_w(S_o), 0.0, 1.0)**self._corey_exponents()[1]
+
+    def capillary_pressure(self, S_o):                         # (:140-152)
+        """p_c(S_o) = p_o - p_w in MPa; zero without ``capillary``."""
+        check_satfn(self.satfn_dict())
+        Se_w = self.effective_saturation_w(S_o)
+        if self.capillary is None:
+            return 0.0*Se_w
+        if self.capillary == "linear":
+            return self.p_ct*(1.0 - np.clip(Se_w, 0.0, 1.0))
+        return self.p_ct*np.clip(Se_w, self.pc_se_min, 1.0)**(-1.0/self.lmbda)
+
+    def satfn_dict(self):
+        """The saturation-function setting as plain data (spec["satfn"], HipEngine.set_saturation_functions)."""
+        d = {"relperm": self.relperm, "capillary": self.capillary}
+        d.update({k: getattr(self, k) for k in SATFN_NUMBERS})          # (as set: check_satfn names what is no number)
+        return d
 
     def as_dict(self):
         """Scalar parameters handed to the compute engine (tp_set_params)."""
         keys = ("ko", "kw", "kr", "c_v_w", "c_v_o", "c_r", "rho_r", "p_inj", "p_prod", "T_inj",
                 "T_prod", "API", "p_ref", "g", "S_o", "U", "rate")
         return {k: float(getattr(self, k)) for k in keys}
+
+
+SATFN_NUMBERS = ("Sr_o", "Sr_w", "n_o", "n_w", "kro_max", "krw_max", "lmbda", "p_ct", "pc_se_min")
+SATFN_DEFAULT = {"relperm": "linear", "capillary": None, "Sr_o": 0.0, "Sr_w": 0.0, "n_o": 2.0, "n_w": 2.0, "kro_max": 1.0,
+                 "krw_max": 1.0, "lmbda": 2.0, "p_ct": 0.0, "pc_se_min": 0.05}
+RELPERMS = ("linear", "corey", "brooks_corey")
+CAPILLARIES = (None, "linear", "brooks_corey")
+
+
+def check_satfn(d):
+    """A saturation-function setting against its ranges; every refusal names the key.  Returns the dict completed with the
+    defaults."""
+    unknown = sorted(set(d) - set(SATFN_DEFAULT))
+    if unknown:
+        raise ValueError("saturation functions: unknown key(s) %s: the keys are %s" % (unknown, sorted(SATFN_DEFAULT)))
+    d = {**SATFN_DEFAULT, **d}
+    if d["relperm"] not in RELPERMS:
+        raise ValueError("relperm = %r: 'linear', 'corey' or 'brooks_corey'" % (d["relperm"],))
+    if d["capillary"] not in CAPILLARIES:
+        raise ValueError("capillary = %r: None, 'linear' or 'brooks_corey'" % (d["capillary"],))
+    for k in SATFN_NUMBERS:
+        v = d[k]
+        if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v):
+            raise ValueError("%s = %r: a finite number" % (k, v))
+        d[k] = float(v)
+    if d["Sr_o"] < 0.0:
+        raise ValueError("Sr_o = %r: the residual oil saturation, >= 0" % d["Sr_o"])
+    if d["Sr_w"] < 0.0:
+        raise ValueError("Sr_w = %r: the connate water saturation, >= 0" % d["Sr_w"])
+    if not d["Sr_o"] + d["Sr_w"] < 1.0:
+        raise ValueError("Sr_o + Sr_w = %r: the residual saturations must leave a mobile range, Sr_o + Sr_w < 1"
+                         % (d["Sr_o"] + d["Sr_w"],))
+    for k in ("n_o", "n_w"):
+        if d[k] < 1.0:
+            raise ValueError("%s = %r: a Corey exponent, >= 1" % (k, d[k]))
+    for k in ("kro_max", "krw_max"):
+        if not d[k] > 0.0:
+            raise ValueError("%s = %r: an end-point relative permeability, > 0" % (k, d[k]))
+    if not d["lmbda"] > 0.0:
+        raise ValueError("lmbda = %r: the Brooks-Corey pore-size index, > 0" % d["lmbda"])
+    if d["p_ct"] < 0.0:
+        raise ValueError("p_ct = %r: the capillary entry pressure in MPa, >= 0" % d["p_ct"])
+    if not 0.0 < d["pc_se_min"] <= 1.0:
+        raise ValueError("pc_se_min = %r: the floor of Se_w in the Brooks-Corey p_c, in (0, 1]" % d["pc_se_min"])
+    return d
+
+
+def satfn_is_default(d):
+    """True for the linear / no-p_c setting, whatever the other numbers hold: nothing reads them then."""
+    return d is None or (d.get("relperm", "linear") == "linear" and d.get("capillary") is None)

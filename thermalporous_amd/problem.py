@@ -10,11 +10,13 @@ the C-ABI consumes through tp_create / tp_set_field / tp_set_params / tp_set_sou
 * fields transposed to internal order, shape (n2, n1, n0);
 * wells/heaters flattened to per-cell source entries with their Peaceman index
   (wellcase.py:182-191 of the reference: hard-coded Dx=Dy=h=5, rw=0.1; Kx,Ky at the cell);
-* ``hs``: the cell widths per internal axis of a graded grid (``geo.set_spacing``), absent on a uniform one.
+* ``hs``: the cell widths per internal axis of a graded grid (``geo.set_spacing``), absent on a uniform one;
+* ``satfn``: the saturation functions (``params.satfn_dict()``), absent for the linear curves without capillary pressure.
 """
 import numpy as np
 
 from .boundary import boundary_spec
+from .physicalparameters import check_satfn, satfn_is_default
 from .spacing import lock_spacing
 from .wellcase import peaceman_WI
 
@@ -126,6 +128,13 @@ def build_spec(geo, case, params, nphase, axes=None):
     bnd = boundary_spec(geo, params, nphase, axes)      # Dirichlet sides (boundary.py); no key when none is set
     if bnd:
         spec["boundary"] = bnd
+    # saturation functions (physicalparameters.py): no key for the linear / no-p_c default
+    sat = check_satfn(params.satfn_dict()) if hasattr(params, "satfn_dict") else None
+    if not satfn_is_default(sat):
+        if int(nphase) != 2:
+            raise NotImplementedError("relperm = %r, capillary = %r with the single-phase model: saturation functions need a "
+                                      "saturation, which only the two-phase model has" % (sat["relperm"], sat["capillary"]))
+        spec["satfn"] = sat
     return spec
 
 

@@ -109,6 +109,12 @@ class ThermalModel:
             raise NotImplementedError("a graded grid (geo.set_spacing, spec[\"hs\"]) with the engine %r: per-axis cell widths "
                                       "are implemented by HipEngine; this engine would read the mean widths spec[\"h\"] as "
                                       "every cell's size" % (getattr(factory, "__name__", factory),))
+        if "satfn" in self.spec and not getattr(factory, "supports_satfn", False):
+            raise NotImplementedError("saturation functions (params.relperm = %r, params.capillary = %r, spec[\"satfn\"]) with "
+                                      "the engine %r: they are implemented by HipEngine; this engine would run the linear "
+                                      "curves without capillary pressure"
+                                      % (self.spec["satfn"]["relperm"], self.spec["satfn"]["capillary"],
+                                         getattr(factory, "__name__", factory)))
         if self.comm.size > 1:
             # one process per GPU: this rank's slab of internal axis 2, RCCL bootstrapped through torch.distributed
             from . import parallel
