@@ -350,6 +350,67 @@ typedef struct tp_satfn {
 int tp_set_saturation_functions(tp_ctx *ctx, const tp_satfn *sat);
 int tp_saturation_info(tp_ctx *ctx, tp_satfn *out, int32_t *active);
 
+/* Completed wells (tp_version >= 101): a well perforates many cells, shares ONE bottom-hole pressure along its
+ * bore, sees the hydrostatic head between its perforations, and is operated at a TOTAL rate until its BHP limit is reached, then
+ * at that limit.  Beside tp_set_sources, whose entries keep a private bhp per cell; a cell may carry legacy entries (a heater) and
+ * one perforation.  With u_k the state of perforation k's cell:
+ *   a_k     = WI_k lambda_k      lambda: what a tp_source entry of the kind multiplies its drawdown by -- producer lambda_o +
+ *                                lambda_w (kr/mu of the saturation functions in force), single-phase 1/mu_o(T_k); injector
+ *                                1/mu_w(T_k), single-phase 1/mu_o(T_k)
+ *   theta_k = p_k - rho_w g (z_ref - z_k)   z up, g = tp_params.g; no head on a grid without a gravity axis.  rho_w is FROZEN over
+ *                                a time step: computed whenever the old state is set -- producer: sum_k WI_k (lambda_o rho_o +
+ *                                lambda_w rho_w) / sum_k WI_k lambda_t over all its perforations (0 if none is mobile); injector:
+ *                                the injected fluid at (p_old of the perforation nearest to z_ref, T_inj)
+ *   q_k     = -a_k (theta_k - bhp) on open perforations (producer: theta_k > bhp, injector: theta_k < bhp), 0 on closed ones: no
+ *                                cross-flow.  Production is negative, as in tp_well_rates.
+ * Rate mode: bhp solves sum_k q_k = -Q (producer) or +Q (injector) by active-set rounds -- all perforations open, bhp = (sum_open
+ * a_k theta_k -+ Q) / sum_open a_k, close what that bhp shuts, repeat until nothing changes; a closed perforation stays closed.
+ * BHP mode, bhp = bhp_limit with open/closed decided against it, when the rate-mode bhp violates the limit (a producer's minimum,
+ * an injector's maximum) or no mobile perforation is open.  rate = 0 or shut != 0: the well adds nothing.
+ * A perforation adds to R what a tp_source entry of its kind adds for the rate q_k with wt = 1 (the cell's own normalised delta),
+ * and its derivative AT FIXED bhp to the diagonal block of J and to S~.  In rate mode bhp depends on every perforated cell: the
+ * exact Jacobian is J + c b^T per well, c_k = dR_k/dbhp, b_j = dbhp/du_j, b numbers each per perforation, zeros on closed ones.
+ * tp_newton_solve, tp_fgmres, tp_bcgs and tp_spmv apply J + sum_w c_w b_w^T; the preconditioner, tp_export_jacobian and every
+ * tp_time_kernel product keep the 7-point part.  A well of ONE perforation has no off-diagonal term: its c b^T is added to the
+ * diagonal block and its exported factors are zero.
+ * tp_set_wells: wells[w] owns perfs[first .. first + count); nwells = 0 removes all wells (the results are then bit for bit those
+ * of a context that never had one).  cell: the local index of tp_source.cell; z, z_ref: elevations in the units of tp_grid.h.
+ * Checked, each failure naming the well and perforation: kind 0/1, finite numbers, WI > 0, rate >= 0, cells inside the box, no cell
+ * and no entry of perfs used twice.  One slab only: with nranks > 1 the call fails, and tp_comm_init / tp_comm_init_local fail on a
+ * context with wells.  Callable any time between two solves; an old state that is already set gives the head densities at once.
+ * tp_set_well_control: new rate, bhp_limit and shut flag of one well, between two time steps (rho_w is not recomputed).
+ * tp_well_info: nwells entries describing the last assembly (tp_residual, tp_jacobian, the last one of tp_newton_solve).
+ * tp_well_perf_rates: per entry of perfs the total, water and oil rate of that assembly (two-phase producers split by mobility;
+ * a two-phase injector's rate is water, every single-phase rate is oil); any pointer may be NULL.
+ * tp_well_factors: c and b of the last Jacobian assembly, b * nperfs doubles each, entry [r * nperfs + k] = component r (of R for
+ * c, of u for b) at perforation k; all zero in BHP mode. */
+typedef struct tp_well {
+    int32_t kind;            /* 0 producer, 1 injector                                          */
+    int32_t shut;            /* != 0: contributes nothing                                       */
+    double  rate;            /* Q >= 0: total volumetric rate target, units of tp_source.max_rate */
+    double  bhp_limit;       /* a producer's minimum, an injector's maximum BHP                 */
+    double  z_ref;           /* datum elevation of the BHP                                      */
+    int32_t first, count;    /* its perforations: perfs[first .. first + count)                 */
+} tp_well;
+typedef struct tp_perf {
+    int64_t cell;            /* local index into the slab-with-halo array                       */
+    double  WI;              /* connection index, > 0                                           */
+    double  z;               /* elevation of the cell centre                                    */
+} tp_perf;
+typedef struct tp_well_state {
+    double  bhp;
+    int32_t mode;            /* 0 shut or rate 0, 1 rate, 2 BHP                                 */
+    int32_t rounds;          /* active-set rounds of the last assembly                          */
+    double  rate, water_rate, oil_rate;   /* sums over the perforations                         */
+    double  rho;             /* the head density in force                                       */
+    int32_t nopen, reserved; /* open perforations                                               */
+} tp_well_state;
+int tp_set_wells(tp_ctx *ctx, int32_t nwells, const tp_well *wells, int32_t nperfs, const tp_perf *perfs);
+int tp_set_well_control(tp_ctx *ctx, int32_t well, double rate, double bhp_limit, int32_t shut);
+int tp_well_info(tp_ctx *ctx, tp_well_state *out);
+int tp_well_perf_rates(tp_ctx *ctx, double *rate, double *water_rate, double *oil_rate);
+int tp_well_factors(tp_ctx *ctx, double *c, double *b);
+
 /* state u, old state u_ (thermalmodel.py:93-94,296), time step (thermalmodel.py:13). */
 int tp_set_state(tp_ctx *ctx, const double *u_host);      /* b*ntot doubles */
 int tp_get_state(tp_ctx *ctx, double *u_host);
@@ -367,7 +428,7 @@ int tp_clamp_saturation(tp_ctx *ctx);
 int tp_residual(tp_ctx *ctx, double *norm2);               /* R <- F(u); ||F||_2 over all ranks */
 int tp_jacobian(tp_ctx *ctx);                              /* R, J (and S~ for pc_cptr) <- at u */
 int tp_get_residual(tp_ctx *ctx, double *host);            /* b*ntot */
-int tp_export_jacobian(tp_ctx *ctx, double *host);         /* 7*b*b*ntot */
+int tp_export_jacobian(tp_ctx *ctx, double *host);         /* 7*b*b*ntot: the 7-point part; the wells' rank-1 terms: tp_well_factors */
 int tp_export_schur(tp_ctx *ctx, double *host);            /* 7*ntot: ConvDiffSchur*PC operator */
 int tp_well_rates(tp_ctx *ctx, double *rate, double *water_rate, double *oil_rate); /* per entry */
 
@@ -415,7 +476,7 @@ int tp_fvec_store(tp_ctx *ctx, int32_t batch, int32_t i, int32_t x);
 int tp_fvec_get(tp_ctx *ctx, int32_t batch, int32_t i, float *host);
 int tp_fvec_dot_batch(tp_ctx *ctx, int32_t batch, int32_t n, int32_t w, double *out);
 int tp_fvec_axpy_batch(tp_ctx *ctx, int32_t batch, int32_t n, const double *coef, int32_t w);
-int tp_spmv(tp_ctx *ctx, int32_t x, int32_t y);            /* y = J x */
+int tp_spmv(tp_ctx *ctx, int32_t x, int32_t y);            /* y = J x, plus sum_w c_w (b_w . x) when wells are set: the Krylov operator */
 int tp_pc_setup(tp_ctx *ctx);                              /* PCSetUp: decoupling, AMG setup, ILU factor */
 int tp_pc_apply(tp_ctx *ctx, int32_t x, int32_t y);        /* composite multiplicative (stage1, ILU0) */
 int tp_stage1_update(tp_ctx *ctx);                         /* CPRStage1PC/CPTRStage1PC.update (preconditioners.py:875,1545) */
@@ -526,7 +587,9 @@ int tp_ew_history(tp_ctx *ctx, int32_t cap, double *rtol, double *fnorm, double 
  * S stage in one launch (tp_stage_rhs), 10 the pair of launches it replaces (block residual over all b rows and columns + the
  * decoupled right-hand side per primary field), 11 that block residual alone, 12 the T stage's row right-hand side in one launch
  * (tp_ctr_rhs; needs pc_ctr), 13 the boundary-face kernel alone (needs a side from tp_set_boundary; it adds to R, J and S~, so
- * assemble again before using them; 3 includes it when a side is set).  4 times the pc_order and pc_ctr in force. */
+ * assemble again before using them; 3 includes it when a side is set), 14 the wells' rank-1 kernel alone (needs tp_set_wells; it
+ * adds to a scratch vector), 15 the well kernel alone (needs tp_set_wells; it adds to R, J and S~ like 13), 16 the source kernel's
+ * rates-only form (needs tp_set_sources).  4 times the pc_order and pc_ctr in force. */
 int tp_time_kernel(tp_ctx *ctx, int32_t which, int32_t reps, double *ms_avg);
 int tp_amg_info(tp_ctx *ctx, int32_t which, int32_t *nlevels, double *op_complexity);
 /* level at which hierarchy `which` ends with relaxation only (amg_dom_tau), -1: full V-cycle; ratio0 = the

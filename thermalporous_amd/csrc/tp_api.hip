@@ -314,7 +314,7 @@ static void check_options(const tp_options &o, int nranks) {
 extern "C" {
 
 const char *tp_last_error(void) { return tp::g_err.c_str(); }
-int tp_version(void) { return 100; }
+int tp_version(void) { return 101; }
 
 int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, int device, tp_ctx **out) {
     TP_API_BEGIN
@@ -418,6 +418,7 @@ int tp_comm_init(tp_ctx *c, const void *id128) {
     TP_REQUIRE(c && id128, "null argument");
     TP_REQUIRE(c->grid.nranks >= 1, "bad nranks");     // a 1-rank communicator is legal (exercises the RCCL calls on one GPU)
     TP_REQUIRE(!c->graded, "tp_comm_init: this context has spacing (tp_set_spacing): graded grids exist on one slab without a communicator");
+    TP_REQUIRE(c->wells.nw == 0, "tp_comm_init: this context has wells (tp_set_wells): completed wells exist on one slab without a communicator");
     TP_HIP(hipSetDevice(c->device));
     ncclUniqueId id;
     std::memcpy(&id, id128, sizeof(id));
@@ -453,6 +454,7 @@ int tp_comm_init_local(tp_ctx *c, void *group) {
     TP_REQUIRE(c && group, "null argument");
     LocalGroup *G = (LocalGroup *)group;
     TP_REQUIRE(!c->graded, "tp_comm_init_local: this context has spacing (tp_set_spacing): graded grids exist on one slab without a slab group");
+    TP_REQUIRE(c->wells.nw == 0, "tp_comm_init_local: this context has wells (tp_set_wells): completed wells exist on one slab without a slab group");
     TP_REQUIRE(c->grid.nranks == G->n, "group size differs from the context's nranks");
     int lo, hi;
     slab_of(c, c->grid.rank, lo, hi);
@@ -512,6 +514,39 @@ int tp_set_sources(tp_ctx *c, int32_t n, const tp_source *entries) {
     c->rates.alloc((size_t)3 * std::max(1, n));
     if (n) copy_sync(c, c->src.p, v.data(), sizeof(tp_source) * n, hipMemcpyHostToDevice);
     copy_sync(c, c->src_start.p, start.data(), sizeof(int) * start.size(), hipMemcpyHostToDevice);
+    TP_API_END
+}
+
+int tp_set_wells(tp_ctx *c, int32_t nwells, const tp_well *wells, int32_t nperfs, const tp_perf *perfs) {
+    TP_API_BEGIN
+    wells_set(c, nwells, wells, nperfs, perfs);
+    TP_API_END
+}
+
+int tp_set_well_control(tp_ctx *c, int32_t well, double rate, double bhp_limit, int32_t shut) {
+    TP_API_BEGIN
+    wells_control(c, well, rate, bhp_limit, shut);
+    TP_API_END
+}
+
+int tp_well_info(tp_ctx *c, tp_well_state *out) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "null argument");
+    wells_info(c, out);
+    TP_API_END
+}
+
+int tp_well_perf_rates(tp_ctx *c, double *rate, double *water_rate, double *oil_rate) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "null argument");
+    wells_perf_rates(c, rate, water_rate, oil_rate);
+    TP_API_END
+}
+
+int tp_well_factors(tp_ctx *c, double *cfac, double *bfac) {
+    TP_API_BEGIN
+    TP_REQUIRE(c, "null argument");
+    wells_factors(c, cfac, bfac);
     TP_API_END
 }
 
@@ -841,7 +876,7 @@ int tp_spmv(tp_ctx *c, int32_t x, int32_t y) {
     TP_REQUIRE(c->jac_ready, "Jacobian not assembled");
     TP_REQUIRE(x != y, "tp_spmv: x and y must differ");
     if (c->dist) halo_exchange(c, c->g, vec_of(c, x).p, c->b, c->g.ntot);
-    spmv_block(c, c->J.p, vec_of(c, x).p, vec_of(c, y).p);
+    krylov_apply(c, vec_of(c, x).p, vec_of(c, y).p, false);     // (J x plus the wells' rank-1 terms: the operator the Krylov methods see)
     TP_API_END
 }
 
@@ -1164,6 +1199,18 @@ int tp_time_kernel(tp_ctx *c, int32_t which, int32_t reps, double *ms_avg) {
             case 13:        // k_assemble_bc alone: it ADDS to R, J and S~, which are no assembly afterwards (re-assemble)
                 TP_REQUIRE(c->bc.ncells > 0, "no boundary set (tp_set_boundary)");
                 assemble_bc(c, true, schur_of(c->opt));
+                break;
+            case 14:        // k_well_apply alone: it ADDS the rank-1 terms of R to w2
+                TP_REQUIRE(c->wells.nw > 0, "no well set (tp_set_wells)");
+                wells_apply_only(c, c->R.p, c->w2.p);
+                break;
+            case 15:        // k_wells alone: it ADDS to R, J and S~, which are no assembly afterwards (re-assemble)
+                TP_REQUIRE(c->wells.nw > 0, "no well set (tp_set_wells)");
+                wells_assemble(c, true, schur_of(c->opt));
+                break;
+            case 16:        // k_sources alone (the rates-only form, which writes nothing but the rates)
+                TP_REQUIRE(c->nsrc_groups > 0, "no source set (tp_set_sources)");
+                well_rates(c);
                 break;
             default: throw Error("unknown kernel id");
         }

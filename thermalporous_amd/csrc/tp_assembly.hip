@@ -925,6 +925,7 @@ void accum_old(tp_ctx *c) {
         hipLaunchKernelGGL(k_accum_old<1>, grid_for(g.nown), dim3(256), 0, c->stream, g, c->dprm, c->u_old.p,
                            c->phi.p, c->acc_old.p);
     TP_HIP(hipGetLastError());
+    wells_rho(c);                                  // the completed wells' head densities follow the old state (nothing without wells)
 }
 
 static AsmArgs asm_args(tp_ctx *c) {
@@ -1278,6 +1279,7 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
                                c->nsrc_groups, c->u.p, c->R.p, J, Sm, (double *)nullptr, c->nsrc);
     }
     TP_HIP(hipGetLastError());
+    if (c->wells.nw > 0) wells_assemble(c, want_jac, want_schur);
     if (want_jac) c->jac_ready = true;
 }
 

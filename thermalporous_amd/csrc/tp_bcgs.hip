@@ -448,7 +448,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
     for (int its = 1;; ++its) {
         BC_LAUNCH(k_bcgs_p, g, B, (const double *)st, (const double *)r, (const double *)v, p, nw);
         pc_apply(c, p, ph);                                                       // p^ = M p
-        spmv_block_halo(c, c->J.p, ph, v);                                         // v = J p^
+        krylov_apply(c, ph, v);                                                    // v = J p^ (plus the wells' rank-1 terms)
         BC_LAUNCH(k_bcgs_dot, g, B, (const double *)rh, (const double *)v, part, nw);
         reduce(1);
         hipLaunchKernelGGL(k_bcgs_alpha, one, wv, 0, c->stream, st);
@@ -456,7 +456,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
         reduce(1);
         hipLaunchKernelGGL(k_bcgs_half, one, wv, 0, c->stream, st);
         pc_apply(c, s, sh);                                                       // s^ = M s
-        spmv_block_halo(c, c->J.p, sh, t);                                         // t = J s^
+        krylov_apply(c, sh, t);                                                    // t = J s^
         BC_LAUNCH(k_bcgs_dot2, g, B, (const double *)t, (const double *)s, part, nw);
         reduce(2);
         hipLaunchKernelGGL(k_bcgs_omega, one, wv, 0, c->stream, st);
@@ -476,7 +476,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
             std::vector<double> fn(B, 0.0);
             double *rm = c->w4.p;                                                   // free between pc_apply calls
             if (c->dist) halo_exchange(c, g, x, B, g.ntot);
-            resid_block_cols(c, c->J.p, bvec, x, B, rm);
+            krylov_resid(c, bvec, x, rm);
             for (int f = 0; f < B; ++f) {
                 const double *one_f[1] = {rm + (long)f * g.ntot};
                 multi_norm2sq(c, 1, 1, one_f, &fn[f]);

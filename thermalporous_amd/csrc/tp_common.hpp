@@ -326,6 +326,27 @@ struct Bc {
     int ncells = 0;
 };
 
+// Completed wells (tp_set_wells; tp_wells.hip).  With no well set (nw == 0) nothing of this is allocated, launched
+// or read.  Per-perforation planes are np entries long, entry k of the caller's perforation array.
+struct WellDev {
+    int kind, shut, first, count, datum;   // datum: the perforation whose old pressure an injector's head density is taken at
+    double rate, limit;
+};
+struct Wells {
+    int nw = 0, np = 0;
+    std::vector<tp_well> wells;            // host copies: tp_set_well_control edits them and uploads the controls again
+    std::vector<tp_perf> perfs;
+    DBuf<WellDev> wd;
+    DBuf<long> cell;
+    DBuf<double> WI, dz;                   // dz = z_ref - z_k (0 without a gravity axis)
+    DBuf<double> rho;                      // per well: the head density, frozen over a time step (k_well_rho)
+    DBuf<double> pa, pth;                  // scratch of k_wells: a_k, theta_k
+    DBuf<double> fc, fb;                   // the rank-1 factors c and b of the last Jacobian assembly, b planes of np each
+    DBuf<double> pq;                       // per-perforation rates of the last assembly: total, water, oil
+    DBuf<double> info;                     // per well, 8 doubles (tp_well_info)
+    DBuf<int> r1;                          // per well: 1 if the last Jacobian assembly left it a rank-1 term
+};
+
 struct IluData {
     int t0 = 0, t1 = 8, t2 = 8, nt0 = 0, nt1 = 0, nt2 = 0, ntiles = 0, nsteps = 0;
     DBuf<double> fwd, bwd, ytmp;   // streaming factor data in consumption order
@@ -380,6 +401,7 @@ struct tp_ctx {
     int nsrc = 0, nsrc_groups = 0;
     tp::DBuf<double> rates;       // 3*nsrc
     tp::Bc bc;                    // Dirichlet sides (tp_set_boundary)
+    tp::Wells wells;              // completed wells (tp_set_wells)
     // graded tensor-product grid (tp_set_spacing): widths of the cells along each internal axis, on the host and
     // on the device.  graded == false: nothing of this is allocated or read and grid.h / vol describe every cell.
     bool graded = false;
@@ -492,6 +514,21 @@ void bc_set(tp_ctx *c, int side, int kind, const double *values, long nfaces);
 void bc_trans(tp_ctx *c);
 void assemble_bc(tp_ctx *c, bool want_jac, bool want_schur);
 void bc_flux(tp_ctx *c, double *out);
+// completed wells (tp_wells.hip): wells_set checks and stores them (0 wells removes them), wells_control changes one well's targets,
+// wells_rho refreshes the head densities from the old state (accum_old calls it), wells_assemble adds the perforations to R, the
+// diagonal block of J and the diagonal of S~ and stores the rank-1 factors (assemble calls it behind the source kernel)
+void wells_set(tp_ctx *c, int nw, const tp_well *wells, int np, const tp_perf *perfs);
+void wells_control(tp_ctx *c, int w, double rate, double limit, int shut);
+void wells_rho(tp_ctx *c);
+void wells_assemble(tp_ctx *c, bool want_jac, bool want_schur);
+void wells_info(tp_ctx *c, tp_well_state *out);
+void wells_perf_rates(tp_ctx *c, double *rate, double *water, double *oil);
+void wells_factors(tp_ctx *c, double *fc, double *fb);
+// The Krylov operator A = J + sum_w c_w b_w^T on the assembled Jacobian: y = A x (halo: through spmv_block_halo) and r = b - A x over
+// all b columns.  The outer Krylov methods and tp_spmv use these two; the preconditioner's own products keep the 7-point J.
+void krylov_apply(tp_ctx *c, double *x, double *y, bool halo = true);
+void krylov_resid(tp_ctx *c, const double *b, const double *x, double *r);
+void wells_apply_only(tp_ctx *c, const double *x, double *y);     // y += sum_w c_w (b_w . x): the kernel alone (tp_time_kernel)
 // graded grid (tp_set_spacing): spacing_set checks and stores the widths (all null: back to uniform) and marks the fields as not
 // finalised; conduction_strengths gives the per-axis coarsening strengths of amg_T and the pc_ctr hierarchy on grid `gam`: |E|/h_a^2,
 // or with spacing the mean of |e|/(d_P + d_M) over the axis's interior faces

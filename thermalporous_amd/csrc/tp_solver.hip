@@ -728,7 +728,7 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
         double *v = single ? W : c->V.p + (long)j * nv, *z = single ? Zt : c->Z.p + (long)j * nv;
         pc_apply(c, v, z);
         if (single) basis_round_store(c, B, Zt, c->Zs.p + (long)j * vs);
-        spmv_block_halo(c, c->J.p, z, w_of(j));                  // (multi-GPU: exchange of z_j's halos overlapped)
+        krylov_apply(c, z, w_of(j));                             // J z_j plus the wells' rank-1 terms (multi-GPU: exchange of z_j's halos overlapped)
     };
     auto orth = [&](int j, double *host_out) {                   // h = V^T w ; w -= V h ; ||w||^2 (host_out null: no host wait yet)
         if (single) orthogonalize_s(c, B, c->Vs.p, vs, j + 1, W, host_out);
@@ -810,7 +810,7 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
                 vec_copy(c, x, xm, nv);
                 add_Zy(k, ym.data(), xm);
                 if (c->dist) halo_exchange(c, g, xm, B, g.ntot);
-                resid_block_cols(c, c->J.p, bvec, xm, B, rm);
+                krylov_resid(c, bvec, xm, rm);
                 // (each field plane as a 1-field vector)
                 for (int f = 0; f < B; ++f) { const double *one[1] = {rm + (long)f * g.ntot}; multi_norm2sq(c, 1, 1, one, &fn[f]); fn[f] = std::sqrt(fn[f]); }
                 c->monitor(its, res, fn.data(), B, c->monitor_user);
@@ -834,7 +834,7 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
         }
         // r = b - J x: to restart from and, in the fp32 form, the only verdict
         if (c->dist) halo_exchange(c, g, x, B, g.ntot);
-        resid_block_cols(c, c->J.p, bvec, x, B, c->w2.p);
+        krylov_resid(c, bvec, x, c->w2.p);
         beta = norm2(c, B, c->w2.p);
         rsrc = c->w2.p;
         // (fp64: no finiteness test here -- a non-finite beta surfaces as -9 one iteration later, with that iteration counted)

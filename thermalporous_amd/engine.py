@@ -75,6 +75,23 @@ class tp_satfn(C.Structure):
                 ("lmbda", C.c_double), ("p_ct", C.c_double), ("pc_se_min", C.c_double)]
 
 
+class tp_well(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("shut", C.c_int32), ("rate", C.c_double), ("bhp_limit", C.c_double), ("z_ref", C.c_double),
+                ("first", C.c_int32), ("count", C.c_int32)]
+
+
+class tp_perf(C.Structure):
+    _fields_ = [("cell", C.c_int64), ("WI", C.c_double), ("z", C.c_double)]
+
+
+class tp_well_state(C.Structure):
+    _fields_ = [("bhp", C.c_double), ("mode", C.c_int32), ("rounds", C.c_int32), ("rate", C.c_double), ("water_rate", C.c_double),
+                ("oil_rate", C.c_double), ("rho", C.c_double), ("nopen", C.c_int32), ("reserved", C.c_int32)]
+
+
+WELL_KINDS = {"prod": 0, "inj": 1, 0: 0, 1: 1}
+WELL_MODES = {0: "shut", 1: "rate", 2: "bhp"}
+
 # every symbol include/thermalporous_hip.h declares (tests check that the library exports them all)
 API_SYMBOLS = (
     "tp_last_error", "tp_version", "tp_create", "tp_destroy", "tp_set_options", "tp_comm_unique_id", "tp_comm_init",
@@ -91,6 +108,7 @@ API_SYMBOLS = (
     "tp_stage_rhs", "tp_ew_next_rtol", "tp_ew_info", "tp_ew_history", "tp_ctr_rhs", "tp_ctr_apply", "tp_ctr_info",
     "tp_schur_info", "tp_set_boundary", "tp_boundary_flux", "tp_set_spacing", "tp_spacing_info",
     "tp_set_saturation_functions", "tp_saturation_info",
+    "tp_set_wells", "tp_set_well_control", "tp_well_info", "tp_well_perf_rates", "tp_well_factors",
 )
 
 DEFAULT_OPTS = dict(
@@ -590,6 +608,50 @@ def check_boundary_slabs(boundary, nranks=1):
                                   % (sorted(boundary), int(nranks)))
 
 
+def check_wells_slabs(wells, nranks=1, local_group=None, comm_bootstrap=None):
+    """Completed wells (spec["wells"], HipEngine.set_wells) against the slab count: refused naming both."""
+    if wells and (int(nranks) > 1 or local_group is not None or comm_bootstrap is not None):
+        raise NotImplementedError("wells (%s) with nranks = %d or a communicator: completed wells are implemented for one slab"
+                                  % (", ".join(str(w.get("name", i)) for i, w in enumerate(wells)), int(nranks)))
+
+
+def check_wells(wells, ncells):
+    """spec["wells"] as the library will check it, with the well's name in every message: a list of dicts with name, kind
+    ("prod" | "inj"), rate (>= 0), bhp (the limit), cells (flat internal indices), WI (> 0), z (elevations), optional z_ref (the
+    highest perforation's elevation by default) and shut.  Returns the list with arrays and defaults filled in."""
+    out, seen = [], {}
+    for i, w in enumerate(wells or []):
+        name = str(w.get("name", "well%d" % i))
+        if w.get("kind") not in WELL_KINDS:
+            raise ValueError("well %r: kind = %r: 'prod' or 'inj'" % (name, w.get("kind")))
+        cells = np.asarray(w["cells"], dtype=np.int64).reshape(-1)
+        WI = np.asarray(w["WI"], dtype=float).reshape(-1)
+        z = np.asarray(w["z"], dtype=float).reshape(-1)
+        if cells.size == 0:
+            raise ValueError("well %r has no perforation" % name)
+        if not (cells.size == WI.size == z.size):
+            raise ValueError("well %r: %d cells, %d WI, %d z: one of each per perforation" % (name, cells.size, WI.size, z.size))
+        rate, bhp = float(w["rate"]), float(w["bhp"])
+        z_ref = float(z.max() if w.get("z_ref") is None else w["z_ref"])
+        if not (np.isfinite([rate, bhp, z_ref]).all() and np.isfinite(WI).all() and np.isfinite(z).all()):
+            raise ValueError("well %r: rate, bhp, z_ref, WI and z must be finite numbers" % name)
+        if rate < 0.0:
+            raise ValueError("well %r: rate = %r: the total rate target, >= 0" % (name, rate))
+        if not (WI > 0.0).all():
+            raise ValueError("well %r: WI = %r at perforation %d: the connection index, > 0" % (name, float(WI[WI <= 0.0][0]), int(np.argmax(WI <= 0.0))))
+        if cells.min() < 0 or cells.max() >= int(ncells):
+            raise ValueError("well %r: cell %d lies outside the box of %d cells" % (name, int(cells[(cells < 0) | (cells >= ncells)][0]), int(ncells)))
+        for c in cells.tolist():
+            if c in seen:
+                raise ValueError("well %r: cell %d is already perforated by well %r: a cell may carry one perforation" % (name, c, seen[c]))
+            seen[c] = name
+        if name in [o["name"] for o in out]:
+            raise ValueError("two wells are called %r" % name)
+        out.append({"name": name, "kind": "inj" if WELL_KINDS[w["kind"]] else "prod", "rate": rate, "bhp": bhp, "z_ref": z_ref,
+                    "shut": bool(w.get("shut", False)), "cells": cells, "WI": WI, "z": z})
+    return out
+
+
 def check_spacing_slabs(hs, nranks=1, local_group=None, comm_bootstrap=None):
     """Graded widths (spec["hs"]) against slabs: refused, naming both, before any context exists."""
     if hs is None:
@@ -670,10 +732,12 @@ def slab_range(gn2, rank, nranks):
 class HipEngine:
     """Same interface as oracle.engine.OracleEngine; all arithmetic on the GPU."""
     supports_satfn = True          # spec["satfn"] is honoured (thermalmodel.init_solver refuses engines that do not say so)
+    supports_wells = True          # spec["wells"] likewise
 
     def __init__(self, spec, opts=None, rank=0, nranks=1, device=None, comm_bootstrap=None, local_group=None):
         check_boundary_slabs(spec.get("boundary"), nranks)       # (host-side: before the library and any context)
         check_spacing_slabs(spec.get("hs"), nranks, local_group, comm_bootstrap)
+        check_wells_slabs(spec.get("wells"), nranks, local_group, comm_bootstrap)
         self.lib = load_library()
         self.spec = spec
         self.opts = dict(DEFAULT_OPTS)
@@ -726,7 +790,10 @@ class HipEngine:
         if spec.get("satfn") is not None:
             self.set_saturation_functions(spec["satfn"])
         self._set_sources(spec.get("sources"))
-        self.boundary = {}                     # side id -> the entry in force (spec["boundary"] layout)
+        self.wells = []                        # completed wells in force (check_wells' dicts; spec["wells"] layout)
+        if spec.get("wells"):
+            self.set_wells(spec["wells"])
+        self.boundary = {}                   # side id -> the entry in force (spec["boundary"] layout)
         for side, e in sorted((spec.get("boundary") or {}).items()):
             self.set_boundary(side, e["kind"], p=e["p"], T=e["T"], S=e.get("S"))
         self.last = {}
@@ -992,6 +1059,84 @@ class HipEngine:
         inv = np.empty(n, dtype=int)
         inv[self._src_order] = np.arange(n)
         return {"rate": r[inv], "water_rate": w[inv], "oil_rate": o[inv]}
+
+    # ---- completed wells (completedwells.py; include/thermalporous_hip.h: tp_set_wells) ----------------
+    def set_wells(self, wells):
+        """The completed wells (spec["wells"]: check_wells' list of dicts), or None / [] to remove them."""
+        check_wells_slabs(wells, self.nranks)
+        ws = check_wells(wells, self.gn[0]*self.gn[1]*self.gn[2])
+        if not ws:
+            self._ck(self.lib.tp_set_wells(self.ctx, 0, None, 0, None))
+            self.wells = []
+            return
+        nperf = sum(w["cells"].size for w in ws)
+        warr, parr = (tp_well*len(ws))(), (tp_perf*nperf)()
+        k = 0
+        for i, w in enumerate(ws):
+            warr[i] = tp_well(WELL_KINDS[w["kind"]], int(w["shut"]), w["rate"], w["bhp"], w["z_ref"], k, w["cells"].size)
+            for c, wi, z in zip(w["cells"], w["WI"], w["z"]):
+                parr[k] = tp_perf(int(c) + self.np_, float(wi), float(z))       # (one slab: local = global + the halo plane)
+                k += 1
+        self._ck(self.lib.tp_set_wells(self.ctx, len(ws), warr, nperf, parr))
+        self.wells = ws
+
+    def _well_index(self, well):
+        if isinstance(well, str):
+            names = [w["name"] for w in self.wells]
+            if well not in names:
+                raise KeyError("no well called %r (wells: %s)" % (well, ", ".join(names) or "none"))
+            return names.index(well)
+        return int(well)
+
+    def set_well_control(self, well, rate=None, bhp=None, shut=None):
+        """New targets of one well (by name or index) between two time steps; None keeps what is in force."""
+        i = self._well_index(well)
+        if not 0 <= i < len(self.wells):
+            raise IndexError("well %r: the engine has %d wells" % (well, len(self.wells)))
+        w = self.wells[i]
+        rate = w["rate"] if rate is None else float(rate)
+        bhp = w["bhp"] if bhp is None else float(bhp)
+        shut = w["shut"] if shut is None else bool(shut)
+        self._ck(self.lib.tp_set_well_control(self.ctx, i, C.c_double(rate), C.c_double(bhp), int(shut)))
+        w.update(rate=rate, bhp=bhp, shut=shut)
+
+    def well_info(self):
+        """Per well, from the last assembly: name, kind, bhp, mode ("shut" | "rate" | "bhp"), rate, water_rate, oil_rate (sums
+        over the perforations; production negative), rho (the head density), rounds (active-set rounds), nopen."""
+        n = len(self.wells)
+        if n == 0:
+            return []
+        st = (tp_well_state*n)()
+        self._ck(self.lib.tp_well_info(self.ctx, st))
+        return [{"name": w["name"], "kind": w["kind"], "bhp": s.bhp, "mode": WELL_MODES[s.mode], "rate": s.rate,
+                 "water_rate": s.water_rate, "oil_rate": s.oil_rate, "rho": s.rho, "rounds": s.rounds, "nopen": s.nopen}
+                for w, s in zip(self.wells, st)]
+
+    def _perf_split(self, a):
+        out, k = [], 0
+        for w in self.wells:
+            out.append(a[..., k:k + w["cells"].size].copy())
+            k += w["cells"].size
+        return out
+
+    def well_perf_rates(self):
+        """Per well a dict of arrays over its perforations: rate, water_rate, oil_rate of the last assembly."""
+        n = sum(w["cells"].size for w in self.wells)
+        if n == 0:
+            return []
+        r, wt, o = (np.zeros(n) for _ in range(3))
+        self._ck(self.lib.tp_well_perf_rates(self.ctx, _dptr(r), _dptr(wt), _dptr(o)))
+        return [{"rate": a, "water_rate": b, "oil_rate": c}
+                for a, b, c in zip(self._perf_split(r), self._perf_split(wt), self._perf_split(o))]
+
+    def well_factors(self):
+        """Per well (c, b), arrays (b, perforations): the rank-1 term c b^T of the last Jacobian assembly (zeros in BHP mode)."""
+        n = sum(w["cells"].size for w in self.wells)
+        if n == 0:
+            return []
+        c, b = np.zeros((self.b, n)), np.zeros((self.b, n))
+        self._ck(self.lib.tp_well_factors(self.ctx, _dptr(c), _dptr(b)))
+        return list(zip(self._perf_split(c), self._perf_split(b)))
 
     # device vectors for the PC plug-in API / tests
     def vec(self, name):

@@ -10,6 +10,8 @@ the C-ABI consumes through tp_create / tp_set_field / tp_set_params / tp_set_sou
 * fields transposed to internal order, shape (n2, n1, n0);
 * wells/heaters flattened to per-cell source entries with their Peaceman index
   (wellcase.py:182-191 of the reference: hard-coded Dx=Dy=h=5, rw=0.1; Kx,Ky at the cell);
+* ``wells``: the completed wells of a ``CompletedWellCase`` (one dict per well: kind, rate, bhp limit, datum, and per
+  perforation the cell in internal order, the connection index from the cell's true geometry and the elevation), absent without;
 * ``hs``: the cell widths per internal axis of a graded grid (``geo.set_spacing``), absent on a uniform one;
 * ``satfn``: the saturation functions (``params.satfn_dict()``), absent for the linear curves without capillary pressure.
 """
@@ -120,6 +122,10 @@ def build_spec(geo, case, params, nphase, axes=None):
         "WI": np.array([peaceman_WI(kx[c], ky[c]) if e[1] != HEATER else 0.0 for e, c in zip(ent, cells)], dtype=float),
         "const": np.array([1 if e[5] else 0 for e in ent], dtype=np.int32),
     }
+    # completed wells (completedwells.py): their cells in internal order; no key for a case without them
+    wells = case.well_entries() if case is not None and hasattr(case, "well_entries") else []
+    if wells:
+        spec["wells"] = [dict(w, cells=phys_flat_to_internal(w["cells"], geo, axes)) for w in wells]
     if getattr(geo, "graded", False):
         # graded grid (spacing.py): the widths per internal axis; "h" above stays the mean widths, which nothing reads as a
         # cell's size once "hs" is present

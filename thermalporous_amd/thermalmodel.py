@@ -115,6 +115,10 @@ class ThermalModel:
                                       "curves without capillary pressure"
                                       % (self.spec["satfn"]["relperm"], self.spec["satfn"]["capillary"],
                                          getattr(factory, "__name__", factory)))
+        if self.spec.get("wells") and not getattr(factory, "supports_wells", False):
+            raise NotImplementedError("completed wells (%s, spec[\"wells\"]) with the engine %r: they are implemented by HipEngine; "
+                                      "this engine would ignore them" % (", ".join(w["name"] for w in self.spec["wells"]),
+                                                                         getattr(factory, "__name__", factory)))
         if self.comm.size > 1:
             # one process per GPU: this rank's slab of internal axis 2, RCCL bootstrapped through torch.distributed
             from . import parallel
@@ -177,6 +181,9 @@ class ThermalModel:
         """Total injection / production (/ water / oil) rates = sum over entries of delta_i|E_i| * rate_i."""
         r = self.engine.well_rates()
         bnd = self._boundary_energy()
+        wells = self.engine.well_info() if hasattr(self.engine, "well_info") and getattr(self.engine, "wells", None) else []
+        if wells:                                   # completed wells: per well bhp, mode and rates of the last assembly
+            bnd["wells"] = wells
         if not r:
             return bnd
         src = self.spec["sources"]
@@ -212,6 +219,14 @@ class ThermalModel:
         sid, entry = to_internal_side(side, e, (geo.Nx, geo.Ny, geo.Nz), self.spec["axes"], self.nfields - 1, self.params)
         self.engine.set_boundary(sid, entry["kind"], p=entry["p"], T=entry["T"], S=entry["S"])
         self.spec.setdefault("boundary", {})[sid] = entry
+
+    # ---- completed wells (completedwells.py) ---------------------------------------------------------
+    def set_well_control(self, name, rate=None, bhp=None, shut=None):
+        """New rate target, BHP limit or shut flag of the completed well `name`, between two time steps (None keeps a value)."""
+        self.engine.set_well_control(name, rate=rate, bhp=bhp, shut=shut)
+        for w in self.spec.get("wells", []):
+            if w["name"] == name:
+                w.update({k: v for k, v in (("rate", rate), ("bhp", bhp), ("shut", shut)) if v is not None})
 
     def _check_checkpoint_widths(self, chk):
         """A checkpoint holds the cell widths of the grid it was written on (a file from before graded grids holds none: a
@@ -256,6 +271,7 @@ class ThermalModel:
         self.total_nits = 0
         self.nits_vec, self.lits_vec, self.dt_vec, self.timings = [], [], [], []
         self.failed_solves = 0
+        self.well_history = []      # completed wells: (time in days, [(name, bhp, mode, rate, water, oil)]) per time step
         self._outfiles = None
         if self.save:           # (:113-133) initial fields
             self._write_fields()
@@ -325,6 +341,12 @@ class ThermalModel:
             self._log("Total production rate is ", r["prod"])
         for side, q in r.get("boundary_energy", {}).items():
             self._log("Energy flux through side ", side, " is ", q)
+        for w in r.get("wells", []):
+            self._log("Well ", w["name"], ": bhp ", w["bhp"], ", mode ", w["mode"], ", rate ", w["rate"], ", water ", w["water_rate"],
+                      ", oil ", w["oil_rate"])
+        if r.get("wells"):
+            self.well_history.append((self.t/DAY, [(w["name"], w["bhp"], w["mode"], w["rate"], w["water_rate"], w["oil_rate"])
+                                                   for w in r["wells"]]))
 
         u_.assign(u)
         current_dt = float(self.dt.values()[0])
@@ -394,6 +416,8 @@ class ThermalModel:
             self.resultprint("lits = ", lits_vec, ";")
             self.resultprint("dts = ", dt_vec, ";")
             self.resultprint("timings = ", timings, ";")
+            if getattr(self, "well_history", None):
+                self.resultprint("wells = ", self.well_history, ";    # (days, [(name, bhp, mode, rate, water, oil)])")
             self.resultprint("----------------------------------------------------------------------")
             self.resultprint(self.name, "thermal model")
             self.resultprint("Geo model: ", self.geo.name)
