@@ -324,9 +324,13 @@ struct LevelDevT {
 // saves one plane in eleven of a Jacobi sweep.  (REG = false: the stored plane, TP_AMG_INVD_LOAD=1; the line, Gauss-Seidel and
 // tail kernels always read the plane; pre2_cell, which needs it at neighbours too, has its own form of this.)
 template <class R, bool REG>
+__device__ __forceinline__ double invd_from(const LevelDevT<R> &L, R s) {      // s: the cell's diagonal (REG), or its stored omega / diag
+    if constexpr (REG) return (double)(R)(L.omega / (double)s);
+    else return (double)s;
+}
+template <class R, bool REG>
 __device__ __forceinline__ double invd_at(const LevelDevT<R> &L, long c) {
-    if constexpr (REG) return (double)(R)(L.omega / (double)L.op.slot(0)[c]);
-    else return (double)L.invd[c];
+    return invd_from<R, REG>(L, REG ? L.op.slot(0)[c] : L.invd[c]);
 }
 
 __device__ __forceinline__ void nb_offsets(const GridDev &g, long (&off)[7]) {
@@ -361,16 +365,28 @@ __device__ __forceinline__ double pre2_cell(const LevelDevT<R> &L, const double 
     return x1 + ic * (b[c] - s);
 }
 
+// one damped-Jacobi update from its operands: the row's coefficients a, the iterate v at the cell and its six neighbours (slot
+// order), omega / diag and the right-hand side.  The ONE statement of the sweep's arithmetic: jacobi_cell and the tiled
+// k_amg_prolong_jacobi_tile both call it, so the compiler contracts the two paths alike and their results agree bit for bit.
+template <class R>
+__device__ __forceinline__ double jacobi_update(const R (&a)[7], const double (&v)[7], double iv, double bc) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) s += a[k] * v[k];
+    return v[0] + iv * (bc - s);
+}
+
 template <class R, bool REG = false>
 __device__ __forceinline__ double jacobi_cell(const LevelDevT<R> &L, const double *__restrict__ b,
                                               const double *__restrict__ x, long tid) {
     const long c = L.g.np + tid;
     long off[7];
     nb_offsets(L.g, off);
-    double s = 0.0;
+    R a[7];
+    double v[7];
 #pragma unroll
-    for (int k = 0; k < 7; ++k) s += L.op.slot(k)[c] * x[c + off[k]];
-    return x[c] + invd_at<R, REG>(L, c) * (b[c] - s);
+    for (int k = 0; k < 7; ++k) { a[k] = L.op.slot(k)[c]; v[k] = x[c + off[k]]; }
+    return jacobi_update<R>(a, v, invd_at<R, REG>(L, c), b[c]);
 }
 
 template <class R>
@@ -457,6 +473,14 @@ __device__ __forceinline__ double prolong_val(const LevelDevT<R> &Lf, const Grid
     if constexpr (!MASK) return isF ? wm * e0 + (hasR ? wp * e1 : 0.0) : e0;
     const double fF = isF ? 1.0 : 0.0, fR = hasR ? 1.0 : 0.0;
     return (1.0 - fF) * e0 + fF * (wm * e0 + fR * (wp * e1));
+}
+
+// x' = x + P ec at the fine cell (F0, F1, F2), rounded once: what k_amg_prolong_add stores, and what k_amg_prolong_jacobi_tile
+// keeps on chip instead -- one statement for both, so that they hold the same bits
+template <class R>
+__device__ __forceinline__ double prolong_added(const LevelDevT<R> &Lf, const GridDev &gc, const double *__restrict__ ec,
+                                                const double *x, int F0, int F1, int F2) {
+    return x[Lf.g.np + (long)F0 + (long)Lf.g.n0 * F1 + Lf.g.np * F2] + prolong_val<R, false>(Lf, gc, ec, F0, F1, F2);
 }
 
 template <class R, bool REG = false>
@@ -771,9 +795,68 @@ __global__ __launch_bounds__(256) void k_amg_prolong_add(LevelDevT<R> Lf, GridDe
     if (tid >= Lf.g.nown) return;
     int i0, i1, i2;
     cell_ijk(Lf.g, tid, i0, i1, i2);
-    x[Lf.g.np + tid] += prolong_val<R, false>(Lf, gc, ec, i0, i1, i2);
+    x[Lf.g.np + tid] = prolong_added<R>(Lf, gc, ec, x, i0, i1, i2);
 }
 
+// Coarse correction + first post-sweep of a top level in ONE launch that neither stores the corrected iterate x' = x + P ec
+// (k_amg_prolong_add -> k_amg_jacobi: a plane written and read back) nor forms it seven times per cell (k_amg_prolong_jacobi:
+// issue-bound up here).  A workgroup owns a RUN of TP_BLOCK consecutive cells of one plane (flat in-plane index q = i0 + n0 i1, cut
+// anywhere: lines of any length), one cell per thread:
+//   - x' of the run (prolong_added, the value k_amg_prolong_add stores) goes to LDS together with the run's halo -- the n0 cells
+//     before and the n0 cells after it, which hold the -+n0 neighbours of its first and last cells and the -+1 neighbours of its
+//     ends --, formed by the same expression, at most NH per thread (2 n0 <= NH TP_BLOCK); after ONE barrier the four in-plane
+//     neighbours come from LDS;
+//   - x' of the two out-of-plane neighbours is formed directly, by the same expression;
+//   - jacobi_update adds the row in jacobi_cell's order.
+// x' is formed 3 + 2 n0 / TP_BLOCK times per cell instead of 7 (C4, n0 = 85: 3.66), in prolong_val's select form: the weight
+// loads a C cell skips are traffic up here.  The row's own operands are requested after the first two x', in front of the others
+// (measured: DESIGN.md 4.5).  Every coordinate is clamped into the level and every address is in its array: cells outside the
+// level (the overhang of a plane's last run, a halo slot beyond the plane's ends, the planes below the first and above the last)
+// compute on real cells and are either never selected or multiplied by the exact zero coefficient every level keeps towards a
+// physical boundary.  The whole workgroup reaches the barrier; only whole workgroups of the grid's padding return, before it.
+// Levels that are not slab-distributed only (par_of = 0, no open ends: vcycle_impl keeps the two launches and the halo exchange
+// between them there).
+constexpr int PJ_NH_MAX = 4;                // n0 <= PJ_NH_MAX TP_BLOCK / 2 = 512 (vcycle_impl: wider levels keep the two launches)
+template <class R, bool REG, int NH>
+__global__ __launch_bounds__(TP_BLOCK) void k_amg_prolong_jacobi_tile(LevelDevT<R> Lf, GridDev gc, unsigned nruns, unsigned ntiles,
+                                                                      const double *__restrict__ b,
+                                                                      const double *__restrict__ x,
+                                                                      const double *__restrict__ ec, double *__restrict__ out) {
+    __shared__ double s_x[(NH + 1) * TP_BLOCK];                     // n0 halo cells, the run, n0 halo cells
+    const unsigned nb = gridDim.x, bi = blockIdx.x;
+    const unsigned tile = (bi & 7u) * (nb >> 3) + (bi >> 3);       // xcd_tid's block order: neighbouring runs share an L2
+    if (tile >= ntiles) return;                                     // (whole workgroups of the grid's padding)
+    const int t = (int)threadIdx.x;
+    const GridDev &g = Lf.g;
+    const int n0 = g.n0, npl = (int)g.np;
+    const int k = (int)(tile / nruns);
+    const int q0 = (int)(tile - (unsigned)k * nruns) * TP_BLOCK;
+    const int q = q0 + t, qc = min(q, npl - 1);
+    const int i1 = (int)((unsigned)qc / (unsigned)n0), i0 = qc - i1 * n0;
+    const long c = g.np + (long)qc + g.np * k;
+    const double xm = prolong_added<R>(Lf, gc, ec, x, i0, i1, max(k - 1, 0));
+    const double xc = prolong_added<R>(Lf, gc, ec, x, i0, i1, k);
+    R a[7];
+#pragma unroll
+    for (int s = 0; s < 7; ++s) a[s] = Lf.op.slot(s)[c];
+    const R ivs = REG ? a[0] : Lf.invd[c];
+    const double bc = b[c];
+    const double xp = prolong_added<R>(Lf, gc, ec, x, i0, i1, min(k + 1, g.n2 - 1));
+    s_x[n0 + t] = xc;
+#pragma unroll
+    for (int m = 0; m < NH; ++m) {
+        const int h = m * TP_BLOCK + t;
+        const int r = h < n0 ? h : h + TP_BLOCK;                    // slot r holds the plane's cell q0 - n0 + r
+        const int qh = min(max(q0 - n0 + r, 0), npl - 1);
+        const int h1 = (int)((unsigned)qh / (unsigned)n0);
+        const double xh = prolong_added<R>(Lf, gc, ec, x, qh - h1 * n0, h1, k);
+        if (h < 2 * n0) s_x[r] = xh;
+    }
+    __syncthreads();
+    const double v[7] = {xc, s_x[n0 + t - 1], s_x[n0 + t + 1], s_x[t], s_x[2 * n0 + t], xm, xp};
+    const double y = jacobi_update<R>(a, v, invd_from<R, REG>(Lf, ivs), bc);
+    if (q < npl) out[c] = y;
+}
 // ---- line relaxation along axis 0 (tp_options.amg_line_levels) ------------------------------------------------
 // x <- x + omega T^-1 (b - A x), T = tridiag(A[1], A[0], A[2]) along axis 0: one independent system per line (i1, i2), solved
 // by the Thomas algorithm with factors computed once per set-up.  Axis 0 is the fastest in memory, so G consecutive lines
@@ -1534,6 +1617,13 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         if (invd_reg) hipLaunchKernelGGL((KERNEL<R, true>), __VA_ARGS__);                                      \
         else hipLaunchKernelGGL((KERNEL<R, false>), __VA_ARGS__);                                              \
     } while (0)
+    // correction + first post-sweep of the top levels in one tiled launch; TP_AMG_PJ_FUSE=0: k_amg_prolong_add, then k_amg_jacobi
+    static const bool pj_fuse = !(getenv("TP_AMG_PJ_FUSE") && atoi(getenv("TP_AMG_PJ_FUSE")) == 0);
+#define TP_AMG_PJ_LAUNCH(NH)                                                                                                           \
+    do {                                                                                                                       \
+        if (invd_reg) hipLaunchKernelGGL((k_amg_prolong_jacobi_tile<R, true, NH>), gt, dim3(TP_BLOCK), 0, c->stream, Ld, cv.g, nruns, ntiles, bl_, (const double *)src, ec, dst); \
+        else hipLaunchKernelGGL((k_amg_prolong_jacobi_tile<R, false, NH>), gt, dim3(TP_BLOCK), 0, c->stream, Ld, cv.g, nruns, ntiles, bl_, (const double *)src, ec, dst); \
+    } while (0)
     auto paired = [&](int l) {
         if (!pair_on || l < lg || l + 2 > lt || amg->lv[l]->g.nown >= amg->fuse_below) return false;
         if (trunc >= 0 && l + 2 > trunc) return false;          // (the truncation level is among the V(nu,nu) levels: never paired)
@@ -1693,7 +1783,8 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
         double *out = (l == 0) ? x : L->e.p;
         const double *ec = Lc->e.p + cv.off;
         const dim3 gr = xcd_grid(L->g.nown);
-        double *src = xs[l];                        // its halo is still the one exchanged before the residual
+        double *src = xs[l];                        // its halo is still the one exchanged before the residual; the tiled launch
+                                                    // only reads it, the two launches add P ec to it in place
         double *dst = (Ld.post == 1) ? out : (src == L->x.p ? L->x2.p : L->x.p);
         if (l >= 1 && paired(l - 1)) continue;      // transfer-only level folded into its parent's launch
         if (paired(l)) {
@@ -1729,7 +1820,13 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             }
             continue;
         }
-        if (src && L->g.nown >= amg->fuse_below) {
+        if (pj_fuse && l >= lg && src && L->g.nown >= amg->fuse_below && 2 * L->g.n0 <= PJ_NH_MAX * TP_BLOCK) {
+            // x' = src + P ec stays in LDS and registers: one launch, xs[l] is only read (k_amg_prolong_jacobi_tile)
+            const unsigned nruns = (unsigned)((L->g.np + TP_BLOCK - 1) / TP_BLOCK), ntiles = nruns * (unsigned)L->g.n2;
+            const dim3 gt((ntiles + 7u) / 8u * 8u);
+            if (2 * L->g.n0 <= TP_BLOCK) TP_AMG_PJ_LAUNCH(1);
+            else TP_AMG_PJ_LAUNCH(PJ_NH_MAX);
+        } else if (src && L->g.nown >= amg->fuse_below) {
             hipLaunchKernelGGL(k_amg_prolong_add<R>, gr, bl, 0, c->stream, Ld, cv.g, ec, src);
             hx(l, src);
             TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
@@ -1743,6 +1840,7 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
             TP_AMG_REG_LAUNCH(k_amg_jacobi, gr, bl, 0, c->stream, Ld, bl_, (const double *)src, dst);
         }
     }
+#undef TP_AMG_PJ_LAUNCH
 #undef TP_AMG_REG_LAUNCH
     TP_HIP(hipGetLastError());
 }
