@@ -17,11 +17,12 @@ derivative of the energy row with respect to the temperature that enters it EXPL
 the advected heat, the T+ - T- of the conduction, the T of the producers' and heaters' terms -- with densities, mobilities, fluxes
 and conductivities held: residual() takes that temperature from ``self._Tx`` when it is set, and S~ is its complex step.
 
-``SatfnBcProblem`` and ``SatfnGradedProblem`` compose the same overrides with tests/bc_ref.py and tests/graded_ref.py."""
+``SatfnBcProblem``, ``SatfnGradedProblem`` and ``SatfnGradedBcProblem`` compose the same overrides with tests/bc_ref.py and
+tests/graded_ref.py."""
 import numpy as np
 
 from bc_ref import BcProblem
-from graded_ref import GradedProblem
+from graded_ref import GradedBcProblem, GradedProblem
 from oracle import closures as cl
 from oracle import linalg as la
 from oracle.tpfa import HEATER, INJ, PROD, Problem, _hi, _lo, harmonic
@@ -221,9 +222,9 @@ class SatfnGradedProblem(SatfnMixin, GradedProblem):
         super().__init__(spec, hs, satfn=satfn)
 
 
-class SatfnBcProblem(SatfnMixin, BcProblem):
-    def __init__(self, spec, boundary=None, satfn=None):
-        super().__init__(spec, boundary, satfn=satfn)
+class SatfnSidesMixin(SatfnMixin):
+    """The boundary face under saturation functions, for BcProblem or GradedBcProblem behind it: whatever ``_side`` gives as the
+    face's geometry, the phase pressures go through p_c and the water density is taken at p_w on both sides of the face."""
 
     def _bc_flux(self, side, u):
         a, d, sl, sub, (pP, TP, prP), (pM, TM, prM), TK, gam, Ga = self._side(side, u)
@@ -249,11 +250,34 @@ class SatfnBcProblem(SatfnMixin, BcProblem):
         return d, sl, f, phis
 
 
+class SatfnBcProblem(SatfnSidesMixin, BcProblem):
+    def __init__(self, spec, boundary=None, satfn=None):
+        super().__init__(spec, boundary, satfn=satfn)
+
+
+class SatfnGradedBcProblem(SatfnSidesMixin, GradedBcProblem):
+    """All three at once: GradedBcProblem._side gives the boundary cell's own width and face area (gam = g h/4, Ga = 2A/h, T^K =
+    2 K A/h).  With c_P = c_M = h/(4A) the series conduction k_P k_M/(c_P k_M + c_M k_P) is harmonic(k_P, k_M) Ga, so the flux
+    body above carries over unchanged; the interior faces are SatfnGradedProblem's."""
+
+    def __init__(self, spec, boundary=None, hs=None, satfn=None):
+        super().__init__(spec, boundary, hs, satfn=satfn)
+
+
 def satfn_oracle(spec, opts, satfn=None):
     """An OracleEngine whose problem is a SatfnProblem (its preconditioner rebuilt on the new problem)."""
     from oracle.engine import OracleEngine
     o = OracleEngine(spec, opts)
     o.prob = SatfnProblem(spec, satfn=satfn)
+    o.pc = la.TwoStagePC(o.prob, o.opts)
+    return o
+
+
+def satfn_graded_bc_oracle(spec, opts):
+    """An OracleEngine whose problem is a SatfnGradedBcProblem on spec's own widths, sides and curves."""
+    from oracle.engine import OracleEngine
+    o = OracleEngine(spec, opts)
+    o.prob = SatfnGradedBcProblem(spec)
     o.pc = la.TwoStagePC(o.prob, o.opts)
     return o
 

@@ -267,3 +267,78 @@ def test_the_two_calls_are_declared_and_exported():
     lib = engine.load_library()
     assert lib.tp_set_boundary and lib.tp_boundary_flux
     assert hasattr(engine.HipEngine, "set_boundary") and hasattr(engine.HipEngine, "boundary_flux")
+
+
+# ---- the edge inputs of tests/test_gpu_assembly_combos.py -----------------------------------------------------------------------
+@pytest.mark.parametrize("row", [1, 2, 3, 4, 5, 6, 7])
+def test_combination_inputs_meet_their_conditions(row):
+    """Every case of the matrix (edge_cases.COMBO_ROWS): combo_input asserts the check_* condition of the case's builder on the
+    matching reference, whose R, J, S~ and side sums are finite; the kinds that a row must hold are there."""
+    import edge_cases as ec
+    todo = ec.combo_cases(rows=(row,))
+    kinds = {c["kind"] for c in todo}
+    sides = todo[0]["sides"]
+    assert {"sat", "ties", "dead", "no_conduction"} <= kinds
+    assert ({"boundary_ties", "boundary_sat_edges", "dead_on_side"} <= kinds) == bool(sides)
+    assert ("plain" in kinds) == bool(todo[0]["graded"]) and ("all_tie" in kinds) == (row == 2)
+    for case in todo:
+        spec, u = ec.combo_input(case)
+        P, R, J, Sm = ec.combo_reference(spec, u)
+        assert (spec.get("hs") is not None, bool(spec.get("boundary")), spec.get("satfn") is not None) == \
+            (bool(case["graded"]), bool(sides), case["model"] is not None)
+        if row == 7:
+            on = np.zeros(P.shape, dtype=bool)
+            for side in spec["boundary"]:
+                on[side_slice(side)] = True
+            assert on.sum() == 330 > 256                       # more boundary cells than one workgroup of k_assemble_bc holds
+
+
+def test_tie_states_with_a_patch_constant_saturation():
+    import edge_cases as ec
+    spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
+    a, b = ec.edge_state(spec, 3, "ties"), ec.edge_state(spec, 3, "ties", tie_S=True)
+    assert a[:2].tobytes() == b[:2].tobytes() and not np.array_equal(a[2], b[2])
+    assert a[2].tobytes() == cases.perturbed_state(spec, seed=3)[2].tobytes()         # (without the keyword: S as it was)
+    assert np.array_equal(b[2][::2, ::2, ::2], b[2][1::2, ::2, ::2][:, :, :]) and np.array_equal(b[2][:, :, ::2], b[2][:, :, 1::2])
+    # under a capillary pressure the water phase ties only with it
+    from satfn_ref import DEFAULT, M2
+    sat = dict(spec, satfn={**DEFAULT, **M2})
+    assert ec.check_combo_ties(sat, b) > 0
+    with pytest.raises(AssertionError):
+        ec.check_combo_ties(sat, a)
+
+
+@pytest.mark.parametrize("side", [0, 3, 5])
+def test_dead_cells_on_a_side(side):
+    import edge_cases as ec
+    for nphase in (1, 2):
+        spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=nphase)
+        dead = ec.dead_on_side(spec, side)
+        assert not ec.check_dead_on_side(dead, side)
+        sl = side_slice(side)
+        zero = np.all([k == 0.0 for k in dead["K"]], axis=0)
+        assert zero.sum() == 8 and zero[sl].sum() == 4 and (dead["phi"][sl] == 0.0).sum() == 1 and (dead["phi"] == 1.0).sum() == 1
+        a = side//2
+        i0, i1 = np.argwhere(dead["phi"] == 0.0)[0], np.argwhere(dead["phi"] == 1.0)[0]
+        assert abs(i0[2 - a] - i1[2 - a]) == 1 and np.abs(i0 - i1).sum() == 1              # the inward neighbour
+        u = cases.perturbed_state(spec, seed=3)
+        B = make_boundary(spec, u, {side: "open"}, seed=4)
+        P = BcProblem(dead, B)
+        P.set_old(u)
+        P.set_dt(8640.0)
+        P.residual(u)
+        J = P.jacobian(u)
+        # the dead cell with phi == 0 on the side: no mass row at all
+        c = tuple(i0)
+        rows = [0] if nphase == 1 else [0, 2]
+        assert all(np.all(J[(slice(None), r, slice(None)) + c] == 0.0) for r in rows)
+    # a box that is all block: the whole side is dead and carries no mass
+    spec, *_ = cases.c4_spe10_3d(Nx=2, Ny=2, Nz=2, nphase=2)
+    dead = ec.dead_on_side(spec, side)
+    assert ec.check_dead_on_side(dead, side)
+    u = cases.perturbed_state(spec, seed=3)
+    P = BcProblem(dead, make_boundary(spec, u, {side: "open"}, seed=4))
+    P.set_old(u)
+    P.set_dt(8640.0)
+    P.residual(u)
+    assert np.all(P.last_flux[side, [0, 2]] == 0.0) and P.last_flux[side, 1] != 0.0

@@ -68,6 +68,8 @@ ENTRY = [
     ("2ph_3d_6x5x4_open_side", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=2), _four_wells, PLAN4, dict(side=True)),
     ("2ph_3d_6x5x4_M2", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=2), _four_wells, PLAN4, dict(satfn=M2)),
     ("2ph_3d_5x6x4_M2_graded", cases.c4_spe10_3d, dict(Nx=5, Ny=6, Nz=4, nphase=2), _four_wells, PLAN4, dict(satfn=M2, graded=True)),
+    ("2ph_3d_6x5x4_M2_graded_open_side", cases.c4_spe10_3d, dict(Nx=6, Ny=5, Nz=4, nphase=2), _four_wells, PLAN4,
+     dict(satfn=M2, graded=True, side=True)),
 ]
 _CACHE = {}
 

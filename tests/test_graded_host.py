@@ -98,6 +98,47 @@ def test_graded_sides_reduce_to_the_uniform_sides_and_differentiate_exactly():
             _close(J2[:, r, c], Jc[:, r, c], ("J", r, c))
 
 
+def test_per_row_bound_of_the_combination_tests():
+    """test_gpu_assembly_combos.py bounds, per cell and equation, the difference of a row of J by TOL_ROW times the row's own
+    largest entry.  The bound is not chosen: at that file's graded inputs with sides (row 3 of edge_cases.COMBO_ROWS, every
+    edge kind and the geometric widths), the largest such per-row difference between two evaluations of the reference itself --
+    GradedBcProblem's analytic Jacobian and the complex step of its residual -- is measured here, and
+    TOL_ROW = max(1e-11, 10 x that): the factor 10 for the GPU's other summation order over at most 13 terms per entry."""
+    import edge_cases as ec
+    worst, n = 0.0, 0
+    for case in ec.combo_cases(rows=(3,)):
+        spec, u = ec.combo_input(case)
+        G = GradedBcProblem(spec)
+        G.set_old(u)
+        G.set_dt(ec.COMBO_DT)
+        J, Sm = G.jacobian(u, want_schur=True)
+        eJ, _ = ec.per_row_errors(J, Sm, G.jacobian_complex_step(u), Sm)
+        print("%s: largest per-row difference analytic - complex step %.3e" % (case["id"], eJ))
+        worst, n = max(worst, eJ), n + 1
+    print("largest per-row difference over %d cases: %.3e; TOL_ROW = %.3e" % (n, worst, ec.TOL_ROW))
+    assert n >= 20 and np.isfinite(worst) and worst > 0.0
+    assert ec.TOL_ROW == max(1e-11, 10.0*worst)
+
+
+def test_per_row_rule_sees_a_thin_cell_that_the_per_block_rule_misses():
+    """Neighbour ratio 4 (row 3's geometric case): an error of half the per-block bound -- 0.5e-11 of the grid's largest dT
+    entry of the energy row -- in the cell whose energy row is the smallest passes the rule per block and misses the per-row
+    rule by the ratio of the two scales, more than two orders of magnitude."""
+    import edge_cases as ec
+    from test_gpu_assembly_edges import assert_entries
+    case = [c for c in ec.combo_cases(rows=(3,)) if c["kind"] == "plain"][0]
+    spec, u = ec.combo_input(case)
+    P, R, J, Sm = ec.combo_reference(spec, u)
+    scale = np.abs(J[:, 1]).max(axis=(0, 1))
+    cell = np.unravel_index(np.argmin(scale), scale.shape)
+    top = np.abs(J[:, 1, 1]).max()
+    assert scale[cell] < 1e-2*top
+    bad = np.array(J)
+    bad[(0, 1, 1) + cell] += 0.5e-11*top
+    assert_entries(R, bad, Sm, R, J, Sm, "thin cell")
+    assert ec.per_row_errors(bad, Sm, J, Sm)[0] > 10.0*ec.TOL_ROW
+
+
 def test_the_reference_alone_meets_the_hydrostatic_bound():
     spec, u, scale = hydrostatic_graded_column()
     res = []

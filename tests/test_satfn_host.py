@@ -284,3 +284,91 @@ def test_capillary_gravity_column_is_an_equilibrium_of_the_reference():
     Q.set_dt(1e10)
     F0 = column_face_fluxes(Q, Q.residual(u))
     assert np.abs(F0[0]/scale[0]).max() > 0.05
+
+
+# ---- a graded grid, Dirichlet sides and saturation functions at once ----------------------------------------------------------
+def _triple_box():
+    """Two-phase 5x6x4 with its wells and heaters, an open top (gravity in the driving force), an open lateral side and a thermal
+    one, at perturbed_state."""
+    from bc_ref import make_boundary
+    spec, *_ = cases.c4_spe10_3d(Nx=5, Ny=6, Nz=4, nphase=2)
+    assert spec["gaxis"] == 0
+    u = cases.perturbed_state(spec, seed=3)
+    return spec, u, make_boundary(spec, u, {1: "open", 4: "open", 3: "thermal"}, seed=4)
+
+
+def _max_close(a, b, bound, tag):
+    assert np.abs(a - b).max() <= bound*np.abs(b).max(), (tag, np.abs(a - b).max(), np.abs(b).max())
+
+
+def test_triple_with_equal_widths_is_the_uniform_sides_reference():
+    from graded_ref import equal_widths
+    from satfn_ref import SatfnBcProblem, SatfnGradedBcProblem
+    spec, u, B = _triple_box()
+    for sat in (M2, M3):
+        R0, J0, S0 = _all(SatfnBcProblem(spec, B, satfn=sat), u)
+        P = SatfnGradedBcProblem(spec, B, equal_widths(spec), satfn=sat)
+        R1, J1, S1 = _all(P, u)
+        assert np.abs(P.last_flux[[1, 3, 4], 1]).min() > 0.0 and np.abs(P.last_flux[[1, 4]]).min() > 0.0
+        for f in range(3):
+            _max_close(R1[f], R0[f], 1e-12, ("R", f))
+            for c in range(3):
+                _max_close(J1[:, f, c], J0[:, f, c], 1e-12, ("J", f, c))
+        _max_close(S1, S0, 1e-12, "S~")
+
+
+def test_triple_in_the_degenerate_corey_case_is_the_graded_sides_reference():
+    """GradedBcProblem's Jacobian is analytic: it thereby checks the complex-step one of the composed class, sides included."""
+    from graded_ref import GradedBcProblem, random_widths, spec_lengths
+    from satfn_ref import SatfnGradedBcProblem
+    spec, u, B = _triple_box()
+    hs = random_widths(spec["n"], spec_lengths(spec), 7)
+    G = GradedBcProblem(spec, B, hs)
+    Ro, Jo, So = _all(G, u)
+    P = SatfnGradedBcProblem(spec, B, hs, satfn=DEGENERATE)
+    R, J, Sm = _all(P, u)
+    assert_entries(R, J, Sm, Ro, Jo, So, "degenerate triple")
+    for q in range(3):
+        assert np.abs(P.last_flux[:, q] - G.last_flux[:, q]).max() <= TOL*np.abs(G.last_flux[:, q]).max()
+
+
+def test_triple_without_sides_is_the_graded_reference_bit_for_bit():
+    from graded_ref import random_widths, spec_lengths
+    from satfn_ref import SatfnGradedBcProblem, SatfnGradedProblem
+    spec, u, _ = _triple_box()
+    hs = random_widths(spec["n"], spec_lengths(spec), 7)
+    a = _all(SatfnGradedProblem(spec, hs, satfn=M2), u)
+    b = _all(SatfnGradedBcProblem(spec, {}, hs, satfn=M2), u)
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_wells_reference_composes_the_triple():
+    from satfn_ref import SatfnGradedBcProblem
+    from graded_ref import random_widths, spec_lengths
+    from wells_ref import wells_problem
+    spec, u, B = _triple_box()
+    spec = dict(spec, hs=random_widths(spec["n"], spec_lengths(spec), 7), boundary=B, satfn={**M2})
+    W = wells_problem(spec, wells=[])
+    assert isinstance(W, SatfnGradedBcProblem) and type(W).__name__ == "WellsSatfnGradedBcProblem"
+    a, b = _all(W, u), _all(SatfnGradedBcProblem(spec), u)
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_the_lines_saturation_edge_cases_hold_every_pair_together():
+    """Five cells cannot hold S_o = Sr_o, S_o = 1 - Sr_w and the four values of SAT_EDGES: each model's case holds two or three
+    of the four (each against S_b = 0 and S_b = 1), the three together all of them; every other box holds all in each case."""
+    import edge_cases as ec
+    line, other = set(), 0
+    for case in ec.combo_cases(rows=(6,)):
+        if case["kind"] != "boundary_sat_edges":
+            continue
+        spec, u = ec.combo_input(case)
+        pairs = ec.boundary_sat_pairs(spec, u)
+        if "line" in case["box"]:
+            line |= pairs
+        else:
+            other += 1
+            assert pairs == ec.ALL_SIDE_SAT_PAIRS
+    assert line == ec.ALL_SIDE_SAT_PAIRS and other == 9

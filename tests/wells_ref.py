@@ -319,7 +319,8 @@ def wells_problem(spec, hs=None, boundary=None, satfn=None, wells=None):
         return type("WellsBcProblem", (WellsMixin, BcProblem), {})(spec, boundary, wells=wells)
     if hs is None and not boundary and satfn is None:
         return WellsProblem(spec, wells=wells)
-    raise NotImplementedError("no reference composes a graded grid, a Dirichlet side and saturation functions at once")
+    from satfn_ref import SatfnGradedBcProblem
+    return type("WellsSatfnGradedBcProblem", (WellsMixin, SatfnGradedBcProblem), {})(spec, boundary, hs, satfn=satfn, wells=wells)
 
 
 def wells_oracle(spec, opts, wells=None):
