@@ -156,10 +156,16 @@ class OracleEngine:
         return rates
 
     # the hot path --------------------------------------------------------------------------
+    def operator(self, J):
+        """x -> J x, plus the wells' rank-1 terms sum_w c_w (b_w . x) of the last jacobian() call where the problem has wells."""
+        if self.prob.wells:
+            return lambda x: la.spmv_block(J, x) + self.prob.rank1(x)
+        return lambda x: la.spmv_block(J, x)
+
     def linear_solve(self, J, Sm, F):
         o = self.opts
-        self.pc.setup(J, Sm)
-        return la.fgmres(lambda x: la.spmv_block(J, x), self.pc.apply, F, rtol=o["ksp_rtol"], atol=o["ksp_atol"],
+        self.pc.setup(J, Sm)                     # (on J alone: the rank-1 terms are the Krylov operator's only)
+        return la.fgmres(self.operator(J), self.pc.apply, F, rtol=o["ksp_rtol"], atol=o["ksp_atol"],
                          restart=o["ksp_restart"], maxit=o["ksp_max_it"])
 
     def newton_solve(self):

@@ -11,10 +11,27 @@ Restates the UFL forms of the reference for a DG0 space on a rectangle/box mesh,
 Layout ("internal" axes): cell arrays have shape (n2, n1, n0), internal axis 0 fastest.
 ``spec`` (plain data, produced by thermalporous_amd.problem.build_spec) holds
   nphase, n=(n0,n1,n2), h=(h0,h1,h2), gaxis (internal axis with gravity or -1),
-  phi, K=[K0,K1,K2], kT (1-phase static conductivity), prm (dict), sources (dict of arrays).
+  phi, K=[K0,K1,K2], kT (1-phase static conductivity), prm (dict), sources (dict of arrays)
+and, beyond the reference, each optional and each also an argument of ``Problem``:
+  hs        per internal axis one width per cell index: the graded grid (``GradedGeometry``; without it ``UniformGeometry``)
+  boundary  {side 2a+d: {"kind": "open" | "thermal", "p", "T", "S"}}: Dirichlet sides, arrays shaped like the side
+  satfn     Corey / Brooks-Corey relative permeabilities and a capillary pressure (``curves``)
+  wells     completed wells: many cells, one BHP (oracle/wells.py)
 Orientation: along every internal axis '+' is the lower-index cell; on the gravity axis
 this is the lower cell in space (z up), so that hydrostatic equilibrium gives zero flux
 (singlephase.py:215, twophase.py:317-318).
+
+A boundary face of side ``2*a + d`` is an interior face between the cell and a ghost state (p_b, T_b[, S_b]) half a cell away, the
+ghost's properties evaluated with the cell's own phi and static kT.  On a high side (d = 1) the cell is P, the ghost M and R += f,
+Jdiag += dP, S~diag += sP; on a low side the ghost is P, the cell M and R -= f, Jdiag -= dM, S~diag -= sM.  A thermal side has
+T^K = 0.  ``last_flux`` (6, b) and ``last_phi`` hold the per-side sums and driving forces of the last residual() call.
+
+Saturation functions: p_w = p - p_c(S_o) is the water's pressure in its density (accumulation, mobility, gravity head) and in its
+driving force; wells take drawdown and densities at p.  Every branch is taken on the real part, so a complex perturbation
+differentiates the branch in force: the Jacobian is then the complex step of residual(), and S~ the complex step over the
+temperature that enters the energy row EXPLICITLY (``_Tx``: the T of (e0 + rock) T, the upwind T of the advected heat, the
+T+ - T- of the conduction, the T of the producers' and heaters' terms), densities, mobilities, fluxes and conductivities held.
+Without them the closures are linear and carry their derivatives, and the Jacobian and S~ are analytic.
 
 Stencil slots of the Jacobian: 0 diag, 1 (-a0), 2 (+a0), 3 (-a1), 4 (+a1), 5 (-a2), 6 (+a2).
 Unknown/equation order: (p,T[,S_o]) <-> (mass|pressure-eq, energy[, oil]).
@@ -22,6 +39,7 @@ Unknown/equation order: (p,T[,S_o]) <-> (mass|pressure-eq, energy[, oil]).
 import numpy as np
 
 from . import closures as cl
+from .wells import HSTEP, Wells
 
 PROD, INJ, HEATER = 0, 1, 2
 
@@ -42,6 +60,14 @@ def _hi(a):
     return tuple(s)
 
 
+def side_slice(side):
+    """Index of the side's cells in an (n2, n1, n0) array."""
+    a, d = divmod(int(side), 2)
+    sl = [slice(None)]*3
+    sl[2 - a] = -1 if d else 0
+    return tuple(sl)
+
+
 def harmonic(ap, am):
     """conditional(gt(avg(a),0), a('+')a('-')/avg(a), 0)  (singlephase.py:98-103)."""
     s = ap + am
@@ -50,8 +76,169 @@ def harmonic(ap, am):
     return h
 
 
+def harmonic_conduction(kP, kM, G, deriv=False):
+    """H = harmonic(k_P, k_M) G and, if asked (real k only), dH/dk_P and dH/dk_M."""
+    H = harmonic(kP, kM) * G
+    if not deriv:
+        return H, None, None
+    s2 = kP + kM
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dHP = np.where(s2 > 0, 2 * kM ** 2 / np.where(s2 == 0, 1, s2) ** 2, 0.0)
+        dHM = np.where(s2 > 0, 2 * kP ** 2 / np.where(s2 == 0, 1, s2) ** 2, 0.0)
+    return H, G * dHP, G * dHM
+
+
+def series(cP, cM, kP, kM):
+    """k_P k_M/(c_P k_M + c_M k_P), 0 where the denominator is not positive; and the denominator."""
+    D = cP*kM + cM*kP
+    with np.errstate(divide="ignore", invalid="ignore"):
+        H = np.where(D.real > 0.0, kP*kM/np.where(D == 0, 1.0, D), 0.0)
+    return H, D
+
+
+# ---- geometry: what differs between a uniform and a graded grid -----------------------------------------------------------------
+class UniformGeometry:
+    """One width h_a per axis, scalar arithmetic: T^K = H(K) V/h^2, conduction H(k) G dT with G = V/h^2, gam = g h/2.
+    Sides: T^K = 2 K V/h^2, Ga = 2 V/h^2, gam = g h/4."""
+
+    def __init__(self, n, h, K, gaxis, g):
+        self.n, self.h, self.K, self.gaxis, self.g = n, h, K, gaxis, g
+        self.vol = h[0] * h[1] * h[2]
+        self.TK, self.G = [], []
+        for a in range(3):
+            t = np.zeros(K[a].shape)
+            if n[a] > 1:
+                t[_lo(a)] = harmonic(K[a][_lo(a)], K[a][_hi(a)]) * (self.vol / h[a] ** 2)
+            self.TK.append(t)
+            self.G.append(self.vol / h[a] ** 2)
+
+    def gam(self, a):
+        return self.g * self.h[a] * 0.5 if a == self.gaxis else 0.0
+
+    def conduction(self, a, kP, kM, deriv=False):
+        return harmonic_conduction(kP, kM, self.G[a], deriv)
+
+    def side(self, a, sl):
+        geom = self.vol/self.h[a]**2
+        return 2.0*self.K[a][sl]*geom, (self.g*self.h[a]*0.25 if a == self.gaxis else 0.0), 2.0*geom
+
+
+class GradedGeometry:
+    """Widths ``hs[a][i]`` per cell index along each internal axis, cell volume V_c = hs[0][i0] hs[1][i1] hs[2][i2].  A face
+    along a between the cells P and M: area A = V_P/h_a[i_P], half distances d = h_a/2, c = d/A on each side.  T^K = K_P K_M/(c_P
+    K_M + c_M K_P) (0 where the denominator is not positive), gam = g (d_P + d_M)/2, conduction H = k_P k_M/D, D = c_P k_M + c_M
+    k_P, dH/dk_P = c_P k_M^2/D^2, dH/dk_M = c_M k_P^2/D^2.  Sides: K_M = K_P and both half distances h_a/4 of the boundary cell,
+    i.e. T^K = 2 K A/h, Ga = 2A/h and gam = g h/4 with the cell's own width and face area.
+    ``G[a]``: the coarsening strengths the library takes for amg_T with spacing (``mean_strength``), so that the oracle's
+    TwoStagePC coarsens as the GPU does."""
+
+    def __init__(self, n, hs, K, gaxis, g):
+        self.n, self.K, self.gaxis, self.g = n, K, gaxis, g
+        self.hs = tuple(np.asarray(hs[a], dtype=float).reshape(-1).copy() for a in range(3))
+        assert all(self.hs[a].size == n[a] and (self.hs[a] > 0).all() for a in range(3))
+        h0, h1, h2 = self.hs
+        self.vol = h2[:, None, None]*h1[None, :, None]*h0[None, None, :]          # (n2, n1, n0)
+        # per axis: the cell's width as an array over the cells, the face area, c = (h/2)/A per cell
+        self.ha, self.Aa, self.ca = [], [], []
+        for a in range(3):
+            sh = [1, 1, 1]
+            sh[2 - a] = n[a]
+            ha = np.broadcast_to(self.hs[a].reshape(sh), self.vol.shape)
+            A = self.vol/ha
+            self.ha.append(ha)
+            self.Aa.append(A)
+            self.ca.append(0.5*ha/A)
+        self.TK, self.G = [], []
+        for a in range(3):
+            t = np.zeros(self.vol.shape)
+            if n[a] > 1:
+                lo, hi = _lo(a), _hi(a)
+                t[lo] = series(self.ca[a][lo], self.ca[a][hi], K[a][lo], K[a][hi])[0]
+            self.TK.append(t)
+            self.G.append(self.mean_strength(a))
+
+    def mean_strength(self, a):
+        """Mean of A/(d_P + d_M) over the interior faces of axis a, formed as the library forms it."""
+        if self.n[a] <= 1:
+            return 0.0
+        area = 1.0
+        for o in range(3):
+            if o != a:
+                area *= float(np.sum(self.hs[o]))/self.hs[o].size
+        w = self.hs[a]
+        inv = float(np.sum(1.0/(0.5*(w[:-1] + w[1:]))))
+        return area*inv/(w.size - 1)
+
+    def gam(self, a):
+        lo, hi = _lo(a), _hi(a)
+        if a != self.gaxis:
+            return np.zeros(self.ha[a][lo].shape)
+        return self.g*0.25*(self.ha[a][lo] + self.ha[a][hi])
+
+    def conduction(self, a, kP, kM, deriv=False):
+        cP, cM = self.ca[a][_lo(a)], self.ca[a][_hi(a)]
+        H, D = series(cP, cM, kP, kM)
+        if not deriv:
+            return H, None, None
+        with np.errstate(divide="ignore", invalid="ignore"):
+            D2 = np.where(D == 0, 1.0, D)**2
+            return H, np.where(D > 0, cP*kM**2/D2, 0.0), np.where(D > 0, cM*kP**2/D2, 0.0)
+
+    def side(self, a, sl):
+        h, A = self.ha[a][sl], self.Aa[a][sl]                   # the boundary cell's own width and face area
+        return 2.0*self.K[a][sl]*A/h, (self.g*h*0.25 if a == self.gaxis else np.zeros(h.shape)), 2.0*A/h
+
+
+# ---- saturation functions -------------------------------------------------------------------------------------------------------
+SATFN_DEFAULT = {"relperm": "linear", "capillary": None, "Sr_o": 0.0, "Sr_w": 0.0, "n_o": 2.0, "n_w": 2.0, "kro_max": 1.0,
+                 "krw_max": 1.0, "lmbda": 2.0, "p_ct": 0.0, "pc_se_min": 0.05}
+
+
+def _inside(x, lo=0.0):
+    return (x.real > lo) & (x.real < 1.0)
+
+
+def curves(sat, S):
+    """kr_o, kr_w, p_c at S_o = S (real or complex arrays), branches on the real part.
+
+    With D = 1 - Sr_o - Sr_w, Se_o = (S_o - Sr_o)/D, Se_w = (1 - S_o - Sr_w)/D:
+      kr_o = kro_max Se_o^n_o inside 0 < Se_o < 1, 0 at and below 0, kro_max at and above 1 (kr_w alike on Se_w); "brooks_corey"
+      is "corey" with both exponents (2 + 3 lmbda)/lmbda; "linear" is S_o and 1 - S_o.
+      p_c = p_ct (1 - min(max(Se_w, 0), 1)) ("linear") or p_ct s^(-1/lmbda), s = min(max(Se_w, pc_se_min), 1) ("brooks_corey")."""
+    sat = {**SATFN_DEFAULT, **sat}
+    S = np.asarray(S)
+    D = 1.0 - sat["Sr_o"] - sat["Sr_w"]
+    Se_o = (S - sat["Sr_o"])/D
+    Se_w = ((1.0 - sat["Sr_w"]) - S)/D                  # (this order: S_o = 1 - Sr_w is the end exactly, as S_o = Sr_o is)
+    if sat["relperm"] == "linear":
+        kr_o, kr_w = S + 0.0, 1.0 - S
+    else:
+        n_o, n_w = sat["n_o"], sat["n_w"]
+        if sat["relperm"] == "brooks_corey":
+            n_o = n_w = (2.0 + 3.0*sat["lmbda"])/sat["lmbda"]
+        z = 0.0*S
+        io, iw = _inside(Se_o), _inside(Se_w)
+        kr_o = np.where(io, sat["kro_max"]*np.where(io, Se_o, 0.5)**n_o, np.where(Se_o.real >= 1.0, sat["kro_max"] + z, z))
+        kr_w = np.where(iw, sat["krw_max"]*np.where(iw, Se_w, 0.5)**n_w, np.where(Se_w.real >= 1.0, sat["krw_max"] + z, z))
+    z = 0.0*S
+    if sat["capillary"] is None:
+        pc = z
+    elif sat["capillary"] == "linear":
+        iw = _inside(Se_w)
+        pc = np.where(iw, sat["p_ct"]*(1.0 - Se_w), np.where(Se_w.real >= 1.0, z, sat["p_ct"] + z))
+    else:
+        smin, e = sat["pc_se_min"], -1.0/sat["lmbda"]
+        iw = _inside(Se_w, smin)
+        pc = np.where(iw, sat["p_ct"]*np.where(iw, Se_w, 0.5)**e, np.where(Se_w.real >= 1.0, sat["p_ct"] + z, sat["p_ct"]*smin**e + z))
+    return kr_o, kr_w, pc
+
+
+def _given(spec, key, arg):
+    return spec.get(key) if arg is None else arg
+
+
 class Problem:
-    def __init__(self, spec):
+    def __init__(self, spec, hs=None, boundary=None, satfn=None, wells=None):
         self.spec = spec
         self.nph = int(spec["nphase"])
         self.b = 2 if self.nph == 1 else 3
@@ -61,20 +248,22 @@ class Problem:
         self.h = tuple(float(v) for v in spec["h"])
         self.gaxis = int(spec["gaxis"])
         self.prm = dict(spec["prm"])
-        self.V = self.h[0] * self.h[1] * self.h[2]
         f = lambda x: np.broadcast_to(np.asarray(x, dtype=float), self.shape).copy()
         self.phi = f(spec["phi"])
         self.K = [f(k) for k in spec["K"]]
         self.kT_static = f(spec["kT"]) if spec.get("kT") is not None else None
-        # face transmissibilities  T^K_f = H(K)|e|/Delta_h   
-        self.TK = []
-        self.G = []
-        for a in range(3):
-            t = np.zeros(self.shape)
-            if self.n[a] > 1:
-                t[_lo(a)] = harmonic(self.K[a][_lo(a)], self.K[a][_hi(a)]) * (self.V / self.h[a] ** 2)
-            self.TK.append(t)
-            self.G.append(self.V / self.h[a] ** 2)
+        # face transmissibilities  T^K_f = H(K)|e|/Delta_h   (SURVEY 9.1); graded if and only if widths are given
+        hs = _given(spec, "hs", hs)
+        self.geom = (UniformGeometry(self.n, self.h, self.K, self.gaxis, self.prm["g"]) if hs is None else
+                     GradedGeometry(self.n, hs, self.K, self.gaxis, self.prm["g"]))
+        self.TK, self.G, self.vol = self.geom.TK, self.geom.G, self.geom.vol
+        self.boundary = dict(_given(spec, "boundary", boundary) or {})
+        self.last_flux = np.zeros((6, self.b))
+        self.last_phi = {}
+        satfn = _given(spec, "satfn", satfn)
+        self.sat = None if satfn is None else {**SATFN_DEFAULT, **satfn}
+        assert self.sat is None or self.nph == 2, "saturation functions need the two-phase model"
+        self._Tx = None                   # the explicit temperature of the energy row, when it is differentiated alone (S~)
         src = spec.get("sources") or {}
         self.src = {k: np.asarray(v) for k, v in src.items()} if len(src) else None
         if self.src is not None and len(self.src["cell"]) == 0:
@@ -89,11 +278,26 @@ class Problem:
             self.w2 = 0.0
         self.dt = None
         self.old = None
+        self.well = Wells(self, _given(spec, "wells", wells) or [])
 
     # ---------------------------------------------------------------- properties
-    def props(self, p, T, S):
-        """Per-cell phase densities/mobilities and their derivatives."""
+    def relperm(self, S):
+        """kr_o, kr_w at S_o = S."""
+        return (S, 1.0 - S) if self.sat is None else curves(self.sat, S)[:2]
+
+    def props(self, p, T, S, at=None):
+        """Per-cell phase densities/mobilities and, for the linear closures, their derivatives.  `at`: the index of the cells
+        (a side's, for its ghost states) whose phi and static kT apply."""
         prm = self.prm
+        phi = self.phi if at is None else self.phi[at]
+        if self.sat is not None:
+            kr_o, kr_w, pc = curves(self.sat, S)
+            ro = cl.oil_rho(p, T, prm["API"])[0]
+            mo = cl.oil_mu(T, prm["API"])[0]
+            rw = cl.water_rho(p - pc, T)[0]                   # water at its own pressure p_w = p - p_c(S_o)
+            mw = cl.water_mu(T)[0]
+            return {"ro": (ro,), "rw": (rw,), "Lo": (kr_o*ro/mo,), "Lw": (kr_w*rw/mw,), "pc": (pc,),
+                    "kT": (phi*(S*prm["ko"] + (1 - S)*prm["kw"]) + (1 - phi)*prm["kr"], phi*(prm["ko"] - prm["kw"]))}
         d = {}
         ro, ro_p, ro_T = cl.oil_rho(p, T, prm["API"])
         mo, mo_T = cl.oil_mu(T, prm["API"])
@@ -106,14 +310,12 @@ class Problem:
             # L = kr*rho/mu and derivatives (p, T, S)
             d["Lw"] = (kw_ * rw / mw, kw_ * rw_p / mw, kw_ * (rw_T / mw - rw * mw_T / mw ** 2), -rw / mw)
             d["Lo"] = (S * ro / mo, S * ro_p / mo, S * (ro_T / mo - ro * mo_T / mo ** 2), ro / mo)
-            phi = self.phi
             d["kT"] = (phi * (S * prm["ko"] + (1 - S) * prm["kw"]) + (1 - phi) * prm["kr"],   # twophase.py:135,311
                        phi * (prm["ko"] - prm["kw"]))
-            d["mu"] = (mo, mo_T, mw, mw_T)
         else:
+            kT = self.kT_static if at is None else self.kT_static[at]
             d["Lo"] = (ro / mo, ro_p / mo, ro_T / mo - ro * mo_T / mo ** 2, 0.0 * ro)
-            d["kT"] = (self.kT_static, 0.0 * self.kT_static)
-            d["mu"] = (mo, mo_T)
+            d["kT"] = (kT, 0.0 * kT)
         return d
 
     def phases(self):
@@ -124,6 +326,9 @@ class Problem:
                     ("Lo", "ro", prm["c_v_o"], prm["c_v_o"], True)]
         return [("Lo", "ro", prm["c_v_o"], 1.0, False)]
 
+    def _explicit_T(self, T):
+        return T if self._Tx is None else self._Tx
+
     # ---------------------------------------------------------------- accumulation
     def accum(self, p, T, S, pr=None):
         """Accumulation densities per cell (times phi etc.), shape (b,...).
@@ -133,19 +338,20 @@ class Problem:
         pr = pr or self.props(p, T, S)
         phi = self.phi
         rock = (1 - phi) * prm["rho_r"] * prm["c_r"]
+        Tx = self._explicit_T(T)
         if self.nph == 2:
             Mw = phi * pr["rw"][0] * (1.0 - S)
             Mo = phi * pr["ro"][0] * S
-            return np.array([prm["c_v_w"] * Mw + prm["c_v_o"] * Mo,
-                             (prm["c_v_w"] * Mw + prm["c_v_o"] * Mo) * T + rock * T,
-                             Mo])
+            e0 = prm["c_v_w"] * Mw + prm["c_v_o"] * Mo
+            return np.array([e0, e0 * Tx + rock * Tx, Mo])
         Mo = phi * pr["ro"][0]
-        return np.array([Mo, prm["c_v_o"] * Mo * T + rock * T])
+        return np.array([Mo, prm["c_v_o"] * Mo * Tx + rock * Tx])
 
     def set_old(self, u_old):
         u_old = self.as_fields(u_old)
         self.u_old = u_old.copy()
         self.old = self.accum(*self.split(u_old))
+        self.well.set_old(u_old)
 
     def set_dt(self, dt):
         self.dt = float(dt)
@@ -158,6 +364,102 @@ class Problem:
             return u[0], u[1], u[2]
         return u[0], u[1], None
 
+    # ---------------------------------------------------------------- faces
+    def _phase_pressure(self, rk, p, pr):
+        return p - pr["pc"][0] if rk == "rw" and self.sat is not None else p
+
+    def _phi_face(self, pP, pM, rhoP, rhoM, gam):
+        """Driving force Phi = jump(p) - gam*(rho+ + rho-), gam = g*(half distances) on the gravity axis (singlephase.py:215)."""
+        return pP - pM - gam * (rhoP + rhoM)
+
+    def _face(self, P, M, TK, gam, cond, TxP, TxM, deriv=False):
+        """The face between the states P ('+') and M ('-'), each (p, T, props): T^K, gam and the conduction (H, dH/dk_P, dH/dk_M)
+        are the geometry's, TxP and TxM the explicit temperatures (S~).  Returns the flux rows, the phases' driving forces and,
+        if `deriv` (linear closures), the blocks dP, dM and the S~ entries sP, sM (row P / col P, row P / col M)."""
+        (pP, TP, prP), (pM, TM, prM) = P, M
+        b, w = self.b, [self.w0, 1.0, self.w2]
+        f, kept = [0.0] * b, {}
+        for (Lk, rk, ce, c0, to2) in self.phases():
+            Phi = self._phi_face(self._phase_pressure(rk, pP, prP), self._phase_pressure(rk, pM, prM), prP[rk][0], prM[rk][0], gam)
+            up = Phi.real > 0.0                       # gt(flow, 0): strict, ties -> '-' side
+            L = np.where(up, prP[Lk][0], prM[Lk][0])
+            Tu = np.where(up, TxP, TxM)
+            F = TK * L * Phi
+            f[0] = f[0] + w[0] * c0 * F
+            f[1] = f[1] + ce * Tu * F
+            if to2:
+                f[2] = f[2] + w[2] * F
+            kept[rk] = (Phi, up, L, Tu, F)
+        Hk, dHP, dHM = cond
+        f[1] = f[1] + Hk * (TxP - TxM)
+        phis = [k[0] for k in kept.values()]
+        if not deriv:
+            return f, phis
+        dP, dM = np.zeros((b, b) + TK.shape), np.zeros((b, b) + TK.shape)
+        sP, sM = np.zeros(TK.shape), np.zeros(TK.shape)
+        for (Lk, rk, ce, c0, to2) in self.phases():
+            Phi, up, L, Tu, F = kept[rk]
+            rP, rM, LP, LM = prP[rk], prM[rk], prP[Lk], prM[Lk]
+            # dPhi/du on both sides (p, T; S does not enter)
+            dPhiP = [1.0 - gam * rP[1], -gam * rP[2], 0.0]
+            dPhiM = [-1.0 - gam * rM[1], -gam * rM[2], 0.0]
+            for c in range(b):
+                dFP = TK * (L * dPhiP[c] + np.where(up, LP[c + 1], 0.0) * Phi)
+                dFM = TK * (L * dPhiM[c] + np.where(up, 0.0, LM[c + 1]) * Phi)
+                dP[0, c] += w[0] * c0 * dFP
+                dM[0, c] += w[0] * c0 * dFM
+                dP[1, c] += ce * Tu * dFP
+                dM[1, c] += ce * Tu * dFM
+                if to2:
+                    dP[2, c] += w[2] * dFP
+                    dM[2, c] += w[2] * dFM
+            dP[1, 1] += np.where(up, ce * F, 0.0)
+            dM[1, 1] += np.where(up, 0.0, ce * F)
+            sP += np.where(up, ce * F, 0.0)
+            sM += np.where(up, 0.0, ce * F)
+        dP[1, 1] += Hk
+        dM[1, 1] -= Hk
+        sP += Hk
+        sM -= Hk
+        if self.nph == 2:
+            dT = TP - TM
+            dP[1, 2] += dT * dHP * prP["kT"][1]
+            dM[1, 2] += dT * dHM * prM["kT"][1]
+        return f, phis, dP, dM, sP, sM
+
+    def _interior(self, a, p, T, pr, deriv=False):
+        """_face over the interior faces of axis a."""
+        lo, hi = _lo(a), _hi(a)
+        cut = lambda x, sl: x[sl] if np.shape(x) == self.shape else np.broadcast_to(x, self.shape)[sl]
+        at = lambda sl: {k: tuple(cut(x, sl) for x in v) for k, v in pr.items()}
+        prP, prM = at(lo), at(hi)
+        Tx = self._explicit_T(T)
+        cond = self.geom.conduction(a, prP["kT"][0], prM["kT"][0], deriv and self.nph == 2)
+        return self._face((p[lo], T[lo], prP), (p[hi], T[hi], prM), self.TK[a][lo], self.geom.gam(a), cond, Tx[lo], Tx[hi], deriv)
+
+    def _side(self, side, u, deriv=False):
+        """_face over the boundary faces of one side: cell and ghost (the ghost's explicit temperature is data)."""
+        a, d = divmod(int(side), 2)
+        B = self.boundary[side]
+        sl = side_slice(side)
+        p, T, S = self.split(u)
+        pc, Tc = p[sl], T[sl]
+        Sc = S[sl] if S is not None else None
+        shp = pc.shape
+        z = 0*pc                                                # (carries a complex dtype through)
+        pb = np.asarray(B["p"], dtype=float).reshape(shp) + z
+        Tb = np.asarray(B["T"], dtype=float).reshape(shp) + z
+        Sb = (np.asarray(B["S"], dtype=float).reshape(shp) + z) if S is not None else None
+        cell = (pc, Tc, self.props(pc, Tc, Sc, at=sl))
+        ghost = (pb, Tb, self.props(pb, Tb, Sb, at=sl))
+        TK, gam, Ga = self.geom.side(a, sl)
+        if B["kind"] != "open":
+            TK = np.zeros(shp)
+        c, g = (cell, self._explicit_T(T)[sl]), (ghost, Tb)
+        (P, TxP), (M, TxM) = (c, g) if d else (g, c)
+        cond = harmonic_conduction(P[2]["kT"][0], M[2]["kT"][0], Ga, deriv and self.nph == 2)
+        return d, sl, self._face(P, M, TK, gam, cond, TxP, TxM, deriv)
+
     # ---------------------------------------------------------------- residual
     def residual(self, u):
         """F(u) with accumulation against the stored old state; returns array (b, n2, n1, n0)."""
@@ -165,14 +467,14 @@ class Problem:
         p, T, S = self.split(u)
         pr = self.props(p, T, S)
         w = [self.w0, 1.0, self.w2]
-        R = (self.accum(p, T, S, pr) - self.old) * (self.V / self.dt)
+        R = (self.accum(p, T, S, pr) - self.old) * (self.vol / self.dt)
         R = R.astype(u.dtype, copy=False)
         for q in range(self.b):
             R[q] = R[q] * w[q]
         for a in range(3):
             if self.n[a] == 1:
                 continue
-            f = self._face_flux(a, p, T, pr)
+            f, _ = self._interior(a, p, T, pr)
             lo, hi = _lo(a), _hi(a)
             for q in range(self.b):
                 R[q][lo] += f[q]
@@ -185,33 +487,17 @@ class Problem:
             Rf = R.reshape(self.b, -1)
             for q in range(self.b):
                 np.subtract.at(Rf[q], c, s[q])
-        return R
-
-    def _phi_face(self, a, p, rho):
-        """Driving force Phi = jump(p) - g*Dh*avg(rho) on the gravity axis (singlephase.py:215)."""
-        lo, hi = _lo(a), _hi(a)
-        Phi = p[lo] - p[hi]
-        if a == self.gaxis:
-            Phi = Phi - (self.prm["g"] * self.h[a] * 0.5) * (rho[lo] + rho[hi])
-        return Phi
-
-    def _face_flux(self, a, p, T, pr):
-        lo, hi = _lo(a), _hi(a)
-        TK = self.TK[a][lo]
-        f = [0.0] * self.b
-        for (Lk, rk, ce, c0, to2) in self.phases():
-            Phi = self._phi_face(a, p, pr[rk][0])
-            up = Phi.real > 0.0                       # gt(flow, 0): strict, ties -> '-' side
-            L = np.where(up, pr[Lk][0][lo], pr[Lk][0][hi])
-            Tu = np.where(up, T[lo], T[hi])
-            F = TK * L * Phi
-            f[0] = f[0] + self.w0 * c0 * F
-            f[1] = f[1] + ce * Tu * F
-            if to2:
-                f[2] = f[2] + self.w2 * F
-        kT = pr["kT"][0]
-        f[1] = f[1] + harmonic(kT[lo], kT[hi]) * self.G[a] * (T[lo] - T[hi])
-        return f
+        flux = np.zeros((6, self.b))
+        self.last_phi = {}
+        for side in sorted(self.boundary):
+            d, sl, (f, phis) = self._side(side, u)
+            sg = 1.0 if d else -1.0
+            for q in range(self.b):
+                R[q][sl] += sg*f[q]
+                flux[side, q] = float(np.sum((sg*f[q]).real))
+            self.last_phi[side] = [np.array(Phi.real) for Phi in phis]
+        self.last_flux = flux
+        return self.well.add_to(R, u)
 
     # ---------------------------------------------------------------- sources
     def source_terms(self, p, T, S, return_rates=False):
@@ -224,16 +510,18 @@ class Problem:
         kind, wt, bhp, qmax, WI, const = (e[k] for k in ("kind", "wt", "bhp", "max_rate", "WI", "const"))
         API = prm["API"]
         is_prod, is_inj, is_heat = kind == PROD, kind == INJ, kind == HEATER
+        Tx = T if self._Tx is None else self._Tx.reshape(-1)[e["cell"]]
         mo, _ = cl.oil_mu(T, API)
-        ro, _, _ = cl.oil_rho(p, T, API)
+        ro, _, _ = cl.oil_rho(p, T, API)              # wells: densities at p, drawdown on p (wellcase.py:204-235)
         dd_raw = bhp - p
         dd = np.where(is_prod, np.where(dd_raw.real >= 0.0, 0.0, dd_raw), np.where(dd_raw.real <= 0.0, 0.0, dd_raw))
-        out = np.zeros((self.b, len(kind)), dtype=np.result_type(p, T))
-        rates = {}
-        if self.nph == 1:
-            rate = WI / mo * dd
+
+        def cap(rate):
             rate = np.where(np.abs(rate.real) - np.abs(qmax) >= 0.0, qmax, rate)
-            rate = np.where(const != 0, qmax, rate)
+            return np.where(const != 0, qmax, rate)
+        out = np.zeros((self.b, len(kind)), dtype=np.result_type(p, T, Tx, *([] if S is None else [S])))
+        if self.nph == 1:
+            rate = cap(WI / mo * dd)
             ro_inj, _, _ = cl.oil_rho(p, prm["T_inj"] + 0 * T, API)
             cv = prm["c_v_o"]
             m = np.where(is_prod, ro * rate, np.where(is_inj, ro_inj * rate, 0.0))
@@ -244,25 +532,25 @@ class Problem:
         else:
             mw, _ = cl.water_mu(T)
             rw, _, _ = cl.water_rho(p, T)
-            lam_t = S / mo + (1.0 - S) / mw           # 1/mu, wellcase.py:212
+            kr_o, kr_w = self.relperm(S)
+            lam_o, lam_w = kr_o / mo, kr_w / mw
+            lam_t = lam_o + lam_w                     # 1/mu, wellcase.py:212
             # producers: total-mobility Peaceman, split by mobility fractions (:204-235)
-            rate_p = WI * lam_t * dd
-            rate_p = np.where(np.abs(rate_p.real) - np.abs(qmax) >= 0.0, qmax, rate_p)
-            rate_p = np.where(const != 0, qmax, rate_p)
-            qw = (1.0 - S) / mw / lam_t * rate_p
-            qo = S / mo / lam_t * rate_p
+            rate_p = cap(WI * lam_t * dd)
+            # (curves: both phases immobile gives no split; S_o in [Sr_o, 1 - Sr_w] never is)
+            safe = lam_t if self.sat is None else np.where(lam_t.real > 0.0, lam_t, 1.0)
+            qw = lam_w / safe * rate_p
+            qo = lam_o / safe * rate_p
             # injectors: water only, viscosity at the cell temperature (twophase.py:225)
-            rate_i = WI / mw * dd
-            rate_i = np.where(np.abs(rate_i.real) - np.abs(qmax) >= 0.0, qmax, rate_i)
-            rate_i = np.where(const != 0, qmax, rate_i)
+            rate_i = cap(WI / mw * dd)
             rw_inj, _, _ = cl.water_rho(p, prm["T_inj"] + 0 * T)
             cw, co = prm["c_v_w"], prm["c_v_o"]
             out[0] = self.w0 * np.where(is_prod, cw * rw * qw + co * ro * qo,
                                         np.where(is_inj, cw * rw_inj * rate_i, 0.0)) * wt
             out[2] = self.w2 * np.where(is_prod, ro * qo, 0.0) * wt
-            out[1] = np.where(is_prod, (rw * qw * cw + ro * qo * co) * T,
+            out[1] = np.where(is_prod, (rw * qw * cw + ro * qo * co) * Tx,
                               np.where(is_inj, rw_inj * rate_i * cw * prm["T_inj"],
-                                       prm["U"] * (prm["T_inj"] - T))) * wt
+                                       prm["U"] * (prm["T_inj"] - Tx))) * wt
             rates = {"rate": np.where(is_prod, rate_p, np.where(is_inj, rate_i, 0.0)),
                      "water_rate": np.where(is_prod, qw, 0.0), "oil_rate": np.where(is_prod, qo, 0.0)}
         if return_rates:
@@ -271,23 +559,34 @@ class Problem:
 
     def source_jac(self, p, T, S):
         """d s / d(p,T,S) per entry by complex step (exact to rounding; branches frozen)."""
-        hstep = 1e-30
         nent = len(self.src["cell"])
         J = np.zeros((self.b, self.b, nent))
         args = [p.astype(complex), T.astype(complex), None if S is None else S.astype(complex)]
         for c in range(self.b):
             a2 = [None if x is None else x.copy() for x in args]
-            a2[c] = a2[c] + 1j * hstep
-            J[:, c, :] = self.source_terms(*a2).imag / hstep
+            a2[c] = a2[c] + 1j * HSTEP
+            J[:, c, :] = self.source_terms(*a2).imag / HSTEP
         return J
 
     # ---------------------------------------------------------------- Jacobian
     def jacobian(self, u, want_schur=False):
-        """Exact dF/du with upwind/limiter branches frozen.
+        """Exact dF/du with upwind/limiter branches (and the wells' bhp, mode and open sets) frozen: analytic for
+        the linear closures, the complex step of residual() under saturation functions.  With wells the exact Jacobian is
+        J + sum_w c_w b_w^T, which ``rank1`` applies.
 
         Returns J of shape (7, b, b, n2, n1, n0) (and, if want_schur, the temperature
         convection-diffusion operator S~ of shape (7, n2, n1, n0), preconditioners.py:165-333)."""
-        u = self.as_fields(u)
+        u = self.as_fields(np.asarray(u, dtype=float))
+        with self.well.frozen_at(u):
+            if self.sat is not None:
+                J, Sm = self.jacobian_complex_step(u), (self.schur_complex_step(u) if want_schur else None)
+            else:
+                J, Sm = self._jacobian_analytic(u, want_schur)
+                self.well.add_diagonal(u, J, Sm)
+            self.well.set_factors(u, J)
+        return (J, Sm) if want_schur else J
+
+    def _jacobian_analytic(self, u, want_schur):
         p, T, S = self.split(u)
         pr = self.props(p, T, S)
         b = self.b
@@ -295,7 +594,7 @@ class Problem:
         J = np.zeros((7, b, b) + self.shape)
         Sm = np.zeros((7,) + self.shape) if want_schur else None
         w = [self.w0, 1.0, self.w2]
-        Vdt = self.V / self.dt
+        Vdt = self.vol / self.dt
         phi = self.phi
         rock = (1 - phi) * prm["rho_r"] * prm["c_r"]
         # accumulation derivatives
@@ -322,63 +621,11 @@ class Problem:
             J[0, 1, 1] += (cv * Mo[0] + rock) * Vdt
             if want_schur:   # preconditioners.py:73,85
                 Sm[0] += (phi * cv * ro + rock) * Vdt
-        # faces
         for a in range(3):
             if self.n[a] == 1:
                 continue
             lo, hi = _lo(a), _hi(a)
-            TK = self.TK[a][lo]
-            fs = (b, b) + TK.shape
-            dP = np.zeros(fs)
-            dM = np.zeros(fs)
-            sP = np.zeros(TK.shape)   # S~ entries: row P / col P, row P / col M
-            sM = np.zeros(TK.shape)
-            gam = prm["g"] * self.h[a] * 0.5 if a == self.gaxis else 0.0
-            for (Lk, rk, ce, c0, to2) in self.phases():
-                rho = pr[rk]
-                Phi = self._phi_face(a, p, rho[0])
-                up = Phi > 0.0
-                Lt = pr[Lk]
-                L = np.where(up, Lt[0][lo], Lt[0][hi])
-                Tu = np.where(up, T[lo], T[hi])
-                F = TK * L * Phi
-                # dPhi/du on both sides (p, T; S does not enter)
-                dPhiP = [1.0 - gam * rho[1][lo], -gam * rho[2][lo], 0.0]
-                dPhiM = [-1.0 - gam * rho[1][hi], -gam * rho[2][hi], 0.0]
-                for c in range(b):
-                    dLP = np.where(up, np.broadcast_to(Lt[c + 1], self.shape)[lo], 0.0)
-                    dLM = np.where(up, 0.0, np.broadcast_to(Lt[c + 1], self.shape)[hi])
-                    dFP = TK * (L * dPhiP[c] + dLP * Phi)
-                    dFM = TK * (L * dPhiM[c] + dLM * Phi)
-                    dP[0, c] += w[0] * c0 * dFP
-                    dM[0, c] += w[0] * c0 * dFM
-                    dP[1, c] += ce * Tu * dFP
-                    dM[1, c] += ce * Tu * dFM
-                    if to2:
-                        dP[2, c] += w[2] * dFP
-                        dM[2, c] += w[2] * dFM
-                dP[1, 1] += np.where(up, ce * F, 0.0)
-                dM[1, 1] += np.where(up, 0.0, ce * F)
-                if want_schur:
-                    sP += np.where(up, ce * F, 0.0)
-                    sM += np.where(up, 0.0, ce * F)
-            kT, kT_S = pr["kT"]
-            kP, kM = kT[lo], kT[hi]
-            Hk = harmonic(kP, kM)
-            Gk = self.G[a]
-            dP[1, 1] += Hk * Gk
-            dM[1, 1] -= Hk * Gk
-            if want_schur:
-                sP += Hk * Gk
-                sM -= Hk * Gk
-            if self.nph == 2:
-                s2 = kP + kM
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    dHP = np.where(s2 > 0, 2 * kM ** 2 / np.where(s2 == 0, 1, s2) ** 2, 0.0)
-                    dHM = np.where(s2 > 0, 2 * kP ** 2 / np.where(s2 == 0, 1, s2) ** 2, 0.0)
-                dT = T[lo] - T[hi]
-                dP[1, 2] += Gk * dT * dHP * np.broadcast_to(kT_S, self.shape)[lo]
-                dM[1, 2] += Gk * dT * dHM * np.broadcast_to(kT_S, self.shape)[hi]
+            _, _, dP, dM, sP, sM = self._interior(a, p, T, pr, deriv=True)
             for r in range(b):
                 for c in range(b):
                     J[0, r, c][lo] += dP[r, c]
@@ -405,9 +652,14 @@ class Problem:
                 # (preconditioners.py:102-108, 269-276)
                 sd = self.schur_source_diag(pc, Tc, Sc)
                 np.subtract.at(Sm[0].reshape(-1), cidx, sd)
-        if want_schur:
-            return J, Sm
-        return J
+        for side in sorted(self.boundary):
+            d, sl, (_, _, dP, dM, sP, sM) = self._side(side, u, deriv=True)
+            for r in range(b):
+                for c in range(b):
+                    J[0, r, c][sl] += dP[r, c] if d else -dM[r, c]
+            if want_schur:
+                Sm[0][sl] += sP if d else -sM
+        return J, Sm
 
     def schur_source_diag(self, p, T, S):
         prm = self.prm
@@ -421,29 +673,79 @@ class Problem:
             prod = ro * rates["rate"] * prm["c_v_o"]
         return np.where(kind == PROD, prod, np.where(kind == HEATER, -prm["U"], 0.0)) * wt
 
-    # ---------------------------------------------------------------- checker
-    def jacobian_complex_step(self, u):
-        """Independent Jacobian by complex-step differentiation of residual() with a
-        distance-2 colouring of the 7-point stencil ((i0 + 2 i1 + 3 i2) mod 7)."""
-        u = self.as_fields(u).astype(float)
-        b = self.b
+    # ---------------------------------------------------------------- complex steps
+    def _colour_slots(self):
+        """The distance-2 colouring (i0 + 2 i1 + 3 i2) mod 7 of the 7-point stencil, and per stencil slot the cells whose
+        neighbour of that slot exists, with the neighbour's colour."""
         n0, n1, n2 = self.n
         i2, i1, i0 = np.meshgrid(np.arange(n2), np.arange(n1), np.arange(n0), indexing="ij")
-        col = (i0 + 2 * i1 + 3 * i2) % 7
-        J = np.zeros((7, b, b) + self.shape)
-        hstep = 1e-30
+        col = (i0 + 2*i1 + 3*i2) % 7
         offs = [(0, 0, 0), (-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)]
+        masks = []
+        for (d0, d1, d2) in offs:
+            j0, j1, j2 = i0 + d0, i1 + d1, i2 + d2
+            ok = (j0 >= 0) & (j0 < n0) & (j1 >= 0) & (j1 < n1) & (j2 >= 0) & (j2 < n2)
+            masks.append((ok, (j0 + 2*j1 + 3*j2) % 7))
+        return col, masks
+
+    def jacobian_complex_step(self, u):
+        """Independent Jacobian by complex-step differentiation of residual() over the colouring."""
+        u = self.as_fields(u).astype(float)
+        b = self.b
+        col, masks = self._colour_slots()
+        J = np.zeros((7, b, b) + self.shape)
         for c in range(b):
             for k in range(7):
                 uc = u.astype(complex)
-                uc[c][col == k] += 1j * hstep
-                dR = self.residual(uc).imag / hstep     # (b, ...)
-                for s, (d0, d1, d2) in enumerate(offs):
+                uc[c][col == k] += 1j * HSTEP
+                dR = self.residual(uc).imag / HSTEP     # (b, ...)
+                for s, (ok, cj) in enumerate(masks):
                     # row cell i gets column of neighbour j = i + off if colour(j) == k
-                    j0, j1, j2 = i0 + d0, i1 + d1, i2 + d2
-                    ok = (j0 >= 0) & (j0 < n0) & (j1 >= 0) & (j1 < n1) & (j2 >= 0) & (j2 < n2)
-                    cj = (j0 + 2 * j1 + 3 * j2) % 7
                     m = ok & (cj == k)
                     for r in range(b):
                         J[s, r, c][m] = dR[r][m]
         return J
+
+    def schur_complex_step(self, u):
+        """S~ as the complex step of the energy row over the explicit temperature alone."""
+        u = self.as_fields(u).astype(float)
+        col, masks = self._colour_slots()
+        Sm = np.zeros((7,) + self.shape)
+        uc = u.astype(complex)
+        try:
+            for k in range(7):
+                self._Tx = uc[1].copy()
+                self._Tx[col == k] += 1j*HSTEP
+                dR = self.residual(uc)[1].imag/HSTEP
+                for s, (ok, cj) in enumerate(masks):
+                    m = ok & (cj == k)
+                    Sm[s][m] = dR[m]
+        finally:
+            self._Tx = None
+        return Sm
+
+    def dense_jacobian(self, u):
+        """dF/du, every entry, by a complex step per unknown of the residual with NOTHING frozen: (b, ncell, b, ncell)."""
+        u = self.as_fields(np.asarray(u, dtype=float))
+        n = int(np.prod(self.shape))
+        D = np.zeros((self.b, n, self.b, n))
+        for col in range(self.b):
+            for j in range(n):
+                uc = u.astype(complex)
+                uc[col].reshape(-1)[j] += 1j*HSTEP
+                D[:, :, col, j] = self.residual(uc).imag.reshape(self.b, n)/HSTEP
+        return D
+
+    # ---------------------------------------------------------------- the wells, under the problem's name
+    wells = property(lambda self: self.well.wells)
+    rho_w = property(lambda self: self.well.rho_w)
+    last_factors = property(lambda self: self.well.last_factors)
+
+    def well_state(self, u):
+        return self.well.state(u)
+
+    def kink_margin(self, u):
+        return self.well.kink_margin(u)
+
+    def rank1(self, x):
+        return self.well.rank1(x)

@@ -211,7 +211,8 @@ def check_ties(spec, u, min_share=0.10):
             continue
         tie_all = None
         for (Lk, rk, ce, c0, to2) in P.phases():
-            Phi = P._phi_face(a, p, pr[rk][0])
+            rho = pr[rk][0]
+            Phi = P._phi_face(p[_lo(a)], p[_hi(a)], rho[_lo(a)], rho[_hi(a)], P.geom.gam(a))
             assert np.all((Phi == 0.0) | (np.abs(Phi) > 1e-9*pmax)), (a, rk)
             tie = Phi == 0.0
             tie_all = tie if tie_all is None else (tie_all & tie)
@@ -227,8 +228,8 @@ class PlusTieProblem(Problem):
     moved to the smallest positive number, which the strict comparison of the face loop then sends to '+'; every product
     with it underflows to 0, like the products with Phi == 0 themselves.  Used only to show that a tie carries information."""
 
-    def _phi_face(self, a, p, rho):
-        Phi = super()._phi_face(a, p, rho)
+    def _phi_face(self, *face):
+        Phi = super()._phi_face(*face)
         return np.where(Phi == 0.0, np.nextafter(0.0, 1.0), Phi)
 
 
@@ -262,8 +263,7 @@ def per_cell_scales(prob, u, R, J):
     open source is.  Jacobian: per row of the cell's diagonal block, the largest magnitude of that row."""
     u = prob.as_fields(np.asarray(u, dtype=float))
     w = np.array([prob.w0, 1.0, prob.w2][:prob.b]).reshape(-1, 1, 1, 1)
-    vol = prob.V if prob.V is not None else prob.Vc          # (the graded classes: one volume per cell)
-    acc = np.abs(prob.accum(*prob.split(u))*w*(vol/prob.dt)).max(axis=0)
+    acc = np.abs(prob.accum(*prob.split(u))*w*(prob.vol/prob.dt)).max(axis=0)
     rs = np.maximum(np.abs(R).max(axis=0), acc)
     js = np.abs(J[0]).max(axis=1)          # (b rows, cells)
     return rs, js
@@ -317,21 +317,14 @@ def edge_input(builder, kw, kind, seed=3):
 
 # ---- Dirichlet sides, graded grids and saturation functions at edge states (test_gpu_assembly_combos.py) ---------------------
 COMBO_DT = 8640.0
-# The per-row bound of test_gpu_assembly_combos.py: max(1e-11, 10 x the largest per-row difference between GradedBcProblem's
+# The per-row bound of test_gpu_assembly_combos.py: max(1e-11, 10 x the largest per-row difference between the graded problem with sides'
 # analytic and complex-step Jacobians at the inputs of row 3), which test_graded_host.py measures and compares with this value.
 TOL_ROW = 1e-11
 
 
 def combo_problem(spec):
-    """The reference class that matches the keys of `spec`: "hs" (graded), "boundary" (sides), "satfn" (curves)."""
-    from bc_ref import BcProblem
-    from graded_ref import GradedBcProblem, GradedProblem
-    from satfn_ref import SatfnBcProblem, SatfnGradedBcProblem, SatfnGradedProblem, SatfnProblem
-    key = (spec.get("hs") is not None, bool(spec.get("boundary")), spec.get("satfn") is not None)
-    cls = {(False, False, False): Problem, (False, True, False): BcProblem, (True, False, False): GradedProblem,
-           (True, True, False): GradedBcProblem, (False, False, True): SatfnProblem, (False, True, True): SatfnBcProblem,
-           (True, False, True): SatfnGradedProblem, (True, True, True): SatfnGradedBcProblem}[key]
-    return cls(spec)
+    """The reference on the keys of `spec`: "hs" (graded), "boundary" (sides), "satfn" (curves)."""
+    return Problem(spec)
 
 
 def combo_reference(spec, u, dt=COMBO_DT):
@@ -341,7 +334,7 @@ def combo_reference(spec, u, dt=COMBO_DT):
     P.set_dt(dt)
     R = P.residual(u)
     J, Sm = P.jacobian(u, want_schur=True)
-    for a in (R, J, Sm, P.last_flux if hasattr(P, "last_flux") else R):
+    for a in (R, J, Sm, P.last_flux):
         assert np.isfinite(a).all()
     for a in (R, J, Sm):
         a.setflags(write=False)
@@ -375,8 +368,8 @@ def _face_phis(P, u):
             continue
         phis = []
         for (Lk, rk, ce, c0, to2) in P.phases():
-            pp = P._phase_pressure(rk, p, pr) if hasattr(P, "_phase_pressure") else p
-            phis.append(P._phi_face(a, pp, pr[rk][0]))
+            pp, rho = P._phase_pressure(rk, p, pr), pr[rk][0]
+            phis.append(P._phi_face(pp[_lo(a)], pp[_hi(a)], rho[_lo(a)], rho[_hi(a)], P.geom.gam(a)))
         out.append((a, phis))
     return out
 

@@ -11,8 +11,9 @@ equation, the row of J (7 b entries) and of S~ (7 entries) within TOL_ROW of the
 per cell within TOL_ROW of edge_cases.per_cell_scales' scale -- under which a thin cell of a graded grid is held to its own
 size and not to the grid's largest entry; rows the reference has exactly zero exactly zero; the side sums.
 
-TOL_ROW = max(1e-11, 10 x 3.1e-15) = 1e-11: 3.1e-15 is the largest per-row difference between GradedBcProblem's analytic and
-complex-step Jacobians at the inputs of row 3, measured by test_graded_host.test_per_row_bound_of_the_combination_tests.
+TOL_ROW = max(1e-11, 10 x 3.1e-15) = 1e-11: 3.1e-15 is the largest per-row difference between the analytic and the
+complex-step Jacobian of the graded reference with sides at the inputs of row 3, measured by
+test_graded_host.test_per_row_bound_of_the_combination_tests.
 
 The conditions that make a case informative are asserted on the reference, on the CPU, by edge_cases.combo_input.  Every input is
 finite and so is every reference output."""
@@ -120,12 +121,14 @@ def test_combination_against_its_reference(case):
 # ---- Newton ------------------------------------------------------------------------------------------------------------------
 def test_newton_parity_on_a_graded_box_with_sides_and_curves():
     """Two-phase 6x5x4 with its wells and heaters, pc_cptr, geometric widths along x and z, an open lateral side and a thermal
-    top, model M2: two time steps against the oracle engine on SatfnGradedBcProblem, with test_gpu_graded_model's assertions
+    top, model M2: two time steps against the oracle engine on the same spec, with test_gpu_graded_model's assertions
     (equal Newton counts, linear iterations within max(2, 10 %), states to 1e-8)."""
     import cases
     from bc_ref import side_shape
     from graded_ref import equal_widths, spec_lengths
-    from satfn_ref import DEFAULT, M2, satfn_graded_bc_oracle
+    from oracle.engine import OracleEngine
+    from oracle.tpfa import GradedGeometry
+    from satfn_ref import DEFAULT, M2
     from thermalporous_amd.engine import HipEngine
     from thermalporous_amd.spacing import geometric_widths
     spec, u0, p, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
@@ -143,8 +146,8 @@ def test_newton_parity_on_a_graded_box_with_sides_and_curves():
         spec["boundary"][side] = {"kind": kind, "p": np.full(shape, float(p.p_ref)), "T": np.full(shape, float(p.T_prod)),
                                   "S": np.full(shape, float(p.S_o))}
     opts = dict(pc="cptr", ksp_rtol=1e-8, snes_max_it=25)
-    o, h = satfn_graded_bc_oracle(spec, opts), HipEngine(spec, opts)
-    assert type(o.prob).__name__ == "SatfnGradedBcProblem"
+    o, h = OracleEngine(spec, opts), HipEngine(spec, opts)
+    assert isinstance(o.prob.geom, GradedGeometry) and o.prob.sat is not None and sorted(o.prob.boundary) == sorted(spec["boundary"])
     assert h.spacing_info()["graded"] and h.saturation_info()["active"] and sorted(h.boundary) == sorted(spec["boundary"])
     for e in (o, h):
         e.set_state(u0)

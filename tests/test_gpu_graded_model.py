@@ -1,5 +1,5 @@
 """Graded grids in the time loop: ``geo.set_spacing`` -> case (wells and a heater picked by coordinate on the graded grid) -> model ->
-engine, two time steps against ``graded_oracle`` stepping the same spec, oil in place with the cells' own volumes, and the
+engine, two time steps against the oracle engine stepping the same spec, oil in place with the cells' own volumes, and the
 RectilinearGrid field output."""
 import glob
 import os
@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from graded_ref import graded_oracle
+from oracle.engine import OracleEngine
 from test_gpu_parity import rel2
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +57,7 @@ def test_two_time_steps_against_the_graded_oracle(tmp_path, nphase):
     assert np.all(prod % 6 == 0) and np.all(prod // 30 == 0) and abs(m.case.deltas_prod.weights.sum() - 1.0) < 1e-14
     assert edges[0][1] < g.Dx/2 and edges[2][1] < g.Dz/2                  # (thin cells: mean widths would name others)
     m.start()
-    o = graded_oracle(m.spec, m.engine_opts)
+    o = OracleEngine(m.spec, m.engine_opts)
     o.set_state(m._to_internal(m.u._read()))
     for step in range(2):
         dt = float(m.dt.values()[0])

@@ -15,8 +15,8 @@ import cases
 from bc_ref import assert_both_directions, make_boundary
 from graded_ref import field_change, random_widths, spec_lengths
 from oracle.tpfa import INJ, PROD, Problem
-from satfn_ref import (DEFAULT, DEGENERATE, M1, M2, M3, MODELS, SatfnBcProblem, SatfnGradedProblem, SatfnProblem, capillary_gravity_column,
-                       column_face_fluxes, satfn_oracle)
+from oracle.engine import OracleEngine
+from satfn_ref import DEFAULT, DEGENERATE, M1, M2, M3, MODELS, capillary_gravity_column, column_face_fluxes
 from test_gpu_assembly_edges import TOL, assert_entries
 from test_gpu_bc import _assert_step
 from test_gpu_slabs import rel2, run_slabs
@@ -111,13 +111,13 @@ def test_entries_against_the_reference(model, pid, builder, kw):
         # S_o = 1 - Sr_w the quotient rounds to 1 - 2^-52); the three boxes above hold that branch
         want -= {("kr_o", "high")}
     assert _branches(sat, S) >= want, (model, pid, sorted(want - _branches(sat, S)))
-    Ro, Jo, So = _reference(SatfnProblem(spec), u)
+    Ro, Jo, So = _reference(Problem(spec), u)
     h = _engine(spec, u)
     assert h.saturation_info()["active"]
     Rh, Jh, Sh = _gpu(h)
     assert_entries(Rh, Jh, Sh, Ro, Jo, So, (model, pid))
     # the curves are visible in what is compared: the result is not the linear model's
-    Pl = Problem(spec)
+    Pl = Problem({k: v for k, v in spec.items() if k != "satfn"})
     Pl.set_old(u)
     Pl.set_dt(8640.0)
     change = field_change(Rh, Pl.residual(u), spec)
@@ -149,7 +149,6 @@ def test_default_path_is_untouched():
 
 
 def test_degenerate_corey_equals_the_existing_oracle():
-    from oracle.engine import OracleEngine
     pid, builder, kw = B654
     spec, *_ = builder(**kw)
     u = cases.perturbed_state(spec, seed=3)
@@ -218,7 +217,7 @@ def test_capillary_gravity_column_carries_no_flow():
     """1 x 1 x 8, API 40, linear p_c: the state tests/satfn_ref.py marches up from Se_w = 0.9 at the bottom so that both driving
     forces vanish on every face; old state = state: each phase's flux through each face is below 1e-8 of T^K L rho g dz."""
     spec, u, scale = capillary_gravity_column()
-    P = SatfnProblem(spec)
+    P = Problem(spec)
     h = _engine(spec, u, dt=COLUMN_DT)
     F = column_face_fluxes(P, h.residual())
     print("face fluxes / (T^K L rho g dz): water", F[0]/scale[0], "oil", F[1]/scale[1])
@@ -250,7 +249,7 @@ def test_wells_follow_the_curves():
     u = _edge_state(spec, M1)
     S = u[2].reshape(-1)
     S[13], S[41], S[66] = 0.1, 0.9, 0.55
-    P = SatfnProblem(spec)
+    P = Problem(spec)
     Ro, Jo, So = _reference(P, u)
     c = cells
     _, ro = P.source_terms(u[0].reshape(-1)[c], u[1].reshape(-1)[c], S[c], return_rates=True)
@@ -278,7 +277,7 @@ def test_with_dirichlet_sides():
     axes = spec["axes"]
     z_lo, x_hi = 2*axes.index(2), 2*axes.index(0) + 1           # 'z-' and 'x+' as internal sides
     spec["boundary"] = make_boundary(spec, u, {z_lo: "open", x_hi: "thermal"}, seed=4)
-    P = SatfnBcProblem(spec)
+    P = Problem(spec)
     Ro, Jo, So = _reference(P, u)
     assert_both_directions(P)
     ref = P.last_flux.copy()
@@ -297,7 +296,7 @@ def test_on_a_graded_grid():
     spec = _with(spec, M2)
     spec["hs"] = random_widths(spec["n"], spec_lengths(spec), 7)
     u = _edge_state(spec, M2)
-    Ro, Jo, So = _reference(SatfnGradedProblem(spec), u)
+    Ro, Jo, So = _reference(Problem(spec), u)
     h = _engine(spec, u)
     assert h.spacing_info()["graded"] and h.saturation_info()["active"]
     Rh, Jh, Sh = _gpu(h)
@@ -339,7 +338,7 @@ def test_newton_parity(model):
     spec, u0, *_ = builder(**kw)
     spec = _with(spec, MODELS[model])
     opts = dict(pc="cptr", ksp_rtol=1e-8, snes_max_it=25)
-    o, h = satfn_oracle(spec, opts), HipEngine(spec, opts)
+    o, h = OracleEngine(spec, opts), HipEngine(spec, opts)
     for e in (o, h):
         e.set_state(u0)
     for step in range(3):

@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 import cases
-from bc_ref import BcProblem, make_boundary
-from graded_ref import (GradedBcProblem, GradedProblem, equal_widths, field_change, graded_oracle, hydrostatic_graded_column, random_widths,
-                        spec_lengths)
+from bc_ref import make_boundary
+from graded_ref import equal_widths, field_change, hydrostatic_graded_column, random_widths, spec_lengths
 from oracle.tpfa import Problem
 from thermalporous_amd import utils
 from thermalporous_amd.homogeneousboxgeo import HomogeneousBoxGeo
@@ -48,7 +47,7 @@ def test_equal_widths_reproduce_the_oracle(pid, builder, kw):
     spec, *_ = builder(**kw)
     u = cases.perturbed_state(spec, seed=3)
     R0, J0, S0 = _all(Problem(spec), u)
-    R1, J1, S1 = _all(GradedProblem(spec, equal_widths(spec)), u)
+    R1, J1, S1 = _all(Problem(spec, hs=equal_widths(spec)), u)
     for f in range(R0.shape[0]):
         _close(R1[f], R0[f], ("residual", f))
         for c in range(R0.shape[0]):
@@ -61,7 +60,7 @@ def test_random_widths_change_every_field_and_the_analytic_jacobian_is_exact(pid
     spec, *_ = builder(**kw)
     u = cases.perturbed_state(spec, seed=3)
     R0, J0, S0 = _all(Problem(spec), u)
-    G = GradedProblem(spec, random_widths(spec["n"], spec_lengths(spec), 7))
+    G = Problem(spec, hs=random_widths(spec["n"], spec_lengths(spec), 7))
     R1, J1, S1 = _all(G, u)
     change = field_change(R1, R0, spec)
     print(pid, "change of the residual fields:", change)
@@ -72,7 +71,7 @@ def test_random_widths_change_every_field_and_the_analytic_jacobian_is_exact(pid
             _close(J1[:, r, c], Jc[:, r, c], ("J", r, c))
     assert np.abs(S1[1:] - S0[1:]).max() > 0.01*np.abs(S0[1:]).max()      # (the off-diagonals: the faces alone)
     # a closed box conserves: with no sources the residual sums to nothing
-    P = GradedProblem(dict(spec, sources=None), G.hs)
+    P = Problem(dict(spec, sources=None), hs=G.geom.hs)
     P.set_old(u)
     P.set_dt(8640.0)
     R = P.residual(u)
@@ -84,14 +83,14 @@ def test_graded_sides_reduce_to_the_uniform_sides_and_differentiate_exactly():
     spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
     u = cases.perturbed_state(spec, seed=3)
     spec["boundary"] = make_boundary(spec, u, {s: "open" for s in range(6)}, seed=4)
-    R0, J0, S0 = _all(BcProblem(spec), u)
-    R1, J1, S1 = _all(GradedBcProblem(spec, hs=equal_widths(spec)), u)
+    R0, J0, S0 = _all(Problem(spec), u)
+    R1, J1, S1 = _all(Problem(spec, hs=equal_widths(spec)), u)
     _close(R1, R0, "R")
     _close(J1, J0, "J")
     _close(S1, S0, "S~")
-    G = GradedBcProblem(spec, hs=random_widths(spec["n"], spec_lengths(spec), 9))
+    G = Problem(spec, hs=random_widths(spec["n"], spec_lengths(spec), 9))
     R2, J2, _ = _all(G, u)
-    assert np.abs(G.last_flux - BcProblem(spec).last_flux).max() > 0.0
+    assert np.abs(G.last_flux - Problem(spec).last_flux).max() > 0.0
     Jc = G.jacobian_complex_step(u)
     for r in range(3):
         for c in range(3):
@@ -102,13 +101,13 @@ def test_per_row_bound_of_the_combination_tests():
     """test_gpu_assembly_combos.py bounds, per cell and equation, the difference of a row of J by TOL_ROW times the row's own
     largest entry.  The bound is not chosen: at that file's graded inputs with sides (row 3 of edge_cases.COMBO_ROWS, every
     edge kind and the geometric widths), the largest such per-row difference between two evaluations of the reference itself --
-    GradedBcProblem's analytic Jacobian and the complex step of its residual -- is measured here, and
+    the graded problem with sides: its analytic Jacobian and the complex step of its residual -- is measured here, and
     TOL_ROW = max(1e-11, 10 x that): the factor 10 for the GPU's other summation order over at most 13 terms per entry."""
     import edge_cases as ec
     worst, n = 0.0, 0
     for case in ec.combo_cases(rows=(3,)):
         spec, u = ec.combo_input(case)
-        G = GradedBcProblem(spec)
+        G = Problem(spec)
         G.set_old(u)
         G.set_dt(ec.COMBO_DT)
         J, Sm = G.jacobian(u, want_schur=True)
@@ -142,7 +141,7 @@ def test_per_row_rule_sees_a_thin_cell_that_the_per_block_rule_misses():
 def test_the_reference_alone_meets_the_hydrostatic_bound():
     spec, u, scale = hydrostatic_graded_column()
     res = []
-    for P in (GradedProblem(spec), Problem(spec)):
+    for P in (Problem(spec), Problem({k: v for k, v in spec.items() if k != "hs"})):
         P.set_old(u)
         P.set_dt(864.0)
         R = P.residual(u)[0].reshape(-1)
@@ -153,16 +152,16 @@ def test_the_reference_alone_meets_the_hydrostatic_bound():
 
 def test_strengths_follow_the_library_rule():
     spec, *_ = cases.c4_spe10_3d(Nx=6, Ny=5, Nz=4, nphase=2)
-    P, G = Problem(spec), GradedProblem(spec, equal_widths(spec))
+    P, G = Problem(spec), Problem(spec, hs=equal_widths(spec))
     assert np.allclose(G.G, P.G, rtol=1e-13)
     hs = random_widths(spec["n"], spec_lengths(spec), 7)
-    G = GradedProblem(spec, hs)
+    G = Problem(spec, hs=hs)
     for a in range(3):
         lo = [slice(None)]*3
         lo[2 - a] = slice(None, -1)
         hi = [slice(None)]*3
         hi[2 - a] = slice(1, None)
-        brute = np.mean(G.Aa[a][tuple(lo)]/(0.5*(G.ha[a][tuple(lo)] + G.ha[a][tuple(hi)])))
+        brute = np.mean(G.geom.Aa[a][tuple(lo)]/(0.5*(G.geom.ha[a][tuple(lo)] + G.geom.ha[a][tuple(hi)])))
         assert abs(G.G[a] - brute) < 1e-12*brute
 
 
@@ -304,7 +303,7 @@ def test_vtr_round_trip(tmp_path):
 
 
 def _factory(spec, opts):
-    return graded_oracle(spec, opts) if "hs" in spec else __import__("oracle.engine").engine.OracleEngine(spec, opts)
+    return __import__("oracle.engine").engine.OracleEngine(spec, opts)
 
 
 _factory.supports_spacing = True

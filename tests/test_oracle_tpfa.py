@@ -33,7 +33,7 @@ def test_flux_terms_conserve(nphase):
     P.set_dt(1000.0)
     R = P.residual(u)
     w = [P.w0, 1.0, P.w2]
-    acc = (P.accum(*P.split(u)) - P.old)*(P.V/P.dt)
+    acc = (P.accum(*P.split(u)) - P.old)*(P.vol/P.dt)
     for q in range(P.b):
         total, ref = R[q].sum(), (w[q]*acc[q]).sum()
         scale = np.abs(R[q]).sum()

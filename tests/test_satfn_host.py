@@ -10,7 +10,7 @@ import pytest
 
 import cases
 from oracle.tpfa import Problem
-from satfn_ref import (DEGENERATE, M1, M2, M3, SatfnProblem, capillary_gravity_column, column_face_fluxes, curves)
+from satfn_ref import DEGENERATE, M1, M2, M3, capillary_gravity_column, column_face_fluxes, curves
 from test_gpu_assembly_edges import TOL, assert_entries
 from thermalporous_amd.physicalparameters import SATFN_DEFAULT, PhysicalParameters, check_satfn, satfn_is_default
 from thermalporous_amd.problem import build_spec
@@ -121,7 +121,7 @@ def test_degenerate_corey_reproduces_the_oracle(pid, builder, kw):
     spec, *_ = builder(**kw)
     u = cases.perturbed_state(spec, seed=3)
     Ro, Jo, So = _all(Problem(spec), u)
-    R, J, Sm = _all(SatfnProblem(spec, satfn=DEGENERATE), u)
+    R, J, Sm = _all(Problem(spec, satfn=DEGENERATE), u)
     assert_entries(R, J, Sm, Ro, Jo, So, pid)
 
 
@@ -131,12 +131,12 @@ def test_the_models_change_every_residual_field():
     u = cases.perturbed_state(spec, seed=3)
     Ro, _, _ = _all(Problem(spec), u)
     for sat in (M1, M2, M3):
-        P = SatfnProblem(spec, satfn=sat)
+        P = Problem(spec, satfn=sat)
         P.set_old(u)
         P.set_dt(8640.0)
         assert min(field_change(P.residual(u), Ro, spec)) > 0.01
     # a closed box conserves under M2
-    P = SatfnProblem(dict(spec, sources=None), satfn=M2)
+    P = Problem(dict(spec, sources=None), satfn=M2)
     P.set_old(u)
     P.set_dt(8640.0)
     R = P.residual(u)
@@ -163,7 +163,7 @@ def test_spec_carries_satfn_only_when_set():
     assert spec["satfn"]["relperm"] == "brooks_corey" and spec["satfn"]["capillary"] == "linear" and spec["satfn"]["p_ct"] == 0.05
     assert len(q.as_dict()) == 17 and spec["prm"] == q.as_dict()
     # the reference reads the same dict
-    P = SatfnProblem(dict(spec, sources=None))
+    P = Problem(dict(spec, sources=None))
     assert {k: P.sat[k] for k in spec["satfn"]} == spec["satfn"]
     r = _params(capillary="linear", p_ct=0.02)         # capillary pressure alone, linear curves
     assert _box(r)["satfn"]["relperm"] == "linear"
@@ -244,15 +244,15 @@ def test_single_phase_model_refuses():
 def test_the_time_loop_runs_the_model_on_the_reference():
     """TwoPhase.solve() through the numpy reference as its engine: the model reaches the engine through spec["satfn"], the run
     ends without a failed solve and S_o stays in [0, 1]."""
-    from satfn_ref import satfn_oracle
+    from oracle.engine import OracleEngine
     from thermalporous_amd.twophase import TwoPhase
-    factory = lambda spec, opts: satfn_oracle(spec, opts)
+    factory = lambda spec, opts: OracleEngine(spec, opts)
     factory.supports_satfn = True
     p = _params(**M1)
     geo, case = _wells(p)
     m = TwoPhase(geo, case, p, end=0.002, maxdt=0.001, small_dt_start=False, solver_parameters="pc_cptr", filename=None,
                  verbosity=False, _engine_factory=factory)
-    assert m.spec["satfn"]["relperm"] == "corey" and isinstance(m.engine.prob, SatfnProblem)
+    assert m.spec["satfn"]["relperm"] == "corey" and m.engine.prob.sat["relperm"] == "corey"
     m.solve()
     S = m.u._read()[2]
     assert S.min() >= 0.0 and S.max() <= 1.0 and S.min() < 0.9
@@ -270,7 +270,7 @@ def test_capillary_gravity_column_is_an_equilibrium_of_the_reference():
     print("S_o up the column:", S, "Se_w:", Se_w)
     assert abs(Se_w[0] - 0.9) < 1e-15 and np.all((Se_w > 0.0) & (Se_w < 1.0))
     assert np.all(np.diff(S) > 0.0) and S[-1] - S[0] > 0.2
-    P = SatfnProblem(spec)
+    P = Problem(spec)
     P.set_old(u)
     P.set_dt(1e10)
     R = P.residual(u)
@@ -279,7 +279,7 @@ def test_capillary_gravity_column_is_an_equilibrium_of_the_reference():
     assert np.all(np.abs(F) < 1e-8*scale) and np.all(scale > 0.0)
     assert np.abs(R[1]).max() == 0.0 or np.abs(R[1]).max() < 1e-8*np.abs(u[1]).max()*scale.max()*spec["prm"]["c_v_w"]
     # without the capillary pressure the same state is no equilibrium
-    Q = SatfnProblem(spec, satfn=dict(sat, capillary=None))
+    Q = Problem(spec, satfn=dict(sat, capillary=None))
     Q.set_old(u)
     Q.set_dt(1e10)
     F0 = column_face_fluxes(Q, Q.residual(u))
@@ -303,11 +303,10 @@ def _max_close(a, b, bound, tag):
 
 def test_triple_with_equal_widths_is_the_uniform_sides_reference():
     from graded_ref import equal_widths
-    from satfn_ref import SatfnBcProblem, SatfnGradedBcProblem
     spec, u, B = _triple_box()
     for sat in (M2, M3):
-        R0, J0, S0 = _all(SatfnBcProblem(spec, B, satfn=sat), u)
-        P = SatfnGradedBcProblem(spec, B, equal_widths(spec), satfn=sat)
+        R0, J0, S0 = _all(Problem(spec, boundary=B, satfn=sat), u)
+        P = Problem(spec, hs=equal_widths(spec), boundary=B, satfn=sat)
         R1, J1, S1 = _all(P, u)
         assert np.abs(P.last_flux[[1, 3, 4], 1]).min() > 0.0 and np.abs(P.last_flux[[1, 4]]).min() > 0.0
         for f in range(3):
@@ -318,14 +317,13 @@ def test_triple_with_equal_widths_is_the_uniform_sides_reference():
 
 
 def test_triple_in_the_degenerate_corey_case_is_the_graded_sides_reference():
-    """GradedBcProblem's Jacobian is analytic: it thereby checks the complex-step one of the composed class, sides included."""
-    from graded_ref import GradedBcProblem, random_widths, spec_lengths
-    from satfn_ref import SatfnGradedBcProblem
+    """Without curves the Jacobian is analytic: it thereby checks the complex-step one under curves, sides included."""
+    from graded_ref import random_widths, spec_lengths
     spec, u, B = _triple_box()
     hs = random_widths(spec["n"], spec_lengths(spec), 7)
-    G = GradedBcProblem(spec, B, hs)
+    G = Problem(spec, hs=hs, boundary=B)
     Ro, Jo, So = _all(G, u)
-    P = SatfnGradedBcProblem(spec, B, hs, satfn=DEGENERATE)
+    P = Problem(spec, hs=hs, boundary=B, satfn=DEGENERATE)
     R, J, Sm = _all(P, u)
     assert_entries(R, J, Sm, Ro, Jo, So, "degenerate triple")
     for q in range(3):
@@ -334,24 +332,23 @@ def test_triple_in_the_degenerate_corey_case_is_the_graded_sides_reference():
 
 def test_triple_without_sides_is_the_graded_reference_bit_for_bit():
     from graded_ref import random_widths, spec_lengths
-    from satfn_ref import SatfnGradedBcProblem, SatfnGradedProblem
     spec, u, _ = _triple_box()
     hs = random_widths(spec["n"], spec_lengths(spec), 7)
-    a = _all(SatfnGradedProblem(spec, hs, satfn=M2), u)
-    b = _all(SatfnGradedBcProblem(spec, {}, hs, satfn=M2), u)
+    a = _all(Problem(spec, hs=hs, satfn=M2), u)
+    b = _all(Problem(spec, hs=hs, boundary={}, satfn=M2), u)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
 
 
 def test_wells_reference_composes_the_triple():
-    from satfn_ref import SatfnGradedBcProblem
     from graded_ref import random_widths, spec_lengths
+    from oracle.tpfa import GradedGeometry
     from wells_ref import wells_problem
     spec, u, B = _triple_box()
     spec = dict(spec, hs=random_widths(spec["n"], spec_lengths(spec), 7), boundary=B, satfn={**M2})
     W = wells_problem(spec, wells=[])
-    assert isinstance(W, SatfnGradedBcProblem) and type(W).__name__ == "WellsSatfnGradedBcProblem"
-    a, b = _all(W, u), _all(SatfnGradedBcProblem(spec), u)
+    assert type(W) is Problem and isinstance(W.geom, GradedGeometry) and sorted(W.boundary) == sorted(B) and W.sat["capillary"] == "linear"
+    a, b = _all(W, u), _all(Problem(spec), u)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
 

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import cases
-from wells_ref import (WellsProblem, line_cells, make_well, peaceman, solve_bhp, solve_bhp_brute, tune_wells, wells_problem)
+from wells_ref import (line_cells, make_well, peaceman, solve_bhp, solve_bhp_brute, tune_wells, wells_problem)
 
 
 def _small(nphase, seed=3, **kw):
@@ -17,7 +17,7 @@ def _small(nphase, seed=3, **kw):
              make_well(spec, "I", "inj", line_cells(spec, 0, (0, 2), 1, n[0]), 0, 1.0, 1.0),
              make_well(spec, "H", "prod", line_cells(spec, 2, (2, 2)), 2, 1.0, 1.0),
              make_well(spec, "B", "inj", line_cells(spec, 1, (3, 0)), 1, 1.0, 1.0)]
-    prob = WellsProblem(spec, wells=wells)
+    prob = wells_problem(spec, wells=wells)
     wells = tune_wells(prob, u, wells, {"P": ("rate", 0.3), "I": ("rate", 0.3), "H": ("bhp", 0.4), "B": ("bhp", 0.4)})
     prob.set_dt(8640.0)
     return spec, u, prob, wells
