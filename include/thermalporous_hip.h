@@ -269,6 +269,11 @@ typedef struct tp_solve_info {
 
 const char *tp_last_error(void);
 int tp_version(void);
+/* The TP_* runtime switches (environment variables) the library reads, DESIGN.md 10: their number, and switch i as five
+ * static strings -- environment name, kind ("flag" | "int" | "real"), default as documented, when it is read ("process":
+ * once per process | "setup": at every preconditioner set-up) and a one-line effect.  No context, no GPU. */
+int tp_switch_count(void);
+int tp_switch_entry(int i, const char **name, const char **kind, const char **dflt, const char **when, const char **effect);
 
 /* lifetime ------------------------------------------------------------------------------------ */
 int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, int device, tp_ctx **out);

@@ -4,22 +4,16 @@ cannot pipeline either; TP_GRAPH: recorded or eager pc_apply; TP_MD_CHUNK: 8 or 
 cannot be changed inside one process, so the parent runs this script once per setting.  It runs tp_fgmres with ksp_basis_single
 on two inputs of basis_single_ref.PARITY -- c3_cptr and c4_cptr -- with the right-hand side the GPU assembles, and writes to
 the .npz path given as argv[1], per input <name>: <name>.its, .reason, .rnorm, .cycles, .programs and <name>.x."""
-import os
-import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import basis_single_ref as R                            # noqa: E402
-import cases                                            # noqa: E402
-from thermalporous_amd.engine import HipEngine         # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import basis_single_ref as R
+import cases
+from thermalporous_amd.engine import HipEngine
 
 NAMES = ("c3_cptr", "c4_cptr")
 
 
-def main(path):
+def main():
     out = {}
     for name, shape, opts, dt, seed, kw in R.PARITY:
         if name not in NAMES:
@@ -40,9 +34,8 @@ def main(path):
         out[name + ".programs"] = h.ksp_info()["pc_programs"]
         out[name + ".x"] = h.vec_get("x")
         h.close()
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

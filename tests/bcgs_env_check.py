@@ -4,22 +4,16 @@ eager pc_apply) cannot be changed inside one process, so the parent runs this sc
 inputs of bcgs_ref.PARITY -- c3_cptr (even plane size: 16-byte items by default) and c4_cptr (7 x 13 planes: 8-byte items
 always) -- with the right-hand side the GPU assembles, and writes to the .npz path given as argv[1], per input <name>:
 <name>.its, .reason, .rnorm, .programs (tp_ksp_info's pc_apply programs) and <name>.x."""
-import os
-import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bcgs_ref as R                                    # noqa: E402
-import cases                                            # noqa: E402
-from thermalporous_amd.engine import HipEngine         # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import bcgs_ref as R
+import cases
+from thermalporous_amd.engine import HipEngine
 
 NAMES = ("c3_cptr", "c4_cptr")
 
 
-def main(path):
+def main():
     out = {}
     for name, shape, opts, dt, seed in R.PARITY:
         if name not in NAMES:
@@ -39,9 +33,8 @@ def main(path):
         out[name + ".programs"] = h.ksp_info()["pc_programs"]
         out[name + ".x"] = h.vec_get("x")
         h.close()
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

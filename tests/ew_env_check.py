@@ -4,19 +4,15 @@ application, or a host wait per iteration) cannot be changed inside one process,
 setting, each time as a fresh process.  It runs the ramp of tests/ew_ref.py under Eisenstat-Walker version 2 with FGMRES and with
 BiCGStab and writes to the .npz path given as argv[1], per method: <ksp>.counts = per step (nits, lits, reason), <ksp>.rtol /
 .fnorm / .lresid / .kits = the histories of all steps one after the other, and the final state <ksp>.x."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import ew_ref as R                                      # noqa: E402
-from thermalporous_amd.engine import HipEngine         # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import ew_ref as R
+from thermalporous_amd.engine import HipEngine
 
 
-def main(path):
+def main():
     out = {}
     spec, u0, *_ = R.ramp_case()
     for ksp in ("fgmres", "bcgs"):
@@ -35,9 +31,8 @@ def main(path):
             out[ksp + "." + k] = np.array(hist[k])
         out[ksp + ".x"] = h.get_state()
         h.close()
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

@@ -1,17 +1,12 @@
 """Child process of tests/test_gpu_parity.py::test_env_selected_sweep_kernels: the kernel variants that are selected by
 environment variables read once per process (ILU(0) sweeps: TP_ILU_MW, TP_ILU_BLOCK, TP_ILU_YLDS; ILU(1): TP_ILU1_PACK, TP_ILU1_FACTOR_TILE, TP_ILU1_PF; system AMG: TP_BAMG_*;
 LDS-tiled assembly: TP_ASM_LDS) against the oracle."""
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import cases                                            # noqa: E402
-from oracle.engine import OracleEngine                  # noqa: E402
-from thermalporous_amd.engine import HipEngine          # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import cases
+from oracle.engine import OracleEngine
+from thermalporous_amd.engine import HipEngine
 
 
 def rel2(a, b):
@@ -28,34 +23,40 @@ CASES = [(cases.c4_spe10_3d, dict(Nx=11, Ny=13, Nz=17, nphase=2), dict(pc="cptr"
          # system AMG: tail kernel / fused correction / LDS dense inverse (defaults) or the per-level kernels
          # (TP_BAMG_TAIL_CELLS=0, TP_BAMG_FUSE_BELOW=0, TP_BAMG_DENSE_LDS=0)
          (cases.c4_spe10_3d, dict(Nx=12, Ny=20, Nz=10, nphase=2), dict(pc="cptramg", decoup="QI"))]
-for builder, kw, opts in CASES:
-    spec, u0, *_ = builder(**kw)
-    o, h = OracleEngine(spec, opts), HipEngine(spec, opts)
-    u = cases.perturbed_state(spec, seed=5, amp=0.3)
-    for e in (o, h):
-        e.set_old(u0)
-        e.set_dt(8640.0)
-        e.set_state(u)
-    schur = opts["pc"] == "cptr"
-    out = o.jacobian(want_schur=schur)
-    J, Sm = out if schur else (out, None)
-    outh = h.jacobian(want_schur=schur)
-    Jh, Smh = outh if schur else (outh, None)
-    # assembly entries (the kernel variant TP_ASM_LDS selects must reproduce the default's entries)
-    assert np.abs(h.residual() - o.residual()).max() <= 1e-11*np.abs(o.residual()).max()
-    for r in range(o.b):
-        for cc in range(o.b):
-            sc = np.abs(J[:, r, cc]).max()
-            assert np.abs(Jh[:, r, cc] - J[:, r, cc]).max() <= 1e-11*sc, (builder.__name__, kw, r, cc)
-    if schur:
-        assert np.abs(Smh - Sm).max() <= 1e-11*np.abs(Sm).max()
-    o.pc.setup(J, Sm)
-    h.pc_setup()
-    x = np.random.default_rng(11).standard_normal(u.shape)
-    h.vec_set("x", x)
-    h.ilu_solve("x", "y")
-    assert rel2(h.vec_get("y"), o.pc.ilu.solve(x)) < 1e-10, (builder.__name__, kw)
-    h.pc_apply("x", "y")
-    assert rel2(h.vec_get("y"), o.pc.apply(x)) < 1e-9, (builder.__name__, kw)
-    h.close()
-print("ok")
+
+
+def main():
+    for builder, kw, opts in CASES:
+        spec, u0, *_ = builder(**kw)
+        o, h = OracleEngine(spec, opts), HipEngine(spec, opts)
+        u = cases.perturbed_state(spec, seed=5, amp=0.3)
+        for e in (o, h):
+            e.set_old(u0)
+            e.set_dt(8640.0)
+            e.set_state(u)
+        schur = opts["pc"] == "cptr"
+        out = o.jacobian(want_schur=schur)
+        J, Sm = out if schur else (out, None)
+        outh = h.jacobian(want_schur=schur)
+        Jh, Smh = outh if schur else (outh, None)
+        # assembly entries (the kernel variant TP_ASM_LDS selects must reproduce the default's entries)
+        assert np.abs(h.residual() - o.residual()).max() <= 1e-11*np.abs(o.residual()).max()
+        for r in range(o.b):
+            for cc in range(o.b):
+                sc = np.abs(J[:, r, cc]).max()
+                assert np.abs(Jh[:, r, cc] - J[:, r, cc]).max() <= 1e-11*sc, (builder.__name__, kw, r, cc)
+        if schur:
+            assert np.abs(Smh - Sm).max() <= 1e-11*np.abs(Sm).max()
+        o.pc.setup(J, Sm)
+        h.pc_setup()
+        x = np.random.default_rng(11).standard_normal(u.shape)
+        h.vec_set("x", x)
+        h.ilu_solve("x", "y")
+        assert rel2(h.vec_get("y"), o.pc.ilu.solve(x)) < 1e-10, (builder.__name__, kw)
+        h.pc_apply("x", "y")
+        assert rel2(h.vec_get("y"), o.pc.apply(x)) < 1e-9, (builder.__name__, kw)
+        h.close()
+
+
+if __name__ == "__main__":
+    child_main(main)

@@ -5,17 +5,13 @@ in a process of its own and the parent compares what the two processes wrote, bi
 
 writes one array per case: a whole pc_apply, or the pressure and S~ V-cycles."""
 import ctypes as C
-import os
-import sys
 import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import cases                                            # noqa: E402
-from thermalporous_amd import engine as E               # noqa: E402
+from switches import child_main, setup_env     # first: it puts the repository root on the path
+import cases
+from thermalporous_amd import engine as E
 
 # (name, grid, options, environment of the hierarchy's build, what to run)
 CASES = [
@@ -35,29 +31,13 @@ CASES = [
 SLABS = ("slabs2_8x21x7", dict(Nx=8, Ny=21, Nz=7, nphase=2), dict(pc="cptr", amg_gather_cells=0), 3000.0)
 
 
-class build_env:
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        os.environ.update(self.env)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def main(path):
+def main():
     out = {}
     for name, kw, opts, env, what in CASES:
         spec, u0, *_ = cases.c4_spe10_3d(**kw)
         u = cases.perturbed_state(spec, seed=5, amp=0.3)
         x = np.random.default_rng(11).standard_normal(u.shape)
-        with build_env(env):
+        with setup_env(**env):
             h = E.HipEngine(spec, opts)
             h.set_old(u0)
             h.set_dt(8640.0)
@@ -108,9 +88,8 @@ def main(path):
     assert not err, err
     out[name + "_v0"] = np.concatenate([r[0] for r in res], axis=-3)
     out[name + "_dist"] = np.array([res[0][1]])
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

@@ -6,17 +6,13 @@ It runs a fixed list of linear and Newton solves and writes what they returned t
   Newton run <name>:   <name>.nits, .lits, .reason, .vcycles (one entry per time step) and <name>.u (final state);
                        1, 2 and 3 slabs, and one single-slab run with ksp_restart 5."""
 import ctypes as C
-import os
-import sys
 import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import cases                                            # noqa: E402
-from thermalporous_amd import engine as E              # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import cases
+from thermalporous_amd import engine as E
 
 LINEAR = [
     ("cptr3d", cases.c4_spe10_3d, dict(Nx=7, Ny=13, Nz=9, nphase=2), dict(pc="cptr", ksp_rtol=1e-10)),
@@ -84,16 +80,15 @@ def newton(out, name, nranks, **extra):
     out[name + ".u"] = np.concatenate([r[1] for r in res], axis=1)
 
 
-def main(path):
+def main():
     out = {}
     for name, builder, kw, opts in LINEAR:
         linear(out, name, builder, kw, opts)
     for nranks in (1, 2, 3):
         newton(out, "newton%d" % nranks, nranks)
     newton(out, "newton_restart5", 1, ksp_restart=5)     # a speculation may not be issued on a cycle's last iteration
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

@@ -12,14 +12,12 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from switches import ROOT, child_main
 
 
-def main(path, root):
-    sys.path.insert(0, root)
-    sys.path.insert(0, HERE)                                 # cases.py and pc_order_ref.py of THIS checkout (inputs only)
-    import cases
+def main(root=ROOT):
+    sys.path.insert(0, root)                                 # in front of this checkout's root; cases.py and pc_order_ref.py
+    import cases                                             # stay those of THIS checkout (inputs only)
     import pc_order_ref as PR
     from thermalporous_amd import engine as E
     assert os.path.dirname(os.path.dirname(os.path.abspath(E.__file__))) == os.path.abspath(root), E.__file__
@@ -54,8 +52,7 @@ def main(path, root):
     out["newton.fnorm"] = np.array(r["fnorm"])
     out["newton.x"] = h.get_state()
     h.close()
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 def compare(a, b):
@@ -73,4 +70,4 @@ def compare(a, b):
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
-    main(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else ROOT)
+    child_main(lambda: main(*sys.argv[2:3]))

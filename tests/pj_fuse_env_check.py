@@ -5,16 +5,12 @@ the default form against the numpy oracle.
 
 writes per case the pressure and S~ V-cycles of a seeded random vector (and one whole pc_apply), the truncation levels and the
 hierarchies' layouts (tp_amg_layout).  The cases, inputs and the two-slab run of rr_fuse_env_check as they are, and more."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import rr_fuse_env_check as K                           # noqa: E402
-from thermalporous_amd import engine as E               # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import rr_fuse_env_check as K
+from thermalporous_amd import engine as E
 
 TOP = K.TOP         # every level above an 8-cell tail is a "big" level, every V(nu,nu) level takes the top levels' up-leg path
 SMALL = dict(pc="cptr", amg_min_cells=4)
@@ -37,11 +33,11 @@ CASES.update({
 SLABS, DT, AMP, inputs = K.SLABS, K.DT, K.AMP, K.inputs
 
 
-def main(path):
+def main():
     out = {}
     for name, (kw, opts, env, whole) in CASES.items():
         spec, u0, u, x = K.inputs(kw)
-        with K.build_env(env):
+        with K.setup_env(**env):
             h = E.HipEngine(spec, opts)
             h.set_old(u0)
             h.set_dt(K.DT)
@@ -59,8 +55,7 @@ def main(path):
             out[name + "_pc"] = h.vec_get("z").copy()
         h.close()
     out.update(slabs_run())
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 def slabs_run():
@@ -88,7 +83,7 @@ def slabs_run():
             h.close()
         except Exception as e:      # noqa: BLE001
             err.append((rank, repr(e)))
-    with K.build_env(env):
+    with K.setup_env(**env):
         ts = [threading.Thread(target=worker, args=(r,)) for r in range(2)]
         for t in ts:
             t.start()
@@ -101,4 +96,4 @@ def slabs_run():
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

@@ -4,19 +4,15 @@ TP_REORTH_DOT_REVERSE: the direction of the second dot pass) cannot be changed i
 script once per setting.  It runs a Newton solve of the 7 x 13 x 9 two-phase case with ksp_reorth "always" and "ifneeded" and
 writes to the .npz path given as argv[1], per mode: <mode>.counts = (nits, lits, reason, second passes executed), <mode>.fnorm and
 the final state <mode>.x."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bcgs_ref as R                                    # noqa: E402
-from thermalporous_amd.engine import HipEngine         # noqa: E402
+from switches import child_main     # first: it puts the repository root on the path
+import bcgs_ref as R
+from thermalporous_amd.engine import HipEngine
 
 
-def main(path):
+def main():
     out = {}
     builder, kw = R._shapes()["c4"]
     spec, u0, *_ = builder(**kw)
@@ -30,9 +26,8 @@ def main(path):
         out[mode + ".fnorm"] = r["fnorm"]
         out[mode + ".x"] = h.get_state()
         h.close()
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

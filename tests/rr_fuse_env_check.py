@@ -7,17 +7,13 @@ against the numpy oracle.
 writes per case the pressure and S~ V-cycles of a seeded random vector (and one whole pc_apply), the truncation levels and the
 hierarchies' layouts (tp_amg_layout)."""
 import ctypes as C
-import os
-import sys
 import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import cases                                            # noqa: E402
-from thermalporous_amd import engine as E               # noqa: E402
+from switches import child_main, setup_env     # first: it puts the repository root on the path
+import cases
+from thermalporous_amd import engine as E
 
 # Every level above an 8-cell tail runs as a "big" level and every V(2,2) level takes the top levels' residual -> restriction path
 TOP = {"TP_AMG_TAIL_CELLS": "8", "TP_AMG_FUSE_BELOW": "1"}
@@ -49,22 +45,6 @@ CASES = {
 SLABS = ("slabs2_8x21x7", dict(Nx=8, Ny=21, Nz=7, nphase=2), dict(pc="cptr", amg_gather_cells=0), TOP, 3000.0, 0.2)
 
 
-class build_env:
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        os.environ.update(self.env)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
 def inputs(kw, amp=AMP):
     spec, u0, *_ = cases.c4_spe10_3d(**kw)
     u = cases.perturbed_state(spec, seed=SEED_STATE, amp=amp)
@@ -76,11 +56,11 @@ def layout_row(h, which):
     return np.array([nd] + list(axes))
 
 
-def main(path):
+def main():
     out = {}
     for name, (kw, opts, env, whole) in CASES.items():
         spec, u0, u, x = inputs(kw)
-        with build_env(env):
+        with setup_env(**env):
             h = E.HipEngine(spec, opts)
             h.set_old(u0)
             h.set_dt(DT)
@@ -118,7 +98,7 @@ def main(path):
             h.close()
         except Exception as e:      # noqa: BLE001
             err.append((rank, repr(e)))
-    with build_env(env):
+    with setup_env(**env):
         ts = [threading.Thread(target=worker, args=(r,)) for r in range(2)]
         for t in ts:
             t.start()
@@ -129,9 +109,8 @@ def main(path):
     assert not err, err
     out[name + "_v0"] = np.concatenate([r[0] for r in res], axis=-3)
     out[name + "_layout0"] = res[0][1]
-    np.savez(path, **out)
-    print("ok")
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    child_main(main)

@@ -5,10 +5,7 @@ porosity 0 and 1 -- entry by entry against the CPU oracle, on one slab and slab 
 assertions (1e-11 of the largest entry of the same field / block; rates rtol 1e-12).  The saturation guard
 (tp_saturation_range / tp_clamp_saturation) gets its own tests.  Every input is finite and so is the oracle's output."""
 import ctypes as C
-import functools
 import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -16,6 +13,7 @@ import pytest
 
 import cases
 import edge_cases as ec
+import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -199,17 +197,10 @@ def test_saturation_range_is_that_of_the_owned_cells():
 
 
 # ---- the LDS-tiled variant ---------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def _child(tmp, lds):
-    here = os.path.dirname(os.path.abspath(__file__))
-    path = os.path.join(tmp, "asm_lds%d.npz" % lds)
-    env = {k: v for k, v in os.environ.items() if k != "TP_ASM_LDS"}
-    if lds:
-        env["TP_ASM_LDS"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(here, "asm_env_check.py"), path], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
-    return path
+    """The arrays tests/asm_env_check.py wrote under TP_ASM_LDS=1, or with the switch unset (one run each, shared)."""
+    return switches.run_child("asm_env_check.py", {"TP_ASM_LDS": "1"} if lds else {}, out=os.path.join(tmp, "asm_lds%d.npz" % lds),
+                              timeout=300, cache=True)
 
 
 @pytest.mark.parametrize("lds", [1, 0], ids=["lds", "default"])
@@ -227,10 +218,10 @@ def test_lds_tiled_assembly_is_bitwise_the_default(tmp_path_factory):
     into the sum rho+ + rho- of the driving force; under -ffp-contract=fast k_assemble, which inlines eval_props, contracts the
     two into one fma, and a product rounded into the image first cannot be.  The image now holds the two factors."""
     tmp = str(tmp_path_factory.getbasetemp())
-    a, b = np.load(_child(tmp, 1)), np.load(_child(tmp, 0))
-    assert sorted(a.files) == sorted(b.files) and len(a.files) == 3*len(PAIRS)
+    a, b = _child(tmp, 1), _child(tmp, 0)
+    assert sorted(a) == sorted(b) and len(a) == 3*len(PAIRS)
     bad = []
-    for k in a.files:
+    for k in a:
         if a[k].tobytes() != b[k].tobytes():
             x, y = a[k].ravel(), b[k].ravel()
             d = x != y

@@ -15,8 +15,6 @@ recorded: the program count the tests expect is PROGRAMS (1, or 0 under TP_GRAPH
 covered by child processes (test_env_switches, tests/basis_single_env_check.py)."""
 import ctypes as C
 import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -24,12 +22,11 @@ import pytest
 
 import basis_single_ref as R
 import cases
+import switches
 
 pytestmark = pytest.mark.gpu
 
 _REF = {}
-HERE = os.path.dirname(os.path.abspath(__file__))
-SWITCHES = ("TP_FGMRES_PIPE", "TP_PIN", "TP_GRAPH", "TP_MD_CHUNK", "TP_BASIS_VEC")
 BY_NAME = {p[0]: p for p in R.PARITY + [R.LONG]}
 
 
@@ -409,22 +406,9 @@ def test_slabs_match_one_slab(nslabs):
 
 
 # ---- switches read once per process ----------------------------------------------------------------------------------------
-_CHILD = {}
-
-
 def run_child(tmp_path_factory, env):
-    """tests/basis_single_env_check.py with the switches removed from the environment and `env` set: its .npz as a dict (shared)."""
-    key = tuple(sorted(env.items()))
-    if key not in _CHILD:
-        path = str(tmp_path_factory.mktemp("basis_env")/"out.npz")
-        full = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        full.update(env)
-        r = subprocess.run([sys.executable, os.path.join(HERE, "basis_single_env_check.py"), path], env=full, capture_output=True,
-                           text=True, timeout=300)
-        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
-        with np.load(path) as z:
-            _CHILD[key] = {k: z[k] for k in z.files}
-    return _CHILD[key]
+    """tests/basis_single_env_check.py in a fresh process with only `env` of the switches set (one run per setting, shared): its .npz as a dict."""
+    return switches.run_child("basis_single_env_check.py", env, out=tmp_path_factory.mktemp("basis_env")/"out.npz", cache=True)
 
 
 @pytest.mark.parametrize("env", [{"TP_FGMRES_PIPE": "0"}, {"TP_PIN": "0"}, {"TP_GRAPH": "0"}, {"TP_MD_CHUNK": "4"},

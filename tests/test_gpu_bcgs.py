@@ -14,8 +14,6 @@ recorded, so the count the tests expect is PROGRAMS (2, or 0 under TP_GRAPH=0). 
 (TP_PIN, TP_BCGS_WIDE, TP_GRAPH) are covered by child processes (test_env_switches, tests/bcgs_env_check.py)."""
 import ctypes as C
 import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -23,12 +21,11 @@ import pytest
 
 import bcgs_ref as R
 import cases
+import switches
 
 pytestmark = pytest.mark.gpu
 
 _REF = {}
-HERE = os.path.dirname(os.path.abspath(__file__))
-SWITCHES = ("TP_PIN", "TP_BCGS_WIDE", "TP_GRAPH")
 
 
 def _off(name):
@@ -297,22 +294,9 @@ def test_default_path_is_untouched():
 
 
 # ---- switches read once per process ----------------------------------------------------------------------------------------
-_CHILD = {}
-
-
 def run_child(tmp_path_factory, env):
-    """tests/bcgs_env_check.py with the three switches removed from the environment and `env` set: its .npz as a dict (shared)."""
-    key = tuple(sorted(env.items()))
-    if key not in _CHILD:
-        path = str(tmp_path_factory.mktemp("bcgs_env")/"out.npz")
-        full = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        full.update(env)
-        r = subprocess.run([sys.executable, os.path.join(HERE, "bcgs_env_check.py"), path], env=full, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
-        with np.load(path) as z:
-            _CHILD[key] = {k: z[k] for k in z.files}
-    return _CHILD[key]
+    """tests/bcgs_env_check.py in a fresh process with only `env` of the switches set (one run per setting, shared): its .npz as a dict."""
+    return switches.run_child("bcgs_env_check.py", env, out=tmp_path_factory.mktemp("bcgs_env")/"out.npz", cache=True)
 
 
 @pytest.mark.parametrize("env", [{"TP_PIN": "0"}, {"TP_GRAPH": "0"}, {"TP_BCGS_WIDE": "0"}, {"TP_PIN": "0", "TP_BCGS_WIDE": "0"}],

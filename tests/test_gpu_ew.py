@@ -11,9 +11,6 @@ GPU, whose Krylov solves differ from the oracle's by the summation order and +-1
 (ew_ref.PARITY_TOL; profiles/ew_parity.txt; tests/test_ew_host.py re-measures it).  The eta of the run's own record are recomputed
 with the reference's chooser to 1e-14 relative: the same libm pow on the same recorded numbers."""
 import ctypes as C
-import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -22,11 +19,11 @@ import pytest
 import cases
 import ew_ref as R
 import newton_ls_ref as L
+import switches
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_REF, _GPU, _CHILD = {}, {}, {}
+_REF, _GPU = {}, {}
 KSP_RTOL = R.RAMP_OPTS["ksp_rtol"]
 KSP_ATOL = 1e-50
 
@@ -315,21 +312,9 @@ def test_two_slabs():
 
 
 # ---- 7: environment paths ----------------------------------------------------------------------------------------------------------
-SWITCHES = ("TP_PIN", "TP_FGMRES_PIPE")
-
-
 def run_child(tmp_path_factory, env):
-    key = tuple(sorted(env.items()))
-    if key not in _CHILD:
-        path = str(tmp_path_factory.mktemp("ew_env")/"out.npz")
-        full = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        full.update(env)
-        r = subprocess.run([sys.executable, os.path.join(HERE, "ew_env_check.py"), path], env=full, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
-        with np.load(path) as z:
-            _CHILD[key] = {k: z[k] for k in z.files}
-    return _CHILD[key]
+    """tests/ew_env_check.py in a fresh process with only `env` of the switches set (one run per setting, shared): its .npz as a dict."""
+    return switches.run_child("ew_env_check.py", env, out=tmp_path_factory.mktemp("ew_env")/"out.npz", cache=True)
 
 
 @pytest.mark.parametrize("env", [{"TP_FGMRES_PIPE": "0"}, {"TP_PIN": "0"}], ids=["pipe0", "pin0"])

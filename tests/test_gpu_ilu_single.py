@@ -5,9 +5,6 @@ rounded to float32.  Both sides round fp64 products to fp32, and a product that 
 and numpy may round to the neighbouring float: the bound is the one the project uses wherever both sides round stored
 operators to fp32, rel <= 1e-6 in the 2-norm (2e-6 on slabs), not the 1e-10 of the fp64 sweeps."""
 import ctypes as C
-import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -15,6 +12,7 @@ import pytest
 
 import cases
 from ilu_single_ref import swap_into
+from switches import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -89,11 +87,7 @@ def test_sweep_parity(name, builder, kw, opts):
 
 def test_one_wave_kernel():
     """TP_ILU_MW=0 (read once per process): k_ilu_solve's fp32 instantiation in ONE fresh child process."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "ilu_single_env_check.py")], env={**os.environ, "TP_ILU_MW": "0"},
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_child("ilu_single_env_check.py", {"TP_ILU_MW": "0"}, timeout=300)
 
 
 PCS = [("cpr", dict(pc="cpr")), ("cptr", dict(pc="cptr")), ("cptr_amg_single", dict(pc="cptr", amg_single=True))]

@@ -4,14 +4,12 @@ recurrence residual) with the oracle's own V-cycle as preconditioner, dropped in
 
 Tolerances: stage outputs rel2 < 1e-10 as in tests/test_gpu_parity.py (1e-9 at C4's true size); Krylov counts +-1; inner
 iteration counts equal on inputs whose reference residual history stays a factor 2 away from the tolerance."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import cases
+from switches import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -351,13 +349,10 @@ def test_outer_solve_counts(name, opts, s1):
 def test_graph_and_eager_agree(s1):
     """TP_GRAPH is read once per process: tests/inner_env_check.py prints a digest of pc_apply outputs; the captured-graph
     path and the eager path (TP_GRAPH=0) must print the same one."""
-    here = os.path.dirname(os.path.abspath(__file__))
     outs = []
     for env in ({}, {"TP_GRAPH": "0"}):
-        r = subprocess.run([sys.executable, os.path.join(here, "inner_env_check.py"), s1], env={**os.environ, **env},
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
-        outs.append([ln for ln in r.stdout.splitlines() if ln.startswith("digest")])
+        so = run_child("inner_env_check.py", env, args=(s1,), timeout=300)
+        outs.append([ln for ln in so.splitlines() if ln.startswith("digest")])
     assert outs[0] and outs[0] == outs[1], outs
 
 

@@ -4,33 +4,19 @@ division and the same rounding to the storage type, so every comparison is BITWI
 
 The switch is read once per process: tests/invd_env_check.py runs every case in one child process per setting, once for the
 whole module, and the tests compare the arrays the two children wrote."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from switches import run_children
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SETTINGS = {"registers": {}, "load": {"TP_AMG_INVD_LOAD": "1"}}
 
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("invd")
-    procs = {}
-    for name, env in SETTINGS.items():          # the two children side by side
-        clean = {k: v for k, v in os.environ.items() if k != "TP_AMG_INVD_LOAD"}
-        procs[name] = subprocess.Popen([sys.executable, os.path.join(HERE, "invd_env_check.py"), str(d/(name + ".npz"))],
-                                       env={**clean, **env}, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    out = {}
-    for name, p in procs.items():
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0 and so.strip().endswith("ok"), (name, so[-2000:], se[-2000:])
-        out[name] = dict(np.load(d/(name + ".npz")))
-    return out
+    return run_children("invd_env_check.py", SETTINGS, tmp_path_factory.mktemp("invd"), timeout=600)         # the children side by side
 
 
 def same_bits(a, b):

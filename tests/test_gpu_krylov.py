@@ -9,18 +9,15 @@ solves and extended-precision residuals), and exact sums for the reductions.  "B
 patterns: the code claims those paths perform the same IEEE operations in the same order."""
 import ctypes as C
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import cases
+import switches
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def rel2(a, b):
@@ -310,15 +307,7 @@ BITWISE_ENVS = [{"TP_FGMRES_PIPE": "0"}, {"TP_PIN": "0"}, {"TP_GRAPH": "0"}, {"T
 
 
 def run_child(tmp_path, env, tag):
-    path = str(tmp_path/("krylov_%s.npz" % tag))
-    full = {k: v for k, v in os.environ.items() if not k.startswith(("TP_FGMRES_PIPE", "TP_PIN", "TP_GRAPH", "TP_SPEC_MARGIN",
-                                                                    "TP_GS_REVERSE", "TP_HALO_OVERLAP", "TP_MD_CHUNK"))}
-    full.update(env)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "krylov_env_check.py"), path], env=full,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
+    return switches.run_child("krylov_env_check.py", env, out=tmp_path/("krylov_%s.npz" % tag), timeout=300)
 
 
 def test_env_switches_keep_krylov_results(tmp_path):

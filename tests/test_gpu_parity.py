@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import cases
+from switches import run_child, setup_env
 
 pytestmark = pytest.mark.gpu
 
@@ -240,11 +241,9 @@ def test_coarse_inverse_kernels(mfma):
     """TP_AMG_DENSE_MFMA (read at every set-up): the coarsest-grid inverse by a blocked Gauss-Jordan whose trailing update runs on
     v_mfma_f64_16x16x4_f64 (default) or by the scalar LDS kernel -- the V-cycle and the whole preconditioner against the oracle,
     full (64-cell) and padded coarsest grids."""
-    import os
     from oracle.engine import OracleEngine
     from thermalporous_amd.engine import HipEngine
-    os.environ["TP_AMG_DENSE_MFMA"] = mfma
-    try:
+    with setup_env(TP_AMG_DENSE_MFMA=mfma):
         for kw in (dict(Nx=16, Ny=18, Nz=16, nphase=2), dict(Nx=9, Ny=14, Nz=8, nphase=2), dict(Nx=7, Ny=5, Nz=3, nphase=1)):
             opts = dict(pc="cptr" if kw["nphase"] == 2 else "cpr")
             spec, u0, *_ = cases.c4_spe10_3d(**kw)
@@ -267,8 +266,6 @@ def test_coarse_inverse_kernels(mfma):
             h.pc_apply("x", "y")
             assert rel2(h.vec_get("y"), o.pc.apply(x)) < 1e-10, kw
             h.close()
-    finally:
-        del os.environ["TP_AMG_DENSE_MFMA"]
 
 
 def test_newton_random_boxes_and_presets():
@@ -424,13 +421,7 @@ def test_env_selected_sweep_kernels(env):
     without block transfers and with y through HBM -- are selected by environment variables the library reads once per
     process: each runs tests/ilu_env_check.py (sweeps and whole preconditioner vs the oracle, 3-D and 2-D, partial tiles) in
     ONE child process."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "ilu_env_check.py")], env={**os.environ, **env},
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
+    run_child("ilu_env_check.py", env, timeout=300)
 
 
 def test_exported_vector_ops():

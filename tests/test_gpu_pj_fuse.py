@@ -10,21 +10,16 @@ Each case asserts from tp_amg_layout that its V(nu,nu) levels coarsen the axes a
 
 Measured on MI355X, default form against the oracle (each test prints its figures): V-cycles 8.5e-17 ... 5.3e-13, the whole
 pc_apply 1.7e-12 and 7.6e-16 (amg_nu = 1), two slabs 5.0e-16."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import pj_fuse_env_check as K
+from switches import run_children
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-10
 RUN = 256               # cells of a run: TP_BLOCK
-SWITCHES = ("TP_AMG_PJ_FUSE", "TP_AMG_INVD_LOAD")
 SETTINGS = {"tile": {}, "two_launches": {"TP_AMG_PJ_FUSE": "0"},
             "tile_invd_load": {"TP_AMG_INVD_LOAD": "1"}, "two_launches_invd_load": {"TP_AMG_PJ_FUSE": "0", "TP_AMG_INVD_LOAD": "1"}}
 
@@ -59,18 +54,7 @@ def same_bits(a, b):
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("pj_fuse")
-    procs = {}
-    for name, env in SETTINGS.items():          # the children side by side
-        clean = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        procs[name] = subprocess.Popen([sys.executable, os.path.join(HERE, "pj_fuse_env_check.py"), str(d/(name + ".npz"))],
-                                       env={**clean, **env}, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    out = {}
-    for name, p in procs.items():
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0 and so.strip().endswith("ok"), (name, so[-2000:], se[-2000:])
-        out[name] = dict(np.load(d/(name + ".npz")))
-    return out
+    return run_children("pj_fuse_env_check.py", SETTINGS, tmp_path_factory.mktemp("pj_fuse"), timeout=600)         # the children side by side
 
 
 def oracle_of(name, kw, opts, dt=K.DT, amp=K.AMP):

@@ -10,9 +10,6 @@ Solver tests: the linear systems of tests/bcgs_ref.py; the first min(its, 6) res
 columns against reorth_ref.fgmres_ref within reorth_ref.FGMRES_TOL = 10 x the deviation between two summation orders of that
 reference on those systems (4.32e-12, case c4_cpr; re-measured by tests/test_reorth_host.py), iteration counts +-1."""
 import ctypes as C
-import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
@@ -21,10 +18,10 @@ import pytest
 import bcgs_ref as R
 import cases
 import reorth_ref as RR
+import switches
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 _REF = {}
 
 
@@ -332,22 +329,9 @@ def test_two_slabs_match_one_slab(mode):
 
 
 # ---- switches the library reads once per process -----------------------------------------------------------------------------
-_CHILD = {}
-SWITCHES = ("TP_PIN", "TP_FGMRES_PIPE", "TP_REORTH_DOT_REVERSE")
-
-
 def run_child(tmp_path_factory, env):
-    key = tuple(sorted(env.items()))
-    if key not in _CHILD:
-        path = str(tmp_path_factory.mktemp("reorth_env")/"out.npz")
-        full = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        full.update(env)
-        r = subprocess.run([sys.executable, os.path.join(HERE, "reorth_env_check.py"), path], env=full, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (env, r.stdout[-2000:], r.stderr[-2000:])
-        with np.load(path) as z:
-            _CHILD[key] = {k: z[k] for k in z.files}
-    return _CHILD[key]
+    """tests/reorth_env_check.py in a fresh process with only `env` of the switches set (one run per setting, shared): its .npz as a dict."""
+    return switches.run_child("reorth_env_check.py", env, out=tmp_path_factory.mktemp("reorth_env")/"out.npz", cache=True)
 
 
 @pytest.mark.parametrize("env", [{"TP_PIN": "0"}, {"TP_FGMRES_PIPE": "0"}, {"TP_REORTH_DOT_REVERSE": "1"}], ids=["pin0", "pipe0", "dotrev"])

@@ -9,21 +9,16 @@ the whole module.  Each case asserts from tp_amg_layout that its V(2,2) levels c
 
 Measured on MI355X, default form against the oracle (each test prints its figures): V-cycles 8.5e-17 ... 1.8e-14, the whole
 pc_apply 2.5e-14, two slabs 5.0e-16; fp32 operators 8.5e-17 and 1.2e-15 (the oracle rounds its stored operators to fp32 as well)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import cases
 import rr_fuse_env_check as K
+from switches import run_children
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-10
-SWITCHES = ("TP_AMG_RR_FUSE", "TP_AMG_INVD_LOAD")
 SETTINGS = {"tile": {}, "two_launches": {"TP_AMG_RR_FUSE": "0"}, "invd_load": {"TP_AMG_INVD_LOAD": "1"}}
 
 # name -> per hierarchy (0 pressure, 1 S~): (coarsening axis, fine extent along it) of the levels with pre-sweeps, from level 0 on
@@ -49,18 +44,7 @@ def same_bits(a, b):
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("rr_fuse")
-    procs = {}
-    for name, env in SETTINGS.items():          # the children side by side
-        clean = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        procs[name] = subprocess.Popen([sys.executable, os.path.join(HERE, "rr_fuse_env_check.py"), str(d/(name + ".npz"))],
-                                       env={**clean, **env}, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    out = {}
-    for name, p in procs.items():
-        so, se = p.communicate(timeout=600)
-        assert p.returncode == 0 and so.strip().endswith("ok"), (name, so[-2000:], se[-2000:])
-        out[name] = dict(np.load(d/(name + ".npz")))
-    return out
+    return run_children("rr_fuse_env_check.py", SETTINGS, tmp_path_factory.mktemp("rr_fuse"), timeout=600)         # the children side by side
 
 
 def oracle_of(name, kw, opts, dt=K.DT, amp=K.AMP):

@@ -17,14 +17,12 @@ also TP_AMG_TAIL_CELLS=8 on the truncated 2-D layer.  Round-off only: the multil
 (V-cycles), 2.4e-14 (stage 1), the unfused kernels (TP_AMG_FUSE_BELOW=1, TP_AMG_TAIL_CELLS=8) against the fused ones <= 1.1e-16
 (V-cycles), 5.7e-14 (stage 1), 2.2e-13 (pc_apply)."""
 import collections
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import cases
+from switches import run_child, setup_env
 
 pytestmark = pytest.mark.gpu
 
@@ -35,24 +33,6 @@ KEYS = ("vp", "vS", "s1", "pc")
 
 def rel2(a, b):
     return np.linalg.norm((a - b).ravel())/max(np.linalg.norm(b.ravel()), 1e-300)
-
-
-class amg_env:
-    """TP_AMG_TAIL_CELLS / TP_AMG_FUSE_BELOW / TP_AMG_TAIL_LDS (read at every build of a hierarchy) and TP_AMG_TAIL_DENSE (read at
-    every set-up) for the construction and set-ups inside the block."""
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        os.environ.update(self.env)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def levels_of(amg):
@@ -310,7 +290,7 @@ def reference(cid):
 def hip_engine(c, ref, env=None):
     """A fresh engine at the case's state with the Jacobian assembled and the preconditioner set up (under `env`)."""
     from thermalporous_amd.engine import HipEngine
-    with amg_env(env or {}):
+    with setup_env(**(env or {})):
         h = HipEngine(ref["spec"], ref["opts"])
         h.set_old(ref["u0"])
         h.set_dt(c.dt)
@@ -509,13 +489,7 @@ def test_pair_switch_child(tmp_path):
     """TP_AMG_PAIR is read once per process: tests/scalar_amg_env_check.py runs the paired case and the default shape with only
     that variable set, in one child process, against the oracle, and hands its vectors back for the comparison with this
     process's paired kernels."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = str(tmp_path/"pair0.npz")
-    r = subprocess.run([sys.executable, os.path.join(here, "scalar_amg_env_check.py"), out], env={**os.environ, "TP_AMG_PAIR": "0"},
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
-    z = np.load(out)
+    z = run_child("scalar_amg_env_check.py", {"TP_AMG_PAIR": "0"}, out=tmp_path/"pair0.npz", timeout=300)
     for cid in PAIR_CHILD_CASES:
         base = default_variant(cid)
         d = [rel2(z["%s/%s" % (cid, k)], base[k]) for k in KEYS]

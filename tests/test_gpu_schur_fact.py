@@ -17,6 +17,7 @@ import pytest
 
 import cases
 import schur_fact_ref as SR
+from switches import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -163,23 +164,9 @@ def test_counters_and_vcycles(name):
 
 
 def test_eager_applications_count_alike():
-    """Without the recording (TP_GRAPH=0 is read once per process: a child) the counters and the results are the same."""
-    import os
-    import subprocess
-    import sys
-    code = ("import sys; sys.path.insert(0, %r); import numpy as np, schur_fact_ref as SR, test_gpu_schur_fact as T\n"
-            "_, b, kw, opts = T.SYS['c4_2ph_cptr']; spec, u0, u, o, J, F = T.oracle(b, kw, opts); x = T.rand(u)\n"
-            "h = T.engine(spec, u0, u, opts); h.vec_set('x', x)\n"
-            "for fact in SR.FACTS:\n"
-            "    T.switch(h, schur_fact=fact)\n"
-            "    for _ in range(3): h.pc_apply('x', 'y')\n"
-            "    i = h.schur_info(); assert (i['k0_applies'], i['ks_applies']) == ((6, 3) if fact == 'full' else (3, 3)), (fact, i)\n"
-            "    assert T.rel2(h.vec_get('y'), SR.apply_fact(o.pc, 'SI', x, fact)) < 1e-10, fact\n"
-            "assert h.ksp_info()['pc_programs'] == 0\n"
-            "h.close(); print('eager ok')\n") % os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, TP_GRAPH="0", PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__)))] + sys.path))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "eager ok" in out.stdout, out.stdout + out.stderr
+    """Without the recording (TP_GRAPH=0 is read once per process: tests/schur_fact_env_check.py in a child) the counters and the
+    results are the same."""
+    run_child("schur_fact_env_check.py", {"TP_GRAPH": "0"}, timeout=300)
 
 
 # ---- 3. FGMRES ------------------------------------------------------------------------------------------------------------------

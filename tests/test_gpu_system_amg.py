@@ -8,15 +8,13 @@ ilu_env_check.py; a one-ulp perturbation of J and x moves the oracle itself by <
 these cases (transfer_only_big_levels: 2.8e-12, 3.7e-13, 6.8e-14).  Each case also asserts, from the oracle's level shapes, that it
 reaches the path it is named for.  Measured differences on an MI355X: <= 2.3e-12 (V-cycle), 4.6e-12 (stage 1), 4.3e-12
 (pc_apply) over all cases; the per-level and unfused kernel variants equal the default kernels bit for bit."""
-import os
-import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
 import cases
+from switches import run_child, setup_env
 
 pytestmark = pytest.mark.gpu
 
@@ -26,23 +24,6 @@ DT, SEED, AMP = 8640.0, 5, 0.3
 
 def rel2(a, b):
     return np.linalg.norm((a - b).ravel())/max(np.linalg.norm(b.ravel()), 1e-300)
-
-
-class bamg_env:
-    """TP_BAMG_TAIL_CELLS / TP_BAMG_FUSE_BELOW (read at every build of the hierarchy) for the set-ups inside the block."""
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        os.environ.update(self.env)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def levels_of(amg):
@@ -161,7 +142,7 @@ def reference(cid):
 def hip_engine(ref, env=None):
     """A fresh engine at the case's state with the Jacobian assembled and the preconditioner set up (under `env`)."""
     from thermalporous_amd.engine import HipEngine
-    with bamg_env(env or {}):
+    with setup_env(**(env or {})):
         h = HipEngine(ref["spec"], ref["opts"])
         h.set_old(ref["u0"])
         h.set_dt(DT)
@@ -254,11 +235,7 @@ def test_kernel_variants(vid, env, cid):
 def test_global_memory_dense_inverse_child():
     """TP_BAMG_DENSE_LDS is read once per process: tests/bamg_env_check.py runs the default and the V(3,3) case with only that
     variable set, in one child process."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, os.path.join(here, "bamg_env_check.py")], env={**os.environ, "TP_BAMG_DENSE_LDS": "0"},
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-2000:])
+    run_child("bamg_env_check.py", {"TP_BAMG_DENSE_LDS": "0"}, timeout=300)
 
 
 def test_live_option_changes_rebuild_the_hierarchy():

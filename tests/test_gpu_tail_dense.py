@@ -4,12 +4,12 @@ DESIGN.md 4.5) against the multilevel tail kernel it replaces and against the or
 T b is another evaluation order of the same linear map, so the bound is the project's stage tolerance, rel <= 1e-10 in the
 2-norm; whole solves: Krylov counts within +-1 of each other, solutions rel <= 1e-8.  The switch is read at every set-up, so
 both forms run in one process."""
-import os
 
 import numpy as np
 import pytest
 
 import cases
+from switches import setup_env
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +18,6 @@ TOL = 1e-10
 
 def rel2(a, b):
     return np.linalg.norm((a - b).ravel())/max(np.linalg.norm(b.ravel()), 1e-300)
-
-
-class tail_dense:
-    """TP_AMG_TAIL_DENSE for the set-ups inside the block."""
-    def __init__(self, on):
-        self.v = "1" if on else "0"
-
-    def __enter__(self):
-        self.old = os.environ.get("TP_AMG_TAIL_DENSE")
-        os.environ["TP_AMG_TAIL_DENSE"] = self.v
-
-    def __exit__(self, *a):
-        if self.old is None:
-            del os.environ["TP_AMG_TAIL_DENSE"]
-        else:
-            os.environ["TP_AMG_TAIL_DENSE"] = self.old
 
 
 def engines(builder, kw, opts, dt=8640.0, seed=5, amp=0.3):
@@ -62,7 +46,7 @@ def set_operator(o, h, spec, u0, dt, seed, amp):
 
 def vcycle(h, which, dense):
     """Set up with the switch at `dense`, one V-cycle of hierarchy `which` on vector x -> result, tail info."""
-    with tail_dense(dense):
+    with setup_env(TP_AMG_TAIL_DENSE="1" if dense else "0"):
         h.pc_setup()
     h.amg_vcycle(which, "x", which, "y", which)
     return h.vec_get("y")[which].copy(), h.amg_tail_info(which)
@@ -185,7 +169,7 @@ def test_whole_solves_with_both_tails(name, builder, kw, opts):
     h.copy_residual_to("b")
     res = {}
     for dense in (True, False):
-        with tail_dense(dense):
+        with setup_env(TP_AMG_TAIL_DENSE="1" if dense else "0"):
             h.pc_setup()
         its, reason, rn = h.fgmres("b", "d")
         assert reason > 0, (name, dense, reason)
@@ -204,7 +188,7 @@ def test_captured_pc_apply_sees_the_new_operator():
     spec, u0, o, h = engines(cases.c4_spe10_3d, dict(Nx=20, Ny=26, Nz=18, nphase=2), dict(pc="cptr"))
     x = np.random.default_rng(15).standard_normal(np.shape(u0))
     h.vec_set("x", x)
-    with tail_dense(True):
+    with setup_env(TP_AMG_TAIL_DENSE="1"):
         h.pc_setup()
         h.pc_apply("x", "y")                 # captured
         h.pc_apply("x", "y")                 # replayed
@@ -217,7 +201,7 @@ def test_captured_pc_apply_sees_the_new_operator():
         y2 = h.vec_get("y").copy()
         info = h.amg_tail_info(0)
     assert info["dense"] and info["builds"] == 2 and info["dense_applies"] == captured, info      # no new capture: a replay
-    with tail_dense(False):
+    with setup_env(TP_AMG_TAIL_DENSE="0"):
         h.pc_setup()
         h.pc_apply("x", "y")
     y2m = h.vec_get("y").copy()

@@ -1358,7 +1358,7 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
     amg = new Amg();
     c->graph_epoch++;            // a new hierarchy may reuse the old one's addresses: never replay graphs across a rebuild
     amg->single = c->opt.amg_single != 0;
-    const long tail_cells = getenv("TP_AMG_TAIL_CELLS") ? atol(getenv("TP_AMG_TAIL_CELLS")) : 1024;
+    const long tail_cells = tp_switch_int(TP_SW_AMG_TAIL_CELLS);
     amg->plan = amg_plan(g0, strength, c->opt, c->dist ? c->grid.rank : 0, rank_slabs(c), gather_cells, tail_cells);
     for (const AmgPlan::Level &P : amg->plan.lv) {
         AmgLevel *L = new AmgLevel();
@@ -1402,14 +1402,14 @@ void amg_build(tp_ctx *c, Amg *&amg, const GridDev &g0, const double strength[3]
     TP_HIP(hipHostMalloc((void **)&amg->ratio_host, 64 * 8 * sizeof(double)));
     TP_HIP(hipEventCreateWithFlags(&amg->ev_ratio, hipEventDisableTiming));
     amg->coarse_inv.alloc((size_t)2 * amg->ncoarse * amg->ncoarse);
-    amg->fuse_below = getenv("TP_AMG_FUSE_BELOW") ? atol(getenv("TP_AMG_FUSE_BELOW")) : 200000;
+    amg->fuse_below = tp_switch_int(TP_SW_AMG_FUSE_BELOW);
     amg->lvdev.alloc(amg->lv.size() * sizeof(LevelDevT<double>));
     // the tail keeps its vectors (b, e, x, x2 of every level) in LDS when they fit next to the level descriptors
     long tot = 0;
     for (size_t l = (size_t)amg->plan.tail_level; l < amg->lv.size(); ++l) tot += amg->lv[l]->g.ntot;
-    const bool lds_on = !(getenv("TP_AMG_TAIL_LDS") && atoi(getenv("TP_AMG_TAIL_LDS")) == 0);
+    const bool lds_on = tp_switch_flag(TP_SW_AMG_TAIL_LDS);
     amg->tail_lds = (lds_on && 4 * tot * (long)sizeof(double) <= 120 * 1024) ? (int)tot : 0;
-    if (getenv("TP_DEBUG")) fprintf(stderr, "[tp] amg tail: level %d of %zu, %ld doubles per vector set, lds %d\n", amg->plan.tail_level, amg->lv.size(), tot, amg->tail_lds);
+    if (tp_switch_int(TP_SW_DEBUG) >= 1) fprintf(stderr, "[tp] amg tail: level %d of %zu, %ld doubles per vector set, lds %d\n", amg->plan.tail_level, amg->lv.size(), tot, amg->tail_lds);
     if (amg->tail_lds > 0) {
         const int bytes = 120 * 1024;      // per-function limit shared by every hierarchy: always the maximum
         const void *fns[4] = {reinterpret_cast<const void *>(&k_amg_tail<double, false>),
@@ -1526,7 +1526,7 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     const int n = amg->ncoarse;
     const StencilT<R> opc{(R *)Lc->op.base, Lc->op.slot_stride};
     if (n <= 64) {
-        const bool mfma = !(getenv("TP_AMG_DENSE_MFMA") && atoi(getenv("TP_AMG_DENSE_MFMA")) == 0);  // (read per set-up: A/B in one process)
+        const bool mfma = tp_switch_flag(TP_SW_AMG_DENSE_MFMA);  // (read per set-up: A/B in one process)
         if (mfma) {
             const int bytes = (64 * 128 + 4 * 128 + 64 * 4 + 16) * (int)sizeof(double);
             TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_amg_dense_inverse_mfma<R>),
@@ -1559,7 +1559,7 @@ static void setup_impl(tp_ctx *c, Amg *amg, const Stencil &A0) {
     // shape never reached the tail, or, at the first set-up, no shape has been resolved yet (amg_resolve_trunc forms it
     // when the cycles turn out to need it).  (switch read per set-up: A/B in one process)
     amg->setup_id++;
-    const bool dense_env = !(getenv("TP_AMG_TAIL_DENSE") && atoi(getenv("TP_AMG_TAIL_DENSE")) == 0);
+    const bool dense_env = tp_switch_flag(TP_SW_AMG_TAIL_DENSE);
     const bool dense = dense_env && amg->tdense_eligible && amg->plan.tail_level >= nratio;
     if (dense != amg->tdense_on) {
         amg->tdense_on = dense;
@@ -1607,18 +1607,18 @@ static void vcycle_impl(tp_ctx *c, Amg *amg, const double *b, double *x) {
     const dim3 bl(256);
     std::vector<double *> xs(nlev, nullptr);       // pre-smoothed iterate of each big level (null: none)
     // level l (smoothed, no pre-sweeps) + level l+1 (pure transfer): both transfers in one launch each way
-    static const bool pair_on = !(getenv("TP_AMG_PAIR") && atoi(getenv("TP_AMG_PAIR")) == 0);
+    static const bool pair_on = tp_switch_flag(TP_SW_AMG_PAIR);
     // the sweeps' centre-cell omega / diag: recomputed in registers (invd_at), or TP_AMG_INVD_LOAD=1: read from the stored plane
-    static const bool invd_reg = !(getenv("TP_AMG_INVD_LOAD") && atoi(getenv("TP_AMG_INVD_LOAD")) != 0);
+    static const bool invd_reg = !tp_switch_flag(TP_SW_AMG_INVD_LOAD);
     // residual + restriction of the top levels in one tiled launch; TP_AMG_RR_FUSE=0: k_amg_resid, then k_amg_restrict
-    static const bool rr_fuse = !(getenv("TP_AMG_RR_FUSE") && atoi(getenv("TP_AMG_RR_FUSE")) == 0);
+    static const bool rr_fuse = tp_switch_flag(TP_SW_AMG_RR_FUSE);
 #define TP_AMG_REG_LAUNCH(KERNEL, ...)                                                                         \
     do {                                                                                                       \
         if (invd_reg) hipLaunchKernelGGL((KERNEL<R, true>), __VA_ARGS__);                                      \
         else hipLaunchKernelGGL((KERNEL<R, false>), __VA_ARGS__);                                              \
     } while (0)
     // correction + first post-sweep of the top levels in one tiled launch; TP_AMG_PJ_FUSE=0: k_amg_prolong_add, then k_amg_jacobi
-    static const bool pj_fuse = !(getenv("TP_AMG_PJ_FUSE") && atoi(getenv("TP_AMG_PJ_FUSE")) == 0);
+    static const bool pj_fuse = tp_switch_flag(TP_SW_AMG_PJ_FUSE);
 #define TP_AMG_PJ_LAUNCH(NH)                                                                                                           \
     do {                                                                                                                       \
         if (invd_reg) hipLaunchKernelGGL((k_amg_prolong_jacobi_tile<R, true, NH>), gt, dim3(TP_BLOCK), 0, c->stream, Ld, cv.g, nruns, ntiles, bl_, (const double *)src, ec, dst); \

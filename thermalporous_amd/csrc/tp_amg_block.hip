@@ -715,8 +715,8 @@ void bamg_build(tp_ctx *c, BAmg *&amg, const GridDev &g0, const double strength[
     c->graph_epoch++;
     const int NB = amg->nb;
     // first level of the single-workgroup tail; replicated levels below fuse_below cells fuse prolongation + first post-sweep
-    const long tail_cells = getenv("TP_BAMG_TAIL_CELLS") ? atol(getenv("TP_BAMG_TAIL_CELLS")) : 1024;
-    amg->fuse_below = getenv("TP_BAMG_FUSE_BELOW") ? atol(getenv("TP_BAMG_FUSE_BELOW")) : 200000;
+    const long tail_cells = tp_switch_int(TP_SW_BAMG_TAIL_CELLS);
+    amg->fuse_below = tp_switch_int(TP_SW_BAMG_FUSE_BELOW);
     amg->plan = amg_plan(g0, strength, c->opt, c->dist ? c->grid.rank : 0, rank_slabs(c), c->opt.amg_gather_cells, tail_cells);
     for (size_t l = 0; l < amg->plan.lv.size(); ++l) {
         const AmgPlan::Level &P = amg->plan.lv[l];
@@ -785,7 +785,7 @@ void bamg_setup(tp_ctx *c, BAmg *amg, const BStencil &A0) {
     }
     BAmgLevel *Lc = amg->lv.back();
     const size_t nd = (size_t)amg->ncoarse * NB;
-    static const bool lds_inv = !(getenv("TP_BAMG_DENSE_LDS") && atoi(getenv("TP_BAMG_DENSE_LDS")) == 0);
+    static const bool lds_inv = tp_switch_flag(TP_SW_BAMG_DENSE_LDS);
     if (lds_inv && nd <= 128) {
         const size_t bytes = nd * nd * sizeof(double);
         TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bamg_dense_inverse_lds<NB>),

@@ -237,7 +237,7 @@ static void drop_hierarchies(tp_ctx *c) {
 }  // namespace tp
 
 tp_ctx::~tp_ctx() {
-    if (getenv("TP_DEBUG") && spec_issued + spec_skipped > 0)
+    if (tp_switch_int(TP_SW_DEBUG) >= 1 && spec_issued + spec_skipped > 0)
         fprintf(stderr, "[tp] pipelined FGMRES: %ld speculative applications issued, %ld discarded, %ld iterations without one\n",
                 spec_issued, spec_wasted, spec_skipped);
     for (auto *v : vecs) delete v;
@@ -315,6 +315,14 @@ extern "C" {
 
 const char *tp_last_error(void) { return tp::g_err.c_str(); }
 int tp_version(void) { return 101; }
+int tp_switch_count(void) { return TP_SW_COUNT; }
+int tp_switch_entry(int i, const char **name, const char **kind, const char **dflt, const char **when, const char **effect) {
+    TP_API_BEGIN
+    TP_REQUIRE(i >= 0 && i < TP_SW_COUNT && name && kind && dflt && when && effect, "tp_switch_entry: bad index or null argument");
+    const tp_switch_info &s = tp_switch_infos[i];
+    *name = s.name, *kind = s.kind, *dflt = s.dflt, *when = s.when, *effect = s.effect;
+    TP_API_END
+}
 
 int tp_create(const tp_grid *grid, const tp_params *prm, const tp_options *opt, int device, tp_ctx **out) {
     TP_API_BEGIN

@@ -1226,7 +1226,7 @@ void assemble(tp_ctx *c, bool want_jac, bool want_schur) {
     const AsmArgs a = asm_args(c);
     if (want_schur) TP_REQUIRE(c->Sm.p, "S~ storage not allocated");
     const dim3 gr = xcd_grid(g.nown), bl(256);
-    static const bool lds_tiled = getenv("TP_ASM_LDS") && atoi(getenv("TP_ASM_LDS")) == 1;
+    static const bool lds_tiled = tp_switch_flag(TP_SW_ASM_LDS);
     const dim3 grl((g.n0 + ATX - 1) / ATX, (g.n1 + ATY - 1) / ATY, (g.n2 + ATZ - 1) / ATZ);
     // a context with spacing always launches the plain graded kernel (the LDS-tiled variant has no graded twin)
     AsmArgsG ag;

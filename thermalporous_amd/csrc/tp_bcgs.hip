@@ -408,7 +408,7 @@ int bcgs(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm_o
     for (const double *q : {bvec, (const double *)x, (const double *)rh, (const double *)t})
         wide = wide && ((uintptr_t)q % 16 == 0);
     wide = wide && (nv % 2 == 0);
-    static const bool allow_wide = !(getenv("TP_BCGS_WIDE") && atoi(getenv("TP_BCGS_WIDE")) == 0);
+    static const bool allow_wide = tp_switch_flag(TP_SW_BCGS_WIDE);
     wide = wide && allow_wide;
     const long nw = bc_nwaves(g, B, wide ? 2 : 1);
     const dim3 gw = xcd_grid(nw * 64, TP_BLOCK), bl(TP_BLOCK), one(1), wv(64);

@@ -11,6 +11,7 @@
 #include <functional>
 #include "../../include/thermalporous_hip.h"
 #include "tp_ew.hpp"
+#include "tp_switches.hpp"
 
 struct ncclComm;
 

@@ -1572,7 +1572,7 @@ static bool ilu_compact(const tp_ctx *c) { return c->g.gn2 > 1 && c->ilu.t1 * c-
 
 // ILU(1) factorisation: one wavefront per tile (k_ilu1_factor_tile, default) or one launch per step (k_ilu1_level)
 static bool ilu1_per_tile() {
-    static const bool v = !(getenv("TP_ILU1_FACTOR_TILE") && atoi(getenv("TP_ILU1_FACTOR_TILE")) == 0);
+    static const bool v = tp_switch_flag(TP_SW_ILU1_FACTOR_TILE);
     return v;
 }
 
@@ -1661,7 +1661,7 @@ void ilu_setup(tp_ctx *c) {
     TP_REQUIRE(!(c->opt.ilu_single && multi), "ilu_single (fp32 factor) is implemented for one tile per block: not with an ilu_block of several tiles");
     d.single = c->opt.ilu_single != 0;
     d.levels = c->opt.ilu_levels;
-    static const bool mw_on = !(getenv("TP_ILU_MW") && atoi(getenv("TP_ILU_MW")) == 0);
+    static const bool mw_on = tp_switch_flag(TP_SW_ILU_MW);
     d.mw = mw_on && d.levels == 0;
     d.nsteps = d.levels ? t0 + 2 * (t1 - 1) + 4 * (t2 - 1) : t0 + t1 + t2 - 2;
     d.slots = (long)d.ntiles * d.nsteps * 64;
@@ -1669,7 +1669,7 @@ void ilu_setup(tp_ctx *c) {
     if (d.levels) {
         d.fwd32.free(); d.bwd32.free();
         const size_t chunks = (size_t)d.ntiles * d.nsteps, bb = (size_t)c->b * c->b;
-        static const bool pack1 = !(getenv("TP_ILU1_PACK") && atoi(getenv("TP_ILU1_PACK")) == 0);
+        static const bool pack1 = tp_switch_flag(TP_SW_ILU1_PACK);
         if (pack1 && ilu1_per_tile()) {     // the per-tile factorisation writes the packed rows itself: no padded arrays
             d.fwd.free(); d.bwd.free();
         } else {
@@ -1809,6 +1809,16 @@ static void ilu_solve_launch(tp_ctx *c, const IluGeom &G, bool ylds, size_t ybyt
     }
 }
 
+// TP_ILU_BLOCK as set (1: block moves, 0: none), or -1: unset, by dimension
+static int ilu_block_env() {
+    static const int v = (int)tp_switch_int(TP_SW_ILU_BLOCK, -1);
+    return v;
+}
+static bool ilu_ylds_on() {
+    static const bool on = tp_switch_flag(TP_SW_ILU_YLDS);
+    return on;
+}
+
 void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int nadd) {
     if (nadd < 0) nadd = c->b;
     TP_REQUIRE(c->ilu.slots > 0, "ILU not factored");
@@ -1818,7 +1828,7 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
         const bool pk = c->ilu.ptot > 0;
         if (pk) G1.pref = c->ilu.pref.p;
         const double *ff = pk ? c->ilu.fwdp.p : c->ilu.fwd.p, *bbk = pk ? c->ilu.bwdp.p : c->ilu.bwd.p;
-        static const int pf = getenv("TP_ILU1_PF") ? atoi(getenv("TP_ILU1_PF")) : 3;
+        static const int pf = (int)tp_switch_int(TP_SW_ILU1_PF);
         const dim3 gr(c->ilu.ntiles), bl(64);
 #define TP_ILU1_LAUNCH(BQ, PFQ, PKQ) \
     hipLaunchKernelGGL((k_ilu1_solve<BQ, PFQ, PKQ>), gr, bl, (size_t)(G.nsteps + 2) * sizeof(int), c->stream, G1, ff, bbk, r, c->ilu.ytmp.p, x, addto, nadd)
@@ -1839,7 +1849,7 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
         const size_t full = ((size_t)G.nsteps + 1 + 2) * slot + dump, ring = 4 * slot + dump;
         if (c->ilu.whole) {
             // one block per rank: forward over the tile-diagonals in ascending order, backward in descending order
-            static const int blk_env_w = getenv("TP_ILU_BLOCK") ? atoi(getenv("TP_ILU_BLOCK")) : -1;
+            const int blk_env_w = ilu_block_env();
             const bool blkw = (blk_env_w >= 0 ? blk_env_w == 1 : c->g.gn2 > 1) && c->g.np >= 8;
             const IluData &d = c->ilu;
 #define TP_ILU_WS_LAUNCH(BB, KK, DG, PH)                                                                               \
@@ -1856,8 +1866,7 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
             TP_HIP(hipGetLastError());
             return;
         }
-        static const bool ylds_mw = !(getenv("TP_ILU_YLDS") && atoi(getenv("TP_ILU_YLDS")) == 0);
-        const bool yl = ylds_mw && full <= 156 * 1024;
+        const bool yl = ilu_ylds_on() && full <= 156 * 1024;
 #define TP_ILU_MW_LAUNCH_R(BB, YY, KK, RR, FW, BW)                                                                      \
         do {                                                                                                            \
             TP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu_solve_mw<BB, YY, KK, false, RR>),          \
@@ -1870,7 +1879,7 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
             if (c->ilu.single) TP_ILU_MW_LAUNCH_R(BB, YY, KK, float, c->ilu.fwd32.p, c->ilu.bwd32.p);                   \
             else TP_ILU_MW_LAUNCH_R(BB, YY, KK, double, c->ilu.fwd.p, c->ilu.bwd.p);                                    \
         } while (0)
-        static const int blk_env = getenv("TP_ILU_BLOCK") ? atoi(getenv("TP_ILU_BLOCK")) : -1;
+        const int blk_env = ilu_block_env();
         // 3-D tiles: whole axis-0 lines, long sweeps.  The block loads clamp their start into the vector; that is harmless only
         // while every cell of a clamped block is a halo-plane cell, i.e. a plane holds at least one block (RF = 8 values; the
         // fp32 instantiation: its deepest ring)
@@ -1887,11 +1896,10 @@ void ilu_solve(tp_ctx *c, const double *r, double *x, const double *addto, int n
         TP_HIP(hipGetLastError());
         return;
     }
-    static const bool deep = !(getenv("TP_ILU_DEPTH") && atoi(getenv("TP_ILU_DEPTH")) == 1);
-    static const bool ylds_on = !(getenv("TP_ILU_YLDS") && atoi(getenv("TP_ILU_YLDS")) == 0);
+    static const bool deep = tp_switch_int(TP_SW_ILU_DEPTH) != 1;
     // y in LDS when the tile's whole intermediate vector fits one CU's 160 KB (one workgroup per CU then)
     const size_t ybytes = (size_t)G.nsteps * c->b * 64 * sizeof(double);
-    const bool ylds = ylds_on && ybytes <= 152 * 1024;
+    const bool ylds = ilu_ylds_on() && ybytes <= 152 * 1024;
     const bool cp = ilu_compact(c);
 #define TP_ILU_PICK_R(BB, FW, BW)                                                                                     \
     do {                                                                                                              \

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(1024) void k_reduce_partials(const double *__restri
 
 // entries per lane in the Gram-Schmidt kernels: 4 or 8 (TP_MD_CHUNK; 8 halves the cross-lane reductions per byte)
 static int md_chunk() {
-    static const int ch = (getenv("TP_MD_CHUNK") && atoi(getenv("TP_MD_CHUNK")) == 4) ? 4 : 8;
+    static const int ch = tp_switch_int(TP_SW_MD_CHUNK) == 4 ? 4 : 8;
     return ch;
 }
 // (an XCD-aware chunk order, as in the stencil kernels, was measured in round 3: Gram-Schmidt step at k = 16 0.181-0.183 ms
@@ -189,7 +189,7 @@ static long md_nwaves(const tp_ctx *c, int nf) {
     return (nall + 64L * md_chunk() - 1) / (64L * md_chunk());
 }
 bool tp_use_pin() {
-    static const bool on = !(getenv("TP_PIN") && atoi(getenv("TP_PIN")) == 0);
+    static const bool on = tp_switch_flag(TP_SW_PIN);
     return on;
 }
 // second stage of a reduction + hand-over to the host: n sums of nw partials -> red_out (device) and host_out.  One GPU: the
@@ -772,7 +772,7 @@ void basis_scale_store_dev(tp_ctx *c, int nf, const double *n2_dev, double *x, f
 // (the mappings measured against it)
 static int basis_vec() {
     static const int vw = [] {
-        const int v = getenv("TP_BASIS_VEC") ? atoi(getenv("TP_BASIS_VEC")) : 4;
+        const int v = (int)tp_switch_int(TP_SW_BASIS_VEC);
         return (v == 1 || v == 2) ? v : 4;
     }();
     return vw;
@@ -824,7 +824,7 @@ static void reorth_pass(tp_ctx *c, int nf, const double *V, long vstride, int k,
     TP_REQUIRE(V, "ksp_reorth needs the fp64 Krylov basis");
     if (c->ro_stat.n < 4) c->ro_stat.alloc(4);
     if ((long)c->ro_c.n < k + 1) c->ro_c.alloc(k + 65);
-    static const int dot_flip = getenv("TP_REORTH_DOT_REVERSE") && atoi(getenv("TP_REORTH_DOT_REVERSE")) != 0;
+    static const int dot_flip = tp_switch_flag(TP_SW_REORTH_DOT_REVERSE);
     const int dot_rev = (gs_rev ? 0 : 1) ^ dot_flip;
     const long long *flag = c->ro_stat.p;
     hipLaunchKernelGGL(k_reorth_decide, dim3(1), dim3(64), 0, c->stream, (const double *)c->red_out.p, k, mode, eta * eta, c->ro_stat.p);
@@ -868,7 +868,7 @@ static void orthogonalize_any(tp_ctx *c, int nf, const double *V, const float *V
     double *pin = (use_pin && !c->dist && k + 1 <= tp_ctx::H_PIN) ? c->h_pin : nullptr;
     hipLaunchKernelGGL(k_reduce_partials, dim3(k), dim3(1024), 0, c->stream, c->gs_partial.p, nw, c->red_out.p, pin);
     allreduce_sum(c, c->red_out.p, k);
-    static const int gs_rev = !(getenv("TP_GS_REVERSE") && atoi(getenv("TP_GS_REVERSE")) == 0);
+    static const int gs_rev = tp_switch_flag(TP_SW_GS_REVERSE);
     if (Vs) TP_MDS_LAUNCH(k_multi_axpy_norm_s, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, Vs, vstride, k,
                           c->red_out.p, w, c->gs_partial.p, nw, gs_rev);
     else TP_MD_LAUNCH(k_multi_axpy_norm, md_grid(nw), dim3(256), 0, c->stream, c->g, nf, V, vstride, k,
@@ -1137,7 +1137,7 @@ void spmv_block(tp_ctx *c, const double *J, const double *x, double *y) {
 // interior rows").  Per-cell arithmetic unchanged: bitwise the result of exchange-then-SpMV.
 void spmv_block_halo(tp_ctx *c, const double *J, double *x, double *y) {
     const GridDev &g = c->g;
-    static const bool overlap = !(getenv("TP_HALO_OVERLAP") && atoi(getenv("TP_HALO_OVERLAP")) == 0);
+    static const bool overlap = tp_switch_flag(TP_SW_HALO_OVERLAP);
     if (!c->dist) { spmv_block(c, J, x, y); return; }
     if (!overlap || g.n2 < 3) {
         halo_exchange(c, g, x, c->b, g.ntot);

@@ -532,7 +532,7 @@ static void pc_apply_stages(tp_ctx *c, const double *x, double *y) {
 // ---- recording of pc_apply programs: one capture segment between two exchanges ------------------------------------------
 // TP_DEBUG=2: one line per HIP graph call (used to locate the profiler crash described in DESIGN.md 6)
 static void pc_trace(const tp_ctx::PcProgram &pr, const char *what) {
-    static const bool trace = getenv("TP_DEBUG") && atoi(getenv("TP_DEBUG")) >= 2;
+    static const bool trace = tp_switch_int(TP_SW_DEBUG) >= 2;
     if (trace) { fprintf(stderr, "[tp] pc_apply(%p,%p): %s\n", (const void *)pr.x, (void *)pr.y, what); fflush(stderr); }
 }
 void seg_begin(tp_ctx *c) {
@@ -570,7 +570,7 @@ void seg_end(tp_ctx *c) {
 // slabs graph segments between the exchanges with the exchanges themselves as host closures.
 void pc_apply(tp_ctx *c, const double *x, double *y) {
     TP_REQUIRE(c->pc_ready, "pc_apply before pc_setup");
-    static const bool use_graph = !(getenv("TP_GRAPH") && atoi(getenv("TP_GRAPH")) == 0);
+    static const bool use_graph = tp_switch_flag(TP_SW_GRAPH);
     c->vcycles += vcycles_per_apply(c);
     if (c->opt.pc_ctr) ++c->ctr_applies;
     schur_count(c, c->opt.pc_order == 3 ? 2 : 1);
@@ -763,8 +763,8 @@ int fgmres(tp_ctx *c, const double *bvec, double *x, int *its_out, double *rnorm
     // BEFORE the host waits -- on an event behind the reductions, not on the stream.  Speculative: if iteration j turns out
     // to be the last, that work is discarded (~0.9 ms), so it is only issued while the residual, extrapolated with the last
     // reduction factor, stays 4x above the cycle's threshold.  Same arithmetic either way (bit-identical iterates).
-    static const bool pipe_on = !(getenv("TP_FGMRES_PIPE") && atoi(getenv("TP_FGMRES_PIPE")) == 0);
-    static const double spec_margin = getenv("TP_SPEC_MARGIN") ? atof(getenv("TP_SPEC_MARGIN")) : 4.0;
+    static const bool pipe_on = tp_switch_flag(TP_SW_FGMRES_PIPE);
+    static const double spec_margin = tp_switch_real(TP_SW_SPEC_MARGIN);
     while (true) {
         const int m = std::min(restart, maxit - its);
         H.assign((size_t)(m + 1) * m, 0.0);

@@ -109,6 +109,7 @@ API_SYMBOLS = (
     "tp_schur_info", "tp_set_boundary", "tp_boundary_flux", "tp_set_spacing", "tp_spacing_info",
     "tp_set_saturation_functions", "tp_saturation_info",
     "tp_set_wells", "tp_set_well_control", "tp_well_info", "tp_well_perf_rates", "tp_well_factors",
+    "tp_switch_count", "tp_switch_entry",
 )
 
 DEFAULT_OPTS = dict(
@@ -716,6 +717,26 @@ def load_library(path=None):
     if path is None:
         _LIB = lib
     return lib
+
+
+# TP_* environment variables read in Python, not by the library: no entries of switch_table()
+PYTHON_SIDE_SWITCHES = {
+    "TP_LOCAL_DEVICE": "pin every rank to one GPU index (engine.py, parallel.py)",
+    "TP_CPU_THREADS": "OpenMP threads of oracle/cport (tests, bench.py's CPU leg)",
+}
+
+
+def switch_table():
+    """The library's TP_* runtime switches (csrc/tp_switches.hpp) as a list of dicts with the keys name, kind
+    ("flag" | "int" | "real"), default, when ("process" | "setup") and effect.  Needs no GPU."""
+    lib = load_library()
+    out = []
+    for i in range(lib.tp_switch_count()):
+        f = [C.c_char_p() for _ in range(5)]
+        if lib.tp_switch_entry(i, *[C.byref(x) for x in f]) != 0:
+            raise EngineError(lib.tp_last_error().decode())
+        out.append(dict(zip(("name", "kind", "default", "when", "effect"), (x.value.decode() for x in f))))
+    return out
 
 
 def _dptr(a):
